@@ -17,6 +17,12 @@ worker.apply_gradients (Adam + Polyak).  So every step is 4096 env-steps and 1 g
 Rank 0 prints ONE JSON line.  value = whole-job env-steps/s (all GPUs); grad_steps_per_sec beside it; scaling is
 weak (per-GPU batch fixed, global batch = N * 4096, gradient all-reduced over RCCL).
 
+A plain run does only what the headline needs: set up, burn in + warm up, time ONE region of exactly K steps
+(value, ms_per_step), write the last step's outputs if `--dump-outputs DIR` is given, print the line.
+`--full` adds, after that region, everything else the line used to carry: the kernel timer's passes (roofline, kernel
+groups, `timed_regions` profiled regions of K steps each, per-step distribution), the stand-alone env-kernel and exchange
+measurements, the exact-fp32 engine and the side configurations as child processes, and the CPU baseline.
+
 What happens around the timed region (all of it disclosed in the JSON line):
   * `burn_in_steps` (fixed, 200 ~ 0.1 s) untimed steps BEFORE the W warm-up steps: the GPU's clocks and caches take
     ~40-100 steps to settle (kernels are 8-10 % slower until then), which a 5-step warm-up does not cover;
@@ -24,9 +30,15 @@ What happens around the timed region (all of it disclosed in the JSON line):
     (`gc`): a generation-2 collection of the ~10^6 objects that `import torch` leaves behind takes 40-100 ms, and
     round 1's driver run caught one inside its 20 timed steps (4.62 ms/step against 0.47; tools/stall_scan.py shows it
     at the same step index run after run).  A training loop that cares does the same (`mpg_amd.optimizer.quiesce_gc`);
-  * the kernel timer's HIP events all exist before the burn-in (`ops.Profiler`), nothing is created in the loop;
-  * after the timed region, a second pass of the same K steps with one HIP event per step gives the per-step
+  * no kernel timer is attached during the timed region: the `--full` passes create theirs (`ops.Profiler`) after it;
+  * `--full`: after the timed region, a pass of the same K steps with one HIP event per step gives the per-step
     distribution (`step_ms_median/min/max`); it is NOT part of `value`.
+
+`--dump-outputs DIR` writes, right after the timed region, what the last timed step left for its caller (rank 0):
+DIR/params.npy, targets.npy, adam_m.npy, adam_v.npy (the flat [Q1 | Q2 | policy] parameters, Polyak targets and Adam
+moments after apply_gradients), grad.npy (the clipped flat gradient), stats.npy (the learner's statistics slots),
+grad_norms.npy (the per-network norms before clipping) and worker_obs.npy (the worker's observations after its env
+step), all float32.  Every input is seeded, so the same arguments give the same inputs run after run.
 """
 import argparse
 import gc
@@ -60,10 +72,10 @@ FP32_MFMA_PEAK_TFLOPS = 157.3          # MI355X_MICROARCH.md: v_mfma_f32_16x16x4
 F16_MFMA_PEAK_TFLOPS = 2500.0          # MI355X_MICROARCH.md: f16 / bf16 dense peak
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 # The kernel durations behind `roofline` are measured live, with HIP events on the launch stream, on every PROF_EVERY-th
-# launch of the timed region: an event record is a stream packet of its own (~4-5 us between two otherwise back-to-back
+# launch of the --full profiled regions: an event record is a stream packet of its own (~4-5 us between two otherwise back-to-back
 # kernels; 8 of them per step with every launch timed = 6 % of a 0.5 ms step - profiles/README.md has the trace).
 PROF_EVERY = 16
-N_REGIONS = 5          # timed regions of K steps each; value = the median region
+N_REGIONS = 5          # --full: profiled regions of K steps each after the timed one
 ENV_SAT_AGENTS = 1 << 20      # agents per launch of the stand-alone env-kernel measurement at a saturating size
 ENV_FLOP_PER_STEP = 2300.0    # ~2.3 kflop per env-step (20 sub-steps x ~115, transcendentals counted as 1)
 
@@ -85,9 +97,40 @@ def build_stack(dev, seed, always_exchange=False):
     return args, worker, learner, rb, opt
 
 
+def timed_region(step, k):
+    """seconds for exactly k calls of step(): barrier + synchronize on both sides, MAX over the ranks, no gc inside"""
+    import torch
+    from mpg_amd import dist as D
+    gc.disable()
+    D.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(k):
+        step()
+    D.barrier()
+    torch.cuda.synchronize()
+    dt = D.max_over_ranks(time.perf_counter() - t0)
+    gc.enable()
+    return dt
+
+
+def dump_outputs(out_dir, worker, learner):
+    """what the last optimizer step left for its caller, as float32 .npy files (module docstring); a few MB at the bench sizes"""
+    import numpy as np
+    pw = worker.policy_with_value
+    arrays = {'params': pw.params, 'targets': pw.targets, 'adam_m': pw.m, 'adam_v': pw.v, 'grad': learner.flat[:learner.n_grad],
+              'stats': learner.flat[learner.n_grad:], 'grad_norms': learner.norms, 'worker_obs': worker.obs}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 # ---- CPU baseline: the oracle, the way the reference scales (1 thread per process x P processes) -------------------
 CPU_ROWS = 1024            # rows (agents / replay rows) per CPU step: a bounded sample of the 4096-row step (the unit, env-steps/s, scales)
 CPU_LEGS = (64, 128, 256)  # processes side by side: per-core regime ... memory-bound regime of a 2-socket host
+# at most 16 processes may hold a shared GPU box's device at once, and the CPU actors count among them beside this process
+# (the one that runs the timed region)
+MAX_CPU_PROCS = 15
 
 
 def _cpu_worker(budget_s, min_timed, seed, q, go, rows=None):
@@ -181,10 +224,10 @@ def _run_leg(target, args_of, procs, timeout_s):
     return res, time.perf_counter() - t0
 
 
-def cpu_baseline(budget_s=8.0, min_timed=3, max_procs=256):
+def cpu_baseline(budget_s=8.0, min_timed=3, max_procs=MAX_CPU_PROCS):
     """`kind: port` - the oracle timed on the host cores on a bounded sample of the SAME workload, shaped like the
     reference's own scaling: P single-threaded processes side by side, for P = 64 / 128 / 256 (capped by
-    the host's cores and by what the free memory allows at ~1.5 GB per process: `import torch` alone is 0.6 GB of private
+    the host's cores, by MAX_CPU_PROCS and by what the free memory allows at ~1.5 GB per process: `import torch` alone is 0.6 GB of private
     pages), so that the per-core regime (few processes) and the memory-bound regime (every hardware thread busy) are both in
     the line.  Every process: one untimed step, then >= 3 timed steps of CPU_ROWS rows.  `value` = the best leg."""
     host, mem_cap, cap = _host_limits(max_procs)
@@ -272,7 +315,8 @@ def launch_ranks(a):
     (torch.distributed.run, one process per GPU), then leaves with their exit code."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus), '--master-addr',
            '127.0.0.1', '--master-port', str(_free_port()), os.path.abspath(__file__), '--gpus', str(a.gpus), '--steps',
-           str(a.steps), '--warmup', str(a.warmup), '--config', a.config, '--rows-per-gpu', str(a.rows_per_gpu)] + (['--no-cpu-baseline'] if a.no_cpu_baseline else [])
+           str(a.steps), '--warmup', str(a.warmup), '--config', a.config, '--rows-per-gpu', str(a.rows_per_gpu)] + (['--no-cpu-baseline'] if a.no_cpu_baseline else []) + \
+        (['--full'] if a.full else []) + (['--dump-outputs', os.path.abspath(a.dump_outputs)] if a.dump_outputs else [])
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     env.setdefault('OMP_NUM_THREADS', '1')
@@ -351,7 +395,7 @@ def _cpu_side_worker(budget_s, seed, config, q, go):
     q.put(('done', n_done * rows, el))
 
 
-def cpu_side_baseline(config, budget_s=8.0, max_procs=256):
+def cpu_side_baseline(config, budget_s=8.0, max_procs=MAX_CPU_PROCS):
     host, mem_cap, procs = _host_limits(max_procs)
     for k in ('OMP_NUM_THREADS', 'MKL_NUM_THREADS', 'OPENBLAS_NUM_THREADS', 'NUMEXPR_NUM_THREADS'):
         os.environ[k] = '1'
@@ -413,78 +457,73 @@ def side_config(a):
     assert (opt._fused is not None) == (a.side_driver == 'native')
     pw = worker.policy_with_value
     pw.sync_from_rank0()
-    prof = ops.Profiler(max_samples=4096)
-    opt.set_profiler(prof)
     step = opt.step
     quiesce_gc()
     for _ in range(max(a.warmup, 5)):
         step()
-    gc.disable()
-    regions = []
-    for _ in range(N_REGIONS):              # like the main line: value from the median of N_REGIONS regions of K steps
-        D.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
+    dt = timed_region(step, a.steps)        # the headline: ONE region of exactly K steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, worker, learner)
+    if a.full:
+        # --full: N_REGIONS further regions of K steps (the spread), then the kernel groups: a short pass with EVERY launch of the
+        # library's timer slots bracketed by HIP events (the records cost ~4-5 us each, which is why this pass is not the timed one)
+        prof = ops.Profiler(max_samples=4096)
+        opt.set_profiler(prof)
+        regions = [timed_region(step, a.steps) for _ in range(N_REGIONS)]
+        nprof = min(a.steps, 10)
+        prof.start(1)
+        for _ in range(nprof):
             step()
-        D.barrier()
         torch.cuda.synchronize()
-        regions.append(D.max_over_ranks(time.perf_counter() - t0))
-    gc.enable()
-    dt = sorted(regions)[len(regions) // 2]
-    # kernel groups: a second, short pass with EVERY launch of the library's timer slots bracketed by HIP events (the records
-    # cost ~4-5 us each, which is why this pass is not the timed one)
-    nprof = min(a.steps, 10)
-    prof.start(1)
-    for _ in range(nprof):
-        step()
-    torch.cuda.synchronize()
-    slots = {}
-    for k in range(8):
-        ms, n = prof.read(k)
-        if n:
-            slots[ctypes_name(k)] = {'avg_ms': ms, 'launches_per_step': n / nprof, 'ms_per_step': ms * n / nprof}
-    prof.stop()
-    t_per = None
-    if a.config == 'c4':    # the sampling + gather alone, timed with device events on the launch stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            rb.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        t_per = e0.elapsed_time(e1) / 20
+        slots = {}
+        for k in range(8):
+            ms, n = prof.read(k)
+            if n:
+                slots[ctypes_name(k)] = {'avg_ms': ms, 'launches_per_step': n / nprof, 'ms_per_step': ms * n / nprof}
+        prof.stop()
+        t_per = None
+        if a.config == 'c4':    # the sampling + gather alone, timed with device events on the launch stream
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                rb.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            t_per = e0.elapsed_time(e1) / 20
     assert bool(torch.isfinite(pw.params).all().item()) and int(pw.nonfinite.sum().item()) == 0
     pw.check_status()
     if rank != 0:
         return
     ms = 1e3 * dt / a.steps
-    dom = max(slots, key=lambda k: slots[k]['ms_per_step']) if slots else None
-    executed = (c['flop_per_row'] + 2 * c['hidden_flop_per_row']) * B / (ms * 1e-3) / 1e12
-    algorithmic = c['flop_per_row'] * B / (ms * 1e-3) / 1e12
     out = {
         'metric': c['metric'], 'value': world * B * a.steps / dt, 'unit': 'rows/s', 'grad_steps_per_sec': a.steps / dt,
         'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': ms, 'higher_is_better': True, 'scaling': 'weak',
-        'timed_regions': N_REGIONS, 'region_ms_per_step': [1e3 * r / a.steps for r in regions],
-        'vs_baseline': None, 'dtype': 'f32-via-split-f16', 'data': 'synthetic', 'schema': 4,
+        'vs_baseline': None, 'dtype': 'f32-via-split-f16', 'data': 'synthetic', 'schema': 5,
         'config': {'workload': c['workload'], 'global_batch': world * B, 'parallelism': 'dp%d' % world, 'dist_backend': D.backend(),
                    'driver': 'native step driver (mpg_step_begin / _end)' if a.side_driver == 'native' else 'method by method from Python'},
         'device': _device_info(),
-        # whole-step matrix view (the step is a chain of weight-stationary launches, all on the f16 pipe).  `achieved` / `frac`
-        # count ALGORITHMIC flop (the 3x of the split-fp16 emulation is overhead, not work); the executed view (the
-        # hidden-layer part counted 3x) stays under frac_f16_mfma
-        'roofline': {'bound': 'mfma', 'kernel': 'whole gradient step (%s dominates: %.3f ms of it)' % (dom, slots[dom]['ms_per_step']) if dom else 'whole gradient step',
-                     'achieved': algorithmic, 'peak': F16_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': algorithmic / F16_MFMA_PEAK_TFLOPS,
-                     'frac_f16_mfma': executed / F16_MFMA_PEAK_TFLOPS, 'executed_f16_tflops': executed, 'traffic': None,
-                     'algorithmic_tflops': algorithmic,
-                     'timed_with': 'wall clock over the timed region (kernel groups by HIP events on the launch stream below)'},
-        'kernel_groups_ms_per_step': slots,
     }
-    if t_per is not None:
-        out['per'] = {'sample_gather_ms': t_per, 'algorithmic_bytes_per_index': 212, 'achieved_GBs': 212 * B / (t_per * 1e-3) / 1e9,
-                      'peak_GBs': HBM_PEAK_GBS, 'frac_hbm': 212 * B / (t_per * 1e-3) / 1e9 / HBM_PEAK_GBS}
-    if world == 1 and not a.no_cpu_baseline:
-        out['cpu_baseline'] = cpu_side_baseline(a.config)
+    if a.full:
+        dom = max(slots, key=lambda k: slots[k]['ms_per_step']) if slots else None
+        executed = (c['flop_per_row'] + 2 * c['hidden_flop_per_row']) * B / (ms * 1e-3) / 1e12
+        algorithmic = c['flop_per_row'] * B / (ms * 1e-3) / 1e12
+        out.update({
+            'timed_regions': N_REGIONS, 'region_ms_per_step': [1e3 * r / a.steps for r in regions],
+            # whole-step matrix view (the step is a chain of weight-stationary launches, all on the f16 pipe).  `achieved` / `frac`
+            # count ALGORITHMIC flop (the 3x of the split-fp16 emulation is overhead, not work); the executed view (the
+            # hidden-layer part counted 3x) stays under frac_f16_mfma
+            'roofline': {'bound': 'mfma', 'kernel': 'whole gradient step (%s dominates: %.3f ms of it)' % (dom, slots[dom]['ms_per_step']) if dom else 'whole gradient step',
+                         'achieved': algorithmic, 'peak': F16_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': algorithmic / F16_MFMA_PEAK_TFLOPS,
+                         'frac_f16_mfma': executed / F16_MFMA_PEAK_TFLOPS, 'executed_f16_tflops': executed, 'traffic': None,
+                         'algorithmic_tflops': algorithmic,
+                         'timed_with': 'wall clock over the timed region (kernel groups by HIP events on the launch stream below)'},
+            'kernel_groups_ms_per_step': slots,
+        })
+        if t_per is not None:
+            out['per'] = {'sample_gather_ms': t_per, 'algorithmic_bytes_per_index': 212, 'achieved_GBs': 212 * B / (t_per * 1e-3) / 1e9,
+                          'peak_GBs': HBM_PEAK_GBS, 'frac_hbm': 212 * B / (t_per * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        if world == 1 and not a.no_cpu_baseline:
+            out['cpu_baseline'] = cpu_side_baseline(a.config)
     print(json.dumps(out), flush=True)
 
 
@@ -515,6 +554,12 @@ def main():
     ap.add_argument('--engine', default='split', choices=['split', 'f32'],
                     help='split (default): the product; f32: the same step on libmpg_hip_f32.so, the exact-fp32 engine (the main run '
                          'starts this form itself as a child process and reports it as exact_fp32_ms_per_step)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run every side measurement: kernel timer passes and roofline, per-step '
+                         'distribution, stand-alone env-kernel and exchange timings, the exact-fp32 engine and the side configurations '
+                         '(child processes), the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32; see the module docstring)')
     a = ap.parse_args()
     global B_PER_GPU
     assert a.rows_per_gpu % 16 == 0 and a.rows_per_gpu >= 4096, '--rows-per-gpu: a multiple of 16, at least 4096'
@@ -544,32 +589,59 @@ def main():
     dev = torch.device('cuda', local)
     torch.cuda.set_device(dev)
     args, worker, learner, rb, opt = build_stack(dev, seed=rank, always_exchange=a.always_exchange)
-    n_samples = (N_REGIONS * max(a.steps, 1) + PROF_EVERY - 1) // PROF_EVERY + 1
-    prof = ops.Profiler(max_samples=n_samples)      # every HIP event exists from here on
-    opt.set_profiler(prof)
     quiesce_gc()                                     # gc.collect() + gc.freeze(): see the module docstring
-    prof.start(PROF_EVERY)
     for _ in range(BURN_IN_STEPS):
         opt.step()
     for _ in range(a.warmup):
         opt.step()
+    dt = timed_region(opt.step, a.steps)             # the headline: ONE region of exactly K steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, worker, learner)
+    finite = bool(torch.isfinite(worker.policy_with_value.params).all().item())
+    assert finite and int(worker.policy_with_value.nonfinite.sum().item()) == 0, 'non-finite parameters after the timed region'
+    worker.policy_with_value.check_status()          # raises if the split-fp16 engine left its numerical envelope anywhere
+    out = {
+        'metric': 'env-steps/sec + grad-steps/sec, PathTrackingEnv MPG n=25 batch=%d' % B_PER_GPU,
+        'value': world * B_PER_GPU * a.steps / dt, 'unit': 'env-steps/s',
+        'grad_steps_per_sec': a.steps / dt,
+        'model_steps_per_sec': world * B_PER_GPU * N_STEP * a.steps / dt,
+        # value / ms_per_step / grad_steps_per_sec come from ONE timed region of exactly `steps` steps (barrier + synchronize on
+        # both sides, MAX over ranks)
+        'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': 1e3 * dt / a.steps,
+        'burn_in_steps': BURN_IN_STEPS,
+        'gc': 'gc.collect()+gc.freeze() before the burn-in, gc.disable() inside the timed region',
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f32-via-split-f16' if a.engine == 'split' else 'f32', 'data': 'synthetic',
+        'schema': 5,     # 5: value from ONE region of exactly `steps` steps with no kernel timer; the rest of the line needs --full
+                         # 4: value from the median of 5 timed regions, env_step_kernel at a saturating size, side_configs, cpu_baseline legs
+                         # 3: roofline.frac = HBM view (round 1: fp32-MFMA view), frac_hbm / frac_f16_mfma under stable keys, exact_fp32_*
+        'engine': a.engine,
+        'dtype_note': 'float32 data and accumulation; the 256x256 hidden-layer products run as fp16 hi/lo split operands on the f16 matrix pipe (3 MFMAs per fp32-equivalent step, more accurate than the fp32 fma chain on a single layer; csrc/mlp_core.h)',
+        'config': {'workload': 'PathTrackingEnv, MPG-v2 learner, n=25, M=1, %d vectorised envs + replay batch %d per '
+                               'GPU; step = worker.sample(%d env-steps) + add_batch + replay + compute_gradient + '
+                               '(all-reduce) + apply_gradients' % (B_PER_GPU, B_PER_GPU, B_PER_GPU),
+                   'global_batch': world * B_PER_GPU, 'parallelism': 'dp%d' % world,
+                   'grad_allreduce_floats': int(learner.flat.numel()), 'native_step_driver': opt._fused is not None,
+                   'dist_backend': D.backend(), 'always_exchange': bool(a.always_exchange),
+                   'overlap_exchange': os.environ.get('MPG_OVERLAP_EXCHANGE') == '1', 'rows_per_gpu': B_PER_GPU},
+        'device': _device_info(),
+    }
+    if not a.full:
+        if rank == 0:
+            _flush_c_stdio()
+            print(json.dumps(out), flush=True)
+        return
+
+    # ---- --full: everything below runs after the timed region and is not part of `value` ----
+    # N_REGIONS further regions of EXACTLY K steps each with the kernel timer sampling every PROF_EVERY-th launch (its HIP events
+    # all exist before the first region; the records cost a little, which is why these are not the headline region); the line
+    # lists all of them (one 4.7 ms region is at the mercy of a single host stall -
+    # profiles/r04_final_bench_driver_form_outlier.json)
+    n_samples = (N_REGIONS * max(a.steps, 1) + PROF_EVERY - 1) // PROF_EVERY + 1
+    prof = ops.Profiler(max_samples=n_samples)
+    opt.set_profiler(prof)
     prof.start(PROF_EVERY)                           # clears the samples; no event is created
-    gc.disable()
-    # N_REGIONS consecutive timed regions of EXACTLY K steps each, every one bracketed by barrier + synchronize on both sides and
-    # reduced with MAX over the ranks; `value` comes from the MEDIAN region (one 4.7 ms region is at the mercy of
-    # a single host stall - profiles/r04_final_bench_driver_form_outlier.json - so the line lists all of them)
-    regions = []
-    for _ in range(N_REGIONS):
-        D.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            opt.step()
-        D.barrier()
-        torch.cuda.synchronize()
-        regions.append(D.max_over_ranks(time.perf_counter() - t0))
-    gc.enable()
-    dt = sorted(regions)[len(regions) // 2]
+    regions = [timed_region(opt.step, a.steps) for _ in range(N_REGIONS)]
 
     fwd_ms, fwd_n = prof.read(0)
     bwd_ms, bwd_n = prof.read(1)
@@ -667,7 +739,7 @@ def main():
         sat[name] = es[0].elapsed_time(es[1]) / 10
     del big, b_act, b_obs, b_rew, b_done, b_di, b_robs, b_robs2, b_ract, b_rrew, b_rdone
     finite = bool(torch.isfinite(worker.policy_with_value.params).all().item())
-    assert finite and int(worker.policy_with_value.nonfinite.sum().item()) == 0, 'non-finite parameters after the timed region'
+    assert finite and int(worker.policy_with_value.nonfinite.sum().item()) == 0, 'non-finite parameters after the profiled passes'
     worker.policy_with_value.check_status()          # raises if the split-fp16 engine left its numerical envelope anywhere
     # (checked HERE, before the side measurement below: an abandoned collective may leave the stream blocked for good)
     # N > 1: the exchange on its own in every form this process group can run (RCCL when the group is an nccl group; the one-shot and
@@ -724,7 +796,7 @@ def main():
                 side_hung = True
                 break
         if side_hung and rank != 0:
-            os._exit(0)                          # this rank's part of the line (the timed regions) is done
+            os._exit(0)                          # this rank's part of the line (the timed and profiled regions) is done
     if rank != 0:
         return
     # HBM bytes per launch from the PMC counters (FETCH_SIZE/WRITE_SIZE, separate rocprofv3 --pmc passes, gfx950
@@ -744,7 +816,8 @@ def main():
     children = a.engine == 'split' and world == 1 and not os.environ.get('MPG_BENCH_NO_F32') and not profiled and a.rows_per_gpu == 4096
 
     def child(extra, timeout=900):
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(a.steps), '--warmup', str(a.warmup), '--no-cpu-baseline'] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(a.steps), '--warmup', str(a.warmup), '--full',
+               '--no-cpu-baseline'] + extra
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
         if r.returncode == 0 and line:
@@ -796,7 +869,7 @@ def main():
         return {'kernel': kernel, 'bound': 'hbm', 'achieved': gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                 'frac': gbs / HBM_PEAK_GBS, 'frac_hbm': gbs / HBM_PEAK_GBS, 'frac_f16_mfma': executed / F16_MFMA_PEAK_TFLOPS,
                 'traffic': tr, 'traffic_from': traffic_from if tr else None, 'avg_ms': ms, 'launches': n,
-                'timed_with': 'HIP events on the launch stream around every %d-th launch of the timed region' % PROF_EVERY,
+                'timed_with': 'HIP events on the launch stream around every %d-th launch of the profiled regions' % PROF_EVERY,
                 'algorithmic_bytes_per_launch': nbytes * B_PER_GPU,
                 'traffic_gbs': (tr / sec / 1e9) if tr else None,
                 'mfma_view': {'executed_f16_tflops': executed, 'peak_f16_tflops': F16_MFMA_PEAK_TFLOPS,
@@ -815,36 +888,15 @@ def main():
         side_flat['c5_on_1gpu_env_steps_per_sec'] = side['c5_on_1gpu'].get('value')
         side_flat['c5_on_1gpu_dominant_sweep_frac_hbm'] = side['c5_on_1gpu']['roofline'].get('frac_hbm')
         side_flat['c5_on_1gpu_dominant_sweep_avg_ms'] = side['c5_on_1gpu']['roofline'].get('avg_ms')
-    out = {
-        'metric': 'env-steps/sec + grad-steps/sec, PathTrackingEnv MPG n=25 batch=%d' % B_PER_GPU,
-        'value': world * B_PER_GPU * a.steps / dt, 'unit': 'env-steps/s',
-        'grad_steps_per_sec': a.steps / dt,
-        'model_steps_per_sec': world * B_PER_GPU * N_STEP * a.steps / dt,
-        'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': 1e3 * dt / a.steps,
-        # value / ms_per_step / grad_steps_per_sec come from the MEDIAN of `timed_regions` consecutive regions of exactly `steps`
-        # steps each (barrier + synchronize on both sides of every region, MAX over ranks per region); all regions listed in order
+    out['config'].update(side_flat)
+    out.update({
+        # the profiled regions after the timed one: `timed_regions` regions of exactly `steps` steps each, listed in order
         'timed_regions': N_REGIONS, 'region_ms_per_step': [1e3 * r / a.steps for r in regions],
-        'burn_in_steps': BURN_IN_STEPS,
-        'gc': 'gc.collect()+gc.freeze() before the burn-in, gc.disable() inside the timed region',
         'step_ms_median': per_step[len(per_step) // 2], 'step_ms_min': per_step[0], 'step_ms_max': per_step[-1],
-        'step_ms_from': 'second pass of the same %d steps, one HIP event per step (not part of value)' % a.steps,
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': 'f32-via-split-f16' if a.engine == 'split' else 'f32', 'data': 'synthetic',
-        'schema': 4,     # 4: value from the median of 5 timed regions, env_step_kernel at a saturating size, side_configs, cpu_baseline legs
-                         # 3: roofline.frac = HBM view (round 1: fp32-MFMA view), frac_hbm / frac_f16_mfma under stable keys, exact_fp32_*
+        'step_ms_from': 'a later pass of the same %d steps, one HIP event per step (not part of value)' % a.steps,
         'exact_fp32_ms_per_step': exact.get('ms_per_step'),
         'exact_fp32_from': exact.get('from'),
         'exact_fp32_rollout_kernels_ms': exact.get('rollout_kernels_ms'),
-        'engine': a.engine,
-        'dtype_note': 'float32 data and accumulation; the 256x256 hidden-layer products run as fp16 hi/lo split operands on the f16 matrix pipe (3 MFMAs per fp32-equivalent step, more accurate than the fp32 fma chain on a single layer; csrc/mlp_core.h)',
-        'config': {'workload': 'PathTrackingEnv, MPG-v2 learner, n=25, M=1, %d vectorised envs + replay batch %d per '
-                               'GPU; step = worker.sample(%d env-steps) + add_batch + replay + compute_gradient + '
-                               '(all-reduce) + apply_gradients' % (B_PER_GPU, B_PER_GPU, B_PER_GPU),
-                   'global_batch': world * B_PER_GPU, 'parallelism': 'dp%d' % world,
-                   'grad_allreduce_floats': int(learner.flat.numel()), 'native_step_driver': opt._fused is not None,
-                   'dist_backend': D.backend(), 'always_exchange': bool(a.always_exchange),
-                   'overlap_exchange': os.environ.get('MPG_OVERLAP_EXCHANGE') == '1', 'rows_per_gpu': B_PER_GPU, **side_flat},
-        'device': _device_info(),
         'roofline': dominant,
         'roofline_other_rollout_kernel': other,
         'other_kernels_avg_ms': {'k_target_fused': tgt_ms, 'k_critic_fused': crit_ms, 'k_wgrad_multi': wg_ms,
@@ -855,7 +907,7 @@ def main():
                                  'k_step_store_reset (env)': env_ms,
                                  'k_clip_adam_polyak': adam_ms},
         # the ONE exchange step per gradient step (all-reduce of the flat [gradients | statistics] buffer), HIP events on the
-        # launch stream around every PROF_EVERY-th exchange of the timed region on rank 0; null on one GPU (none is enqueued)
+        # launch stream around every PROF_EVERY-th exchange of the profiled regions on rank 0; null on one GPU (none is enqueued)
         'exchange_ms': xch_ms, 'exchange_launches': xch_n,
         # the exchange alone, per form (ms per exchange of the flat buffer; stand-alone, after the timed region; null on one GPU)
         'exchange_forms_ms': exchange_forms,
@@ -874,7 +926,7 @@ def main():
         'env_step_only_kernel': {'kernel': 'k_step (mpg_env_step)', 'avg_ms': step_only_ms, 'launches': 64,
                                  'timed_with': 'one HIP event pair around 64 launches queued behind a spin kernel (back to back on the '
                                                'GPU, launch boundaries included) after the timed region'},
-    }
+    })
     if world == 1 and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
     _flush_c_stdio()

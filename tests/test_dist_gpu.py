@@ -335,7 +335,7 @@ def test_bench_in_the_drivers_multi_rank_form(backend, nproc):
     env = dict(os.environ, MPG_DIST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY='0', MPG_BENCH_BURN_IN='60')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(nproc), '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', str(nproc), '--steps', '10', '--warmup', '3',
-           '--no-cpu-baseline']
+           '--full', '--no-cpu-baseline']
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=850)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -347,9 +347,9 @@ def test_bench_in_the_drivers_multi_rank_form(backend, nproc):
     np.testing.assert_allclose(d['value'], nproc * 4096 / (d['ms_per_step'] * 1e-3), rtol=1e-6)
     assert 'roofline' in d and d['vs_baseline'] is None
     assert d['exchange_ms'] is not None and d['exchange_ms'] > 0 and d['exchange_launches'] > 0
-    # round 5: the median of five timed regions, and the exchange alone in every form this group can run (both IPC forms here)
-    assert d['timed_regions'] == 5 and len(d['region_ms_per_step']) == 5
-    assert abs(d['ms_per_step'] - sorted(d['region_ms_per_step'])[2]) <= 1e-9 * d['ms_per_step']
+    # --full: five profiled regions of `steps` steps after the timed one, and the exchange alone in every form this group can run
+    # (both IPC forms here)
+    assert d['timed_regions'] == 5 and len(d['region_ms_per_step']) == 5 and all(r > 0 for r in d['region_ms_per_step'])
     forms = d['exchange_forms_ms']
     assert set(forms) >= {'oneshot', 'twoshot'} and all(isinstance(forms[k], float) and forms[k] > 0 for k in ('oneshot', 'twoshot')), forms
 

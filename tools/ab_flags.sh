@@ -9,6 +9,6 @@ for V in "" "$@" ""; do
   if [ "$which" = FUSED ]; then MPG_FUSED_CFLAGS="$V" python3 -m mpg_amd.build --split-only > /tmp/build.log 2>&1 || { echo BUILD FAILED; continue; }
   elif [ "$which" = ENV ]; then MPG_ENV_CFLAGS="$V" python3 -m mpg_amd.build --split-only > /tmp/build.log 2>&1 || { echo BUILD FAILED; continue; }
   else MPG_MLP_CFLAGS="$V" python3 -m mpg_amd.build --split-only > /tmp/build.log 2>&1 || { echo BUILD FAILED; continue; }; fi
-  MPG_BENCH_NO_F32=1 python3 bench.py --steps 600 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "$P"
+  MPG_BENCH_NO_F32=1 python3 bench.py --full --steps 600 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "$P"
 done
 python3 -m mpg_amd.build --split-only > /tmp/build.log 2>&1

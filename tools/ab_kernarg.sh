@@ -6,7 +6,7 @@ STEPS=${STEPS:-400}
 for V in ${VARIANTS:-unset 0 1 0 1 unset}; do
   if [ "$V" = unset ]; then unset HIP_FORCE_DEV_KERNARG; else export HIP_FORCE_DEV_KERNARG=$V; fi
   echo "== HIP_FORCE_DEV_KERNARG=$V"
-  MPG_BENCH_NO_F32=1 python3 bench.py --steps $STEPS --warmup 30 --no-cpu-baseline --no-side-configs 2>/dev/null | tail -1 | python3 -c "
+  MPG_BENCH_NO_F32=1 python3 bench.py --full --steps $STEPS --warmup 30 --no-cpu-baseline --no-side-configs 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); o=d['other_kernels_avg_ms']
 r={d['roofline']['kernel'][:13]:d['roofline']['avg_ms'], d['roofline_other_rollout_kernel']['kernel'][:13]:d['roofline_other_rollout_kernel']['avg_ms']}

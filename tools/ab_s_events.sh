@@ -9,5 +9,5 @@ for rep in 1 2; do
 for mode in oneshot twoshot; do
 for s in 0 1; do
   MPG_DIST_BACKEND=oneshot MPG_ONESHOT_MODE=$mode MPG_ONESHOT_S_EVENTS=$s python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29600 + RANDOM % 300)) bench.py --gpus $N --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "$P" "$mode S_events=$s"
+    --master-port $((29600 + RANDOM % 300)) bench.py --full --gpus $N --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "$P" "$mode S_events=$s"
 done; done; done

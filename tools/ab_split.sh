@@ -8,6 +8,6 @@ for v in "-DMPG_AB_TARGET_SINGLE" ""; do
   echo "== [$v]"
   MPG_EXTRA_CFLAGS="$v" python3 -m mpg_amd.build > /dev/null 2>&1
   timeout 400 python -m pytest tests/test_learner_gpu.py tests/test_dist_gpu.py -x -q -m gpu -k "golden or native_step or bench_size or trained or repeated or replicas" 2>&1 | tail -1
-  for i in 1 2 3; do python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "$P" "${v:-split}"; done
+  for i in 1 2 3; do python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "$P" "${v:-split}"; done
 done
 python3 -m mpg_amd.build > /dev/null 2>&1

@@ -11,8 +11,8 @@ S='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); pri
 run() {  # $1 fused flags, $2 mlp flags, $3 env flags
   MPG_FUSED_CFLAGS="$1" MPG_MLP_CFLAGS="$2" MPG_ENV_CFLAGS="$3" python3 -m mpg_amd.build --split-only > /tmp/build.log 2>&1 || { echo BUILD FAILED; tail -3 /tmp/build.log; return; }
   echo "== fused[$1] mlp[$2] env[$3]"
-  python3 bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-side-configs 2>/dev/null | python3 -c "$P"
-  for c in c4 c3; do python3 bench.py --config $c --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "$S"; done
+  python3 bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-side-configs 2>/dev/null | python3 -c "$P"
+  for c in c4 c3; do python3 bench.py --full --config $c --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "$S"; done
 }
 run "" "" ""
 run "-DMPG_TR_IMAGE" "-DMPG_TR_IMAGE" "-DMPG_TR_IMAGE"

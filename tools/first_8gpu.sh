@@ -23,10 +23,10 @@ echo "== 1. tests/test_dist_gpu.py, one rank per device ==" | tee -a "$OUT/table
 MPG_TEST_RANK_PER_DEVICE=1 timeout 3000 python3 -m pytest tests/test_dist_gpu.py -q -m gpu > "$OUT/dist_tests.log" 2>&1
 tail -3 "$OUT/dist_tests.log" | tee -a "$OUT/table.txt"
 
-echo "== 2. bench.py --gpus N x exchange form x overlap ==" | tee -a "$OUT/table.txt"
+echo "== 2. bench.py --full --gpus N x exchange form x overlap ==" | tee -a "$OUT/table.txt"
 run() {   # name, gpus, then env assignments
     local name=$1 n=$2; shift 2
-    env "$@" timeout 1500 python3 bench.py --gpus "$n" --steps 200 --warmup 20 --no-cpu-baseline --no-side-configs \
+    env "$@" timeout 1500 python3 bench.py --full --gpus "$n" --steps 200 --warmup 20 --no-cpu-baseline --no-side-configs \
         > "$OUT/$name.json" 2> "$OUT/$name.err" || echo "$name: rc $?" | tee -a "$OUT/table.txt"
 }
 run n1 1 MPG_DIST_BACKEND=nccl
@@ -41,7 +41,7 @@ for n in 2 4 8; do
     run "n${n}_oneshot_ov0_Sevents" "$n" MPG_DIST_BACKEND=oneshot MPG_ONESHOT_MODE=oneshot MPG_OVERLAP_EXCHANGE=0 MPG_ONESHOT_S_EVENTS=1
 done
 echo "== 3. config 5's global batch on one GPU ==" | tee -a "$OUT/table.txt"
-timeout 1500 python3 bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-side-configs --rows-per-gpu 32768 \
+timeout 1500 python3 bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-side-configs --rows-per-gpu 32768 \
     > "$OUT/c5_on_1gpu.json" 2> "$OUT/c5_on_1gpu.err"
 
 python3 - "$OUT" <<'PY' | tee -a "$OUT/table.txt"
