@@ -43,12 +43,12 @@ def twoshot_slices(n, world):
 
 class _HostShm(object):
     """A POSIX shared-memory file the ranks of one node use for HOST-to-host hand-shakes of the one-shot exchange:
-      * `calls[r]`   - int64 counter per rank (a cache line each): publish(v) / wait(p, v) order "peer issued its event record"
-        before "I issue my wait" (a wait captures the event's latest record at the time of the call - a fact about the peers'
-        host threads, not about the GPU, so it is settled host to host without draining any stream);
+      * `calls[r][phase]` - int64 counters per rank (a cache line each; phase 0: the exchange's writes, phase 1: the two-shot
+        form's all-gather): publish(phase, v) / wait(p, phase, v) order "peer issued its event record" before "I issue my wait"
+        (a wait captures the event's latest record at the time of the call - a fact about the peers' host threads, not about the
+        GPU, so it is settled host to host without draining any stream);
       * `gen[r]`     - the newest event GENERATION whose handles rank r has published;
-      * `handles[g & 1][r]` - the interprocess-event handles (NEV x 64 bytes) of rank r's generation g;
-      * `calls2[r]`  - the same kind of counter for the second phase of the two-shot form (the all-gather's records)."""
+      * `handles[g & 1][r]` - the interprocess-event handles (NEV x 64 bytes) of rank r's generation g."""
     HB = 64                                        # sizeof(hipIpcEventHandle_t)
     NEV = 6                                        # events per generation: W0 W1 S0 S1 (one-shot) + G0 G1 (two-shot)
 
@@ -76,8 +76,8 @@ class _HostShm(object):
         if rank == 0:
             os.unlink(path)              # the mappings keep it alive; nothing is left behind if a rank dies
 
-    def publish(self, v):
-        self.a[16 * self.rank] = v
+    def publish(self, phase, v):
+        self.a[16 * self.rank + phase] = v
 
     def _spin(self, i, v, what):
         """waits until counter i reaches v: a short pure spin (the common case - the peers' hosts run ahead of their GPUs - is
@@ -94,14 +94,8 @@ class _HostShm(object):
             if time.monotonic() > deadline:
                 raise RuntimeError('one-shot all-reduce: %s %d not reached within %.0f s (a peer died or stalled)' % (what, v, self.TIMEOUT_S))
 
-    def wait(self, p, v):
-        self._spin(16 * p, v, 'rank %d, exchange' % p)
-
-    def publish2(self, v):
-        self.a[16 * self.rank + 1] = v
-
-    def wait2(self, p, v):
-        self._spin(16 * p + 1, v, 'rank %d, all-gather of exchange' % p)
+    def wait(self, p, phase, v):
+        self._spin(16 * p + phase, v, 'rank %d, %s' % (p, ('exchange', 'all-gather of exchange')[phase]))
 
     def publish_handles(self, g, handles):
         import numpy as np
@@ -123,37 +117,31 @@ class OneShotAllReduce(object):
     exchange is
         1. rank r copies its buffer into slot r of EVERY rank's staging array (world device-to-device copies; between GPUs
            these are direct xGMI writes - one hop, all 7 links busy at once, no ring);
-        2. everybody's writes must have landed before anybody sums;
+        2. a FENCE: everybody's writes must have landed before anybody sums;
         3. every rank sums the `world` slots of its own array in rank order 0, 1, 2, ... (mpg_sum_slots): every replica computes
            the SAME association of the same numbers, so the replicas stay bit-identical by construction.
-    Two staging parities alternate by call.
+    Two staging parities alternate by call.  TWO-SHOT form (`mode='twoshot'`, MPG_ONESHOT_MODE=twoshot; the reduce-scatter +
+    all-gather of SURVEY f4): 1. rank r writes slice p of its buffer into slot r of rank p's array (1/world of the bytes per link);
+    2. fence; rank r sums the `world` copies of ITS slice in rank order (the same association: bit-identical results) into every
+    rank's gather array [2 parities][n]; fence; 3. the gather array is the result.
 
-    Step 2, `sync='event'` (default, round 4): INTERPROCESS EVENTS (hipEventInterprocess / hipIpcGetEventHandle /
-    hipIpcOpenEventHandle).  Rank r records W_r[parity] on its stream behind its copies and makes its stream wait
-    (hipStreamWaitEvent) for every peer's W_p[parity]; the sum kernel is enqueued behind those waits.  That a peer does not overwrite r's
-    slots of this parity (two exchanges later) before r has read them follows from the W events alone (round 6; see all_reduce_sum_).  The HOST never waits for the GPU:
-    the only host-side coupling is a per-rank call counter in shared memory (_HostShm) that orders "peer issued its record"
-    before "I issue my wait" - sub-microsecond when the peers' host threads run ahead of their GPUs, which they do (the native
-    step driver enqueues a 0.24 ms step in ~40 us).  So the launch queue of the native driver no longer drains at the exchange.
-    There is still no device-side spin between processes (on the test box several ranks time-share ONE GPU).
-    A HIP interprocess event can be recorded 32 times in its life (ROCm 7.2: the 33rd hipStreamWaitEvent on an opened handle
-    returns hipErrorInvalidValue whatever the owner does in between - archive/proto/ipc_event/probe.py), so the events live in
-    GENERATIONS of GEN_LEN exchanges: the next generation's four events are created and their handles published through the
-    shared-memory file while the current one is in use, and opened by the peers at the generation boundary - host work of a few
-    tens of microseconds every GEN_LEN steps, off the GPU's critical path.
-    `sync='host'` (MPG_ONESHOT_SYNC=host): the round-3 form - stream.synchronize() + dist.barrier() - kept as the control.
+    The fence (_fence) is the one place where the synchronisation forms differ.  `sync='event'` (default): rank r records
+    W_r[parity] (G_r[parity] after the all-gather) on its stream and makes its stream wait (hipStreamWaitEvent) for every peer's
+    INTERPROCESS event.  The host never waits for the GPU: a per-rank counter in shared memory (_HostShm) orders "peer issued its
+    record" before "I issue my wait".  One rank has no peer and fences nothing.  `sync='host'` (MPG_ONESHOT_SYNC=host):
+    stream.synchronize() + dist.barrier() - the control the tests compare against.
 
-    TWO-SHOT form (`mode='twoshot'`, MPG_ONESHOT_MODE=twoshot; round 5 - the reduce-scatter + all-gather SURVEY f4 names): the
-    buffer is cut into `world` slices.  (A) rank r writes slice p of its buffer into slot r of peer p's staging array - 1/world of
-    the bytes per link; (B) behind every peer's writes rank r sums the `world` copies of ITS slice in rank order (the same
-    association as the one-shot sum, computed once instead of `world` times: bit-identical results, identical on every replica by
-    construction) and writes the reduced slice into every rank's gather array [2 parities][n]; behind every peer's slice the
-    gather array is the result.  Two dependent hops and two event hand-shakes instead of one, for 2/world of the one-shot's bytes
-    per link: at 8 ranks and 821 KB, 2 x 103 KB per link against 821 KB.  `mode='auto'` (MPG_ONESHOT_MODE=auto) takes the
-    two-shot form from 4 ranks and 512 KiB on - an untested guess at the cross-over, which is why the default stays 'oneshot'.
+    Slot reuse needs no event of its own: a peer's slots (and gather array) of this parity were last read by its exchange it - 2,
+    and this rank waited for the peer's W of exchange it - 1, which sits BEHIND the whole of exchange it - 2 in the peer's stream.
+    That holds only if all exchanges of one exchanger are enqueued on ONE stream: the first exchange binds it, others are refused.
+    (MPG_ONESHOT_S_EVENTS=1 also records and waits for a "reads done" event S per exchange: the control for a first multi-GPU run.)
 
-    Validated for correctness only - 2, 4 and 8 processes time-sharing one GPU (tests/test_dist_gpu.py); no multi-GPU number is
-    claimed."""
+    A HIP interprocess event can be recorded 32 times in its life (the 33rd hipStreamWaitEvent on an opened handle returns
+    hipErrorInvalidValue whatever the owner does in between - archive/proto/ipc_event/probe.py), so the events live in
+    GENERATIONS of GEN_LEN exchanges: the next generation's events are created and their handles published through the
+    shared-memory file while the current one is in use, and opened by the peers at the generation boundary.
+
+    Validated for correctness only - up to 8 processes time-sharing one GPU; no multi-GPU number is claimed."""
     GEN_LEN = 40          # exchanges per event generation: 20 records per event (+ 1 at creation), under the limit of 32
 
     def __init__(self, n, device, sync=None, mode=None):
@@ -165,11 +153,8 @@ class OneShotAllReduce(object):
         self.sync = sync or os.environ.get('MPG_ONESHOT_SYNC', 'event')
         self.s_events = os.environ.get('MPG_ONESHOT_S_EVENTS') == '1'
         assert self.sync in ('event', 'host')
-        mode = mode or os.environ.get('MPG_ONESHOT_MODE', 'oneshot')
-        assert mode in ('oneshot', 'twoshot', 'auto')
-        if mode == 'auto':
-            mode = 'twoshot' if (self.world >= 4 and 4 * self.n >= (512 << 10)) else 'oneshot'
-        self.mode = mode
+        self.mode = mode or os.environ.get('MPG_ONESHOT_MODE', 'oneshot')
+        assert self.mode in ('oneshot', 'twoshot')
         self.slices = twoshot_slices(self.n, self.world)
         self.dev = torch.device(device) if not isinstance(device, torch.device) else device
         # ONE IPC-mapped allocation per rank: [2 parities][world slots + 1][n] - the staging slots and, behind them, the gather
@@ -201,6 +186,8 @@ class OneShotAllReduce(object):
         self.peers = [b[:, :self.world] for b in self.peer_blocks]
         self.peer_gath = [b[:, self.world] for b in self.peer_blocks]
         self.calls = 0
+        self.slot_call = None            # the exchange (its `calls` value) the slot handed out by grad_slot() belongs to
+        self.stream = None               # the stream of the first exchange: every later one must be issued on it
         if self.sync == 'event':
             global _oneshot_tag
             _oneshot_tag += 1
@@ -224,11 +211,40 @@ class OneShotAllReduce(object):
                           for p in range(self.world) if p != self.rank}
 
     def grad_slot(self):
-        """This rank's slot of its OWN staging array for the NEXT exchange (round 6): a producer that writes its buffer straight into it
-        and then calls all_reduce_sum_(out, in_slot=True) saves the copy into the slot - on one GPU the whole exchange is then ONE
-        launch (the sum), between GPUs world - 1 peer copies + the sum.  Stream-ordered behind this rank's own earlier sums, which are
-        the only readers of that slot."""
+        """This rank's slot of its OWN staging array for the NEXT exchange: a producer that writes its buffer straight into it and
+        then calls all_reduce_sum_(out, in_slot=True) saves the copy into the slot.  Stream-ordered behind this rank's own earlier
+        sums, which are the only readers of that slot.  Until that exchange (or release()) the slot is outstanding: a plain exchange
+        would overwrite it and is refused."""
+        self.slot_call = self.calls
         return self.stage[self.calls & 1, self.rank]
+
+    def release(self):
+        """hands back the slot of grad_slot() when its in-slot exchange will not be made"""
+        self.slot_call = None
+
+    def _check(self, st, in_slot):
+        """refuses a call that would sum the wrong data - before anything is enqueued or `calls` moves"""
+        if in_slot and self.slot_call != self.calls:
+            raise RuntimeError('one-shot all-reduce: in_slot=True but no grad_slot() was taken for this exchange')
+        if not in_slot and self.slot_call is not None:
+            raise RuntimeError('one-shot all-reduce: a plain exchange would overwrite the outstanding slot of grad_slot() (release() it)')
+        if self.stream is not None and st != self.stream:
+            raise RuntimeError('one-shot all-reduce: issued on stream %#x, but this exchanger runs on stream %#x (another stream needs '
+                               'another tag)' % (st.cuda_stream, self.stream.cuda_stream))
+
+    def _fence(self, st, phase, g, par):
+        """everybody's writes of this phase (0: into the staging slots, 1: into the gather arrays) have landed before what this
+        rank enqueues next"""
+        if self.sync == 'host':
+            st.synchronize()                            # my writes have landed ...
+            dist.barrier()                              # ... and so have everybody else's
+        elif self.world > 1:
+            k = 4 * phase + par                         # W[par] / G[par]
+            self.mine[g][k].record(st)
+            self.shm.publish(phase, self.calls)         # host: "my record of exchange `calls` has been issued"
+            for p, ev in self.theirs[g].items():        # behind every peer's writes - a stream wait, not a host wait
+                self.shm.wait(p, phase, self.calls)
+                st.wait_event(ev[k])
 
     def _finish(self, src, n_slots, flat, seg_sizes, sq_part):
         """the final rank-order sum (or, n_slots = 1, the copy out of the gather array); with sq_part also the clip's partial sums of
@@ -248,14 +264,29 @@ class OneShotAllReduce(object):
         """flat <- sum over ranks.  in_slot: this rank's contribution already sits in grad_slot() (taken BEFORE this call) and `flat` is
         only the destination; seg_sizes + sq_part: see _finish."""
         assert flat.numel() == self.n and flat.dtype == torch.float32 and flat.is_contiguous()
+        st = torch.cuda.current_stream()
+        self._check(st, in_slot)
+        self.stream, self.slot_call = st, None
         par = self.calls & 1
         self.calls += 1
         L = self.L
-        st = torch.cuda.current_stream()
         two = self.mode == 'twoshot'
         me = self.rank
         lo, hi = self.slices[me]
         src = self.stage[par, me] if in_slot else flat
+        it = self.calls
+        g = (it - 1) // self.GEN_LEN
+        events = self.sync == 'event' and self.world > 1
+        if events:
+            if (it - 1) % self.GEN_LEN == 0 and g > 0:  # generation boundary: open the peers' events of g, prepare g + 1, drop g - 2
+                self._open_generation(g)
+                self._make_generation(g + 1)
+                self.mine.pop(g - 2, None)
+                self.theirs.pop(g - 2, None)
+            if self.s_events and it > 2:                # 0. behind the peers' reads of this parity (exchange it - 2)
+                g2 = (it - 3) // self.GEN_LEN
+                for p, ev in self.theirs[g2].items():
+                    st.wait_event(ev[2 + par])
 
         def scatter():                                  # two-shot (A): slice p of my buffer into slot `rank` of rank p's array
             for p in range(self.world):
@@ -275,67 +306,19 @@ class OneShotAllReduce(object):
                 for p in range(self.world):
                     if p != me:
                         self.peer_gath[p][par, lo:hi].copy_(self.gath[par, lo:hi], non_blocking=True)
-        if self.sync == 'host':
-            if two:
-                scatter()
-                st.synchronize()
-                dist.barrier()
-                reduce_and_gather()
-                st.synchronize()
-                dist.barrier()
-                self._finish(self.gath[par], 1, flat, seg_sizes, sq_part)
-                return flat
-            spread()                                    # 1.
-            st.synchronize()                            # 2. my writes have landed ...
-            dist.barrier()                              #    ... and so have everybody else's
-            self._finish(self.stage[par], self.world, flat, seg_sizes, sq_part)
-            return flat
-        if self.world == 1:        # no peer: nothing to order (an interprocess event record costs ~16 us of host time and ~20 us on the
-            if two:                # stream, tools/ipc_event_cost.py - the one-rank form measures the exchange path WITHOUT its hand-shakes)
-                scatter()
-                reduce_and_gather()
-                self._finish(self.gath[par], 1, flat, seg_sizes, sq_part)
-            else:
-                spread()
-                self._finish(self.stage[par], 1, flat, seg_sizes, sq_part)
-            return flat
-        it = self.calls
-        g = (it - 1) // self.GEN_LEN
-        if (it - 1) % self.GEN_LEN == 0 and g > 0:      # generation boundary: open the peers' events of g, prepare g + 1, drop g - 2
-            self._open_generation(g)
-            self._make_generation(g + 1)
-            self.mine.pop(g - 2, None)
-            self.theirs.pop(g - 2, None)
-        # 0. A peer's slots (and gather array) of this parity were last read by its exchange it - 2.  No event of their own is needed for
-        #    that (round 6): this rank waited for the peer's W of exchange it - 1 during exchange it - 1, and that record sits BEHIND the
-        #    whole of the peer's exchange it - 2 in the peer's stream - so everything this rank enqueues from here on already follows the
-        #    peer's reads.  (Rounds 4 - 5 recorded and waited for a separate "reads done" event S per exchange; an interprocess event
-        #    record costs ~16 us of host time and a system-scope release on the stream, tools/ipc_event_cost.py.  MPG_ONESHOT_S_EVENTS=1
-        #    keeps them, as the control for a first multi-GPU run.)
-        if self.s_events and it > 2:
-            g2 = (it - 3) // self.GEN_LEN
-            for p, ev in self.theirs[g2].items():
-                st.wait_event(ev[2 + par])
         if two:
             scatter()
         else:
             spread()                                    # 1.
-        self.mine[g][par].record(st)                    # W[par]
-        self.shm.publish(it)                            # host: "my record of exchange `it` has been issued"
-        for p, ev in self.theirs[g].items():            # 2. behind every peer's writes - a stream wait, not a host wait
-            self.shm.wait(p, it)
-            st.wait_event(ev[par])
+        self._fence(st, 0, g, par)                      # 2.
         if two:
-            reduce_and_gather()                         # 3. my slice, reduced, into every rank's gather array
-            self.mine[g][4 + par].record(st)            # G[par]
-            self.shm.publish2(it)
-            for p, ev in self.theirs[g].items():        # 4. behind every peer's slice
-                self.shm.wait2(p, it)
-                st.wait_event(ev[4 + par])
-            self._finish(self.gath[par], 1, flat, seg_sizes, sq_part)
+            reduce_and_gather()                         # my slice, reduced, into every rank's gather array
+            self._fence(st, 1, g, par)                  # behind every peer's slice
+            result, n_slots = self.gath[par], 1
         else:
-            self._finish(self.stage[par], self.world, flat, seg_sizes, sq_part)     # 3.
-        if self.s_events:
+            result, n_slots = self.stage[par], self.world
+        self._finish(result, n_slots, flat, seg_sizes, sq_part)     # 3.
+        if events and self.s_events:
             self.mine[g][2 + par].record(st)            # S[par]: my reads of this parity's slots (and gather array) are done
         return flat
 
@@ -367,6 +350,13 @@ def grad_slot(n, device, force=False, tag=0):
     if dist.is_initialized() and (dist.get_world_size() > 1 or force) and _exchange == 'oneshot':
         return _exchanger(n, device, tag).grad_slot()
     return None
+
+
+def release_slot(n, tag=0):
+    """Hands back the slot of grad_slot(n, ...) when its in-slot exchange will not be made (a no-op when none is outstanding)."""
+    ex = _oneshot.get((n, tag))
+    if ex is not None:
+        ex.release()
 
 
 def all_reduce_sum_(flat, force=False, tag=0, in_slot=False, seg_sizes=None, sq_part=None):

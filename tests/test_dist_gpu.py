@@ -224,9 +224,15 @@ def _oneshot_sum_worker(rank, world, port, q):
     flat = mine.cuda()
     outs = []
     n_ex = int(os.environ.get('MPG_TEST_EXCHANGES', '6'))
+    in_slot = os.environ.get('MPG_TEST_IN_SLOT') == '1'
     for k in range(n_ex):                                 # both staging parities, each re-used (6: twice; 90: across two event generations)
         buf = flat * float(k % 7 + 1)
-        D.all_reduce_sum_(buf)
+        if in_slot:                                       # the contribution written straight into the staging slot; buf: only the destination
+            D.grad_slot(n, flat.device).copy_(buf)
+            buf.fill_(float('nan'))
+            D.all_reduce_sum_(buf, in_slot=True)
+        else:
+            D.all_reduce_sum_(buf)
         if k < 6 or k >= n_ex - 2:
             outs.append((k, buf.cpu().numpy()))
     torch.cuda.synchronize()
@@ -238,16 +244,22 @@ def _oneshot_sum_worker(rank, world, port, q):
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize('world,sync,mode,n_ex', [(2, 'event', 'oneshot', 6), (2, 'host', 'oneshot', 6), (8, 'event', 'oneshot', 6),
                                                   (2, 'event', 'twoshot', 90), (2, 'host', 'twoshot', 6), (8, 'event', 'twoshot', 6),
-                                                  (3, 'event', 'twoshot', 6)])
+                                                  (3, 'event', 'twoshot', 6), (2, 'event-slot', 'oneshot', 6),
+                                                  (3, 'event-slot', 'twoshot', 6), (2, 'event-S', 'oneshot', 6), (2, 'event-S', 'twoshot', 6)])
 def test_oneshot_all_reduce_is_the_in_rank_order_sum_bit_for_bit(monkeypatch, world, sync, mode, n_ex):
     """OneShotAllReduce on its own: exchanges of a 205 334-float buffer with entries over eight orders of magnitude (both
     staging parities re-used: the slot-reuse waits of the event form are exercised; 90 exchanges cross two event generations).
     Every rank must hold exactly fl(..fl(x_0 + x_1) + .. + x_{world-1}) - the rank-order float32 sum - each time; 2 ranks in
     both synchronisation forms and 8 ranks (all time-sharing the one GPU of the test box) in the event form.
     Round 5: the same for the TWO-SHOT form (reduce-scatter + all-gather) with 2, 3 (slices of unequal length) and 8
-    ranks (4 ranks: the native-driver test above) - its slice sums take the same rank order, so the result must be the same bits."""
+    ranks (4 ranks: the native-driver test above) - its slice sums take the same rank order, so the result must be the same bits.
+    `-slot`: every rank writes its buffer into D.grad_slot() and exchanges with in_slot=True (3 ranks, two-shot: unequal slices, the
+    own slice not copied); `-S`: the separate "reads done" events (MPG_ONESHOT_S_EVENTS=1)."""
+    sync, _, variant = sync.partition('-')
     monkeypatch.setenv('MPG_DIST_BACKEND', 'oneshot')
     monkeypatch.setenv('MPG_ONESHOT_SYNC', sync)
+    monkeypatch.setenv('MPG_TEST_IN_SLOT', '1' if variant == 'slot' else '0')
+    monkeypatch.setenv('MPG_ONESHOT_S_EVENTS', '1' if variant == 'S' else '0')
     monkeypatch.setenv('MPG_ONESHOT_MODE', mode)
     monkeypatch.setenv('MPG_TEST_EXCHANGES', str(n_ex))
     out = _run(_oneshot_sum_worker, world=world)
@@ -260,6 +272,111 @@ def test_oneshot_all_reduce_is_the_in_rank_order_sum_bit_for_bit(monkeypatch, wo
         for r in range(world):
             got = dict(out[r][2])[k]
             assert np.array_equal(got, ref), (k, r)
+
+
+def _misuse_worker(rank, world, port, q):
+    D = _init(rank, world, port)
+    n = 4096 + 16
+    dev = torch.device('cuda', torch.cuda.current_device())
+    g = torch.Generator(device='cpu').manual_seed(7)
+    x, y = torch.randn(n, generator=g).cuda(), torch.randn(n, generator=g).cuda()
+    r = {}
+
+    def refusal(fn):
+        try:
+            fn()
+        except RuntimeError as e:
+            return str(e)
+        return None
+
+    def plain(v):                                         # a correct plain exchange: with one rank the sum is v itself
+        buf = v.clone()
+        D.all_reduce_sum_(buf, force=True)
+        return torch.equal(buf, v)
+    out = torch.full((n,), float('nan'), device=dev)
+    # 1. an in-slot exchange with no slot taken for it
+    r['no_slot'] = refusal(lambda: D.all_reduce_sum_(out, force=True, in_slot=True))
+    r['no_slot_then'] = plain(y)
+    # 2. a plain exchange while a slot is outstanding (it would overwrite the slot)
+    slot = D.grad_slot(n, dev, force=True)
+    slot.copy_(x)
+    r['same_slot'] = D.grad_slot(n, dev, force=True).data_ptr() == slot.data_ptr()
+    buf = y.clone()
+    r['outstanding'] = refusal(lambda: D.all_reduce_sum_(buf, force=True))
+    D.all_reduce_sum_(out, force=True, in_slot=True)
+    r['outstanding_then'] = torch.equal(out, x)
+    # 3. an exchange from another stream than the exchanger's first
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        r['stream'] = refusal(lambda: D.all_reduce_sum_(buf, force=True))
+    r['streams'] = ('%#x' % side.cuda_stream, '%#x' % torch.cuda.current_stream().cuda_stream)
+    r['stream_then'] = plain(y)
+    # a slot handed back: plain exchanges go on
+    D.grad_slot(n, dev, force=True)
+    D.release_slot(n)
+    r['released_then'] = plain(x)
+    torch.cuda.synchronize()
+    q.put((rank, r))
+    torch.distributed.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_oneshot_exchange_refuses_a_stale_slot_or_another_stream(monkeypatch):
+    """The staging slot of grad_slot() belongs to the next exchange, and the reuse of the slots is ordered by ONE stream: an in-slot
+    exchange without a slot, a plain exchange while a slot is outstanding (it would overwrite the slot) and an exchange from another
+    stream are refused before anything is enqueued, and a correct exchange after each still returns the right sum (one rank)."""
+    monkeypatch.setenv('MPG_DIST_BACKEND', 'oneshot')
+    monkeypatch.setenv('MPG_ONESHOT_SYNC', 'event')
+    r = _run(_misuse_worker, world=1)[0][1]
+    assert r['no_slot'] is not None and r['no_slot_then']
+    assert r['same_slot'] and r['outstanding'] is not None and r['outstanding_then']
+    assert r['stream'] is not None and all(s in r['stream'] for s in r['streams']), (r['stream'], r['streams'])
+    assert r['stream_then'] and r['released_then']
+
+
+def _step_error_worker(rank, world, port, q):
+    D = _init(rank, world, port)
+    from mpg_amd.buffer import ReplayBuffer
+    from mpg_amd.config import default_args
+    from mpg_amd.learners import MPGLearner
+    from mpg_amd.optimizer import SingleProcessOffPolicyOptimizer
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    args = default_args('MPG-v2', num_agent=64, batch_size=64, replay_batch_size=64, replay_starts=128, max_buffer_size=4096,
+                        seed=0, init_seed=0)
+    worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+    opt = SingleProcessOffPolicyOptimizer(worker, MPGLearner(PolicyWithQs, args), ReplayBuffer(args, 0), None, args,
+                                          sampling_interval=1, always_exchange=True)
+    learner, c = opt.learner, opt._fused.c
+    for _ in range(3):
+        opt.step()
+    real = D.all_reduce_sum_
+
+    def fail_once(*a, **k):
+        D.all_reduce_sum_ = real
+        raise RuntimeError('injected exchange failure')
+    D.all_reduce_sum_ = fail_once
+    try:
+        opt.step()
+        raised = False
+    except RuntimeError:
+        raised = True
+    state = (raised, c.grad == learner.flat.data_ptr(), c.clip_partials_ready)
+    D.all_reduce_sum_(learner.flat, force=True)           # refused if the failed step had left its slot outstanding
+    opt.step()
+    torch.cuda.synchronize()
+    q.put((rank, state, bool(torch.isfinite(worker.policy_with_value.params).all().item())))
+    torch.distributed.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_failed_exchange_leaves_the_step_context_on_the_flat_gradient(monkeypatch):
+    """The native step with the one-shot slot exchange: if the exchange raises, the context points back at the flat gradient with no
+    claim of ready clip partials, the slot is handed back (a plain exchange goes through), and the next step succeeds (one rank)."""
+    monkeypatch.setenv('MPG_DIST_BACKEND', 'oneshot')
+    monkeypatch.setenv('MPG_ONESHOT_SYNC', 'event')
+    _, (raised, grad_is_flat, partials_ready), finite = _run(_step_error_worker, world=1)[0]
+    assert raised and grad_is_flat and partials_ready == 0 and finite
 
 
 def _rccl_worker(rank, world, port, q):
