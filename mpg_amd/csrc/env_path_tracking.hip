@@ -755,7 +755,7 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
     MPG_REQUIRE(policy_params && n > 0 && state && obs_io && act_out && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs &&
                     ring_act && ring_rew && ring_obs2 && ring_done,
                 "mpg_worker_step: bad argument");
-    // (the same refusal as mpg_policy_action's cfg_ok: tanh output WITH an action range is not what the reference computes)
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_step: tanh policy with an action range");
     PreDraw pd{};
     if (draw) {

@@ -1,24 +1,10 @@
 // C-ABI entry points built from the generic network kernels: policy actions, critic targets, critic loss +
 // gradient.  (The fused n-step rollout lives in rollout_kernels.hip, the optimizer in optim_kernels.hip.)
-#include "mlp_launch.h"
+#include "host_glue.h"
 
 using namespace mlp;
 
 namespace {
-
-inline char* align256(char* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~uintptr_t(255)); }
-
-struct Carver {   // carves 256-byte aligned float arrays out of the caller's workspace
-    char *p, *end;
-    Carver(void* ws, size_t bytes) : p(align256((char*)ws)), end((char*)ws + bytes) {}
-    float* take(size_t nfloat) {
-        float* r = reinterpret_cast<float*>(p);
-        p = align256(p + nfloat * sizeof(float));
-        return r;
-    }
-    bool ok() const { return p <= end; }
-};
-inline size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float) + 255) & ~size_t(255)) + 256; }
 
 // y = (rew + shift) * scale + gamma * min(q1, q2)      (q2 == nullptr: q1 only)
 __global__ void k_combine_target(int n, const float* __restrict__ rew, const float* __restrict__ q1,
@@ -204,25 +190,48 @@ __global__ void k_sum_action_grad(int rows, int od, int ad, const float* __restr
     ga[i] = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
 }
 
-inline OutSpec policy_out(const mpg_cfg_t* c) {
-    OutSpec o;
-    const bool ranged = c->action_range > 0.f;
-    o.out_tanh = (c->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    o.out_scale = ranged ? c->action_range : 1.f;
-    o.sigma = 0.f; o.seed = 0; o.ctr = 0;
-    return o;
-}
-inline OutSpec linear_out() {
-    OutSpec o;
-    o.out_tanh = 0; o.out_scale = 1.f; o.sigma = 0.f; o.seed = 0; o.ctr = 0;
-    return o;
+// ---- workspaces: one description each (host_glue.h Arena) ----------------------------------------------------------
+struct QTargetsWs {        // mpg_q_targets, mpg_td3_targets, mpg_nstep_targets (which leaves q2 unused)
+    float *a, *q1, *q2;
+};
+QTargetsWs q_targets_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    QTargetsWs w;
+    w.a = ar.take((size_t)rows * cfg->act_dim);
+    w.q1 = ar.take(rows);
+    w.q2 = ar.take(rows);
+    return w;
 }
 
-inline bool cfg_ok(const mpg_cfg_t* c) {
-    // policy_out_activation='tanh' WITH an action_range would be range*tanh(tanh(z)) in the reference (policy.py:176-177,
-    // 197-199); the kernels implement range*tanh(z) / tanh(z) / z only, so that combination is refused, not approximated
-    return c && ((c->obs_dim >= 6 && c->obs_dim <= 16 && c->act_dim == 2) || (c->obs_dim == 4 && c->act_dim == 1)) &&
-           !(c->policy_out_act == MPG_ACT_TANH && c->action_range > 0.f);
+struct QLossWs {
+    float *h1, *h2, *dz1, *dz2, *q, *dz3, *slabs, *parts;
+};
+QLossWs q_loss_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    QLossWs w;
+    w.h1 = ar.take(stash_floats(rows)); w.h2 = ar.take(stash_floats(rows));
+    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
+    w.q = ar.take(rows); w.dz3 = ar.take(rows);
+    w.slabs = ar.take(wgrad_workspace_floats(rows, cfg->obs_dim + cfg->act_dim, 1));
+    w.parts = ar.take(2 * ERR_PARTS);
+    return w;
+}
+
+struct Td3PolicyWs {
+    float *hp1, *hp2, *h11, *h12, *h21, *h22, *dz1, *dz2, *a, *dz3, *qv1, *qv2, *dy1, *dy2, *dx1, *dx2, *ga, *slabs, *parts;
+};
+Td3PolicyWs td3_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    Td3PolicyWs w;
+    w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
+    w.h11 = ar.take(stash_floats(rows)); w.h12 = ar.take(stash_floats(rows));
+    w.h21 = ar.take(stash_floats(rows)); w.h22 = ar.take(stash_floats(rows));
+    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
+    w.a = ar.take((size_t)rows * ad); w.dz3 = ar.take((size_t)rows * ad);
+    w.qv1 = ar.take(rows); w.qv2 = ar.take(rows); w.dy1 = ar.take(rows); w.dy2 = ar.take(rows);
+    w.dx1 = ar.take((size_t)rows * qin); w.dx2 = ar.take((size_t)rows * qin);
+    w.ga = ar.take((size_t)rows * ad);
+    w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
+    w.parts = ar.take(2 * ERR_PARTS);
+    return w;
 }
 
 }  // namespace
@@ -242,49 +251,40 @@ extern "C" int mpg_mlp_forward(const float* params, int in_dim, int out_dim, int
 
 extern "C" int mpg_policy_action(const mpg_cfg_t* cfg, const float* policy_params, int rows, const float* obs,
                                  float explore_sigma, uint64_t seed, uint64_t ctr, float* act, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && policy_params && obs && act && rows > 0, "mpg_policy_action: bad argument");
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && obs && act && rows > 0, "mpg_policy_action: bad argument");
     OutSpec o = policy_out(cfg);
     o.sigma = explore_sigma; o.seed = seed; o.ctr = ctr;
-    return launch_forward(cfg, policy_params, cfg->obs_dim, 2 * cfg->act_dim, cfg->act_dim, rows,
-                          xspec(obs, cfg->obs_dim, nullptr, 0, cfg->obs_scale, cfg->obs_dim), o, act, cfg->act_dim,
-                          nullptr, nullptr, mpg_stream(stream));
+    return policy_forward(cfg, policy_params, rows, policy_x(cfg, obs), o, act, nullptr, nullptr, mpg_stream(stream));
 }
 
 extern "C" size_t mpg_q_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (!cfg_ok(cfg) || rows <= 0) return 0;
-    return pad256((size_t)rows * cfg->act_dim) + 2 * pad256(rows);
+    if (!net_cfg_ok(cfg) || rows <= 0) return 0;
+    return measured(q_targets_ws, cfg, rows);
 }
 
 extern "C" int mpg_q_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, const float* q2t, int rows,
                              const float* rew, const float* obs_tp1, const float* smooth_eps, float smooth_sigma,
                              float smooth_clip, float* y, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && policy_t && q1t && rew && obs_tp1 && y && ws && rows > 0, "mpg_q_targets: bad argument");
-    if (ws_bytes < mpg_q_targets_workspace_bytes(cfg, rows)) {
-        mpg_set_error("mpg_q_targets: workspace too small");
-        return MPG_EWORKSPACE;
-    }
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_t && q1t && rew && obs_tp1 && y && ws && rows > 0, "mpg_q_targets: bad argument");
+    Arena ar(ws, ws_bytes);
+    const QTargetsWs w = q_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_q_targets", ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
-    Carver cv(ws, ws_bytes);
-    float* a = cv.take((size_t)rows * cfg->act_dim);
-    float* q1 = cv.take(rows);
-    float* q2 = cv.take(rows);
-    const int od = cfg->obs_dim, ad = cfg->act_dim;
-    int rc = launch_forward(cfg, policy_t, od, 2 * ad, ad, rows, xspec(obs_tp1, od, nullptr, 0, cfg->obs_scale, od),
-                            policy_out(cfg), a, ad, nullptr, nullptr, s);
+    int rc = policy_forward(cfg, policy_t, rows, policy_x(cfg, obs_tp1), policy_out(cfg), w.a, nullptr, nullptr, s);
     if (rc) return rc;
     if (smooth_eps) {
-        const int n = rows * ad;
-        hipLaunchKernelGGL(k_smooth, dim3((n + 255) / 256), dim3(256), 0, s, n, a, smooth_eps, smooth_sigma, smooth_clip);
+        const int n = rows * cfg->act_dim;
+        hipLaunchKernelGGL(k_smooth, dim3((n + 255) / 256), dim3(256), 0, s, n, w.a, smooth_eps, smooth_sigma, smooth_clip);
         MPG_CHECK_LAUNCH("k_smooth");
     }
-    const XSpec xq = xspec(obs_tp1, od, a, ad, cfg->obs_scale, od);
-    rc = launch_forward(cfg, q1t, od + ad, 1, 1, rows, xq, linear_out(), q1, 1, nullptr, nullptr, s);
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);
     if (rc) return rc;
     if (q2t) {
-        rc = launch_forward(cfg, q2t, od + ad, 1, 1, rows, xq, linear_out(), q2, 1, nullptr, nullptr, s);
+        rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, q1, q2t ? q2 : nullptr,
+    hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, q2t ? w.q2 : nullptr,
                        cfg->rew_shift, cfg->rew_scale, cfg->gamma, y);
     MPG_CHECK_LAUNCH("k_combine_target");
     return MPG_OK;
@@ -296,38 +296,31 @@ extern "C" int mpg_q_targets(const mpg_cfg_t* cfg, const float* policy_t, const 
 extern "C" int mpg_td3_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, const float* q2t, int rows,
                                const float* rew, const float* obs_tp1, const float* smooth_eps, float smooth_sigma,
                                float smooth_clip, float* y, float* y1, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && policy_t && q1t && q2t && rew && obs_tp1 && y && y1 && ws && rows > 0, "mpg_td3_targets: bad argument");
-    if (ws_bytes < mpg_q_targets_workspace_bytes(cfg, rows)) {
-        mpg_set_error("mpg_td3_targets: workspace too small");
-        return MPG_EWORKSPACE;
-    }
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_t && q1t && q2t && rew && obs_tp1 && y && y1 && ws && rows > 0, "mpg_td3_targets: bad argument");
+    Arena ar(ws, ws_bytes);
+    const QTargetsWs w = q_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_td3_targets", ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
-    Carver cv(ws, ws_bytes);
-    float* a = cv.take((size_t)rows * cfg->act_dim);
-    float* q1 = cv.take(rows);
-    float* q2 = cv.take(rows);
-    const int od = cfg->obs_dim, ad = cfg->act_dim;
-    int rc = launch_forward(cfg, policy_t, od, 2 * ad, ad, rows, xspec(obs_tp1, od, nullptr, 0, cfg->obs_scale, od),
-                            policy_out(cfg), a, ad, nullptr, nullptr, s);
+    int rc = policy_forward(cfg, policy_t, rows, policy_x(cfg, obs_tp1), policy_out(cfg), w.a, nullptr, nullptr, s);
     if (rc) return rc;
-    const XSpec xq = xspec(obs_tp1, od, a, ad, cfg->obs_scale, od);
-    rc = launch_forward(cfg, q1t, od + ad, 1, 1, rows, xq, linear_out(), q1, 1, nullptr, nullptr, s);      // Q1t(s~', pi_t(s~')): y1
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);      // Q1t(s~', pi_t(s~')): y1
     if (rc) return rc;
     if (smooth_eps) {
-        const int n = rows * ad;
-        hipLaunchKernelGGL(k_combine_and_smooth, dim3((n + 255) / 256), dim3(256), 0, s, rows, ad, rew, q1, cfg->rew_shift, cfg->rew_scale,
-                           cfg->gamma, y1, a, smooth_eps, smooth_sigma, smooth_clip);
+        const int n = rows * cfg->act_dim;
+        hipLaunchKernelGGL(k_combine_and_smooth, dim3((n + 255) / 256), dim3(256), 0, s, rows, cfg->act_dim, rew, w.q1, cfg->rew_shift,
+                           cfg->rew_scale, cfg->gamma, y1, w.a, smooth_eps, smooth_sigma, smooth_clip);
         MPG_CHECK_LAUNCH("k_combine_and_smooth");
-        rc = launch_forward(cfg, q1t, od + ad, 1, 1, rows, xq, linear_out(), q1, 1, nullptr, nullptr, s);
+        rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);
         if (rc) return rc;
     } else {
-        hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, q1, (const float*)nullptr, cfg->rew_shift,
+        hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, (const float*)nullptr, cfg->rew_shift,
                            cfg->rew_scale, cfg->gamma, y1);
         MPG_CHECK_LAUNCH("k_combine_target");
     }
-    rc = launch_forward(cfg, q2t, od + ad, 1, 1, rows, xq, linear_out(), q2, 1, nullptr, nullptr, s);
+    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, q1, q2, cfg->rew_shift, cfg->rew_scale,
+    hipLaunchKernelGGL(k_combine_target, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, cfg->rew_shift, cfg->rew_scale,
                        cfg->gamma, y);
     MPG_CHECK_LAUNCH("k_combine_target");
     return MPG_OK;
@@ -351,135 +344,102 @@ extern "C" int mpg_td3_priority_errors(int rows, const float* y1, const float* y
 extern "C" int mpg_nstep_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n,
                                  const float* rewards, const float* last_obs, float* y, void* ws, size_t ws_bytes,
                                  mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && policy_t && q1t && rewards && last_obs && y && ws && rows > 0 && n > 0,
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_t && q1t && rewards && last_obs && y && ws && rows > 0 && n > 0,
                 "mpg_nstep_targets: bad argument");
-    if (ws_bytes < mpg_q_targets_workspace_bytes(cfg, rows)) {
-        mpg_set_error("mpg_nstep_targets: workspace too small");
-        return MPG_EWORKSPACE;
-    }
+    Arena ar(ws, ws_bytes);
+    const QTargetsWs w = q_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_nstep_targets", ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
-    Carver cv(ws, ws_bytes);
-    float* a = cv.take((size_t)rows * cfg->act_dim);
-    float* q1 = cv.take(rows);
-    const int od = cfg->obs_dim, ad = cfg->act_dim;
-    int rc = launch_forward(cfg, policy_t, od, 2 * ad, ad, rows, xspec(last_obs, od, nullptr, 0, cfg->obs_scale, od),
-                            policy_out(cfg), a, ad, nullptr, nullptr, s);
+    int rc = policy_forward(cfg, policy_t, rows, policy_x(cfg, last_obs), policy_out(cfg), w.a, nullptr, nullptr, s);
     if (rc) return rc;
-    rc = launch_forward(cfg, q1t, od + ad, 1, 1, rows, xspec(last_obs, od, a, ad, cfg->obs_scale, od), linear_out(), q1, 1,
-                        nullptr, nullptr, s);
+    rc = critic_forward(cfg, q1t, rows, critic_x(cfg, last_obs, w.a), w.q1, nullptr, nullptr, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_nstep, dim3((rows + 255) / 256), dim3(256), 0, s, rows, n, rewards, q1, cfg->rew_shift,
+    hipLaunchKernelGGL(k_nstep, dim3((rows + 255) / 256), dim3(256), 0, s, rows, n, rewards, w.q1, cfg->rew_shift,
                        cfg->rew_scale, cfg->gamma, y);
     MPG_CHECK_LAUNCH("k_nstep");
     return MPG_OK;
 }
 
 extern "C" size_t mpg_q_loss_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (!cfg_ok(cfg) || rows <= 0) return 0;
-    const int in = cfg->obs_dim + cfg->act_dim;
-    return 4 * pad256(stash_floats(rows)) + 2 * pad256(rows) + pad256(wgrad_workspace_floats(rows, in, 1)) + pad256(2 * ERR_PARTS);
+    if (!net_cfg_ok(cfg) || rows <= 0) return 0;
+    return measured(q_loss_ws, cfg, rows);
 }
 
 extern "C" int mpg_q_loss_grad(const mpg_cfg_t* cfg, const float* q_params, int rows, const float* obs, const float* act,
                                const float* y, float inv_b_global, float* loss_sum, float* grad, float* td, void* ws,
                                size_t ws_bytes, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && q_params && obs && act && y && loss_sum && grad && ws && rows > 0,
+    MPG_REQUIRE(net_cfg_ok(cfg) && q_params && obs && act && y && loss_sum && grad && ws && rows > 0,
                 "mpg_q_loss_grad: bad argument");
-    if (ws_bytes < mpg_q_loss_grad_workspace_bytes(cfg, rows)) {
-        mpg_set_error("mpg_q_loss_grad: workspace too small (%zu < %zu)", ws_bytes, mpg_q_loss_grad_workspace_bytes(cfg, rows));
-        return MPG_EWORKSPACE;
-    }
+    Arena ar(ws, ws_bytes);
+    const QLossWs w = q_loss_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_q_loss_grad", ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
-    const int od = cfg->obs_dim, ad = cfg->act_dim, in = od + ad;
-    Carver cv(ws, ws_bytes);
-    float* h1 = cv.take(stash_floats(rows));
-    float* h2 = cv.take(stash_floats(rows));
-    float* dz1 = cv.take(stash_floats(rows));
-    float* dz2 = cv.take(stash_floats(rows));
-    float* q = cv.take(rows);
-    float* dz3 = cv.take(rows);
-    float* slabs = cv.take(wgrad_workspace_floats(rows, in, 1));
-    float* parts = cv.take(2 * ERR_PARTS);
-    const XSpec xq = xspec(obs, od, act, ad, cfg->obs_scale, od);
-    int rc = launch_forward(cfg, q_params, in, 1, 1, rows, xq, linear_out(), q, 1, h1, h2, s);
+    const int in = cfg->obs_dim + cfg->act_dim;
+    const XSpec xq = critic_x(cfg, obs, act);
+    int rc = critic_forward(cfg, q_params, rows, xq, w.q, w.h1, w.h2, s);
     if (rc) return rc;
     // the thin parameter gradients ride in the backward launch (mlp_launch.h): its per-workgroup partials live where the dz1 stash
     // would (never larger), the weight-gradient launch reads h1 and dz2 only
     const bool thin = backward_takes_thin(in, 1);
     // large batches: the loss partials of the 64-block error kernel are added up by one extra block of the gradient's summation launch
     // (round 5; k_finish_parts' arithmetic) when that launch exists (thin), by k_finish_parts otherwise
-    FinishJob fin{parts, ERR_PARTS, ERR_PARTS, 0.5f * inv_b_global, 0.f, loss_sum, nullptr};
+    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 0.5f * inv_b_global, 0.f, loss_sum, nullptr};
     const bool mb = rows >= ERR_MB_MIN_ROWS;
     if (mb) {
-        hipLaunchKernelGGL(k_q_err_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, q, y, inv_b_global, dz3, td, parts);
-        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, parts, 0.5f * inv_b_global, 0.f, loss_sum, (float*)nullptr);
+        hipLaunchKernelGGL(k_q_err_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.q, y, inv_b_global, w.dz3, td, w.parts);
+        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 0.5f * inv_b_global, 0.f, loss_sum, (float*)nullptr);
     } else
-    hipLaunchKernelGGL(k_q_err, dim3(1), dim3(1024), 0, s, rows, q, y, inv_b_global, dz3, td, loss_sum);
+    hipLaunchKernelGGL(k_q_err, dim3(1), dim3(1024), 0, s, rows, w.q, y, inv_b_global, w.dz3, td, loss_sum);
     MPG_CHECK_LAUNCH("k_q_err");
-    rc = launch_backward(cfg, q_params, in, 1, 1, rows, dz3, 1, nullptr, 0, 0, 1.f, h1, h2, thin ? nullptr : dz1, dz2, nullptr, nullptr, 0, s,
-                         thin ? &xq : nullptr, thin ? dz1 : nullptr);
+    rc = launch_backward(cfg, q_params, in, 1, 1, rows, w.dz3, 1, nullptr, 0, 0, 1.f, w.h1, w.h2, thin ? nullptr : w.dz1, w.dz2, nullptr, nullptr, 0, s,
+                         thin ? &xq : nullptr, thin ? w.dz1 : nullptr);
     if (rc) return rc;
-    return launch_wgrad(cfg, in, 1, 1, rows, xq, h1, h2, dz1, dz2, dz3, inv_b_global, grad, slabs, s, thin, thin ? dz1 : nullptr,
+    return launch_wgrad(cfg, in, 1, 1, rows, xq, w.h1, w.h2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin, thin ? w.dz1 : nullptr,
                         thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
 }
 
 extern "C" size_t mpg_td3_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (!cfg_ok(cfg) || rows <= 0) return 0;
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    return 8 * pad256(stash_floats(rows)) + 2 * pad256((size_t)rows * ad) + 4 * pad256(rows) +
-           2 * pad256((size_t)rows * qin) + pad256((size_t)rows * ad) + pad256(wgrad_workspace_floats(rows, od, 2 * ad)) +
-           pad256(2 * ERR_PARTS);
+    if (!net_cfg_ok(cfg) || rows <= 0) return 0;
+    return measured(td3_policy_ws, cfg, rows);
 }
 
 extern "C" int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, const float* q2,
                                    int rows, const float* obs, float inv_b_global, float* qmin_sum, float* qmin_sqsum,
                                    float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg_ok(cfg) && policy_params && q1 && q2 && obs && qmin_sum && qmin_sqsum && grad && ws && rows > 0,
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && q2 && obs && qmin_sum && qmin_sqsum && grad && ws && rows > 0,
                 "mpg_td3_policy_grad: bad argument");
-    if (ws_bytes < mpg_td3_policy_grad_workspace_bytes(cfg, rows)) {
-        mpg_set_error("mpg_td3_policy_grad: workspace too small");
-        return MPG_EWORKSPACE;
-    }
+    Arena ar(ws, ws_bytes);
+    const Td3PolicyWs w = td3_policy_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_td3_policy_grad", ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
     const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    Carver cv(ws, ws_bytes);
-    float* hp1 = cv.take(stash_floats(rows)); float* hp2 = cv.take(stash_floats(rows));
-    float* h11 = cv.take(stash_floats(rows)); float* h12 = cv.take(stash_floats(rows));
-    float* h21 = cv.take(stash_floats(rows)); float* h22 = cv.take(stash_floats(rows));
-    float* dz1 = cv.take(stash_floats(rows)); float* dz2 = cv.take(stash_floats(rows));
-    float* a = cv.take((size_t)rows * ad); float* dz3 = cv.take((size_t)rows * ad);
-    float* qv1 = cv.take(rows); float* qv2 = cv.take(rows); float* dy1 = cv.take(rows); float* dy2 = cv.take(rows);
-    float* dx1 = cv.take((size_t)rows * qin); float* dx2 = cv.take((size_t)rows * qin);
-    float* ga = cv.take((size_t)rows * ad);
-    float* slabs = cv.take(wgrad_workspace_floats(rows, od, 2 * ad));
-    float* parts = cv.take(2 * ERR_PARTS);
     const OutSpec po = policy_out(cfg);
-    const XSpec xp = xspec(obs, od, nullptr, 0, cfg->obs_scale, od);
-    int rc = launch_forward(cfg, policy_params, od, 2 * ad, ad, rows, xp, po, a, ad, hp1, hp2, s);        // td3.py:123
+    const XSpec xp = policy_x(cfg, obs);
+    int rc = policy_forward(cfg, policy_params, rows, xp, po, w.a, w.hp1, w.hp2, s);        // td3.py:123
     if (rc) return rc;
-    const XSpec xq = xspec(obs, od, a, ad, cfg->obs_scale, od);
-    rc = launch_forward(cfg, q1, qin, 1, 1, rows, xq, linear_out(), qv1, 1, h11, h12, s);                  // :124
+    const XSpec xq = critic_x(cfg, obs, w.a);
+    rc = critic_forward(cfg, q1, rows, xq, w.qv1, w.h11, w.h12, s);                         // :124
     if (rc) return rc;
-    rc = launch_forward(cfg, q2, qin, 1, 1, rows, xq, linear_out(), qv2, 1, h21, h22, s);                  // :125
+    rc = critic_forward(cfg, q2, rows, xq, w.qv2, w.h21, w.h22, s);                         // :125
     if (rc) return rc;
     const bool thin = backward_takes_thin(od, ad);        // (see mpg_q_loss_grad)
-    FinishJob fin{parts, ERR_PARTS, ERR_PARTS, 1.f, 1.f, qmin_sum, qmin_sqsum};
+    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 1.f, 1.f, qmin_sum, qmin_sqsum};
     const bool mb = rows >= ERR_MB_MIN_ROWS;
     if (mb) {
-        hipLaunchKernelGGL(k_td3_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, qv1, qv2, inv_b_global, dy1, dy2, parts);
-        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, parts, 1.f, 1.f, qmin_sum, qmin_sqsum);
+        hipLaunchKernelGGL(k_td3_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, w.parts);
+        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, qmin_sum, qmin_sqsum);
     } else
-    hipLaunchKernelGGL(k_td3_dy, dim3(1), dim3(1024), 0, s, rows, qv1, qv2, inv_b_global, dy1, dy2, qmin_sum, qmin_sqsum);
+    hipLaunchKernelGGL(k_td3_dy, dim3(1), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, qmin_sum, qmin_sqsum);
     MPG_CHECK_LAUNCH("k_td3_dy");
-    rc = launch_backward(cfg, q1, qin, 1, 1, rows, dy1, 1, nullptr, 0, 0, 1.f, h11, h12, nullptr, nullptr, nullptr, dx1, qin, s);
+    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy1, 1, nullptr, 0, 0, 1.f, w.h11, w.h12, nullptr, nullptr, nullptr, w.dx1, qin, s);
     if (rc) return rc;
-    rc = launch_backward(cfg, q2, qin, 1, 1, rows, dy2, 1, nullptr, 0, 0, 1.f, h21, h22, nullptr, nullptr, nullptr, dx2, qin, s);
+    rc = launch_backward(cfg, q2, qin, 1, 1, rows, w.dy2, 1, nullptr, 0, 0, 1.f, w.h21, w.h22, nullptr, nullptr, nullptr, w.dx2, qin, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, dx1, dx2, ga);
+    hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx1, w.dx2, w.ga);
     MPG_CHECK_LAUNCH("k_sum_action_grad");
-    rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, ga, ad, a, ad, po.out_tanh, po.out_scale, hp1, hp2, thin ? nullptr : dz1,
-                         dz2, dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? dz1 : nullptr);
+    rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, w.ga, ad, w.a, ad, po.out_tanh, po.out_scale, w.hp1, w.hp2,
+                         thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
     if (rc) return rc;
-    return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, hp1, hp2, dz1, dz2, dz3, inv_b_global, grad, slabs, s, thin, thin ? dz1 : nullptr,
-                        thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+    return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,
+                        thin ? w.dz1 : nullptr, thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
 }

@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <stdlib.h>
 
-#include "mlp_launch.h"
+#include "host_glue.h"
 
 namespace rollout {
 
@@ -250,9 +250,8 @@ inline void fill_roll(RollArgs& a, const mpg_cfg_t* cfg, const float* policy, in
     a.obs_dim = cfg->obs_dim;
     for (int i = 0; i < 16; ++i) a.obs_scale[i] = i < cfg->obs_dim ? cfg->obs_scale[i] : 1.f;
     a.rew_scale = cfg->rew_scale; a.rew_shift = cfg->rew_shift; a.gamma = cfg->gamma;
-    const bool ranged = cfg->action_range > 0.f;
-    a.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    a.out_scale = ranged ? cfg->action_range : 1.f;
+    const OutSpec po = policy_out(cfg);
+    a.out_tanh = po.out_tanh; a.out_scale = po.out_scale;
     a.pack = weight_cache_lookup(cfg, make_net(policy, cfg->obs_dim, 2 * cfg->act_dim).W2, 0);
     a.status = mpg_status_of(cfg);
 }

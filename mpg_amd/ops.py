@@ -114,7 +114,7 @@ def make_cfg(env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift
     c = CfgStruct()
     c.obs_dim, c.act_dim = (int(obs_dim) if (pt and obs_dim) else 6, 2) if pt else (4, 1)
     if pt and not 6 <= c.obs_dim <= 16:
-        # the library's own answer for such a cfg is MPG_EINVAL at the first launch (cfg_ok): raise it where the cfg is built
+        # the library's own answer for such a cfg is MPG_EINVAL at the first launch (net_cfg_ok, csrc/host_glue.h): raise it where the cfg is built
         raise L.MpgError('MPG_EINVAL: PathTracking observations have 6 + num_future_data entries and the env and network kernels serve '
                          'num_future_data <= 10 (policy inputs up to 16 wide, critic inputs up to 18; got obs_dim %d)' % c.obs_dim)
     if policy_out_activation is None:
@@ -168,6 +168,24 @@ def workspace(device, nbytes, slot=0):
     return _WS[key].get(nbytes)
 
 
+def _ws(device, slot, query, cfg, *sizes):
+    """The caller's half of the workspace contract: ask `query`, refuse what it refuses (0 bytes), hold that many bytes.
+    Returns the (pointer, size) pair the entry point takes."""
+    nb = getattr(L.lib(), query)(ctypes.byref(cfg), *[L.c_int(int(v)) for v in sizes])
+    if nb == 0:
+        raise L.MpgError('%s: unsupported configuration' % query)
+    ws = workspace(device, nb, slot)
+    return L.ptr(ws), L.c_size_t(ws.numel())
+
+
+def _ints(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def _floats(values):
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])
+
+
 def _f32(t):
     assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.is_contiguous())
     return t
@@ -193,12 +211,11 @@ def policy_action(cfg, policy_params, obs, explore_sigma=0.0, seed=0, ctr=0):
 def q_targets(cfg, policy_t, q1t, q2t, rew, obs_tp1, smooth_eps=None, smooth_sigma=0.2, smooth_clip=0.5):
     rows = obs_tp1.shape[0]
     y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
-    nb = L.lib().mpg_q_targets_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(obs_tp1.device, nb)
+    ws = _ws(obs_tp1.device, 0, 'mpg_q_targets_workspace_bytes', cfg, rows)
     L.call('mpg_q_targets', ctypes.byref(cfg), L.ptr(_f32(policy_t)), L.ptr(_f32(q1t)),
            L.ptr(_f32(q2t) if q2t is not None else None), L.c_int(rows), L.ptr(_f32(rew)), L.ptr(_f32(obs_tp1)),
            L.ptr(_f32(smooth_eps) if smooth_eps is not None else None), L.c_float(smooth_sigma),
-           L.c_float(smooth_clip), L.ptr(y), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.c_float(smooth_clip), L.ptr(y), *ws, L.stream())
     return y
 
 
@@ -208,11 +225,10 @@ def td3_targets(cfg, policy_t, q1t, q2t, rew, obs_tp1, smooth_eps, smooth_sigma=
     rows = obs_tp1.shape[0]
     y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
     y1 = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
-    nb = L.lib().mpg_q_targets_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(obs_tp1.device, nb)
+    ws = _ws(obs_tp1.device, 0, 'mpg_q_targets_workspace_bytes', cfg, rows)
     L.call('mpg_td3_targets', ctypes.byref(cfg), L.ptr(_f32(policy_t)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows),
            L.ptr(_f32(rew)), L.ptr(_f32(obs_tp1)), L.ptr(_f32(smooth_eps) if smooth_eps is not None else None),
-           L.c_float(smooth_sigma), L.c_float(smooth_clip), L.ptr(y), L.ptr(y1), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.c_float(smooth_sigma), L.c_float(smooth_clip), L.ptr(y), L.ptr(y1), *ws, L.stream())
     return y, y1
 
 
@@ -233,10 +249,9 @@ def td3_priority_errors(y1, y, td):
 def nstep_targets(cfg, policy_t, q1t, rewards, last_obs):
     n, rows = rewards.shape
     y = torch.empty(rows, dtype=torch.float32, device=last_obs.device)
-    nb = L.lib().mpg_q_targets_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(last_obs.device, nb)
+    ws = _ws(last_obs.device, 0, 'mpg_q_targets_workspace_bytes', cfg, rows)
     L.call('mpg_nstep_targets', ctypes.byref(cfg), L.ptr(_f32(policy_t)), L.ptr(_f32(q1t)), L.c_int(rows), L.c_int(n),
-           L.ptr(_f32(rewards)), L.ptr(_f32(last_obs)), L.ptr(y), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.ptr(_f32(rewards)), L.ptr(_f32(last_obs)), L.ptr(y), *ws, L.stream())
     return y
 
 
@@ -246,11 +261,10 @@ def q_loss_grad(cfg, q_params, obs, act, y, inv_b_global=None, grad_out=None, lo
     grad = grad_out if grad_out is not None else torch.empty(q_size(cfg), dtype=torch.float32, device=dev)
     loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=dev)
     td = torch.empty(rows, dtype=torch.float32, device=dev) if want_td else None
-    nb = L.lib().mpg_q_loss_grad_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(dev, nb)
+    ws = _ws(dev, 0, 'mpg_q_loss_grad_workspace_bytes', cfg, rows)
     L.call('mpg_q_loss_grad', ctypes.byref(cfg), L.ptr(_f32(q_params)), L.c_int(rows), L.ptr(_f32(obs)),
            L.ptr(_f32(act)), L.ptr(_f32(y)), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
-           L.ptr(loss), L.ptr(grad), L.ptr(td), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.ptr(loss), L.ptr(grad), L.ptr(td), *ws, L.stream())
     return loss, grad, td
 
 
@@ -266,17 +280,13 @@ def rollout_pg(cfg, policy_params, q1_params, obs0, eps, select, w, M=1, inv_b_g
     ns = len(select)
     grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
     stats = stats_out if stats_out is not None else torch.empty(2 * ns, dtype=torch.float32, device=dev)
-    sel = (ctypes.c_int * ns)(*[int(k) for k in select])
-    wv = (ctypes.c_float * ns)(*[float(x) for x in w])
-    nb = L.lib().mpg_rollout_pg_workspace_bytes(ctypes.byref(cfg), L.c_int(rows), L.c_int(M), L.c_int(n), L.c_int(ns),
-                                                L.c_int(int(all_steps_param_grad)))
-    if nb == 0:
-        raise L.MpgError('mpg_rollout_pg_workspace_bytes: unsupported configuration')
-    ws = workspace(dev, nb, slot=1)
+    sel = _ints(select)
+    wv = _floats(w)
+    ws = _ws(dev, 1, 'mpg_rollout_pg_workspace_bytes', cfg, rows, M, n, ns, all_steps_param_grad)
     L.call('mpg_rollout_pg', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1_params)), L.c_int(rows),
            L.c_int(M), L.c_int(n), sel, L.c_int(ns), wv, L.ptr(_f32(obs0)), L.ptr(_f32(eps) if eps is not None else None),
            L.c_u64(noise_seed), L.c_u64(noise_ctr), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), L.c_int(int(all_steps_param_grad)),
-           L.ptr(stats[:ns]), L.ptr(stats[ns:]), L.ptr(grad), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.ptr(stats[:ns]), L.ptr(stats[ns:]), L.ptr(grad), *ws, L.stream())
     return stats[:ns], stats[ns:], grad
 
 
@@ -286,7 +296,7 @@ CLIP_PARTS = 272          # MPG_CLIP_PARTS (include/mpg_hip.h)
 def sq_partials(grad, seg_sizes, sq_part=None):
     ns = len(seg_sizes)
     part = sq_part if sq_part is not None else torch.empty(ns * CLIP_PARTS, dtype=torch.float32, device=grad.device)
-    segs = (ctypes.c_int * ns)(*[int(s) for s in seg_sizes])
+    segs = _ints(seg_sizes)
     L.call('mpg_sq_partials', L.ptr(_f32(grad)), segs, L.c_int(ns), L.ptr(part), L.stream())
     return part
 
@@ -295,10 +305,10 @@ def clip_adam_polyak(w, m, v, target, grad, sq_part, seg_sizes, clip, lr_t, do_a
                      wc_w=None, wc_target=None):
     """mpg_clip_adam_polyak: second half of the clip + Adam + Polyak in one launch"""
     ns = len(seg_sizes)
-    segs = (ctypes.c_int * ns)(*[int(s) for s in seg_sizes])
-    lr = (ctypes.c_float * ns)(*[float(x) for x in lr_t])
-    da = (ctypes.c_int * ns)(*[int(x) for x in do_adam])
-    dp = (ctypes.c_int * ns)(*[int(x) for x in do_polyak])
+    segs = _ints(seg_sizes)
+    lr = _floats(lr_t)
+    da = _ints(do_adam)
+    dp = _ints(do_polyak)
     L.call('mpg_clip_adam_polyak', L.ptr(_f32(w)), L.ptr(_f32(m)), L.ptr(_f32(v)), L.ptr(target), L.ptr(_f32(grad)),
            L.ptr(_f32(sq_part)), segs, L.c_int(ns), L.c_float(clip), lr, da, dp, L.c_float(tau), L.ptr(norms), L.ptr(nonfinite),
            _wc(wc_w), _wc(wc_target), L.stream())
@@ -307,7 +317,7 @@ def clip_adam_polyak(w, m, v, target, grad, sq_part, seg_sizes, clip, lr_t, do_a
 def clip_by_global_norm(grad, seg_sizes, clip, norms_out=None, nonfinite=None, scratch=None):
     ns = len(seg_sizes)
     norms = norms_out if norms_out is not None else torch.empty(ns, dtype=torch.float32, device=grad.device)
-    segs = (ctypes.c_int * ns)(*[int(s) for s in seg_sizes])
+    segs = _ints(seg_sizes)
     L.call('mpg_clip_by_global_norm', L.ptr(_f32(grad)), segs, L.c_int(ns), L.c_float(clip), L.ptr(norms),
            L.ptr(nonfinite), L.ptr(scratch), L.stream())
     return norms
@@ -315,10 +325,10 @@ def clip_by_global_norm(grad, seg_sizes, clip, norms_out=None, nonfinite=None, s
 
 def adam_polyak(w, m, v, target, grad, seg_sizes, lr_t, do_adam, do_polyak, tau, skip_flag=None, wc_w=None, wc_target=None):
     ns = len(seg_sizes)
-    segs = (ctypes.c_int * ns)(*[int(s) for s in seg_sizes])
-    lr = (ctypes.c_float * ns)(*[float(x) for x in lr_t])
-    da = (ctypes.c_int * ns)(*[int(x) for x in do_adam])
-    dp = (ctypes.c_int * ns)(*[int(x) for x in do_polyak])
+    segs = _ints(seg_sizes)
+    lr = _floats(lr_t)
+    da = _ints(do_adam)
+    dp = _ints(do_polyak)
     L.call('mpg_adam_polyak', L.ptr(_f32(w)), L.ptr(_f32(m)), L.ptr(_f32(v)), L.ptr(target), L.ptr(_f32(grad)), segs,
            L.c_int(ns), lr, da, dp, L.c_float(tau), L.ptr(skip_flag),
            L.c_int(skip_flag.numel() if skip_flag is not None else 0), _wc(wc_w), _wc(wc_target), L.stream())
@@ -328,11 +338,10 @@ def rollout_q_target(cfg, policy_params, q1t, obs0, act0, eps, n=None, noise_see
     rows = obs0.shape[0]
     n = eps.shape[0] if eps is not None else n
     y = torch.empty(rows, dtype=torch.float32, device=obs0.device)
-    nb = L.lib().mpg_rollout_q_target_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(obs0.device, nb)
+    ws = _ws(obs0.device, 0, 'mpg_rollout_q_target_workspace_bytes', cfg, rows)
     L.call('mpg_rollout_q_target', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1t)), L.c_int(rows), L.c_int(n),
            L.ptr(_f32(obs0)), L.ptr(_f32(act0)), L.ptr(_f32(eps) if eps is not None else None), L.c_u64(noise_seed),
-           L.c_u64(noise_ctr), L.ptr(y), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.c_u64(noise_ctr), L.ptr(y), *ws, L.stream())
     return y
 
 
@@ -340,14 +349,11 @@ def rollout_q_estimation(cfg, policy_params, q1t, obs0, act0, eps, select, M=1, 
     """mpg_rollout_q_estimation -> [n_select * rows] (the reference's concatenation of the selected slices)"""
     rows, ns = obs0.shape[0], len(select)
     y = torch.empty(ns * rows, dtype=torch.float32, device=obs0.device)
-    sel = (ctypes.c_int * ns)(*[int(k) for k in select])
-    nb = L.lib().mpg_rollout_q_estimation_workspace_bytes(ctypes.byref(cfg), L.c_int(rows), L.c_int(M), L.c_int(ns))
-    if nb == 0:
-        raise L.MpgError('mpg_rollout_q_estimation_workspace_bytes: unsupported configuration')
-    ws = workspace(obs0.device, nb)
+    sel = _ints(select)
+    ws = _ws(obs0.device, 0, 'mpg_rollout_q_estimation_workspace_bytes', cfg, rows, M, ns)
     L.call('mpg_rollout_q_estimation', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1t)), L.c_int(rows), L.c_int(M),
            sel, L.c_int(ns), L.ptr(_f32(obs0)), L.ptr(_f32(act0)), L.ptr(_f32(eps) if eps is not None else None),
-           L.c_u64(noise_seed), L.c_u64(noise_ctr), L.ptr(y), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.c_u64(noise_seed), L.c_u64(noise_ctr), L.ptr(y), *ws, L.stream())
     return y
 
 
@@ -355,11 +361,10 @@ def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out
     rows, dev = obs.shape[0], obs.device
     grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
     stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.float32, device=dev)
-    nb = L.lib().mpg_td3_policy_grad_workspace_bytes(ctypes.byref(cfg), L.c_int(rows))
-    ws = workspace(dev, nb, slot=1)
+    ws = _ws(dev, 1, 'mpg_td3_policy_grad_workspace_bytes', cfg, rows)
     L.call('mpg_td3_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)),
            L.c_int(rows), L.ptr(_f32(obs)), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
-           L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad), L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad), *ws, L.stream())
     return stats, grad
 
 
@@ -370,15 +375,11 @@ def mpg_gradients(cfg, n_q, params, target_params, obs, act, rew, obs_tp1, y_in,
     if eps is not None:
         n = eps.shape[0]
     ns = len(select)
-    sel = (ctypes.c_int * ns)(*[int(k) for k in select])
-    wv = (ctypes.c_float * ns)(*[float(x) for x in w])
-    nb = L.lib().mpg_mpg_gradients_workspace_bytes(ctypes.byref(cfg), L.c_int(rows), L.c_int(M), L.c_int(n), L.c_int(ns),
-                                                   L.c_int(n_q))
-    if nb == 0:
-        raise L.MpgError('mpg_mpg_gradients_workspace_bytes: unsupported configuration')
-    ws = workspace(dev, nb, slot=1)
+    sel = _ints(select)
+    wv = _floats(w)
+    ws = _ws(dev, 1, 'mpg_mpg_gradients_workspace_bytes', cfg, rows, M, n, ns, n_q)
     L.call('mpg_mpg_gradients', ctypes.byref(cfg), L.c_int(n_q), L.ptr(_f32(params)), L.ptr(target_params), L.c_int(rows),
            L.ptr(_f32(obs)), L.ptr(_f32(act)), L.ptr(rew), L.ptr(obs_tp1), L.ptr(y_in), L.c_int(M), L.c_int(n), sel,
            L.c_int(ns), wv, L.ptr(eps), L.c_u64(noise_seed), L.c_u64(noise_ctr),
            L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), L.ptr(_f32(grad)), L.ptr(_f32(stats)),
-           L.ptr(_f32(y_out)), L.ptr(sq_part), None, L.ptr(ws), L.c_size_t(ws.numel()), L.stream())
+           L.ptr(_f32(y_out)), L.ptr(sq_part), None, *ws, L.stream())

@@ -79,3 +79,63 @@ def test_the_message_belongs_to_the_calling_thread():
     t.join()
     assert 'uniform_indices' in seen['msg'] and 'sum_slots' in mine
     assert lib.mpg_last_error().decode() == mine
+
+
+# ---- workspaces: every entry point that takes one refuses a buffer one byte short of its own query ----
+MPG_EWORKSPACE = -1001
+ROWS = 4096
+SEL2, W2 = (I * 2)(0, 25), (F * 2)(0.3, 0.7)      # `select` / `w` are read on the host before the size check: real arrays
+
+
+def _pt(obs_dim=6):
+    from mpg_amd import ops
+    return ops.make_cfg('PathTracking-v0', obs_dim=obs_dim)
+
+
+def _rollout_pg(M, asp):
+    return lambda ws, nb: (FAKE, FAKE, I(ROWS), I(M), I(25), SEL2, I(2), W2, FAKE, NULL, U64(1), U64(0), F(1.0 / ROWS), I(asp), FAKE,
+                           FAKE, FAKE, ws, nb, NULL)
+
+
+WS_CASES = [
+    # (entry point, its query, cfg, the query's sizes after cfg, the entry point's arguments after cfg)
+    ('mpg_q_targets', 'mpg_q_targets', 6, (ROWS,),
+     lambda ws, nb: (FAKE, FAKE, FAKE, I(ROWS), FAKE, FAKE, NULL, F(0.2), F(0.5), FAKE, ws, nb, NULL)),
+    ('mpg_td3_targets', 'mpg_q_targets', 6, (ROWS,),
+     lambda ws, nb: (FAKE, FAKE, FAKE, I(ROWS), FAKE, FAKE, FAKE, F(0.2), F(0.5), FAKE, FAKE, ws, nb, NULL)),
+    ('mpg_nstep_targets', 'mpg_q_targets', 6, (ROWS,),
+     lambda ws, nb: (FAKE, FAKE, I(ROWS), I(5), FAKE, FAKE, FAKE, ws, nb, NULL)),
+    ('mpg_q_loss_grad', 'mpg_q_loss_grad', 6, (ROWS,),
+     lambda ws, nb: (FAKE, I(ROWS), FAKE, FAKE, FAKE, F(1.0 / ROWS), FAKE, FAKE, NULL, ws, nb, NULL)),
+    ('mpg_td3_policy_grad', 'mpg_td3_policy_grad', 6, (ROWS,),
+     lambda ws, nb: (FAKE, FAKE, FAKE, I(ROWS), FAKE, F(1.0 / ROWS), FAKE, FAKE, FAKE, ws, nb, NULL)),
+    ('mpg_rollout_pg', 'mpg_rollout_pg', 6, (ROWS, 1, 25, 2, 0), _rollout_pg(1, 0)),
+    ('mpg_rollout_pg', 'mpg_rollout_pg', 6, (ROWS, 1, 25, 2, 1), _rollout_pg(1, 1)),          # with the thin partials
+    ('mpg_rollout_pg', 'mpg_rollout_pg', 9, (ROWS, 3, 25, 2, 0), _rollout_pg(3, 0)),          # with the wide inputs
+    ('mpg_rollout_q_target', 'mpg_rollout_q_target', 6, (ROWS,),
+     lambda ws, nb: (FAKE, FAKE, I(ROWS), I(25), FAKE, FAKE, NULL, U64(1), U64(0), FAKE, ws, nb, NULL)),
+    ('mpg_rollout_q_estimation', 'mpg_rollout_q_estimation', 6, (ROWS, 1, 2),
+     lambda ws, nb: (FAKE, FAKE, I(ROWS), I(1), SEL2, I(2), FAKE, FAKE, NULL, U64(1), U64(0), FAKE, ws, nb, NULL)),
+    ('mpg_mpg_gradients', 'mpg_mpg_gradients', 6, (ROWS, 1, 25, 2, 2),
+     lambda ws, nb: (I(2), FAKE, FAKE, I(ROWS), FAKE, FAKE, FAKE, FAKE, NULL, I(1), I(25), SEL2, I(2), W2, NULL, U64(1), U64(0),
+                     F(1.0 / ROWS), FAKE, FAKE, FAKE, NULL, NULL, ws, nb, NULL)),
+]
+
+
+@pytest.mark.parametrize('name,query,obs_dim,sizes,args', WS_CASES,
+                         ids=['%s-od%d-%s' % (c[0], c[2], 'x'.join(str(v) for v in c[3])) for c in WS_CASES])
+def test_workspace_one_byte_short_is_refused_with_both_sizes(name, query, obs_dim, sizes, args):
+    lib = L.lib()
+    cfg = _pt(obs_dim)
+    q = getattr(lib, query + '_workspace_bytes')
+    need = q(ctypes.byref(cfg), *[I(v) for v in sizes])
+    assert need > 0
+    rc = getattr(lib, name)(ctypes.byref(cfg), *args(FAKE, SZ(need - 1)))
+    msg = lib.mpg_last_error().decode()
+    assert rc == MPG_EWORKSPACE, (name, rc, msg)
+    assert msg.startswith(name + ':') and 'workspace too small' in msg and '%d < %d' % (need - 1, need) in msg, msg
+    # the query itself answers 0 for what every entry point refuses: tanh output with an action range, no rows
+    from mpg_amd import ops
+    refused = ops.make_cfg('PathTracking-v0', obs_dim=obs_dim, policy_out_activation='tanh', action_range=1.0)
+    assert q(ctypes.byref(refused), *[I(v) for v in sizes]) == 0
+    assert q(ctypes.byref(cfg), I(0), *[I(v) for v in sizes[1:]]) == 0
