@@ -40,7 +40,7 @@ enum {
     MPG_EWORKSPACE = -1001 /* workspace too small: call the *_workspace_bytes query */
 };
 
-enum { MPG_ENV_PATH_TRACKING = 0, MPG_ENV_INVERTED_PENDULUM = 1 };
+enum { MPG_ENV_PATH_TRACKING = 0, MPG_ENV_INVERTED_PENDULUM = 1, MPG_ENV_INVERTED_DOUBLE_PENDULUM = 2 };
 enum { MPG_ACT_LINEAR = 0, MPG_ACT_TANH = 1 };
 enum { MPG_HIDDEN = 256 };
 /* floats per agent of the opaque env state block, stored SoA [MPG_ENV_STATE_DIM][n]:
@@ -135,7 +135,25 @@ int mpg_prof_region_end(mpg_prof_t* p, int slot, mpg_stream_t stream);
  *   MPG_ENV_INVERTED_PENDULUM  InvertedPendulumContiEnv (inverted_pendulum_conti.py:5-30 + inverted_pendulum_conti.xml) as
  *                              an analytic RK4 cart-pole (the reference steps it with MuJoCo, which cannot be pinned
  *                              here: csrc/env_cart_pole.hip), act_dim 1, obs_dim 4: [p, theta, pdot, thetadot].
- * state: the opaque block [MPG_ENV_STATE_DIM][n]. */
+ * state: the opaque block [MPG_ENV_STATE_DIM][n].
+ *
+ * MPG_ENV_INVERTED_DOUBLE_PENDULUM (2) names a differentiable MODEL only - InvertedDoublePendulumModel
+ * (envs_and_models/inverted_double_pendulum_model.py:103-144), the third model the reference registers
+ * (envs_and_models/__init__.py:12-15) - as mpg_cfg_t.env_kind of the rollout entry points (mpg_rollout_pg, mpg_rollout_q_target,
+ * mpg_rollout_q_estimation and their workspace queries):
+ *   observation  obs_dim 11: [p, sin t1, sin t2, cos t1, cos t2, pdot, t1dot, t2dot, frc1, frc2, frc3] (:105).  A START observation
+ *                (the caller's batch) carries whatever the env put into the three constraint-force entries, and all 11 entries reach
+ *                the first policy / critic evaluation; its state is [p, atan2(sin t1, cos t1), atan2(sin t2, cos t2), pdot, t1dot,
+ *                t2dot] (:126-132).  Every MODEL observation is that function of the model state with zeros in entries 8..10.
+ *   action       act_dim 1, force u = 500 a (:143-144); one step = five explicit-Euler sub-steps of 0.01 s of f_xu_old (:26-53), the
+ *                reward (:89-100) on the state behind them.  The angles are not wrapped.
+ *   noise        none: `eps`, noise_seed and noise_ctr are accepted and unused for this model.
+ *   limits       exactly (obs_dim 11, act_dim 1, env_kind 2): every other triple with one of these values is MPG_EINVAL (workspace
+ *                queries: 0).  The 3 x 3 mass-matrix system is solved in closed form where the reference calls tf.linalg.inv.
+ * The REAL env is gym's MuJoCo InvertedDoublePendulum-v2 and is not provided: mpg_env_reset_from_obs, mpg_env_reset, mpg_env_step,
+ * mpg_env_step_store_reset(_draw) and mpg_worker_step return MPG_EINVAL for env_kind 2 with a message that says so, and the native
+ * step driver, whose first act is to sample the real env, REFUSES a context with this env_kind in mpg_step_begin before anything
+ * is enqueued (NADP on this model runs through the rollout entry points on caller-supplied batches). */
 enum { MPG_ENV_MAX_FUTURE = 10 };
 
 /* env.reset(init_obs=...)  - path_tracking_env.py:410-421 / DummyVecEnv.reset(init_obs=) for the pendulum.
@@ -202,7 +220,7 @@ typedef struct {
 /* Hyper-parameters of one config (host memory, read at call time). */
 typedef struct {
     int obs_dim, act_dim;       /* path tracking: 6 + num_future_data (0 <= num_future_data <= MPG_ENV_MAX_FUTURE = 10), 2;
-                                   pendulum: 4, 1.  LIMIT: the reference accepts any num_future_data
+                                   pendulum: 4, 1; double pendulum (model only): 11, 1.  LIMIT: the reference accepts any num_future_data
                                    (path_tracking_env.py:385-402); every entry point returns MPG_EINVAL for obs_dim > 16 (first
                                    layers: policy up to 16 wide, critics up to 24; obs_scale[16]) */
     int policy_out_act;         /* MPG_ACT_TANH (train_script.py:267) or MPG_ACT_LINEAR (train_script4mujoco.py:371) */

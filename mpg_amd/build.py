@@ -55,7 +55,11 @@ EXTRA = {'env_path_tracking.hip': ['-ffp-contract=off'] + os.environ.get('MPG_EN
          # the pendulum instantiations (NADP, config 3) measure 10 us slower under those and keep max-memory-clause with SLP
          # (MPG_BWDP_CFLAGS / MPG_FWDP_CFLAGS: experiments, tools/ab_side.sh)
          'rollout_bwd_pendulum.hip': os.environ.get('MPG_BWDP_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split(),
-         'rollout_fwd_pendulum.hip': os.environ.get('MPG_FWDP_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split()}
+         'rollout_fwd_pendulum.hip': os.environ.get('MPG_FWDP_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split(),
+         # the double-pendulum instantiations (16-wide form, five model sub-steps on the chain): the pendulum units' strategy, not
+         # tuned further (MPG_BWDD_CFLAGS / MPG_FWDD_CFLAGS: experiments)
+         'rollout_bwd_double_pendulum.hip': os.environ.get('MPG_BWDD_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split(),
+         'rollout_fwd_double_pendulum.hip': os.environ.get('MPG_FWDD_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split()}
 
 
 def hipcc():

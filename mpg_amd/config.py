@@ -28,6 +28,10 @@ def default_args(alg='MPG-v2', env_id=None, **overrides):
         rew_ptype='scale', rew_scale=1. if pend else 0.01, rew_shift=0.,
         policy_smoothing_sigma=0.2, policy_smoothing_clip=0.5,
         max_iter=100000, seed=0, init_seed=0)
+    if env_id == 'InvertedDoublePendulum-v2':
+        # the reference ships no parser for this env: the single pendulum's NADP settings with this env's dimensions, unit scales and
+        # a = tanh(mean) (ops.make_cfg: this project's choice)
+        d.update(num_agent=1, obs_dim=11, act_dim=1, policy_out_activation='linear', action_range=1., obs_scale=[1.] * 11, rew_scale=1.)
     d.update(overrides)
     if not pend and d['num_future_data'] and 'obs_dim' not in overrides:       # train_script.py:146-147, 794-811
         d['obs_dim'] = 6 + d['num_future_data']

@@ -635,10 +635,15 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
 
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
+// MPG_ENV_INVERTED_DOUBLE_PENDULUM names a differentiable model only (include/mpg_hip.h): every real-env entry point refuses it
+#define MPG_NO_DOUBLE_PENDULUM_ENV \
+    "the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided (only its differentiable model is: the rollout entry points)"
+
 }  // namespace
 
 extern "C" int mpg_env_reset_from_obs(int env_kind, int n, int obs_dim, float* state, const float* init_obs, mpg_stream_t stream) {
     if (env_kind == MPG_ENV_INVERTED_PENDULUM) return cart_pole::reset_from_obs(n, obs_dim, state, init_obs, mpg_stream(stream));
+    MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_reset_from_obs: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_reset_from_obs: unknown env kind %d", env_kind);
     MPG_REQUIRE(n > 0 && state && init_obs && pt_obs_dim_ok(obs_dim), "mpg_env_reset_from_obs: bad argument");
     hipLaunchKernelGGL(k_reset_from_obs, dim3((n + 63) / 64), dim3(64), 0, mpg_stream(stream), n, obs_dim, state, init_obs);
@@ -649,6 +654,7 @@ extern "C" int mpg_env_reset_from_obs(int env_kind, int n, int obs_dim, float* s
 extern "C" int mpg_env_reset(int env_kind, int n, int obs_dim, float* state, const uint8_t* done_mask, uint64_t seed, uint64_t ctr,
                              float* obs, mpg_stream_t stream) {
     if (env_kind == MPG_ENV_INVERTED_PENDULUM) return cart_pole::reset(n, obs_dim, state, done_mask, seed, ctr, obs, mpg_stream(stream));
+    MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_reset: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_reset: unknown env kind %d", env_kind);
     MPG_REQUIRE(n > 0 && state && obs && pt_obs_dim_ok(obs_dim), "mpg_env_reset: bad argument");
     hipLaunchKernelGGL(k_reset, dim3((n + 63) / 64), dim3(64), 0, mpg_stream(stream), n, state, done_mask,
@@ -661,6 +667,7 @@ extern "C" int mpg_env_step(int env_kind, int n, int obs_dim, float* state, cons
                             uint8_t* done, uint8_t* done_intended, mpg_stream_t stream) {
     if (env_kind == MPG_ENV_INVERTED_PENDULUM)
         return cart_pole::step(n, obs_dim, state, action, obs, reward, done, done_intended, mpg_stream(stream));
+    MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_step: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_step: unknown env kind %d", env_kind);
     MPG_REQUIRE(n > 0 && state && action && obs && reward && done && pt_obs_dim_ok(obs_dim), "mpg_env_step: bad argument");
     hipLaunchKernelGGL(k_step, dim3((n + 63) / 64), dim3(64), 0, mpg_stream(stream), n, state, action, obs, reward,
@@ -676,6 +683,7 @@ int step_store_reset_impl(int env_kind, int n, int obs_dim, float* state, const 
     MPG_REQUIRE(n > 0 && state && action && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs && ring_act &&
                     ring_rew && ring_obs2 && ring_done && obs_out,
                 "mpg_env_step_store_reset: bad argument");
+    MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_step_store_reset: " MPG_NO_DOUBLE_PENDULUM_ENV);
     if (env_kind == MPG_ENV_INVERTED_PENDULUM) {
         MPG_REQUIRE(pd_in.rows == 0, "mpg_env_step_store_reset_draw: path-tracking env only");
         return cart_pole::step_store_reset(n, obs_dim, state, action, capacity, next_idx, ring_obs, ring_act, ring_rew, ring_obs2,
@@ -750,6 +758,7 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
                                float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
                                uint64_t env_ctr, uint8_t* done_out, const mpg_replay_draw_t* draw, int rows, float* b_obs, float* b_act,
                                float* b_rew, float* b_obs2, mpg_stream_t stream) {
+    MPG_REQUIRE(!cfg || cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_step: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(cfg && cfg->env_kind == MPG_ENV_PATH_TRACKING && cfg->obs_dim == 6 && cfg->act_dim == 2,
                 "mpg_worker_step: path-tracking env with obs_dim 6 only");
     MPG_REQUIRE(policy_params && n > 0 && state && obs_io && act_out && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs &&

@@ -44,12 +44,15 @@ inline int workspace_too_small(const char* entry, size_t have, size_t need) {
 inline bool net_cfg_ok(const mpg_cfg_t* c) {
     // policy_out_activation='tanh' WITH an action_range would be range*tanh(tanh(z)) in the reference (policy.py:176-177,
     // 197-199); the kernels implement range*tanh(z) / tanh(z) / z only, so that combination is refused, not approximated
-    return c && ((c->obs_dim >= 6 && c->obs_dim <= 16 && c->act_dim == 2) || (c->obs_dim == 4 && c->act_dim == 1)) &&
+    // (obs 11, act 1: the double pendulum's observation, include/mpg_hip.h MPG_ENV_INVERTED_DOUBLE_PENDULUM)
+    return c && ((c->obs_dim >= 6 && c->obs_dim <= 16 && c->act_dim == 2) || ((c->obs_dim == 4 || c->obs_dim == 11) && c->act_dim == 1)) &&
            !(c->policy_out_act == MPG_ACT_TANH && c->action_range > 0.f);
 }
 // ... and the model of the rollout is the one those shapes belong to
 inline bool rollout_cfg_ok(const mpg_cfg_t* c) {
-    return net_cfg_ok(c) && c->env_kind == (c->act_dim == 2 ? MPG_ENV_PATH_TRACKING : MPG_ENV_INVERTED_PENDULUM);
+    return net_cfg_ok(c) && c->env_kind == (c->act_dim == 2   ? MPG_ENV_PATH_TRACKING
+                                            : c->obs_dim == 4 ? MPG_ENV_INVERTED_PENDULUM
+                                                              : MPG_ENV_INVERTED_DOUBLE_PENDULUM);
 }
 
 inline OutSpec linear_out() {

@@ -12,6 +12,8 @@ template <class ENV, bool PK, bool WIDE = false, bool THIN = false>
 __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a) {
     constexpr int OBS = ENV::OBS, ACT = ENV::ACT;
     static_assert(!(THIN && WIDE), "THIN is built for the base observation widths");
+    constexpr bool FEAT = has_features<ENV>::value;     // the networks see ENV::features(state): its adjoint folds their gradients
+    static_assert(!FEAT || WIDE, "feature models run the 16-wide form");
     constexpr int NIN = WIDE ? 16 : OBS, XSW = xs_of<NIN>();
     // per-lane running sums of the thin gradients, in LDS (registers: none to spare): [quad][thread] float4, slot order
     // gb1[2] gb2[2] gW3[2][ACT] gW1[2][OBS] (+ padding); the own lanes' db3 in sB3; the step's scaled network inputs of the 16
@@ -31,6 +33,9 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
     // carry state of the 16 trajectory lanes between steps (adjoint of the next obs, record of the next step): kept in
     // LDS because registers are allocated for all 512 lanes while only 16 use them (the kernel sits at the 256 VGPR limit)
     __shared__ __attribute__((aligned(16))) float sCarry[GROUP * 16];
+    // feature models: what ENV::vjp recomputes per trajectory lane (the states between its sub-steps), in LDS for the same reason
+    constexpr int ADJ = adj_floats<ENV>();
+    __shared__ float sAdj[FEAT ? GROUP * ADJ : 1];
     // dL/d(raw reward) per step from LDS: `a.rho[t]` with a run-time t is a scalar load from the kernel-argument segment plus a
     // wait on the serial chain of EVERY step (and a loop over `a.sel[ks]` with a run-time ks is one per slice)
     __shared__ float sRho[MAXN];
@@ -118,15 +123,21 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
                         float lam_next[8];
 #pragma unroll
                         for (int i = 0; i < 8; ++i) lam_next[i] = sCarry[tid * 16 + i];
+                        if constexpr (FEAT) ENV::vjp(o, act, on, lam_next, sRho[t], lam, ga, sAdj + tid * ADJ);
+                        else
                         ENV::vjp(o, act, on, lam_next, sRho[t], lam, ga);
                     }
                     if ((selmask >> t) & 1u)             // (two of the 26 steps: the slice search stays a plain loop)
                     for (int ks = 0; ks < a.n_sel; ++ks)
                         if (a.sel[ks] == t) {
                             const float* gx = a.GXQ + ((long)ks * R + tr) * QIN;
+                            if constexpr (FEAT) {
+                                ENV::fold(o, gx, a.obs_scale, lam);       // (t = 0: the start observation is an input; lam is not used)
+                            } else {
 #pragma unroll
                             for (int i = 0; i < OBS; ++i) lam[i] += gx[i] * a.obs_scale[i];
-                            if constexpr (WIDE) {
+                            }
+                            if constexpr (WIDE && !FEAT) {
                                 if (t > 0) {
 #pragma unroll
                                     for (int k = 0; k < MAXF; ++k)
@@ -203,9 +214,13 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
                 if (t > 0) {
                     float dxr[XSW];
                     dx_reduce_row<XSW, WIDE ? XSW : OBS>(sPartX, tid, dxr);
+                    if constexpr (FEAT) {
+                        ENV::fold(rec_cur, dxr, a.obs_scale, lam);         // (rec_cur: the state of this step)
+                    } else {
 #pragma unroll
                     for (int i = 0; i < OBS; ++i) lam[i] += dxr[i] * a.obs_scale[i];
-                    if constexpr (WIDE) {       // t > 0 here: the observation of this step came out of the model
+                    }
+                    if constexpr (WIDE && !FEAT) {       // t > 0 here: the observation of this step came out of the model
 #pragma unroll
                         for (int k = 0; k < MAXF; ++k)
                             if (k < nf) lam[ENV::FUT_SRC] += dxr[OBS + k] * a.obs_scale[OBS + k];
@@ -295,10 +310,16 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
 
 }  // namespace
 
-// This file is compiled twice: as itself (path tracking: the bench's kernel, with the flags that suit it - mpg_amd/build.py) and,
+// This file is compiled three times (the third: rollout_bwd_double_pendulum.hip, MPG_BWD_DOUBLE_PENDULUM_PART, that model's
+// instantiations): as itself (path tracking: the bench's kernel, with the flags that suit it - mpg_amd/build.py) and,
 // through rollout_bwd_pendulum.hip (MPG_BWD_PENDULUM_PART), for the pendulum instantiations, which measure 10 us slower under
 // those flags and keep the previous ones.
-#ifdef MPG_BWD_PENDULUM_PART
+#if defined(MPG_BWD_DOUBLE_PENDULUM_PART)
+void launch_rollout_bwd_double_pendulum(const RollBwdArgs& ba, long ngroups, hipStream_t s) {
+    if (ba.pack) hipLaunchKernelGGL((k_rollout_bwd<DoublePendulum, true, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba);
+    else hipLaunchKernelGGL((k_rollout_bwd<DoublePendulum, false, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba);
+}
+#elif defined(MPG_BWD_PENDULUM_PART)
 void launch_rollout_bwd_pendulum(const RollBwdArgs& ba, long ngroups, hipStream_t s) {
     if (ba.thin_part) hipLaunchKernelGGL((k_rollout_bwd<Pendulum, true, false, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba);
     else if (ba.pack) hipLaunchKernelGGL((k_rollout_bwd<Pendulum, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba);
@@ -306,6 +327,7 @@ void launch_rollout_bwd_pendulum(const RollBwdArgs& ba, long ngroups, hipStream_
 }
 #else
 void launch_rollout_bwd_pendulum(const RollBwdArgs& ba, long ngroups, hipStream_t s);
+void launch_rollout_bwd_double_pendulum(const RollBwdArgs& ba, long ngroups, hipStream_t s);
 
 int launch_rollout_bwd(const RollBwdArgs& ba_in, int env_kind, long ngroups, int n, hipStream_t s, mpg_prof_t* prof) {
     RollBwdArgs ba = ba_in;
@@ -323,6 +345,8 @@ int launch_rollout_bwd(const RollBwdArgs& ba_in, int env_kind, long ngroups, int
         hipLaunchKernelGGL((k_rollout_bwd<PathTracking, true, false, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba);
     else if (env_kind == MPG_ENV_PATH_TRACKING)
         { if (ba.pack) hipLaunchKernelGGL((k_rollout_bwd<PathTracking, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba); else hipLaunchKernelGGL((k_rollout_bwd<PathTracking, false>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, ba); }
+    else if (env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM)
+        launch_rollout_bwd_double_pendulum(ba, ngroups, s);
     else
         launch_rollout_bwd_pendulum(ba, ngroups, s);
     mpg_prof_end(prof, 1, s);

@@ -192,6 +192,215 @@ struct Pendulum {
     }
 };
 
+// InvertedDoublePendulumModel (envs_and_models/inverted_double_pendulum_model.py:103-144).  Unlike the two models above the
+// sweeps carry its STATE [p, theta1, theta2, pdot, theta1dot, theta2dot] (the (state | action) record fits SAW), and the networks
+// see a FUNCTION of it: the 11 features [p, sin t1, sin t2, cos t1, cos t2, pdot, t1dot, t2dot, 0, 0, 0] (_get_obs :118-124;
+// has_features).  Only the START observation carries what the env put into entries 8..10; its state is atan2(sin, cos) (:126-132).
+// One rollout_out (:134-141) is five explicit-Euler sub-steps f_xu_old(tau = 0.01) (:26-53: point masses, no damping) with
+// u = 500 a (:143-144), the reward (:89-100) is taken on the state behind them.  No model noise: eps is unused.
+// The angles are not range-limited and every rounding difference grows along the falling pendulum's trajectory, so nothing
+// here uses the hardware approximations: library sincosf, correctly rounded division.  The symmetric 3 x 3 system is solved in
+// closed form (cofactors) where the reference runs tf.linalg.inv + tf.matmul.
+struct DoublePendulum {
+    static constexpr int OBS = 6, ACT = 1;
+    static constexpr int NPRE = 9;
+    static constexpr int FUT_SRC = 0;     // (unused: has_features)
+    static constexpr int NFEAT = 11;
+    static constexpr int NSUB = 5;
+    static constexpr int ADJ = 6 * (NSUB - 1);      // floats of LDS a trajectory lane needs in vjp(): the recomputed states
+    // :16-24
+    static constexpr float M0 = 9.42477796f, M1 = 4.1033127f, M2 = 4.1033127f, L1 = 0.6f, L2 = 0.6f, GR = 9.81f;
+    static constexpr float TAU = 0.01f, USCALE = 500.f;
+    // mass matrix [[A, B c1, C c2], [B c1, D, E c12], [C c2, E c12, F]] (:39-42), gravity terms of f (:43-45)
+    static constexpr float A = M0 + M1 + M2, B = L1 * (M1 + M2), C = M2 * L2, D = L1 * L1 * (M1 + M2), E = L1 * L2 * M2,
+                           F = L2 * L2 * M2, G1 = GR * (M1 + M2) * L1, G2 = GR * L2 * M2;
+
+    // trigonometry and inverse mass matrix (symmetric: six entries) of one sub-step
+    struct Sub {
+        float s1, c1, s2, c2, s12, c12;
+        float i00, i01, i02, i11, i12, i22;
+    };
+    __device__ static void setup(float t1, float t2, Sub& k) {
+        sincosf(t1, &k.s1, &k.c1);
+        sincosf(t2, &k.s2, &k.c2);
+        k.c12 = k.c1 * k.c2 + k.s1 * k.s2;                   // cos(t1 - t2), sin(t1 - t2)
+        k.s12 = k.s1 * k.c2 - k.c1 * k.s2;
+        const float x = B * k.c1, y = C * k.c2, z = E * k.c12;
+        const float a00 = D * F - z * z, a01 = y * z - x * F, a02 = x * z - D * y;
+        const float a11 = A * F - y * y, a12 = x * y - A * z, a22 = A * D - x * x;
+        const float idet = 1.f / (A * a00 + x * a01 + y * a02);
+        k.i00 = a00 * idet; k.i01 = a01 * idet; k.i02 = a02 * idet;
+        k.i11 = a11 * idet; k.i12 = a12 * idet; k.i22 = a22 * idet;
+    }
+    // accelerations q = M^-1 f of the state s under the force u
+    __device__ static void accel(const Sub& k, const float (&s)[8], float u, float (&q)[3]) {
+        const float w1s = s[4] * s[4], w2s = s[5] * s[5];
+        const float f0 = B * w1s * k.s1 + C * w2s * k.s2 + u;
+        const float f1 = -E * w2s * k.s12 + G1 * k.s1;
+        const float f2 = E * w1s * k.s12 + G2 * k.s2;
+        q[0] = k.i00 * f0 + k.i01 * f1 + k.i02 * f2;
+        q[1] = k.i01 * f0 + k.i11 * f1 + k.i12 * f2;
+        q[2] = k.i02 * f0 + k.i12 * f1 + k.i22 * f2;
+    }
+    __device__ static void substep(float (&s)[8], float u) {      // :50-51 (positions move with the OLD velocities)
+        Sub k;
+        setup(s[1], s[2], k);
+        float q[3];
+        accel(k, s, u, q);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            s[i] = fmaf(TAU, s[3 + i], s[i]);
+            s[3 + i] = fmaf(TAU, q[i], s[3 + i]);
+        }
+    }
+
+    // start: the state of a batch observation (:126-132)
+    __device__ static void reset(const float* obs, float (&s)[8]) {
+        s[0] = obs[0];
+        s[1] = atan2f(obs[1], obs[3]);
+        s[2] = atan2f(obs[2], obs[4]);
+        s[3] = obs[5]; s[4] = obs[6]; s[5] = obs[7];
+        s[6] = s[7] = 0.f;
+    }
+    // the observation of a model state (:118-124), from the state's own trigonometry tr = [sin t1, sin t2, cos t1, cos t2]
+    __device__ static void features(const float (&s)[8], const float (&tr)[4], float (&x)[NFEAT]) {
+        x[0] = s[0];
+        x[1] = tr[0]; x[2] = tr[1]; x[3] = tr[2]; x[4] = tr[3];
+        x[5] = s[3]; x[6] = s[4]; x[7] = s[5];
+        x[8] = x[9] = x[10] = 0.f;
+    }
+    __device__ static void features(const float (&s)[8], float (&x)[NFEAT]) {
+        float tr[4];
+        sincosf(s[1], &tr[0], &tr[2]);
+        sincosf(s[2], &tr[1], &tr[3]);
+        features(s, tr, x);
+    }
+    // adjoint of features() times the input scale: lam += J^T (v * scale); nothing flows into entries 8..10
+    template <class V>
+    __device__ static void fold(const float (&s)[8], const V& v, const float (&scale)[16], float (&lam)[8]) {
+        float s1, c1, s2, c2;
+        sincosf(s[1], &s1, &c1);
+        sincosf(s[2], &s2, &c2);
+        lam[0] += v[0] * scale[0];
+        lam[1] += v[1] * scale[1] * c1 - v[3] * scale[3] * s1;
+        lam[2] += v[2] * scale[2] * c2 - v[4] * scale[4] * s2;
+        lam[3] += v[5] * scale[5];
+        lam[4] += v[6] * scale[6];
+        lam[5] += v[7] * scale[7];
+    }
+
+    // The cut of the forward step: the first sub-step's trigonometry and mass matrix do not depend on the action, so its result is
+    // affine in it - pre() runs that sub-step ahead of the action (book lanes); sub-steps 2..5 depend on it and stay in finish().
+    // p: [0..3) positions behind sub-step 1, [3..6) its velocities without the action term, [6..9) d(velocities) / d(action)
+    __device__ static void pre(const float (&o)[8], float eps, float (&p)[NPRE]) {
+        Sub k;
+        setup(o[1], o[2], k);
+        float q[3];
+        accel(k, o, 0.f, q);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            p[i] = fmaf(TAU, o[3 + i], o[i]);
+            p[3 + i] = fmaf(TAU, q[i], o[3 + i]);
+        }
+        p[6] = TAU * USCALE * k.i00; p[7] = TAU * USCALE * k.i01; p[8] = TAU * USCALE * k.i02;
+        (void)eps;
+    }
+    // tr: [sin t1, sin t2, cos t1, cos t2] of the new state (the reward needs them, the next network input is made of them)
+    __device__ static void finish(const float (&p)[NPRE], const float (&a)[2], float (&on)[8], float& rew, float (&tr)[4]) {
+        const float u = USCALE * a[0];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            on[i] = p[i];
+            on[3 + i] = fmaf(p[6 + i], a[0], p[3 + i]);
+        }
+        on[6] = on[7] = 0.f;
+#pragma unroll
+        for (int k = 1; k < NSUB; ++k) substep(on, u);
+        sincosf(on[1], &tr[0], &tr[2]);
+        sincosf(on[2], &tr[1], &tr[3]);
+        const float tip_x = on[0] + L1 * tr[0] + L2 * tr[1], tip_y = L1 * tr[2] + L2 * tr[3];
+        rew = -(0.01f * tip_x * tip_x + (tip_y - 2.f) * (tip_y - 2.f)) - (1e-3f * on[4] * on[4] + 5e-3f * on[5] * on[5]);
+    }
+
+    // adjoint of one rollout_out: lam_in = dL/d(new state), rho = dL/d(raw reward) -> dL/d(state), dL/d(action).
+    // The states entering sub-steps 2..5 are recomputed from the record into `adj` (ADJ floats of LDS owned by this lane:
+    // registers are allocated for all 512 lanes while 16 run this) and read back in reverse order.
+    // (tests/dp_oracle.py:dp_model_step_vjp is the float64 statement of the same formulas)
+    __device__ static void vjp(const float (&o)[8], const float (&a)[2], const float (&on)[8], const float (&lam_in)[8], float rho,
+                               float (&g)[8], float (&ga)[2], float* adj) {
+        const float u = USCALE * a[0];
+        float s[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s[i] = o[i];
+        for (int k = 1; k < NSUB; ++k) {
+            substep(s, u);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) adj[(k - 1) * 6 + i] = s[i];
+        }
+        // the reward is taken on the new state: fold it into that state's adjoint
+        float l[6];
+        {
+            float s1, c1, s2, c2;
+            sincosf(on[1], &s1, &c1);
+            sincosf(on[2], &s2, &c2);
+            const float tip_x = on[0] + L1 * s1 + L2 * s2, tip_y = L1 * c1 + L2 * c2;
+            const float dx = -0.02f * tip_x, dy = -2.f * (tip_y - 2.f);
+            l[0] = lam_in[0] + rho * dx;
+            l[1] = lam_in[1] + rho * (dx * L1 * c1 - dy * L1 * s1);
+            l[2] = lam_in[2] + rho * (dx * L2 * c2 - dy * L2 * s2);
+            l[3] = lam_in[3];
+            l[4] = lam_in[4] + rho * (-2e-3f * on[4]);
+            l[5] = lam_in[5] + rho * (-1e-2f * on[5]);
+        }
+        float gu = 0.f;
+        for (int k = NSUB - 1; k >= 0; --k) {
+            if (k > 0) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) s[i] = adj[(k - 1) * 6 + i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) s[i] = o[i];
+            }
+            Sub t;
+            setup(s[1], s[2], t);
+            float q[3];
+            accel(t, s, u, q);
+            const float w1 = s[4], w2 = s[5];
+            // z = dL/df = M^-1 (tau * dL/d(new velocities)); dL/dM_ij = -z_i q_j
+            const float m0 = TAU * l[3], m1 = TAU * l[4], m2 = TAU * l[5];
+            const float z0 = t.i00 * m0 + t.i01 * m1 + t.i02 * m2;
+            const float z1 = t.i01 * m0 + t.i11 * m1 + t.i12 * m2;
+            const float z2 = t.i02 * m0 + t.i12 * m1 + t.i22 * m2;
+            const float k01 = z0 * q[1] + z1 * q[0], k02 = z0 * q[2] + z2 * q[0], k12 = z1 * q[2] + z2 * q[1];
+            const float g_t1 = k01 * B * t.s1 + k12 * E * t.s12 + z0 * (B * w1 * w1 * t.c1) +
+                               z1 * (-E * w2 * w2 * t.c12 + G1 * t.c1) + z2 * (E * w1 * w1 * t.c12);
+            const float g_t2 = k02 * C * t.s2 - k12 * E * t.s12 + z0 * (C * w2 * w2 * t.c2) + z1 * (E * w2 * w2 * t.c12) +
+                               z2 * (-E * w1 * w1 * t.c12 + G2 * t.c2);
+            const float g_w1 = z0 * (2.f * B * w1 * t.s1) + z2 * (2.f * E * w1 * t.s12);
+            const float g_w2 = z0 * (2.f * C * w2 * t.s2) - z1 * (2.f * E * w2 * t.s12);
+            gu += z0;
+            l[3] += TAU * l[0];
+            l[4] += TAU * l[1] + g_w1;
+            l[5] += TAU * l[2] + g_w2;
+            l[1] += g_t1;
+            l[2] += g_t2;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) g[i] = l[i];
+        g[6] = g[7] = 0.f;
+        ga[0] = USCALE * gu;
+        ga[1] = 0.f;
+    }
+};
+
+// has_features<ENV>: the networks see ENV::features(state) (NFEAT entries) instead of the carried entries themselves
+template <class ENV> struct has_features { static constexpr bool value = false; };
+template <> struct has_features<DoublePendulum> { static constexpr bool value = true; };
+// floats of LDS per trajectory lane that ENV::vjp works in (0: its vjp takes none)
+template <class ENV> constexpr int adj_floats() {
+    if constexpr (has_features<ENV>::value) return ENV::ADJ; else return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // kernel argument blocks
 // ---------------------------------------------------------------------------------------------------------------
@@ -262,5 +471,7 @@ inline int grid_for(long ngroups) { return (int)(ngroups < 256 ? ngroups : 256);
 // prof (nullable): the caller's kernel timer
 int launch_rollout_fwd(const RollArgs& a, int env_kind, long ngroups, int n, hipStream_t s, mpg_prof_t* prof);
 int launch_rollout_bwd(const RollBwdArgs& a, int env_kind, long ngroups, int n, hipStream_t s, mpg_prof_t* prof);
+// feature models (has_features): out [T][R][NFEAT] = the first-layer inputs of the stashed steps, for the weight-gradient launch
+void launch_feature_inputs_double_pendulum(int T, long R, int rows, const float* obs0, const float* SA, float* out, hipStream_t s);
 
 }  // namespace rollout

@@ -10,6 +10,8 @@ namespace {
 template <class ENV, bool PK, bool WIDE = false>
 __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
     constexpr int OBS = ENV::OBS, ACT = ENV::ACT;
+    constexpr bool FEAT = has_features<ENV>::value;     // the networks see ENV::features(state); only the start observation is the batch's
+    static_assert(!FEAT || WIDE, "feature models run the 16-wide form");
     constexpr int NIN = WIDE ? 16 : OBS, XSW = xs_of<NIN>();
     const int nf = WIDE ? a.obs_dim - OBS : 0, OD = OBS + nf, QIN = OD + ACT;
     __shared__ __attribute__((aligned(16))) float smem[A_IMG + GROUP * XSW + NWAVE * GROUP * MAXOUT + MAXN * GROUP];
@@ -69,9 +71,13 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
             // (M == 1: the trajectory IS the batch row - no 64-bit modulo, ~150 instructions, in front of the first loads)
             const long brow = a.M == 1 ? tr : tr % a.rows;
             const float* src = a.obs0 + brow * OD;
+            if constexpr (FEAT) {
+                ENV::reset(src, o);
+            } else {
 #pragma unroll
             for (int i = 0; i < OBS; ++i) o[i] = src[i];
-            if constexpr (WIDE) {
+            }
+            if constexpr (WIDE && !FEAT) {
 #pragma unroll
                 for (int k = 0; k < MAXF; ++k) f0[k] = k < nf ? src[OBS + k] : 0.f;
             }
@@ -84,9 +90,13 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
             float chk = act_first[0] + act_first[1];
 #pragma unroll
             for (int i = 0; i < OBS; ++i) chk += o[i];
-            if constexpr (WIDE) {
+            if constexpr (WIDE && !FEAT) {
 #pragma unroll
                 for (int k = 0; k < MAXF; ++k) chk += f0[k];
+            }
+            if constexpr (FEAT) {       // every entry of the start observation reaches a network
+#pragma unroll
+                for (int i = 0; i < ENV::NFEAT; ++i) chk += src[i];
             }
             saw_nan |= chk != chk;
         }
@@ -140,7 +150,23 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
                 sX[tid * XSW + i] = v;
             }
         };
+        // feature models: the first input is the batch's own observation (re-read here: nothing else needs it in registers), every
+        // later one the features of the new state
+        auto publish_feat = [&](const float* x) {
+            if constexpr (FEAT) {
+#pragma unroll
+                for (int i = 0; i < XSW; ++i) {
+                    float v = 0.f;
+                    if (i < ENV::NFEAT) v = x ? x[i] * a.obs_scale[i] : 0.f;
+                    sX[tid * XSW + i] = v;
+                }
+            }
+        };
+        if constexpr (FEAT) {
+            if (chain) publish_feat(live ? a.obs0 + (a.M == 1 ? tr : tr % a.rows) * OD : nullptr);
+        } else {
         if (chain) publish(o, true);
+        }
         // The output bias was requested in the prologue; consumed HERE once, it is not a pending load anywhere in the step loop.
         // Left pending across the loop header, the wait-count bookkeeping re-waits for it in every step - `s_waitcnt vmcnt(4)` in the
         // middle of the serial chain, which in fact waits for the stash stores of the step before (the counter retires in order).
@@ -189,8 +215,15 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
                     float pre[ENV::NPRE];
 #pragma unroll
                     for (int i = 0; i < ENV::NPRE; ++i) pre[i] = sPre[tid * PRE_STRIDE + i];
+                    if constexpr (FEAT) {
+                        float trig[4], x[ENV::NFEAT];
+                        ENV::finish(pre, act, on, rew, trig);
+                        ENV::features(on, trig, x);
+                        publish_feat(x);
+                    } else {
                     ENV::finish(pre, act, on, rew);
                     publish(on, false);
+                    }
                 }
                 f32x4* tp = reinterpret_cast<f32x4*>(sTraj + tid * TRAJ_STRIDE);
                 tp[0] = f32x4{on[0], on[1], on[2], on[3]};
@@ -211,9 +244,22 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
                     for (int ks = 0; ks < MAXSEL; ++ks)
                         if (ks < a.n_sel && a.sel[ks] == t) {
                             float* xq = a.XQ + ((long)ks * R + tr) * QIN;
+                            if constexpr (FEAT) {       // (two of the 26 steps)
+                                float x[ENV::NFEAT];
+                                if (t == 0) {
+                                    const float* src = a.obs0 + (a.M == 1 ? tr : tr % a.rows) * OD;
+#pragma unroll
+                                    for (int i = 0; i < ENV::NFEAT; ++i) x[i] = src[i];
+                                } else {
+                                    ENV::features(o, x);
+                                }
+#pragma unroll
+                                for (int i = 0; i < ENV::NFEAT; ++i) xq[i] = x[i] * a.obs_scale[i];
+                            } else {
 #pragma unroll
                             for (int i = 0; i < OBS; ++i) xq[i] = o[i] * a.obs_scale[i];
-                            if constexpr (WIDE) {
+                            }
+                            if constexpr (WIDE && !FEAT) {
 #pragma unroll
                                 for (int k = 0; k < MAXF; ++k)
                                     if (k < nf) xq[OBS + k] = (t == 0 ? f0[k] : o[ENV::FUT_SRC]) * a.obs_scale[OBS + k];
@@ -241,15 +287,50 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
 
 }  // namespace
 
-// Compiled twice, like rollout_bwd.hip: as itself (path tracking) and through rollout_fwd_pendulum.hip (MPG_FWD_PENDULUM_PART)
-// for the pendulum instantiations, so that each environment's sweep gets its own scheduling flags (mpg_amd/build.py).
-#ifdef MPG_FWD_PENDULUM_PART
+// Compiled three times, like rollout_bwd.hip: as itself (path tracking), through rollout_fwd_pendulum.hip (MPG_FWD_PENDULUM_PART)
+// and through rollout_fwd_double_pendulum.hip (MPG_FWD_DOUBLE_PENDULUM_PART) for those models' instantiations, so that each
+// environment's sweep gets its own scheduling flags (mpg_amd/build.py).
+#if defined(MPG_FWD_DOUBLE_PENDULUM_PART)
+// first-layer inputs of the stashed steps for the weight-gradient launch: out [T][R][NFEAT], raw (the consumer applies the scale).
+// Step 0: the caller's batch row of the trajectory; steps t > 0: the features of the recorded state.
+namespace {
+template <class ENV>
+__global__ void k_feature_inputs(int T, long R, int rows, const float* __restrict__ obs0, const float* __restrict__ SA,
+                                 float* __restrict__ out) {
+    constexpr int NF = ENV::NFEAT;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;         // one (step, trajectory) each
+    if (idx >= (long)T * R) return;
+    const long tr = idx % R, t = idx / R;
+    float x[NF];
+    if (t == 0) {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) x[i] = obs0[(tr % rows) * NF + i];
+    } else {
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < ENV::OBS; ++i) s[i] = SA[idx * SAW + i];
+        ENV::features(s, x);
+    }
+#pragma unroll
+    for (int i = 0; i < NF; ++i) out[idx * NF + i] = x[i];
+}
+}  // namespace
+void launch_rollout_fwd_double_pendulum(const RollArgs& fa, long ngroups, hipStream_t s) {
+    if (fa.pack) hipLaunchKernelGGL((k_rollout_fwd<DoublePendulum, true, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa);
+    else hipLaunchKernelGGL((k_rollout_fwd<DoublePendulum, false, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa);
+}
+void launch_feature_inputs_double_pendulum(int T, long R, int rows, const float* obs0, const float* SA, float* out, hipStream_t s) {
+    const long nx = (long)T * R;
+    hipLaunchKernelGGL((k_feature_inputs<DoublePendulum>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, T, R, rows, obs0, SA, out);
+}
+#elif defined(MPG_FWD_PENDULUM_PART)
 void launch_rollout_fwd_pendulum(const RollArgs& fa, long ngroups, hipStream_t s) {
     if (fa.pack) hipLaunchKernelGGL((k_rollout_fwd<Pendulum, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa);
     else hipLaunchKernelGGL((k_rollout_fwd<Pendulum, false>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa);
 }
 #else
 void launch_rollout_fwd_pendulum(const RollArgs& fa, long ngroups, hipStream_t s);
+void launch_rollout_fwd_double_pendulum(const RollArgs& fa, long ngroups, hipStream_t s);
 
 int launch_rollout_fwd(const RollArgs& fa_in, int env_kind, long ngroups, int n, hipStream_t s, mpg_prof_t* prof) {
     RollArgs fa = fa_in;
@@ -265,6 +346,8 @@ int launch_rollout_fwd(const RollArgs& fa_in, int env_kind, long ngroups, int n,
         { if (fa.pack) hipLaunchKernelGGL((k_rollout_fwd<PathTracking, true, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa); else hipLaunchKernelGGL((k_rollout_fwd<PathTracking, false, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa); }
     else if (env_kind == MPG_ENV_PATH_TRACKING)
         { if (fa.pack) hipLaunchKernelGGL((k_rollout_fwd<PathTracking, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa); else hipLaunchKernelGGL((k_rollout_fwd<PathTracking, false>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, fa); }
+    else if (env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM)
+        launch_rollout_fwd_double_pendulum(fa, ngroups, s);
     else
         launch_rollout_fwd_pendulum(fa, ngroups, s);
     mpg_prof_end(prof, 0, s);

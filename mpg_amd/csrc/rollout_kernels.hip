@@ -342,7 +342,11 @@ extern "C" int mpg_rollout_pg(const mpg_cfg_t* cfg, const float* policy_params, 
     XSpec xs = policy_x(cfg, a.SA);
     xs.ld0 = SAW;
     if (od > 6) xs = policy_x(cfg, obs0);
-    if (a.XW) {
+    if (a.XW && cfg->env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM) {     // the model's features, not copies of an entry
+        launch_feature_inputs_double_pendulum(T, R, rows, obs0, a.SA, a.XW, s);
+        MPG_CHECK_LAUNCH("k_feature_inputs");
+        xs = policy_x(cfg, a.XW);
+    } else if (a.XW) {
         const long nx = (long)T * R * od;
         hipLaunchKernelGGL(k_wide_inputs, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, T, R, rows, od, PathTracking::OBS,
                            PathTracking::FUT_SRC, obs0, a.SA, a.XW);

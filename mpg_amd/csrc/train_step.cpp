@@ -181,6 +181,10 @@ extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, s
 
 extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
     MPG_REQUIRE(ctx_ok(c), "mpg_step_begin: incomplete context");
+    // the driver's first act is the worker's sample on the REAL env, which this model does not have: refused before anything is enqueued
+    MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
+                "mpg_step_begin: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
+                "samples it) does not serve this model; use the rollout entry points (NADPLearner) on caller-supplied batches");
     const Layout l = layout(c);
     const int od = c->cfg.obs_dim, ad = c->cfg.act_dim, kind = c->cfg.env_kind;
     const float* policy = c->params + l.off[l.n_nets - 1];

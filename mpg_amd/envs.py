@@ -6,7 +6,7 @@ import torch
 
 from . import _lib as L
 
-ENV_KIND = {'PathTracking-v0': 0, 'InvertedPendulumConti-v0': 1}
+ENV_KIND = {'PathTracking-v0': 0, 'InvertedPendulumConti-v0': 1, 'InvertedDoublePendulum-v2': 2}     # MPG_ENV_* (include/mpg_hip.h)
 
 
 class _DeviceVecEnv(object):
@@ -102,4 +102,9 @@ def make_env(env_id, num_agent=1, num_future_data=0, device='cuda', seed=0):
         return PathTrackingEnv(num_future_data=num_future_data, num_agent=num_agent, device=device, seed=seed)
     if env_id == 'InvertedPendulumConti-v0':
         return InvertedPendulumContiEnv(num_agent=num_agent, device=device, seed=seed)
+    if env_id == 'InvertedDoublePendulum-v2':
+        # only the differentiable MODEL of this env exists here (the rollout sweeps, NADPLearner): the real env is gym's MuJoCo
+        # InvertedDoublePendulum-v2, which is not provided, so there is nothing for a worker or an evaluator to step
+        raise ValueError('no device environment for %r: the real env is MuJoCo and not provided; only its differentiable model '
+                         'is (model rollouts, NADPLearner)' % (env_id,))
     raise ValueError('no device environment for %r (PathTracking-v0, InvertedPendulumConti-v0)' % (env_id,))

@@ -111,6 +111,8 @@ def make_cfg(env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift
     """Defaults are the reference's (train_script.py:202-306 / train_script4mujoco.py:296-411).  obs_dim: 6 + num_future_data
     for PathTracking (train_script.py:794-811), up to 16 (num_future_data <= 10, the env's own limit here)."""
     pt = env_id == 'PathTracking-v0'
+    if env_id == DOUBLE_PENDULUM:
+        return _double_pendulum_cfg(obs_scale, rew_scale, rew_shift, gamma, policy_out_activation, action_range)
     c = CfgStruct()
     c.obs_dim, c.act_dim = (int(obs_dim) if (pt and obs_dim) else 6, 2) if pt else (4, 1)
     if pt and not 6 <= c.obs_dim <= 16:
@@ -130,6 +132,28 @@ def make_cfg(env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift
     c.rew_shift = float(rew_shift)
     c.gamma = float(gamma)
     c.env_kind = 0 if pt else 1
+    return c
+
+
+DOUBLE_PENDULUM = 'InvertedDoublePendulum-v2'
+
+
+def _double_pendulum_cfg(obs_scale, rew_scale, rew_shift, gamma, policy_out_activation, action_range):
+    """The reference registers the model (envs_and_models/__init__.py:12-15) but ships no parser for this env, so the defaults are this
+    project's choice: unit observation scale, reward scale 1, linear policy output with action_range 1.0 - a = tanh(mean), the
+    model's own "think of actions are in range [-1, 1]" (inverted_double_pendulum_model.py:134).  Observation: the env's 11 entries
+    [p, sin t1, sin t2, cos t1, cos t2, pdot, t1dot, t2dot, frc x 3] (:105); one action."""
+    c = CfgStruct()
+    c.obs_dim, c.act_dim = 11, 1
+    c.policy_out_act = ACT_TANH if (policy_out_activation or 'linear') == 'tanh' else ACT_LINEAR
+    c.action_range = float((1.0 if action_range is None else action_range) or 0.0)
+    sc = obs_scale if obs_scale is not None else [1.] * 11
+    for i in range(16):
+        c.obs_scale[i] = float(sc[i]) if i < len(sc) else 1.0
+    c.rew_scale = float(rew_scale if rew_scale is not None else 1.0)
+    c.rew_shift = float(rew_shift)
+    c.gamma = float(gamma)
+    c.env_kind = 2       # MPG_ENV_INVERTED_DOUBLE_PENDULUM
     return c
 
 
