@@ -484,14 +484,39 @@ __device__ __forceinline__ void dx_partials(const SmallRegs<IN, OU>& r, const La
 }
 
 // ---- G16 stash ------------------------------------------------------------------------------------------
+// Cache policy of a stash access, chosen per call site (default: plain).  A stash is written once and read once, by another
+// launch.  StashStore::write_through (`sc1`) sends the line to memory at once instead of leaving it dirty in the writer's L2;
+// StashLoad::nontemporal (`nt`) marks a line that will not be read again.  Same values, same addresses.  Which call sites
+// use what was decided by alternating same-box runs per buffer (EXPERIMENTS.md, "Cache policy of the stashes"): only the
+// forward sweep's stores and the reverse sweep's loads of the PathTracking form gain; tests/test_cache_policy_isa.py pins it.
+enum class StashStore { plain, write_through };
+enum class StashLoad { plain, nontemporal };
+template <StashStore P = StashStore::plain>
 __device__ __forceinline__ void stash_store(float* __restrict__ base, long group, const Lane& L, const float (&v)[2][4]) {
     f32x4* p = reinterpret_cast<f32x4*>(base) + (group * 16 + 2 * L.wave) * 64 + L.lane;
-    p[0] = f32x4{v[0][0], v[0][1], v[0][2], v[0][3]};
-    p[64] = f32x4{v[1][0], v[1][1], v[1][2], v[1][3]};
+    const f32x4 a = {v[0][0], v[0][1], v[0][2], v[0][3]}, b = {v[1][0], v[1][1], v[1][2], v[1][3]};
+    if constexpr (P == StashStore::write_through) {
+        // both 16-byte stores on ONE address pair (p[64] = offset 1024); a 4-dword store reads its data registers late, so the
+        // string ends in the two wait states that keep the next instruction from overwriting them.  The stores are vector
+        // memory operations the compiler does not count: with in-order retirement its own waits only become stricter.
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:1024 sc1\n\ts_nop 1"
+                     :: "v"(p), "v"(a), "v"(b) : "memory");
+    } else {
+        p[0] = a;
+        p[64] = b;
+    }
 }
+template <StashLoad P = StashLoad::plain>
 __device__ __forceinline__ void stash_load(const float* __restrict__ base, long group, const Lane& L, float (&v)[2][4]) {
     const f32x4* p = reinterpret_cast<const f32x4*>(base) + (group * 16 + 2 * L.wave) * 64 + L.lane;
-    const f32x4 a = p[0], b = p[64];
+    f32x4 a, b;
+    if constexpr (P == StashLoad::nontemporal) {
+        a = __builtin_nontemporal_load(p);
+        b = __builtin_nontemporal_load(p + 64);
+    } else {
+        a = p[0];
+        b = p[64];
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         v[0][j] = a[j];
@@ -503,7 +528,7 @@ __device__ __forceinline__ void stash_load(const float* __restrict__ base, long 
 // sX  [16][XS]  inputs (already scaled), sA the LDS A image, sPart [NWAVE][16][MAXOUT] output partials.
 // On return h1/h2 hold this lane's C-layout activations and sPart the per-wave partial sums of h2*W3 (no bias);
 // the caller must have synchronised sX before the call and may read sPart right after (ends on a barrier).
-template <int IN, int OU, bool FINAL_BARRIER = true>
+template <int IN, int OU, bool FINAL_BARRIER = true, StashStore ST = StashStore::plain>
 __device__ __forceinline__ void forward_group(const float* sX, float* sA, float* sPart, const Lane& L,
                                               const float (&w2)[128], const SmallRegs<IN, OU>& r,
                                               float (&h1)[2][4], float (&h2)[2][4], float* h1_stash = nullptr,
@@ -523,7 +548,7 @@ __device__ __forceinline__ void forward_group(const float* sX, float* sA, float*
     store_c_to_a(sA, L, h1);
     // h1 is final here: its stash goes out now and drains under the MFMA block instead of queueing behind the h2
     // stash of all eight waves at the end of the step (the CU's store path moves 64 B/clk)
-    if (h1_stash) stash_store(h1_stash, stash_group, L, h1);
+    if (h1_stash) stash_store<ST>(h1_stash, stash_group, L, h1);
     MPG_STAMP_AT(1);
     lds_barrier();
     MPG_STAMP_AT(2);

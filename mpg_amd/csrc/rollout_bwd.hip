@@ -12,6 +12,9 @@ template <class ENV, bool PK, bool WIDE = false, bool THIN = false>
 __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a) {
     constexpr int OBS = ENV::OBS, ACT = ENV::ACT;
     static_assert(!(THIN && WIDE), "THIN is built for the base observation widths");
+    // H1 / H2 are read once and never again: non-temporal loads where that was measured to gain (rollout_common.h: streams_stash).
+    // The step-0 DZ1 / DZ2 stores stay plain: write-through measured null there, and k_wgrad_multi reads them next.
+    constexpr StashLoad LD = streams_stash<ENV, PK, WIDE, THIN>() ? StashLoad::nontemporal : StashLoad::plain;
     constexpr bool FEAT = has_features<ENV>::value;     // the networks see ENV::features(state): its adjoint folds their gradients
     static_assert(!FEAT || WIDE, "feature models run the 16-wide form");
     constexpr int NIN = WIDE ? 16 : OBS, XSW = xs_of<NIN>();
@@ -90,14 +93,14 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
 #pragma unroll
             for (int i = 0; i < 4; ++i) { rec_cur[i] = r0[i]; rec_cur[4 + i] = r1[i]; }
         }
-        stash_load(a.H2, (long)a.n * ngroups + g, L, h2_cur);
+        stash_load<LD>(a.H2, (long)a.n * ngroups + g, L, h2_cur);
         for (int t = a.n; t >= 0; --t) {
             float h1[2][4];
             // h1 of this step is requested at the TOP of the step: nothing older is pending here (the step before consumed its
             // prefetches when it copied them), nothing before the matrix block waits on the vector-memory counter, and the seven
             // waves that would only wait for the chain lanes at the first barrier put the request ~2 k cycles further ahead of
             // its use behind the matrix block - where the ISA showed a drained counter (vmcnt(0)) in every step.
-            stash_load(a.H1, (long)t * ngroups + g, L, h1);
+            stash_load<LD>(a.H1, (long)t * ngroups + g, L, h1);
             // ... and with it the record of step t - 1 (used at the end of this step): requested behind the dz2 phase it was two more
             // loads in flight at the drain in the matrix block
             if (t > 0 && live) {
@@ -199,7 +202,7 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_bwd(const RollBwdArgs a)
             // all global loads of the step are issued HERE, behind the dz2 phase: h1 is consumed after the MFMA block,
             // the record and h2 stash of step t-1 in the next iteration (software pipeline)
             if (t > 0) {
-                stash_load(a.H2, (long)(t - 1) * ngroups + g, L, h2_pre);
+                stash_load<LD>(a.H2, (long)(t - 1) * ngroups + g, L, h2_pre);
             }
             if (t > 0)
                 backward_rest<NIN, ACT, true>(sD3, sA, sA1, sPartX, L, w2t, r, h1, dz1);

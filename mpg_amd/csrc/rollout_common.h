@@ -396,6 +396,16 @@ struct DoublePendulum {
 // has_features<ENV>: the networks see ENV::features(state) (NFEAT entries) instead of the carried entries themselves
 template <class ENV> struct has_features { static constexpr bool value = false; };
 template <> struct has_features<DoublePendulum> { static constexpr bool value = true; };
+// streams_stash<ENV, PK, WIDE, THIN>(): whether this instantiation of a sweep gives its H1 / H2 stash a cache policy (mlp_core.h:
+// write-through stores in the forward sweep, non-temporal loads in the reverse sweep).  True for the one form where alternating
+// same-box runs showed a gain: PathTracking with cached weight images, base width (the bench step: 0.2227 -> 0.2142 ms).  The
+// pendulum model's NADP step at B = 8192 measured SLOWER with the same policies (0.618 -> 0.629 ms) and keeps the plain forms, and
+// so does every form that was not measured; the strided-weight instantiations (!PK) must keep them - the register allocator
+// crashes on the asm operands of the write-through store at their 120+ spilled registers (EXPERIMENTS.md, "Cache policy").
+template <class ENV, bool PK, bool WIDE, bool THIN = false>
+__host__ __device__ constexpr bool streams_stash() { return false; }
+template <>
+__host__ __device__ constexpr bool streams_stash<PathTracking, true, false, false>() { return true; }
 // floats of LDS per trajectory lane that ENV::vjp works in (0: its vjp takes none)
 template <class ENV> constexpr int adj_floats() {
     if constexpr (has_features<ENV>::value) return ENV::ADJ; else return 0;

@@ -11,6 +11,8 @@ template <class ENV, bool PK, bool WIDE = false>
 __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
     constexpr int OBS = ENV::OBS, ACT = ENV::ACT;
     constexpr bool FEAT = has_features<ENV>::value;     // the networks see ENV::features(state); only the start observation is the batch's
+    // the H1 / H2 stash leaves write-through where that was measured to gain (rollout_common.h: streams_stash)
+    constexpr StashStore ST = streams_stash<ENV, PK, WIDE>() ? StashStore::write_through : StashStore::plain;
     static_assert(!FEAT || WIDE, "feature models run the 16-wide form");
     constexpr int NIN = WIDE ? 16 : OBS, XSW = xs_of<NIN>();
     const int nf = WIDE ? a.obs_dim - OBS : 0, OD = OBS + nf, QIN = OD + ACT;
@@ -176,8 +178,8 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_rollout_fwd(const RollArgs a) {
             lds_barrier();
             MPG_STAMP_AT(0);
             float h1[2][4], h2[2][4];
-            forward_group<NIN, ACT, false>(sX, sA, sPart, L, w2, r, h1, h2, a.H1, (long)t * ngroups + g, nullptr, &zmax);
-            if (a.H1) stash_store(a.H2, (long)t * ngroups + g, L, h2);
+            forward_group<NIN, ACT, false, ST>(sX, sA, sPart, L, w2, r, h1, h2, a.H1, (long)t * ngroups + g, nullptr, &zmax);
+            if (a.H1) stash_store<ST>(a.H2, (long)t * ngroups + g, L, h2);
             // book lanes, before B2: fetch what the chain lanes left in sTraj (they overwrite it right after B2) and prepare
             // the action-independent half of this step's model step - the only part of their work the chain waits for
             float pa[2] = {0.f, 0.f}, prew = 0.f;
