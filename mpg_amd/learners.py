@@ -120,6 +120,15 @@ class MPGLearner(_LearnerBase):
         self.M = args.M
         self.num_rollout_list_for_policy_update = list(args.num_rollout_list_for_policy_update)
         self.deriv_interval_policy = bool(getattr(args, 'deriv_interval_policy', False))   # mpg_learner.py:247-248
+        # value_mean is the mean return of slice 0 whether or not 0 is in the list (mpg_learner.py:285).  Where it is not, the launches
+        # carry it as one more slice with weight exactly 0.0 (its dL/dQ coefficient is then an exact zero: no bit of the gradient moves)
+        # - if the statistics block has room for it (n_q losses + 2 sums per slice in 8 jobs, at most 4 slices); else value_mean is None
+        select, n_q = self.num_rollout_list_for_policy_update, len(self.policy_with_value.names) - 1
+        self._value_slice = 0 not in select and len(select) < 4 and n_q + 2 * (len(select) + 1) <= 8
+        if not self.deriv_interval_policy and not ops.mpg_gradients_supported(self.cfg, self.batch_size, self.M, max(select), len(select), n_q):
+            # the library's own answer at the first gradient (mpg_mpg_gradients), raised where the learner is built
+            raise ops.L.MpgError('MPG_EINVAL: mpg_mpg_gradients: too many statistics (n_select <= 3 with two critics) or an unsupported '
+                                 'horizon / slice count: num_rollout_list_for_policy_update %s with %d critic(s)' % (select, n_q))
         self.env = None
         if args.learner_version == 'MPG-v1':
             self.env = PathTrackingEnv(num_agent=self.batch_size, num_future_data=args.num_future_data, device=device)
@@ -196,6 +205,9 @@ class MPGLearner(_LearnerBase):
         inv_b = 1.0 / (rows * world)
         select = self.num_rollout_list_for_policy_update
         ws = rule_based_weights(iteration, self.args.rule_based_bias_total_ite, self.args.eta, select)
+        n = max(select)
+        if self._value_slice:
+            select, ws = select + [0], np.append(ws, np.float32(0.0))
         if self.deriv_interval_policy:
             # every rollout step goes through pi_theta (full BPTT, mpg_learner.py:247-248): the fine-grained entry points
             stats = self.flat[self.n_grad:]
@@ -204,7 +216,7 @@ class MPGLearner(_LearnerBase):
                                 inv_b_global=inv_b, grad_out=self.grad(nm), loss_out=stats[i:i + 1])
             ops.rollout_pg(self.cfg, pw.net('policy'), pw.net('Q1'), b['batch_obs'], eps, select, ws, M=self.M,
                            inv_b_global=inv_b, all_steps_param_grad=True, grad_out=self.grad('policy'),
-                           stats_out=stats[2:2 + 2 * len(select)], n=max(select), noise_seed=self.seed, noise_ctr=self.counter)
+                           stats_out=stats[2:2 + 2 * len(select)], n=n, noise_seed=self.seed, noise_ctr=self.counter)
             out = self._finish(iteration, float(self.args.gradient_clip_norm))
             self._lazy_stats = self._mpg_lazy_stats(iteration)
             return out
@@ -212,7 +224,7 @@ class MPGLearner(_LearnerBase):
         # were computed by get_batch_data (the reference caches them per batch, mpg_learner.py:402-403)
         ops.mpg_gradients(self.cfg, len(pw.names) - 1, pw.params, pw.targets, b['batch_obs'], b['batch_actions'],
                           b['batch_rewards'], b['batch_obs_tp1'], b['batch_targets'], select, ws, self.flat[:self.n_grad],
-                          self.flat[self.n_grad:], b['batch_targets'], M=self.M, n=max(select), eps=eps, noise_seed=self.seed,
+                          self.flat[self.n_grad:], b['batch_targets'], M=self.M, n=n, eps=eps, noise_seed=self.seed,
                           noise_ctr=self.counter, inv_b_global=inv_b)
         out = self._finish(iteration, float(self.args.gradient_clip_norm))
         self._lazy_stats = self._mpg_lazy_stats(iteration)
@@ -220,20 +232,24 @@ class MPGLearner(_LearnerBase):
 
     def _native_lazy_stats(self, iteration):
         """what the native step driver leaves in the statistics slots, as get_stats() reports it"""
-        return self._mpg_lazy_stats(iteration)
+        # (the driver forms the slice weights itself from the list as given: no weight-0 slice, value_mean None where 0 is not selected)
+        return self._mpg_lazy_stats(iteration, value_slice=False)
 
-    def _mpg_lazy_stats(self, iteration):
+    def _mpg_lazy_stats(self, iteration, value_slice=None):
         """stats of mpg_learner.py:433-452, evaluated only when get_stats() is called"""
         pw = self.policy_with_value
         select = self.num_rollout_list_for_policy_update
         ns, nq = len(select), len(pw.names) - 1
         stats = self.flat[self.n_grad:]
         B = self.batch_size * D.world_size()
+        value_slice = self._value_slice if value_slice is None else value_slice
 
         def lazy():
             ws = rule_based_weights(iteration, self.args.rule_based_bias_total_ite, self.args.eta, select)
             mean_ret = stats[2:2 + ns] / B
-            d = dict(iteration=iteration, value_mean=mean_ret[select.index(0)] if 0 in select else None,
+            # (the weight-0 slice 0 of _value_slice sits behind the list's own slices: reported as value_mean only)
+            value_mean = stats[2 + ns] / B if value_slice else (mean_ret[select.index(0)] if 0 in select else None)
+            d = dict(iteration=iteration, value_mean=value_mean,
                      policy_total_loss=-(torch.as_tensor(ws, device=self.device) * mean_ret).sum(),
                      policy_gradient_norm=self.norms[nq], q_loss1=stats[0], q_gradient_norm1=self.norms[0],
                      num_rollout_list=select, w_list=list(map(float, ws)), all_losses=-mean_ret)

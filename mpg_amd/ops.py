@@ -392,6 +392,11 @@ def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out
     return stats, grad
 
 
+def mpg_gradients_supported(cfg, rows, M, n, n_select, n_q):
+    """whether mpg_mpg_gradients serves these sizes: its workspace query answers 0 for what the entry point refuses"""
+    return L.lib().mpg_mpg_gradients_workspace_bytes(ctypes.byref(cfg), *[L.c_int(int(v)) for v in (rows, M, n, n_select, n_q)]) != 0
+
+
 def mpg_gradients(cfg, n_q, params, target_params, obs, act, rew, obs_tp1, y_in, select, w, grad, stats, y_out, M=1, n=None,
                   eps=None, noise_seed=0, noise_ctr=0, inv_b_global=None, sq_part=None):
     """mpg_mpg_gradients: MPGLearner.compute_gradient without the clip (targets unless y_in, critic grads, mixed PG)."""

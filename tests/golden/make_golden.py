@@ -18,6 +18,8 @@ same float32-rounded inputs - the error yard-stick of SURVEY.md §8c):
   mpg_{v1,v2}_H{H}_B{B}.npz   MPGLearner.compute_gradient (a11-a17) at iterations 100 and 9000
   mpg_v2_H256_B64_K3.npz      the same with num_future_data = 3 (obs_dim 9, first layers 9 / 11 wide)
   mpg_v2_H256_B64_K10.npz     the same with num_future_data = 10 (obs_dim 16, first layers 16 / 18 wide)
+  mpg_v2_H256_B64_sel0_5_25.npz (+ ..._it9000.npz)   the same with num_rollout_list_for_policy_update = [0, 5, 25]
+  mpg_v2_H32_B64_sel5_25.npz  the same with [5, 25]: value_mean when slice 0 is not selected
   nadp_H{H}_B{B}.npz     NADPLearner.compute_gradient on the pendulum model (a18)
   td3_H{H}_B{B}.npz      TD3Learner.compute_gradient with recorded smoothing noise (a19)
   segment_tree_ref.npz   SumSegmentTree / MinSegmentTree primitives (a22)
@@ -251,12 +253,17 @@ def make_replay_batch_pt(rng, B, K=0):
     return [obs, act, rew.astype(np.float32), obs2.astype(np.float32), done.astype(np.float32)]
 
 
-def fx_mpg(version, H, B, seed, K=0):
-    """K: num_future_data (train_script.py:90,146-147 - obs_dim 6 + K, obs_scale padded with ones); fixture ..._K{K}.npz"""
+def fx_mpg(version, H, B, seed, K=0, select=(0, 25), lean=False):
+    """K: num_future_data (train_script.py:90,146-147 - obs_dim 6 + K, obs_scale padded with ones); fixture ..._K{K}.npz
+    select: num_rollout_list_for_policy_update; any other list than [0, 25] names the fixture ..._sel{k}_{k}....npz
+    lean: a fixture of 256-unit nets inside the 1 MiB limit for a committed file - the network weights are not stored (seeded draws:
+    golden_inputs.mpg_fixture_weights(seed) regenerates them, `weights_seed`), the un-clipped policy gradient is left out, and the
+    keys of the second iteration go to a file of their own, ..._it9000.npz (golden_inputs.load_lean_mpg_fixture reads both)"""
     from learners.mpg_learner import MPGLearner
     from policy import PolicyWithQs
     rng = np.random.Generator(np.random.PCG64(seed))
     args = mpg_args(version, B, H)
+    args.num_rollout_list_for_policy_update = list(select)
     if K:
         args.num_future_data, args.obs_dim, args.obs_scale = K, 6 + K, OBS_SCALE_PT + [1.] * K
     nets = {'policy': mlp_weights(rng, 6 + K, H, 4), 'Q1': mlp_weights(rng, 8 + K, H, 1)}
@@ -302,7 +309,18 @@ def fx_mpg(version, H, B, seed, K=0):
             out['td_error'] = np.asarray(learner.compute_td_error())
     tf.set_ref_dtype(torch.float32)
     tf.set_noise_source(None)
-    np.savez_compressed(os.path.join(HERE, 'mpg_%s_H%d_B%d%s.npz' % (version[-2:], H, B, '_K%d' % K if K else '')), **out)
+    sel_tag = '' if list(select) == [0, 25] else '_sel' + '_'.join(str(k) for k in select)
+    path = os.path.join(HERE, 'mpg_%s_H%d_B%d%s%s.npz' % (version[-2:], H, B, '_K%d' % K if K else '', sel_tag))
+    if lean:
+        assert version == 'MPG-v2' and K == 0
+        from golden_inputs import mpg_fixture_weights
+        for k, v in mpg_fixture_weights(seed, H).items():
+            assert np.array_equal(out.pop('w_' + k), v), k
+        del out['it100_policy_grad_unclipped']
+        out['weights_seed'] = np.array(seed)
+        late = {k: out.pop(k) for k in list(out) if k.startswith('it9000_')}
+        np.savez_compressed(path[:-4] + '_it9000.npz', **late)
+    np.savez_compressed(path, **out)
 
 
 def fx_nadp(H, B, seed):
@@ -982,6 +1000,10 @@ ROUND2.update({n: (lambda n=n: fx_bench_case(n)) for n in BENCH_CASES})
 ROUND2['trained_c2'] = lambda: fx_bench_case('c2_mpg_v2_B4096', trained=True)      # round 3
 ROUND2['mpg_future'] = lambda: fx_mpg('MPG-v2', 256, 64, seed=12, K=3)               # round 3: num_future_data = 3
 ROUND2['mpg_future10'] = lambda: fx_mpg('MPG-v2', 256, 64, seed=13, K=10)           # round 4: num_future_data = 10 (obs_dim 16, critics 18 wide)
+# slice lists other than [0, 25]: a middle slice (the learners on the device run on this one), and a list without slice 0 (oracle
+# only: it pins that the reference reports value_mean = mean(all_model_returns[0]) whether or not 0 is selected, mpg_learner.py:285)
+ROUND2['mpg_sel3'] = lambda: fx_mpg('MPG-v2', 256, 64, seed=14, select=[0, 5, 25], lean=True)
+ROUND2['mpg_sel_no0'] = lambda: fx_mpg('MPG-v2', 32, 64, seed=15, select=[5, 25])
 ROUND2.update(apply_gradients=fx_apply_gradients, worker_sample=fx_worker_sample,           # round 6: the reference's own loop code
               loop_v2=lambda: fx_loop('v2'), loop_nadp=lambda: fx_loop('nadp'), loop_td3=lambda: fx_loop('td3'), loop_v1=lambda: fx_loop('v1'), per_buffer=fx_per_buffer,
               loop_v2k3=lambda: fx_loop('v2k3'))

@@ -40,6 +40,21 @@ def mlp_weights_list(rng, din, H, dout, bias_jitter=0.05):
             orthogonal(rng, H, dout, 1.), (bias_jitter * rng.standard_normal(dout)).astype(np.float32)]
 
 
+def mpg_fixture_weights(seed, H=256):
+    """the networks of make_golden.fx_mpg('MPG-v2', H, ..., seed) with num_future_data 0: its first draws, flat Keras order"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return {'policy': mlp_weights_flat(rng, 6, 4, H), 'Q1': mlp_weights_flat(rng, 8, 1, H), 'Q2': mlp_weights_flat(rng, 8, 1, H)}
+
+
+def load_lean_mpg_fixture(golden, name):
+    """a `lean` fixture of make_golden.fx_mpg as one dict with the keys of mpg_v2_H256_B64.npz (but it100_policy_grad_unclipped):
+    both of its files, and the weights regenerated from the stored seed"""
+    g = golden(name)
+    g.update(golden(name[:-4] + '_it9000.npz'))
+    g.update({'w_' + k: v for k, v in mpg_fixture_weights(int(g['weights_seed'])).items()})
+    return g
+
+
 BENCH_CASES = {            # name -> (learner, B, seed)
     'c2_mpg_v2_B4096': ('MPG-v2', 4096, 101),
     'c3_nadp_B8192': ('NADP', 8192, 102),

@@ -139,3 +139,21 @@ def test_workspace_one_byte_short_is_refused_with_both_sizes(name, query, obs_di
     refused = ops.make_cfg('PathTracking-v0', obs_dim=obs_dim, policy_out_activation='tanh', action_range=1.0)
     assert q(ctypes.byref(refused), *[I(v) for v in sizes]) == 0
     assert q(ctypes.byref(cfg), I(0), *[I(v) for v in sizes[1:]]) == 0
+
+
+def test_two_critics_with_four_slices_are_refused_before_any_launch():
+    """mpg_mpg_gradients reduces n_q losses + 2 sums per slice in 8 jobs: two critics with MAXSEL = 4 slices do not fit.  The workspace
+    query answers 0 and the entry point MPG_EINVAL with a message that says why - from the host-side checks (every pointer is FAKE:
+    a launch would fault).  One critic with four slices (9 jobs) is refused alike; three slices are served with either count."""
+    lib = L.lib()
+    cfg = _pt()
+    q = lib.mpg_mpg_gradients_workspace_bytes
+    assert q(ctypes.byref(cfg), I(ROWS), I(1), I(25), I(4), I(2)) == 0
+    assert q(ctypes.byref(cfg), I(ROWS), I(1), I(25), I(4), I(1)) == 0
+    assert q(ctypes.byref(cfg), I(ROWS), I(1), I(25), I(3), I(1)) > 0 and q(ctypes.byref(cfg), I(ROWS), I(1), I(25), I(3), I(2)) > 0
+    sel4, w4 = (I * 4)(0, 1, 24, 25), (F * 4)(0.2, 0.3, 0.4, 0.5)
+    rc = lib.mpg_mpg_gradients(ctypes.byref(cfg), I(2), FAKE, FAKE, I(ROWS), FAKE, FAKE, FAKE, FAKE, NULL, I(1), I(25), sel4, I(4), w4, NULL,
+                               U64(1), U64(0), F(1.0 / ROWS), FAKE, FAKE, FAKE, NULL, NULL, FAKE, SZ(1 << 40), NULL)
+    msg = lib.mpg_last_error().decode()
+    assert rc == -1000, (rc, msg)                # MPG_EINVAL
+    assert msg.startswith('mpg_mpg_gradients:') and 'too many statistics' in msg, msg

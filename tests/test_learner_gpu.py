@@ -20,11 +20,11 @@ def dev(x):
     return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(DEV)
 
 
-def _learner(g, version, B=64, K=0):
+def _learner(g, version, B=64, K=0, **kw):
     from mpg_amd.config import default_args
     from mpg_amd.learners import MPGLearner
     from mpg_amd.policy import PolicyWithQs
-    args = default_args('MPG-' + version, replay_batch_size=B, num_batch_reuse=1, num_future_data=K)
+    args = default_args('MPG-' + version, replay_batch_size=B, num_batch_reuse=1, num_future_data=K, **kw)
     learner = MPGLearner(PolicyWithQs, args)
     pw = learner.policy_with_value
     flat = np.concatenate([g['w_' + n] for n in pw.names])
@@ -64,6 +64,105 @@ def test_compute_gradient_vs_reference_golden(golden, version, K):
         Y.check_values(learner.batch_data['batch_targets'].cpu().numpy(), g[p + 'targets'], g[p + 'targets_f64'],
                        what='targets MPG-%s' % version)
     np.testing.assert_allclose(learner.compute_td_error().cpu().numpy(), g['td_error'], rtol=1e-4, atol=2e-5)
+
+
+@pytest.fixture(params=['split', 'f32'])
+def engine(request):
+    """both builds of the library (mpg_amd/_lib.py ENGINES): the split-fp16 product and the exact-fp32 engine"""
+    from mpg_amd import _lib as L
+    with L.engine(request.param):
+        yield request.param
+
+
+def test_compute_gradient_three_slices_vs_reference_golden(golden, engine):
+    """num_rollout_list_for_policy_update = [0, 5, 25] on the reference's fixture (weights [5.6e-6, 1.1e-5, 0.99998] at iteration 100,
+    [0.9967, 3.3e-3, 2.4e-6] at 9000): mpg_mpg_gradients' path for n_select != 2, checked exactly as
+    test_compute_gradient_vs_reference_golden checks the [0, 25] fixtures."""
+    from tests.golden_inputs import load_lean_mpg_fixture
+    g = load_lean_mpg_fixture(golden, 'mpg_v2_H256_B64_sel0_5_25.npz')
+    learner = _learner(g, 'v2', num_rollout_list_for_policy_update=[0, 5, 25])
+    pw = learner.policy_with_value
+    batch = [dev(g[k]) for k in ('batch_obs', 'batch_actions', 'batch_rewards', 'batch_obs_tp1', 'batch_dones')]
+    for it in (100, 9000):
+        learner.counter = 0
+        grads = learner.compute_gradient(batch, None, None, it, eps=dev(g['eps']))
+        assert len(grads) == 18
+        got = torch.cat([x.reshape(-1) for x in grads]).cpu().numpy()
+        p = 'it%d_' % it
+        worst = Y.check_gradients(got, g[p + 'grads'], g[p + 'grads_f64'], [(n,) + tuple(pw.dims[n]) for n in pw.names],
+                                  where='%s [0, 5, 25] it %d' % (engine, it))
+        print('%s [0, 5, 25] it %d: worst error / allowance %.3f' % (engine, it, worst))
+        st = learner.get_stats()
+        for k in ('value_mean', 'policy_total_loss', 'policy_gradient_norm', 'q_loss1', 'q_gradient_norm1', 'q_loss2', 'q_gradient_norm2'):
+            np.testing.assert_allclose(st[k], g[p + k], rtol=2e-5, atol=1e-6, err_msg=k)
+        assert len(st['w_list']) == 3 and len(st['all_losses']) == 3
+        np.testing.assert_allclose(st['w_list'], g[p + 'w_list'], rtol=1e-5, atol=1e-9)
+        np.testing.assert_allclose(st['all_losses'], g[p + 'all_losses'], rtol=2e-5, atol=1e-6)
+        Y.check_values(learner.batch_data['batch_targets'].cpu().numpy(), g[p + 'targets'], g[p + 'targets_f64'], what='targets')
+    np.testing.assert_allclose(learner.compute_td_error().cpu().numpy(), g['td_error'], rtol=1e-4, atol=2e-5)
+
+
+@pytest.mark.parametrize('bptt', [False, True], ids=['fused', 'deriv_interval_policy'])
+def test_value_mean_without_slice_0_in_the_list(golden, bptt):
+    """The reference reports value_mean = mean(all_model_returns[0]) whether or not 0 is selected (mpg_learner.py:285; pinned for the
+    oracle by the [5, 25] fixture, tests/test_oracle_golden.py).  The learner carries slice 0 as one more slice with weight exactly
+    0.0 where the statistics block has room: value_mean is slice 0's mean return (against the float64 oracle), w_list / all_losses
+    keep the list's own length, and the gradient is the one of the launch without that slice - bit for bit where the launch sequence
+    is the same for any slice count (mpg_rollout_pg: here and in the deriv_interval_policy learner), to the gradient bar through
+    mpg_mpg_gradients, where three slices take other kernels than two."""
+    from mpg_amd import ops
+    g = golden('mpg_v2_H256_B64.npz')
+    sel = [5, 25]
+    learner = _learner(g, 'v2', num_rollout_list_for_policy_update=sel, deriv_interval_policy=bptt)
+    assert learner._value_slice
+    pw = learner.policy_with_value
+    batch = [dev(g[k]) for k in ('batch_obs', 'batch_actions', 'batch_rewards', 'batch_obs_tp1', 'batch_dones')]
+    eps, it = dev(g['eps']), 4000
+    learner.compute_gradient(batch, None, None, it, eps=eps)
+    with_slice, st = learner.flat_grad.clone(), learner.get_stats()
+    learner._value_slice = False                      # the launch without the extra slice
+    learner.counter = 0
+    learner.compute_gradient(batch, None, None, it, eps=eps)
+    without, st0 = learner.flat_grad.clone(), learner.get_stats()
+    assert st0['value_mean'] is None and len(st['w_list']) == len(st['all_losses']) == 2
+    tol = dict(rtol=0, atol=0) if bptt else dict(rtol=2e-5, atol=1e-6)
+    np.testing.assert_allclose(st['all_losses'], st0['all_losses'], **tol)
+    np.testing.assert_allclose(st['policy_total_loss'], st0['policy_total_loss'], **tol)
+    assert st['w_list'] == st0['w_list']
+    ocfg = O.Cfg(select=sel)
+    nets = O.Nets(ocfg, {n: g['w_' + n] for n in pw.names}, target_scale=g['target_scale'], dtype=torch.float64)
+    reduced, _, _ = O.model_rollout_for_policy_update(ocfg, nets, torch.as_tensor(g['batch_obs']).double(), torch.as_tensor(g['eps']).double(),
+                                                      rollout_policy='policy' if bptt else 'policy_rollout')
+    np.testing.assert_allclose(st['value_mean'], reduced[0].item(), rtol=2e-5, atol=1e-6)
+    np.testing.assert_allclose(st['all_losses'], -reduced[sel].detach().numpy(), rtol=2e-5, atol=1e-6)
+    if bptt:
+        assert torch.equal(with_slice, without)
+    else:
+        off = pw.offsets
+        for i, n in enumerate(pw.names):
+            e = rel_l2(with_slice[off[i]:off[i + 1]].cpu().numpy(), without[off[i]:off[i + 1]].cpu().numpy())
+            print('   %s: with vs without the weight-0 slice %.2e' % (n, e))
+            assert e <= 5e-5, (n, e)
+    # the entry point itself: a weight of exactly 0.0 moves no bit of the gradient or of the other slices' statistics
+    w = np.array([0.4, 0.6, 0.0], np.float32)
+    a = [x.clone() for x in ops.rollout_pg(pw.cfg, pw.net('policy'), pw.net('Q1'), batch[0], eps, sel + [0], w)]
+    b = ops.rollout_pg(pw.cfg, pw.net('policy'), pw.net('Q1'), batch[0], eps, sel, w[:2])
+    assert torch.equal(a[2], b[2]) and torch.equal(a[0][:2], b[0]) and torch.equal(a[1][:2], b[1])
+
+
+def test_unsupported_slice_count_is_refused_where_the_learner_is_built():
+    """two critics with four slices (mpg_mpg_gradients: n_q + 2 n_select <= 8): the library's refusal at construction, not at the
+    first gradient; with three slices and no room for the weight-0 slice the learner is built and value_mean stays None"""
+    import mpg_amd._lib as L
+    from mpg_amd.config import default_args
+    from mpg_amd.learners import MPGLearner
+    from mpg_amd.policy import PolicyWithQs
+    with pytest.raises(L.MpgError, match='mpg_mpg_gradients: too many statistics'):
+        MPGLearner(PolicyWithQs, default_args('MPG-v2', replay_batch_size=64, num_rollout_list_for_policy_update=[0, 1, 24, 25]))
+    learner = MPGLearner(PolicyWithQs, default_args('MPG-v2', replay_batch_size=64, num_rollout_list_for_policy_update=[3, 5, 25]))
+    assert not learner._value_slice
+    one = MPGLearner(PolicyWithQs, default_args('MPG-v1', replay_batch_size=64, num_rollout_list_for_policy_update=[5, 25]))
+    assert one._value_slice
 
 
 def test_replay_buffer_vs_the_references_own_buffer(golden):
@@ -464,12 +563,13 @@ def test_training_loop_with_look_ahead_observations(fused, K):
     pw.check_status()
 
 
-@pytest.mark.parametrize('alg', ['MPG-v2', 'MPG-v1'])
+@pytest.mark.parametrize('alg', ['MPG-v2', 'MPG-v1', 'MPG-v2-sel0_5_25'])
 def test_native_step_driver_equals_method_by_method_path(alg):
     """mpg_step_begin/_end enqueue the same launches as the python classes: after the same number of iterations the
     counters and the replay ring are identical, and parameters / Adam moments / targets agree to float32 rounding (the
     host-side scalars - rule-based weights, bias-corrected learning rates - are evaluated by libm in one path and by
-    numpy in the other, which may differ in the last bit)."""
+    numpy in the other, which may differ in the last bit).  'MPG-v2-sel0_5_25': MPG-v2 with num_rollout_list_for_policy_update
+    [0, 5, 25] - the driver's own statement of the rule-based weights (train_step.cpp) for three slices."""
     from mpg_amd.buffer import ReplayBuffer
     from mpg_amd.config import default_args
     from mpg_amd.learners import MPGLearner
@@ -477,9 +577,13 @@ def test_native_step_driver_equals_method_by_method_path(alg):
     from mpg_amd.policy import PolicyWithQs
     from mpg_amd.worker import OffPolicyWorker
 
+    extra = {}
+    if alg == 'MPG-v2-sel0_5_25':
+        alg, extra = 'MPG-v2', dict(num_rollout_list_for_policy_update=[0, 5, 25])
+
     def run(fused):
         args = default_args(alg, num_agent=64, batch_size=128, replay_batch_size=96, replay_starts=512, max_buffer_size=1000,
-                            num_batch_reuse=2 if alg == 'MPG-v1' else 1)
+                            num_batch_reuse=2 if alg == 'MPG-v1' else 1, **extra)
         worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
         learner = MPGLearner(PolicyWithQs, args)
         rb = ReplayBuffer(args, 0)

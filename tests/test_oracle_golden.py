@@ -128,6 +128,52 @@ def test_mpg_compute_gradient(golden, version, H, K):
     np.testing.assert_allclose(td.numpy(), g['td_error'], rtol=1e-4, atol=2e-6)
 
 
+@pytest.mark.parametrize('H,select', [(256, [0, 5, 25]), (32, [5, 25])])
+def test_mpg_compute_gradient_other_slice_lists(golden, H, select):
+    """num_rollout_list_for_policy_update = [0, 5, 25] (a middle slice: weights [5.6e-6, 1.1e-5, 0.99998] at iteration 100,
+    [0.9967, 3.3e-3, 2.4e-6] at 9000) and [5, 25]: the reference reports value_mean = mean(all_model_returns[0]) whether or not slice 0
+    is selected (mpg_learner.py:285).  Checked as test_mpg_compute_gradient checks the [0, 25] fixtures, and at H = 256 by the whole
+    rule of tests/yardstick.py on the float64 subsample; at H = 32 the float64 graph must match the reference's float64 run."""
+    from tests import yardstick as Y
+    from tests.golden_inputs import load_lean_mpg_fixture
+    name = 'mpg_v2_H%d_B64_sel%s.npz' % (H, '_'.join(str(k) for k in select))
+    g = load_lean_mpg_fixture(golden, name) if H == 256 else golden(name)
+    cfg = O.Cfg(H=H, select=select)
+    names = ['Q1', 'Q2', 'policy']
+    batch = [g['batch_obs'], g['batch_actions'], g['batch_rewards'], g['batch_obs_tp1'], g['batch_dones']]
+    for it in (100, 9000):
+        nets = _nets(g, cfg, names, torch.float32)
+        grads, st = O.mpg_compute_gradient(cfg, nets, batch, g['eps'], it)
+        p = 'it%d_' % it
+        assert g[p + 'w_list'].shape == (len(select),) and g[p + 'all_losses'].shape == (len(select),)
+        np.testing.assert_allclose(st['w_list'], g[p + 'w_list'], rtol=1e-5, atol=1e-9)
+        np.testing.assert_allclose(st['targets'], g[p + 'targets'], rtol=2e-5, atol=2e-6)
+        np.testing.assert_allclose(st['all_losses'], g[p + 'all_losses'], rtol=2e-5, atol=1e-6)
+        for k in ('value_mean', 'policy_total_loss', 'policy_gradient_norm', 'q_loss1', 'q_gradient_norm1', 'q_loss2', 'q_gradient_norm2'):
+            np.testing.assert_allclose(st[k], g[p + k], rtol=5e-5, atol=1e-7, err_msg=k)
+        _check_grads(grads, g, p + 'grads', cfg, names, H)
+        if H == 256:
+            Y.check_gradients(np.concatenate([x.ravel() for x in grads]), g[p + 'grads'], g[p + 'grads_f64'],
+                              [('Q1', 8, 1), ('Q2', 8, 1), ('policy', 6, 4)], where='%s it%d' % (name, it))
+        else:
+            nets64 = _nets(g, cfg, names, torch.float64)
+            grads64, st64 = O.mpg_compute_gradient(cfg, nets64, batch, g['eps'], it)
+            assert rel_l2(np.concatenate([x.ravel() for x in grads64]), g[p + 'grads_f64']) <= 2e-7
+            np.testing.assert_allclose(st64['value_mean'], g[p + 'value_mean_f64'], rtol=2e-7)       # (the bar of the float64 gradients above)
+        if 0 not in select:      # value_mean is slice 0's mean return all the same: none of the selected ones
+            assert min(abs(float(g[p + 'value_mean']) + float(l)) for l in g[p + 'all_losses']) > 1e-3 * abs(float(g[p + 'value_mean']))
+    nets = _nets(g, cfg, names, torch.float32)
+    td = O.td_error(cfg, nets, *[torch.as_tensor(b) for b in batch[:4]])
+    np.testing.assert_allclose(td.numpy(), g['td_error'], rtol=1e-4, atol=2e-6)
+
+
+def test_lean_fixture_files_are_within_the_committed_file_limit():
+    import os
+    from tests.conftest import GOLDEN
+    for f in ('mpg_v2_H256_B64_sel0_5_25.npz', 'mpg_v2_H256_B64_sel0_5_25_it9000.npz', 'mpg_v2_H32_B64_sel5_25.npz'):
+        assert os.path.getsize(os.path.join(GOLDEN, f)) <= 1 << 20, f
+
+
 def test_mpg_v1_real_env_nstep_rollout(golden):
     g = golden('mpg_v1_H32_B64.npz')
     cfg = O.Cfg(H=32)
@@ -211,17 +257,33 @@ def test_segment_tree(golden):
 
 
 # ---- rule-based weights against the reference's own numpy cross-statement --------------------------
+SLICE_LISTS = ([0, 25], [0, 5, 25], [5, 25], [0, 1, 24, 25], [25, 0, 5])     # both lam branches and the clamp, over WEIGHT_ITERATIONS
+WEIGHT_ITERATIONS = (0, 100, 4499, 4500, 4501, 9000)
+
+
 def test_rule_based_weights_cross_statement():
     """mpg_learner.py:463-477 restates the rule in numpy (with clip upper bound 1+eta instead of 1.5:
-    SURVEY B-8; identical for ite <= total_ite)."""
-    sel, eta, T = [0, 25], 0.1, 9000
-    for ite in (0, 100, 4499, 4500, 4501, 9000):
-        lam = np.clip(1 - eta + 2 * eta * ite / T, 0, 1 + eta)
-        b = np.array([lam ** i for i in sel]) if lam < 1 else np.array([(2 - lam) ** (max(sel) - i) for i in sel])
-        inv = 1. / (b + 1e-8)
-        w = np.exp(inv - inv.max()) / np.exp(inv - inv.max()).sum()
-        got = O.rule_based_weights(ite, T, eta, sel).numpy()
-        np.testing.assert_allclose(got, w, rtol=2e-4, atol=1e-7)
+    SURVEY B-8; identical for ite <= total_ite).  Lists with a middle slice, without slice 0, with MAXSEL slices, unsorted."""
+    eta, T = 0.1, 9000
+    for sel in SLICE_LISTS:
+        for ite in WEIGHT_ITERATIONS:
+            lam = np.clip(1 - eta + 2 * eta * ite / T, 0, 1 + eta)
+            b = np.array([lam ** i for i in sel]) if lam < 1 else np.array([(2 - lam) ** (max(sel) - i) for i in sel])
+            inv = 1. / (b + 1e-8)
+            w = np.exp(inv - inv.max()) / np.exp(inv - inv.max()).sum()
+            got = O.rule_based_weights(ite, T, eta, sel).numpy()
+            np.testing.assert_allclose(got, w, rtol=2e-4, atol=1e-7, err_msg=str((sel, ite)))
+
+
+def test_rule_based_weights_product_statement_vs_oracle():
+    """mpg_amd.learners.rule_based_weights (numpy float32, what the learners hand the kernels) against the oracle on the same grid"""
+    from mpg_amd.learners import rule_based_weights
+    eta, T = 0.1, 9000
+    for sel in SLICE_LISTS:
+        for ite in WEIGHT_ITERATIONS:
+            got = rule_based_weights(ite, T, eta, sel)
+            assert got.dtype == np.float32 and got.shape == (len(sel),)
+            np.testing.assert_allclose(got, O.rule_based_weights(ite, T, eta, sel).numpy(), rtol=2e-4, atol=1e-7, err_msg=str((sel, ite)))
 
 
 def test_adam_restatement_cross_checked_against_an_independent_adam():
