@@ -30,28 +30,49 @@ struct Args {
     uint32_t k0, k1, c1, c2;   // exploration-noise key and counter
     float scale[8];            // obs_scale (1 beyond obs_dim)
 };
+// the same for observations with look-ahead entries (obs_dim 7 .. 16: the 16-wide first layer).  A struct of its own: the six-wide
+// kernels' arguments stay where they are.
+struct WideArgs {
+    const float* params;
+    const float* pack;
+    int* status;
+    int out_tanh;
+    float out_scale, sigma;
+    uint32_t k0, k1, c1, c2;
+    int obs_dim;               // the network's actual input width = the row stride of the observations
+    float scale[16];           // obs_scale (1 beyond obs_dim)
+};
+// IN = 6: six-entry observations; IN = 16 stands for "7 .. 16 entries, the actual width is WideArgs::obs_dim" (mlp_core.h)
+template <int IN> struct args_of { typedef Args type; };
+template <> struct args_of<16> { typedef WideArgs type; };
+__device__ __forceinline__ constexpr int obs_dim_of(const Args&) { return 6; }
+__device__ __forceinline__ int obs_dim_of(const WideArgs& a) { return a.obs_dim; }
 
-constexpr int SMEM_FLOATS = A_IMG + GROUP * 8 + NWAVE * GROUP * MAXOUT;
+template <int IN>
+__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * xs_of<IN>() + NWAVE * GROUP * MAXOUT; }
 
-// One 16-row group of mpg_policy_action: k_forward<6, 2, PK, 1> (mlp_kernels.hip) for unit g - the same device functions on the
-// same operands in the same order, so the actions are bit-identical to the stand-alone launch's (tests: native step driver ==
-// method-by-method path).  The group's actions go to act_out (global) and to sAct [16][2] for the env lanes of wave 0.
-template <bool PK>
-__device__ __forceinline__ void group(const Args& a, int rows, const float* __restrict__ obs, long g, float* smem, float* sAct,
-                                      float* __restrict__ act_out) {
-    constexpr int IN = 6, OU = 2, XSW = 8;
+// One 16-row group of mpg_policy_action: k_forward<6, 2, PK, 1> or k_forward<16, 2, PK, 1> (mlp_kernels.hip) for unit g - the same
+// device functions on the same operands in the same order, so the actions are bit-identical to the stand-alone launch's (tests:
+// native step driver == method-by-method path, tests/test_worker_wide.py).  The group's actions go to act_out (global) and to
+// sAct [16][2] for the env lanes of wave 0.
+template <bool PK, int IN>
+__device__ __forceinline__ void group(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g, float* smem,
+                                      float* sAct, float* __restrict__ act_out) {
+    static_assert(IN == 6 || IN == 16, "the worker launch is built for six-entry observations and for the 16-wide first layer");
+    constexpr int OU = 2, XSW = xs_of<IN>();
+    const int od = obs_dim_of(a);              // a constant at IN = 6
     float* sA = smem;
     float* sX = sA + A_IMG;
     float* sPart = sX + GROUP * XSW;
     const Lane L;
-    const Net net = make_net(a.params, IN, 2 * OU);
+    const Net net = make_net(a.params, od, 2 * OU);
     float w2[128];
     SmallRegs<IN, OU> r;
     float xv = 0.f;
-    if (threadIdx.x < GROUP * XSW) {
+    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 stay zero)
         const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
         const long gr = g * GROUP + row;
-        if (gr < rows && i < IN) xv = obs[gr * IN + i] * a.scale[i];
+        if (gr < rows && i < od) xv = obs[gr * od + i] * a.scale[i];
     }
     float b3v = 0.f;
     if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
@@ -595,42 +616,49 @@ __global__ void __launch_bounds__(64) k_step_store_reset_1(int n, float* __restr
 // workgroup, then env.step -> ring -> env.reset of those 16 agents by the four-lane form on wave 0 (k_step_store_reset's body).  The
 // stand-alone pair is two launches of one wave per CU each (7 + 14 us at 4096 agents); fused, the env lanes start the moment their
 // group's actions exist.  Blocks beyond the policy groups gather the minibatch about to be drawn (predraw_row).
-template <bool PK>
-__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(const worker_policy::Args pa, int n, float* __restrict__ st,
-                                                                              float* __restrict__ obs_io, float* __restrict__ act_out,
-                                                                              RingPtrs ring, int capacity, int next_idx, uint32_t k0,
-                                                                              uint32_t k1, uint32_t c1, uint32_t c2,
-                                                                              uint8_t* __restrict__ done_out, PreDraw pd) {
-    if ((int)blockIdx.x >= pd.env_blocks) {
-        const int gr = ((int)blockIdx.x - pd.env_blocks) * mlp::NTHREAD + threadIdx.x;
-        if (gr < pd.rows) predraw_row(pd, ring, capacity, next_idx, n, gr);
-        return;
+// IN = 6: six-entry observations.  IN = 16: observations with look-ahead entries (obs_dim 7 .. 16 = pa.obs_dim, the row stride of
+// obs_io and of the ring's observation arrays) on the 16-wide first layer; these instantiations gather no draw (predraw_row is
+// six-wide, and the gradient launch that would consume the rows does not exist at these widths): their grid is the policy groups
+// and pd is not read.
+template <bool PK, int IN = 6>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(const typename worker_policy::args_of<IN>::type pa, int n,
+                                                                              float* __restrict__ st, float* __restrict__ obs_io,
+                                                                              float* __restrict__ act_out, RingPtrs ring, int capacity,
+                                                                              int next_idx, uint32_t k0, uint32_t k1, uint32_t c1,
+                                                                              uint32_t c2, uint8_t* __restrict__ done_out, PreDraw pd) {
+    if constexpr (IN == 6) {
+        if ((int)blockIdx.x >= pd.env_blocks) {
+            const int gr = ((int)blockIdx.x - pd.env_blocks) * mlp::NTHREAD + threadIdx.x;
+            if (gr < pd.rows) predraw_row(pd, ring, capacity, next_idx, n, gr);
+            return;
+        }
     }
-    __shared__ __attribute__((aligned(16))) float smem[worker_policy::SMEM_FLOATS];
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN>()];
     __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
     __shared__ float sAct[mlp::GROUP * 2];
-    worker_policy::group<PK>(pa, n, obs_io, blockIdx.x, smem, sAct, act_out);
+    worker_policy::group<PK, IN>(pa, n, obs_io, blockIdx.x, smem, sAct, act_out);
     if (threadIdx.x >= 64) return;                     // the env lanes: wave 0, four lanes per agent (it wrote sAct itself: LDS is in
     __builtin_amdgcn_wave_barrier();                   // order within a wave)
     const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
     if (i >= n) return;
+    const int od = worker_policy::obs_dim_of(pa);
     Agent ag = load_agent(st, n, i);
     const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
     const size_t slot = (size_t)((next_idx + i) % capacity);
     if (q == 0) {
-        write_obs(ring.obs, (int)slot, 6, ag);                  // obs before the step
+        write_obs(ring.obs, (int)slot, od, ag);                 // obs before the step
         reinterpret_cast<float2*>(ring.act)[slot] = an;
     }
     const StepOut o = step_agent_quad(ag, an, q, s_quad + (threadIdx.x >> 2) * 100);
     if (q == 1) {
-        write_obs(ring.obs2, (int)slot, 6, ag);
+        write_obs(ring.obs2, (int)slot, od, ag);
         ring.rew[slot] = o.reward;
         ring.done[slot] = o.done ? 1 : 0;
         if (done_out) done_out[i] = o.done ? 1 : 0;
     }
     if (o.done) reset_agent(ag, i, k0, k1, c1, c2);
     if (q == 2) store_agent(st, n, i, ag);
-    if (q == 3) write_obs(obs_io, i, 6, ag);
+    if (q == 3) write_obs(obs_io, i, od, ag);
 }
 
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
@@ -751,21 +779,41 @@ extern "C" int mpg_env_step_store_reset_draw(int env_kind, int n, int obs_dim, f
                                  ring_done, seed, ctr, obs_out, done_out, pd, stream);
 }
 
-// worker.py:95-112 for the path-tracking env with six-entry observations: mpg_policy_action + mpg_env_step_store_reset(_draw) as one
-// launch (bit-identical actions, ring rows, states and observations).  obs_io [n][6]: the current observations in, the next ones out.
+// worker.py:95-112 for the path-tracking env: mpg_policy_action + mpg_env_step_store_reset(_draw) as one launch (bit-identical actions,
+// ring rows, states and observations).  obs_io [n][obs_dim]: the current observations in, the next ones out.  obs_dim 6 .. 16; the
+// pre-gathered draw with six-entry observations only.
+namespace {
+template <class A>
+void fill_policy_args(A& pa, int n_scale, const mpg_cfg_t* cfg, const float* policy_params, float explore_sigma, uint64_t noise_seed,
+                      uint64_t noise_ctr) {
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, cfg->obs_dim, 4).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    const bool ranged = cfg->action_range > 0.f;
+    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
+    pa.out_scale = ranged ? cfg->action_range : 1.f;
+    pa.sigma = explore_sigma;
+    pa.k0 = (uint32_t)noise_seed; pa.k1 = (uint32_t)(noise_seed >> 32); pa.c1 = (uint32_t)noise_ctr; pa.c2 = (uint32_t)(noise_ctr >> 32);
+    for (int i = 0; i < n_scale; ++i) pa.scale[i] = i < cfg->obs_dim ? cfg->obs_scale[i] : 1.f;
+}
+}  // namespace
+
 extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params, int n, float* state, float* obs_io, float explore_sigma,
                                uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx, float* ring_obs,
                                float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
                                uint64_t env_ctr, uint8_t* done_out, const mpg_replay_draw_t* draw, int rows, float* b_obs, float* b_act,
                                float* b_rew, float* b_obs2, mpg_stream_t stream) {
     MPG_REQUIRE(!cfg || cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_step: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg && cfg->env_kind == MPG_ENV_PATH_TRACKING && cfg->obs_dim == 6 && cfg->act_dim == 2,
-                "mpg_worker_step: path-tracking env with obs_dim 6 only");
+    MPG_REQUIRE(cfg && cfg->env_kind == MPG_ENV_PATH_TRACKING && pt_obs_dim_ok(cfg->obs_dim) && cfg->act_dim == 2,
+                "mpg_worker_step: path-tracking env with obs_dim 6 .. 16 only");
     MPG_REQUIRE(policy_params && n > 0 && state && obs_io && act_out && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs &&
                     ring_act && ring_rew && ring_obs2 && ring_done,
                 "mpg_worker_step: bad argument");
     // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_step: tanh policy with an action range");
+    const bool wide = cfg->obs_dim > 6;
+    // the rows are gathered six wide (predraw_row) for the fused gradient launch, which exists for six-entry observations only
+    MPG_REQUIRE(!(draw && wide), "mpg_worker_step: the pre-gathered draw serves obs_dim 6 only (got obs_dim %d: pass draw = NULL)", cfg->obs_dim);
     PreDraw pd{};
     if (draw) {
         MPG_REQUIRE(rows > 0 && b_obs && b_act && b_rew && b_obs2 && draw->n_storage > 0 && draw->n_storage <= capacity,
@@ -777,26 +825,26 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
         pd.o_obs = b_obs; pd.o_act = b_act; pd.o_rew = b_rew; pd.o_obs2 = b_obs2;
     }
     pd.env_blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
-    worker_policy::Args pa;
-    pa.params = policy_params;
-    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 6, 4).W2, 0);
-    pa.status = mpg_status_of(cfg);
-    const bool ranged = cfg->action_range > 0.f;
-    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    pa.out_scale = ranged ? cfg->action_range : 1.f;
-    pa.sigma = explore_sigma;
-    pa.k0 = (uint32_t)noise_seed; pa.k1 = (uint32_t)(noise_seed >> 32); pa.c1 = (uint32_t)noise_ctr; pa.c2 = (uint32_t)(noise_ctr >> 32);
-    for (int i = 0; i < 8; ++i) pa.scale[i] = i < 6 ? cfg->obs_scale[i] : 1.f;
     RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
     const int blocks = pd.env_blocks + (pd.rows + mlp::NTHREAD - 1) / mlp::NTHREAD;
     hipStream_t s = mpg_stream(stream);
-    mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-    if (pa.pack)
-        hipLaunchKernelGGL((k_policy_step_store_reset<true>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, ring, capacity,
-                           next_idx, (uint32_t)env_seed, (uint32_t)(env_seed >> 32), (uint32_t)env_ctr, (uint32_t)(env_ctr >> 32), done_out, pd);
-    else
-        hipLaunchKernelGGL((k_policy_step_store_reset<false>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, ring, capacity,
-                           next_idx, (uint32_t)env_seed, (uint32_t)(env_seed >> 32), (uint32_t)env_ctr, (uint32_t)(env_ctr >> 32), done_out, pd);
+#define MPG_WORKER_LAUNCH(PK, IN)                                                                                                        \
+    hipLaunchKernelGGL((k_policy_step_store_reset<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, ring, \
+                       capacity, next_idx, (uint32_t)env_seed, (uint32_t)(env_seed >> 32), (uint32_t)env_ctr, (uint32_t)(env_ctr >> 32), \
+                       done_out, pd)
+    if (wide) {             // (pd.rows == 0: the grid is the policy groups)
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        pa.obs_dim = cfg->obs_dim;
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_LAUNCH(true, 16); else MPG_WORKER_LAUNCH(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_LAUNCH(true, 6); else MPG_WORKER_LAUNCH(false, 6);
+    }
+#undef MPG_WORKER_LAUNCH
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_step");
     return MPG_OK;

@@ -89,7 +89,8 @@ bool ctx_ok(const mpg_train_ctx_t* c) {
 }
 
 // ---- worker.sample + replay_buffer.add_batch (optimizer.py:332-337, worker.py:91-119), the plain form (NADP, TD3) ----
-// worker.py:95-112 as one launch (mpg_worker_step) where it exists: path-tracking env, six-entry observations
+// worker.py:95-112 as one launch (mpg_worker_step): path-tracking env, six-entry observations.  mpg_worker_step serves obs_dim 7 .. 16
+// too; the driver does not take it there: its step time against the two launches at K = 3 / 10 has NOT been measured
 inline bool worker_step_fused(const mpg_train_ctx_t* c) {
     return c->cfg.env_kind == MPG_ENV_PATH_TRACKING && c->cfg.obs_dim == 6 && c->cfg.act_dim == 2;
 }
