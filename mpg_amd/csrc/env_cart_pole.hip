@@ -129,12 +129,8 @@ __global__ void __launch_bounds__(64) k_cp_step(int n, float* __restrict__ st, c
     write_obs(obs, i, s);
 }
 
-struct Ring {
-    float *obs, *act, *rew, *obs2;
-    uint8_t* done;
-};
 __global__ void __launch_bounds__(64) k_cp_step_store_reset(int n, float* __restrict__ st, const float* __restrict__ action,
-                                                            Ring ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                            RingPtrs ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
                                                             uint32_t c1, uint32_t c2, float* __restrict__ obs_out,
                                                             uint8_t* __restrict__ done_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -167,8 +163,7 @@ int reset_from_obs(int n, int obs_dim, float* state, const float* init_obs, hipS
 
 int reset(int n, int obs_dim, float* state, const uint8_t* done_mask, uint64_t seed, uint64_t ctr, float* obs, hipStream_t s) {
     MPG_REQUIRE(n > 0 && obs_dim == 4 && state && obs, "mpg_env_reset (cart-pole): bad argument");
-    hipLaunchKernelGGL(k_cp_reset, dim3((n + 63) / 64), dim3(64), 0, s, n, state, done_mask, (uint32_t)seed, (uint32_t)(seed >> 32),
-                       (uint32_t)ctr, (uint32_t)(ctr >> 32), obs);
+    hipLaunchKernelGGL(k_cp_reset, dim3((n + 63) / 64), dim3(64), 0, s, n, state, done_mask, MPG_KEY_CTR(seed, ctr), obs);
     MPG_CHECK_LAUNCH("k_cp_reset");
     return MPG_OK;
 }
@@ -181,13 +176,11 @@ int step(int n, int obs_dim, float* state, const float* action, float* obs, floa
     return MPG_OK;
 }
 
-int step_store_reset(int n, int obs_dim, float* state, const float* action, int capacity, int next_idx, float* ring_obs,
-                     float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t seed, uint64_t ctr,
-                     float* obs_out, uint8_t* done_out, hipStream_t s) {
+int step_store_reset(int n, int obs_dim, float* state, const float* action, int capacity, int next_idx, const RingPtrs& ring,
+                     uint64_t seed, uint64_t ctr, float* obs_out, uint8_t* done_out, hipStream_t s) {
     MPG_REQUIRE(obs_dim == 4, "mpg_env_step_store_reset (cart-pole): obs_dim");
-    Ring ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
     hipLaunchKernelGGL(k_cp_step_store_reset, dim3((n + 63) / 64), dim3(64), 0, s, n, state, action, ring, capacity, next_idx,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), obs_out, done_out);
+                       MPG_KEY_CTR(seed, ctr), obs_out, done_out);
     MPG_CHECK_LAUNCH("k_cp_step_store_reset");
     return MPG_OK;
 }

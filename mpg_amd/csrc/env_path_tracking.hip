@@ -128,6 +128,13 @@ constexpr float PERIOD = 1200.f;                          // path_tracking_env.p
 // vehicle parameters, path_tracking_env.py:60-68 (cast to float32 like :86-93)
 constexpr float C_f = -128915.5f, C_r = -85943.6f, A_ = 1.06f, B_ = 1.85f, MASS = 1412.f, I_z = 1536.7f,
                 MIU = 1.0f, G_ = 9.81f;
+// f_xu's constants, :95-101,135-136: the axle loads and the products with tau = 1/base_freq (a python float, cast on contact, :141)
+constexpr float F_zf = B_ * MASS * G_ / (A_ + B_), F_zr = A_ * MASS * G_ / (A_ + B_);
+constexpr float tau = 0.005f;
+constexpr float K1 = tau * (A_ * C_f - B_ * C_r);
+constexpr float K2 = tau * C_f, K3 = tau * MASS, K4 = tau * (C_f + C_r);
+constexpr float K5 = (tau * A_) * C_f;
+constexpr float K6 = tau * ((A_ * A_) * C_f + (B_ * B_) * C_r);
 
 struct PathRef {
     float y, phi;
@@ -297,8 +304,19 @@ struct StepOut {
     bool done, done_intended;
 };
 
-// PathTrackingEnv.step for one agent (:456-487): reward on the pre-step state, 20 sub-steps, done flags
-__device__ __forceinline__ StepOut step_agent(Agent& ag, const float2 an) {
+// PathTrackingEnv.step for one agent (:456-487): reward on the pre-step state, 20 sub-steps, done flags.  The sub-steps come in two
+// forms that perform the same float32 operations on the same operands in the same order per variable, so their results are
+// bit-identical; everything around them is stated once.
+// LANES = 1: one lane per agent runs the sub-steps one after the other (q and sc are not used).
+// LANES = 4: four lanes per agent (lanes 4a .. 4a+3 of one wave, q = lane & 3).  The sub-steps' serial part is the planar dynamics
+// (v_x, v_y, r) and the heading; the sincos of each heading and the world-frame increments are not on that chain and delta_y /
+// delta_phi only matter after the last sub-step.  So: (A) every lane runs the short serial chain and the 20 (heading, v_x, v_y)
+// triples go to LDS, (B) lane q evaluates the increments of sub-steps q, q+4, .. (5 of the 20 sincos each), (C) every lane adds the
+// increments in order: ~2450 instead of ~4300 instructions per wave, and 256 waves instead of 64 for 4096 agents.  sc: this agent's
+// 100 floats of LDS, [5][20].
+template <int LANES>
+__device__ __forceinline__ StepOut step_agent(Agent& ag, const float2 an, const int q = 0, float* sc = nullptr) {
+    static_assert(LANES == 1 || LANES == 4, "one lane or four lanes per agent");
     StepOut out;
     float vx = ag.vx, vy = ag.vy, r = ag.r, y = ag.y, phi = ag.phi, x = ag.x, dy = ag.dy, dphi = ag.dphi;
     // step(): scale and clip the action, path_tracking_env.py:457-459
@@ -317,43 +335,79 @@ __device__ __forceinline__ StepOut step_agent(Agent& ag, const float2 an) {
     }
 
     // f_xu pieces that depend on the action only, :95-101,135-136
-    const float F_zf = B_ * MASS * G_ / (A_ + B_), F_zr = A_ * MASS * G_ / (A_ + B_);
     const float F_xf = a_x < 0.f ? MASS * a_x / 2.f : 0.f;
     const float F_xr = a_x < 0.f ? MASS * a_x / 2.f : MASS * a_x;
     const float miu_f = sqrtf((MIU * F_zf) * (MIU * F_zf) - F_xf * F_xf) / F_zf;
     const float miu_r = sqrtf((MIU * F_zr) * (MIU * F_zr) - F_xr * F_xr) / F_zr;
 
-    const float tau = 0.005f;                  // 1/base_freq as a python float, cast on contact (:141)
-    const float K1 = tau * (A_ * C_f - B_ * C_r);
-    const float K2 = tau * C_f, K3 = tau * MASS, K4 = tau * (C_f + C_r);
-    const float K5 = (tau * A_) * C_f;
-    const float K6 = tau * ((A_ * A_) * C_f + (B_ * B_) * C_r);
-
     // simulation(), :144-179.  delta_y / delta_phi are overwritten by every sub-step, so the reference path is evaluated once,
-    // for the last one.  The loop is deliberately NOT unrolled: one wave per CU runs this kernel, once per launch, with a cold
-    // instruction cache - 20 unrolled sub-steps (7300 instructions, 58 KB) spent more time fetching code than executing
-    // it (18.5 us -> 22 us when the unrolled body was made cheaper; measured).
+    // for the last one.
     float vx_pre = vx, vy_pre = vy, r_pre = r;  // state entering the LAST sub-step (for `others`)
-    float x_u = x, phi_u = phi;
+    float x_u = x, phi_u = phi;                 // x and phi of the last sub-step before their wraps (:163-165)
+    if constexpr (LANES == 1) {
+        // The loop is deliberately NOT unrolled: one wave per CU runs this kernel, once per launch, with a cold instruction cache -
+        // 20 unrolled sub-steps (7300 instructions, 58 KB) spent more time fetching code than executing it (18.5 us -> 22 us when
+        // the unrolled body was made cheaper; measured).
 #pragma unroll 1
-    for (int s = 0; s < 20; ++s) {
-        vx_pre = vx; vy_pre = vy; r_pre = r;
-        // prediction -> f_xu with tau = 1/200 on (v_x, v_y, r); entries 3-5 are overwritten below
-        float nvx = vx + tau * (a_x + vy * r);
-        float nvy = (((MASS * vy) * vx + K1 * r) - (K2 * steer) * vx - (K3 * (vx * vx)) * r) / (MASS * vx - K4);
-        float nr = ((((-I_z) * r) * vx - K1 * vy) + (K5 * steer) * vx) / (K6 - I_z * vx);
-        nvx = fminf(fmaxf(nvx, 1.f), 35.f);     // :153
-        // world frame, :156-160: phi first, then y and x with the OLD v_x, v_y but the NEW phi (view aliasing)
-        phi = phi + div200(r);
-        float sp, cp;
-        sincos_bounded(phi, sp, cp);
-        y = y + div200(vx * sp + vy * cp);
-        x = x + div200(vx * cp - vy * sp);
-        vx = nvx; vy = nvy; r = nr;             // :161
-        x_u = x; phi_u = phi;                   // :163-165 read x and phi before their wraps
-        phi = wrap_pi(phi);                     // :168-169
-        if (x > PERIOD) x = x - PERIOD;         // :171
-        if (x <= 0.f) x = x + PERIOD;           // :172
+        for (int s = 0; s < 20; ++s) {
+            vx_pre = vx; vy_pre = vy; r_pre = r;
+            // prediction -> f_xu with tau = 1/200 on (v_x, v_y, r); entries 3-5 are overwritten below
+            float nvx = vx + tau * (a_x + vy * r);
+            float nvy = (((MASS * vy) * vx + K1 * r) - (K2 * steer) * vx - (K3 * (vx * vx)) * r) / (MASS * vx - K4);
+            float nr = ((((-I_z) * r) * vx - K1 * vy) + (K5 * steer) * vx) / (K6 - I_z * vx);
+            nvx = fminf(fmaxf(nvx, 1.f), 35.f);     // :153
+            // world frame, :156-160: phi first, then y and x with the OLD v_x, v_y but the NEW phi (view aliasing)
+            phi = phi + div200(r);
+            float sp, cp;
+            sincos_bounded(phi, sp, cp);
+            y = y + div200(vx * sp + vy * cp);
+            x = x + div200(vx * cp - vy * sp);
+            vx = nvx; vy = nvy; r = nr;             // :161
+            x_u = x; phi_u = phi;                   // :163-165 read x and phi before their wraps
+            phi = wrap_pi(phi);                     // :168-169
+            if (x > PERIOD) x = x - PERIOD;         // :171
+            if (x <= 0.f) x = x + PERIOD;           // :172
+        }
+    } else {
+        ENV_TL(2);
+#pragma unroll 1
+        for (int s = 0; s < 20; ++s) {              // (A) dynamics and heading
+            vx_pre = vx; vy_pre = vy; r_pre = r;
+            float nvx = vx + tau * (a_x + vy * r);
+            float nvy = (((MASS * vy) * vx + K1 * r) - (K2 * steer) * vx - (K3 * (vx * vx)) * r) / (MASS * vx - K4);
+            float nr = ((((-I_z) * r) * vx - K1 * vy) + (K5 * steer) * vx) / (K6 - I_z * vx);
+            nvx = fminf(fmaxf(nvx, 1.f), 35.f);     // :153
+            phi = phi + div200(r);                  // :156, the OLD yaw rate
+            if ((s & 3) == q) { sc[s] = phi; sc[20 + s] = vx; sc[40 + s] = vy; }   // new heading, OLD velocities (:157-160)
+            phi_u = phi;
+            vx = nvx; vy = nvy; r = nr;             // :161
+            phi = wrap_pi(phi);                     // :168-169
+        }
+        __builtin_amdgcn_wave_barrier();            // the four lanes of an agent sit in one wave: LDS is in order within it
+        ENV_TL(3);
+#pragma unroll 1
+        for (int s = q; s < 20; s += 4) {           // (B) this lane's five sub-steps
+            float sp, cp;
+            sincos_bounded(sc[s], sp, cp);
+            const float ovx = sc[20 + s], ovy = sc[40 + s];
+            sc[60 + s] = div200(ovx * sp + ovy * cp);
+            sc[80 + s] = div200(ovx * cp - ovy * sp);
+        }
+        __builtin_amdgcn_wave_barrier();
+        ENV_TL(4);
+#pragma unroll 1
+        for (int s4 = 0; s4 < 20; s4 += 4) {        // (C) positions, in order; four increments per LDS round trip
+            const float4 iy = *reinterpret_cast<const float4*>(sc + 60 + s4), ix = *reinterpret_cast<const float4*>(sc + 80 + s4);
+            const float ay[4] = {iy.x, iy.y, iy.z, iy.w}, ax[4] = {ix.x, ix.y, ix.z, ix.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                y = y + ay[u];
+                x = x + ax[u];
+                x_u = x;                            // :163-164 read x before the wrap
+                if (x > PERIOD) x = x - PERIOD;     // :171
+                if (x <= 0.f) x = x + PERIOD;       // :172
+            }
+        }
     }
     ENV_TL(5);
     {
@@ -397,7 +451,7 @@ __global__ void __launch_bounds__(64) k_step(int n, float* __restrict__ st, cons
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Agent ag = load_agent(st, n, i);
-    const StepOut o = step_agent(ag, reinterpret_cast<const float2*>(action)[i]);
+    const StepOut o = step_agent<1>(ag, reinterpret_cast<const float2*>(action)[i]);
     reward[i] = o.reward;
     done[i] = o.done ? 1 : 0;
     if (done_intended) done_intended[i] = o.done_intended ? 1 : 0;
@@ -405,116 +459,6 @@ __global__ void __launch_bounds__(64) k_step(int n, float* __restrict__ st, cons
     write_obs(obs, i, od, ag);
 }
 
-// OffPolicyWorker.sample's inner body after the policy (worker.py:108-112) in one launch: env.step, the transition
-// (obs, action, RAW reward, obs', done) written straight into the replay ring slot (next_idx + i) % capacity
-// (buffer.py:46-55), then env.reset() for the agents that are done (path_tracking_env.py:445).
-// The same step with FOUR lanes per agent (lanes 4a .. 4a+3 of one wave, q = lane & 3; k_step_store_reset).  The sub-steps'
-// serial part is the planar dynamics (v_x, v_y, r) and the heading; the sincos of each heading and the world-frame
-// increments are not on that chain and delta_y / delta_phi only matter after the last sub-step.  So: (A) every lane runs the
-// short serial chain and the 20 (heading, v_x, v_y) triples go to LDS, (B) lane q evaluates the increments of sub-steps
-// q, q+4, .. (5 of the 20 sincos each), (C) every lane adds the increments in order.  Same float32 operations on the same
-// operands in the same order per variable as step_agent: bit-identical results, ~2450 instead of ~4300 instructions per wave,
-// and 256 waves instead of 64 for 4096 agents.  sc: this agent's 100 floats of LDS, [5][20].
-__device__ __forceinline__ StepOut step_agent_quad(Agent& ag, const float2 an, const int q, float* sc) {
-    StepOut out;
-    float vx = ag.vx, vy = ag.vy, r = ag.r, y = ag.y, phi = ag.phi, x = ag.x, dy = ag.dy, dphi = ag.dphi;
-    // step(): scale and clip the action, path_tracking_env.py:457-459
-    const float ACT_HI0 = (float)(1.2 * 3.14159265358979323846 / 9.0), ACT_HI1 = 3.f;
-    float steer = ((an.x * 1.2f) * PI_F) / 9.f;
-    float a_x = an.y * 3.f;
-    steer = fminf(fmaxf(steer, -ACT_HI0), ACT_HI0);
-    a_x = fminf(fmaxf(a_x, -ACT_HI1), ACT_HI1);
-
-    // compute_rewards on the PRE-step veh_state, :181-199
-    {
-        float t = vx - 20.f;
-        float devi_v = -(t * t), devi_y = -(dy * dy), devi_phi = -(dphi * dphi), p_yaw = -(r * r),
-              p_steer = -(steer * steer), p_ax = -(a_x * a_x);
-        out.reward = 0.01f * devi_v + 0.04f * devi_y + 0.1f * devi_phi + 0.02f * p_yaw + 5.f * p_steer + 0.05f * p_ax;
-    }
-
-    // f_xu pieces that depend on the action only, :95-101,135-136
-    const float F_zf = B_ * MASS * G_ / (A_ + B_), F_zr = A_ * MASS * G_ / (A_ + B_);
-    const float F_xf = a_x < 0.f ? MASS * a_x / 2.f : 0.f;
-    const float F_xr = a_x < 0.f ? MASS * a_x / 2.f : MASS * a_x;
-    const float miu_f = sqrtf((MIU * F_zf) * (MIU * F_zf) - F_xf * F_xf) / F_zf;
-    const float miu_r = sqrtf((MIU * F_zr) * (MIU * F_zr) - F_xr * F_xr) / F_zr;
-
-    const float tau = 0.005f;                  // 1/base_freq as a python float, cast on contact (:141)
-    const float K1 = tau * (A_ * C_f - B_ * C_r);
-    const float K2 = tau * C_f, K3 = tau * MASS, K4 = tau * (C_f + C_r);
-    const float K5 = (tau * A_) * C_f;
-    const float K6 = tau * ((A_ * A_) * C_f + (B_ * B_) * C_r);
-
-    float vx_pre = vx, vy_pre = vy, r_pre = r;  // state entering the LAST sub-step (for `others`)
-    float phi_u = phi;
-    ENV_TL(2);
-#pragma unroll 1
-    for (int s = 0; s < 20; ++s) {              // (A) simulation(), :144-179: dynamics and heading
-        vx_pre = vx; vy_pre = vy; r_pre = r;
-        float nvx = vx + tau * (a_x + vy * r);
-        float nvy = (((MASS * vy) * vx + K1 * r) - (K2 * steer) * vx - (K3 * (vx * vx)) * r) / (MASS * vx - K4);
-        float nr = ((((-I_z) * r) * vx - K1 * vy) + (K5 * steer) * vx) / (K6 - I_z * vx);
-        nvx = fminf(fmaxf(nvx, 1.f), 35.f);     // :153
-        phi = phi + div200(r);                  // :156, the OLD yaw rate
-        if ((s & 3) == q) { sc[s] = phi; sc[20 + s] = vx; sc[40 + s] = vy; }   // new heading, OLD velocities (:157-160)
-        phi_u = phi;
-        vx = nvx; vy = nvy; r = nr;             // :161
-        phi = wrap_pi(phi);                     // :168-169
-    }
-    __builtin_amdgcn_wave_barrier();            // the four lanes of an agent sit in one wave: LDS is in order within it
-    ENV_TL(3);
-#pragma unroll 1
-    for (int s = q; s < 20; s += 4) {           // (B) this lane's five sub-steps
-        float sp, cp;
-        sincos_bounded(sc[s], sp, cp);
-        const float ovx = sc[20 + s], ovy = sc[40 + s];
-        sc[60 + s] = div200(ovx * sp + ovy * cp);
-        sc[80 + s] = div200(ovx * cp - ovy * sp);
-    }
-    __builtin_amdgcn_wave_barrier();
-    ENV_TL(4);
-    float x_u = x;
-#pragma unroll 1
-    for (int s4 = 0; s4 < 20; s4 += 4) {        // (C) positions, in order; four increments per LDS round trip
-        const float4 iy = *reinterpret_cast<const float4*>(sc + 60 + s4), ix = *reinterpret_cast<const float4*>(sc + 80 + s4);
-        const float ay[4] = {iy.x, iy.y, iy.z, iy.w}, ax[4] = {ix.x, ix.y, ix.z, ix.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            y = y + ay[u];
-            x = x + ax[u];
-            x_u = x;                            // :163-164 read x before the wrap
-            if (x > PERIOD) x = x - PERIOD;     // :171
-            if (x <= 0.f) x = x + PERIOD;       // :172
-        }
-    }
-    ENV_TL(5);
-    {
-        PathRef p = path_ref(x_u);              // :163-164
-        dphi = wrap_pi(phi_u - p.phi);          // :165, :176-177
-        dy = y - p.y;                           // :166
-    }
-    ENV_TL(6);
-
-    // `others` of the last sub-step (:100-101,135-138), judge_done :474-487
-    const float alpha_f = atanf((vy_pre + A_ * r_pre) / vx_pre) - steer;
-    const float alpha_r = atanf((vy_pre - B_ * r_pre) / vx_pre);
-    const float afb = 3.f * miu_f * F_zf / C_f, arb = 3.f * miu_r * F_zr / C_r;
-    const float rb = miu_r * G_ / fabsf(vx_pre);
-    const bool geo = (fabsf(dy) > 3.f) | (fabsf(dphi) > PI_F / 4.f) | (vx < 2.f);
-    const bool lit = geo | (alpha_f < -afb) | (alpha_f > afb) | (alpha_r < -arb) | (alpha_r > arb) | (r < -rb) |
-                     (r > rb);
-    out.done = lit;
-    out.done_intended = geo | (fabsf(alpha_f) > fabsf(afb)) | (fabsf(alpha_r) > fabsf(arb)) | (fabsf(r) > rb);
-
-    ag.vx = vx; ag.vy = vy; ag.r = r; ag.y = y; ag.phi = phi; ag.x = x; ag.dy = dy; ag.dphi = dphi;
-    return out;
-}
-
-struct RingPtrs {
-    float *obs, *act, *rew, *obs2;
-    uint8_t* done;
-};
 // The next minibatch draw, gathered by spare workgroups of the env launch (mpg_env_step_store_reset_draw): one lane per
 // drawn row, the same Philox draw as k_target_fused / k_sample_gather; rows whose slot the env lanes are writing are left
 // to the consumer.
@@ -544,78 +488,83 @@ __device__ __forceinline__ void predraw_row(const PreDraw& d, const RingPtrs& ri
     d.o_rew[gr] = rw;
     if (d.o_done) d.o_done[gr] = (float)dn;
 }
+// The spare workgroups of an env launch, the blocks from pd.env_blocks on, of NT threads each (the launch's block size, a template
+// argument: as a run-time one it changed the gather's address arithmetic): one drawn row per thread.  Returns whether this block
+// is one of them (it has then done its work and the kernel returns).
+template <int NT>
+__device__ __forceinline__ bool predraw_block(const PreDraw& pd, const RingPtrs& ring, int capacity, int fresh_start, int fresh_count) {
+    if ((int)blockIdx.x < pd.env_blocks) return false;
+    const int gr = ((int)blockIdx.x - pd.env_blocks) * NT + threadIdx.x;
+    if (gr < pd.rows) predraw_row(pd, ring, capacity, fresh_start, fresh_count, gr);
+    return true;
+}
 
-__global__ void __launch_bounds__(64) k_step_store_reset(int n, float* __restrict__ st, const float* __restrict__ action,
-                                                         RingPtrs ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
-                                                         uint32_t c1, uint32_t c2, float* __restrict__ obs_out,
-                                                         uint8_t* __restrict__ done_out, int od, PreDraw pd) {
-    if (pd.rows > 0 && (int)blockIdx.x >= pd.env_blocks) {
-        const int gr = ((int)blockIdx.x - pd.env_blocks) * 64 + threadIdx.x;
-        if (gr < pd.rows) predraw_row(pd, ring, capacity, next_idx, n, gr);
-        return;
-    }
-    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
-    ENV_TL(0);
-    const int t = blockIdx.x * blockDim.x + threadIdx.x, i = t >> 2, q = t & 3;
-    if (i >= n) return;
-    Agent ag = load_agent(st, n, i);
-    const float2 an = reinterpret_cast<const float2*>(action)[i];
+// OffPolicyWorker.sample's inner body after the policy (worker.py:108-112) for agent i, whose state `ag` and action `an` the caller
+// has read: the transition (obs, action, RAW reward, obs', done) written straight into the replay ring slot (next_idx + i) % capacity
+// (buffer.py:46-55) around env.step, then env.reset() if the agent is done (path_tracking_env.py:445), its state and its next
+// observation.  LANES = 4: lane q of the agent's four (step_agent<4>; sc: the agent's LDS) does the q-th share of the stores.
+// LANES = 1: the one lane stores everything.
+template <int LANES>
+__device__ __forceinline__ void env_lane(Agent ag, const float2 an, int n, int i, int q, float* sc, float* st, const RingPtrs& ring,
+                                         int capacity, int next_idx, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, float* obs_out,
+                                         uint8_t* done_out, int od) {
     const size_t slot = (size_t)((next_idx + i) % capacity);
-    if (q == 0) {
+    if (LANES == 1 || q == 0) {
         write_obs(ring.obs, (int)slot, od, ag);                 // obs before the step
         reinterpret_cast<float2*>(ring.act)[slot] = an;
     }
     ENV_TL(1);
-    const StepOut o = step_agent_quad(ag, an, q, s_quad + (threadIdx.x >> 2) * 100);
+    const StepOut o = step_agent<LANES>(ag, an, q, sc);
     ENV_TL(7);
-    if (q == 1) {
+    if (LANES == 1 || q == 1) {
         write_obs(ring.obs2, (int)slot, od, ag);
         ring.rew[slot] = o.reward;
         ring.done[slot] = o.done ? 1 : 0;
         if (done_out) done_out[i] = o.done ? 1 : 0;
     }
     if (o.done) reset_agent(ag, i, k0, k1, c1, c2);
-    if (q == 2) store_agent(st, n, i, ag);
-    if (q == 3) write_obs(obs_out, i, od, ag);
+    if (LANES == 1 || q == 2) store_agent(st, n, i, ag);
+    if (LANES == 1 || q == 3) write_obs(obs_out, i, od, ag);
     ENV_TL(8);
 }
 
-// The same launch with ONE lane per agent (step_agent, like k_step): the four-lane form above buys latency at 4096 agents (256 waves
+// env_lane with four lanes per agent: the latency form (256 waves instead of 64 for 4096 agents).  Blocks beyond the env lanes'
+// gather the draw (pd.rows > 0).
+__global__ void __launch_bounds__(64) k_step_store_reset(int n, float* __restrict__ st, const float* __restrict__ action,
+                                                         RingPtrs ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                         uint32_t c1, uint32_t c2, float* __restrict__ obs_out,
+                                                         uint8_t* __restrict__ done_out, int od, PreDraw pd) {
+    if (pd.rows > 0 && predraw_block<64>(pd, ring, capacity, next_idx, n)) return;
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    ENV_TL(0);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, i = t >> 2, q = t & 3;
+    if (i >= n) return;
+    const Agent ag = load_agent(st, n, i);
+    const float2 an = reinterpret_cast<const float2*>(action)[i];
+    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_out, done_out, od);
+}
+
+// The same launch with ONE lane per agent (step_agent<1>, like k_step): the four-lane form above buys latency at 4096 agents (256 waves
 // instead of 64 on 256 CUs) at the price of ~2.3x the instructions per agent; from MPG_ENV_ONE_LANE_FROM agents on the chip is full either
-// way and the instruction count is what is left (2^20 agents: 264 us four-lane against k_step's 61).  step_agent and step_agent_quad
-// perform the same float32 operations on the same operands in the same order per variable, so the two forms are bit-identical
-// (tests/test_env_gpu.py compares fused and separate calls at both sizes).
+// way and the instruction count is what is left (2^20 agents: 264 us four-lane against k_step's 61).  The two forms are bit-identical
+// (step_agent; tests/test_env_gpu.py compares fused and separate calls at both sizes).
 constexpr int MPG_ENV_ONE_LANE_FROM = 65536;
 __global__ void __launch_bounds__(64) k_step_store_reset_1(int n, float* __restrict__ st, const float* __restrict__ action,
                                                            RingPtrs ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
                                                            uint32_t c1, uint32_t c2, float* __restrict__ obs_out,
                                                            uint8_t* __restrict__ done_out, int od, PreDraw pd) {
-    if (pd.rows > 0 && (int)blockIdx.x >= pd.env_blocks) {
-        const int gr = ((int)blockIdx.x - pd.env_blocks) * 64 + threadIdx.x;
-        if (gr < pd.rows) predraw_row(pd, ring, capacity, next_idx, n, gr);
-        return;
-    }
+    if (pd.rows > 0 && predraw_block<64>(pd, ring, capacity, next_idx, n)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Agent ag = load_agent(st, n, i);
+    const Agent ag = load_agent(st, n, i);
     const float2 an = reinterpret_cast<const float2*>(action)[i];
-    const size_t slot = (size_t)((next_idx + i) % capacity);
-    write_obs(ring.obs, (int)slot, od, ag);                     // obs before the step
-    reinterpret_cast<float2*>(ring.act)[slot] = an;
-    const StepOut o = step_agent(ag, an);
-    write_obs(ring.obs2, (int)slot, od, ag);
-    ring.rew[slot] = o.reward;
-    ring.done[slot] = o.done ? 1 : 0;
-    if (done_out) done_out[i] = o.done ? 1 : 0;
-    if (o.done) reset_agent(ag, i, k0, k1, c1, c2);
-    store_agent(st, n, i, ag);
-    write_obs(obs_out, i, od, ag);
+    env_lane<1>(ag, an, n, i, 0, nullptr, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_out, done_out, od);
 }
 
 // OffPolicyWorker.sample's whole inner body (worker.py:95-112) in ONE launch: the policy pass of a 16-agent group by a 512-thread
-// workgroup, then env.step -> ring -> env.reset of those 16 agents by the four-lane form on wave 0 (k_step_store_reset's body).  The
-// stand-alone pair is two launches of one wave per CU each (7 + 14 us at 4096 agents); fused, the env lanes start the moment their
-// group's actions exist.  Blocks beyond the policy groups gather the minibatch about to be drawn (predraw_row).
+// workgroup, then env_lane<4> for those 16 agents on wave 0.  The stand-alone pair is two launches of one wave per CU each (7 + 14 us
+// at 4096 agents); fused, the env lanes start the moment their group's actions exist.  Blocks beyond the policy groups gather the
+// minibatch about to be drawn (predraw_block).
 // IN = 6: six-entry observations.  IN = 16: observations with look-ahead entries (obs_dim 7 .. 16 = pa.obs_dim, the row stride of
 // obs_io and of the ring's observation arrays) on the 16-wide first layer; these instantiations gather no draw (predraw_row is
 // six-wide, and the gradient launch that would consume the rows does not exist at these widths): their grid is the policy groups
@@ -627,11 +576,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
                                                                               int next_idx, uint32_t k0, uint32_t k1, uint32_t c1,
                                                                               uint32_t c2, uint8_t* __restrict__ done_out, PreDraw pd) {
     if constexpr (IN == 6) {
-        if ((int)blockIdx.x >= pd.env_blocks) {
-            const int gr = ((int)blockIdx.x - pd.env_blocks) * mlp::NTHREAD + threadIdx.x;
-            if (gr < pd.rows) predraw_row(pd, ring, capacity, next_idx, n, gr);
-            return;
-        }
+        if (predraw_block<mlp::NTHREAD>(pd, ring, capacity, next_idx, n)) return;
     }
     __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN>()];
     __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
@@ -641,24 +586,10 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
     __builtin_amdgcn_wave_barrier();                   // order within a wave)
     const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
     if (i >= n) return;
-    const int od = worker_policy::obs_dim_of(pa);
-    Agent ag = load_agent(st, n, i);
+    const Agent ag = load_agent(st, n, i);
     const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
-    const size_t slot = (size_t)((next_idx + i) % capacity);
-    if (q == 0) {
-        write_obs(ring.obs, (int)slot, od, ag);                 // obs before the step
-        reinterpret_cast<float2*>(ring.act)[slot] = an;
-    }
-    const StepOut o = step_agent_quad(ag, an, q, s_quad + (threadIdx.x >> 2) * 100);
-    if (q == 1) {
-        write_obs(ring.obs2, (int)slot, od, ag);
-        ring.rew[slot] = o.reward;
-        ring.done[slot] = o.done ? 1 : 0;
-        if (done_out) done_out[i] = o.done ? 1 : 0;
-    }
-    if (o.done) reset_agent(ag, i, k0, k1, c1, c2);
-    if (q == 2) store_agent(st, n, i, ag);
-    if (q == 3) write_obs(obs_io, i, od, ag);
+    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_io, done_out,
+                worker_policy::obs_dim_of(pa));
 }
 
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
@@ -685,8 +616,8 @@ extern "C" int mpg_env_reset(int env_kind, int n, int obs_dim, float* state, con
     MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_reset: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_reset: unknown env kind %d", env_kind);
     MPG_REQUIRE(n > 0 && state && obs && pt_obs_dim_ok(obs_dim), "mpg_env_reset: bad argument");
-    hipLaunchKernelGGL(k_reset, dim3((n + 63) / 64), dim3(64), 0, mpg_stream(stream), n, state, done_mask,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), obs, obs_dim);
+    hipLaunchKernelGGL(k_reset, dim3((n + 63) / 64), dim3(64), 0, mpg_stream(stream), n, state, done_mask, MPG_KEY_CTR(seed, ctr), obs,
+                       obs_dim);
     MPG_CHECK_LAUNCH("mpg_env_reset");
     return MPG_OK;
 }
@@ -705,39 +636,45 @@ extern "C" int mpg_env_step(int env_kind, int n, int obs_dim, float* state, cons
 }
 
 namespace {
+// what the three step -> ring entry points ask of the agent count and the ring
+inline bool ring_ok(int n, int capacity, int next_idx, const RingPtrs& ring) {
+    return n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done;
+}
+
+// the caller's draw request as the kernels take it (pd.env_blocks is the launch's own); `who`: the entry point, for the refusal
+int make_predraw(const char* who, const mpg_replay_draw_t* draw, int rows, float* b_obs, float* b_act, float* b_rew, float* b_obs2,
+                 int capacity, PreDraw& pd) {
+    MPG_REQUIRE(draw && rows > 0 && b_obs && b_act && b_rew && b_obs2 && draw->n_storage > 0 && draw->n_storage <= capacity,
+                "%s: incomplete draw", who);
+    pd.rows = rows; pd.n_storage = draw->n_storage;
+    pd.k0 = (uint32_t)draw->seed; pd.k1 = (uint32_t)(draw->seed >> 32);
+    pd.c1 = (uint32_t)draw->ctr; pd.c2 = (uint32_t)(draw->ctr >> 32);
+    pd.o_idx = draw->idx_out; pd.o_done = draw->done_out;
+    pd.o_obs = b_obs; pd.o_act = b_act; pd.o_rew = b_rew; pd.o_obs2 = b_obs2;
+    return MPG_OK;
+}
+
 int step_store_reset_impl(int env_kind, int n, int obs_dim, float* state, const float* action, int capacity, int next_idx,
-                          float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t seed,
-                          uint64_t ctr, float* obs_out, uint8_t* done_out, const PreDraw& pd_in, mpg_stream_t stream) {
-    MPG_REQUIRE(n > 0 && state && action && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs && ring_act &&
-                    ring_rew && ring_obs2 && ring_done && obs_out,
-                "mpg_env_step_store_reset: bad argument");
+                          const RingPtrs& ring, uint64_t seed, uint64_t ctr, float* obs_out, uint8_t* done_out, PreDraw pd,
+                          mpg_stream_t stream) {
+    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring) && state && action && obs_out, "mpg_env_step_store_reset: bad argument");
     MPG_REQUIRE(env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_step_store_reset: " MPG_NO_DOUBLE_PENDULUM_ENV);
     if (env_kind == MPG_ENV_INVERTED_PENDULUM) {
-        MPG_REQUIRE(pd_in.rows == 0, "mpg_env_step_store_reset_draw: path-tracking env only");
-        return cart_pole::step_store_reset(n, obs_dim, state, action, capacity, next_idx, ring_obs, ring_act, ring_rew, ring_obs2,
-                                           ring_done, seed, ctr, obs_out, done_out, mpg_stream(stream));
+        MPG_REQUIRE(pd.rows == 0, "mpg_env_step_store_reset_draw: path-tracking env only");
+        return cart_pole::step_store_reset(n, obs_dim, state, action, capacity, next_idx, ring, seed, ctr, obs_out, done_out,
+                                           mpg_stream(stream));
     }
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_step_store_reset: unknown env kind %d", env_kind);
     MPG_REQUIRE(pt_obs_dim_ok(obs_dim), "mpg_env_step_store_reset: obs_dim");
-    RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
-    PreDraw pd = pd_in;
-    if (n >= MPG_ENV_ONE_LANE_FROM) {             // one lane per agent: the throughput form
-        pd.env_blocks = (n + 63) / 64;
-        const int blocks1 = pd.env_blocks + (pd.rows + 63) / 64;
-        hipLaunchKernelGGL(k_step_store_reset_1, dim3(blocks1), dim3(64), 0, mpg_stream(stream), n, state, action, ring,
-                           capacity, next_idx, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), obs_out,
-                           done_out, obs_dim, pd);
-        MPG_CHECK_LAUNCH("mpg_env_step_store_reset");
-        return MPG_OK;
-    }
-    pd.env_blocks = (4 * n + 63) / 64;            // four lanes per agent: the latency form
+    // one lane per agent: the throughput form; four lanes per agent: the latency form
+    const bool one_lane = n >= MPG_ENV_ONE_LANE_FROM;
+    pd.env_blocks = ((one_lane ? 1 : 4) * n + 63) / 64;
     const int blocks = pd.env_blocks + (pd.rows + 63) / 64;
-    hipLaunchKernelGGL(k_step_store_reset, dim3(blocks), dim3(64), 0, mpg_stream(stream), n, state, action, ring,
-                       capacity, next_idx, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), obs_out,
-                       done_out, obs_dim, pd);
+    hipLaunchKernelGGL(one_lane ? k_step_store_reset_1 : k_step_store_reset, dim3(blocks), dim3(64), 0, mpg_stream(stream), n, state,
+                       action, ring, capacity, next_idx, MPG_KEY_CTR(seed, ctr), obs_out, done_out, obs_dim, pd);
 #ifdef MPG_TIMELINE
     static int s_calls = 0;
-    if (++s_calls % 100 == 0) {
+    if (!one_lane && ++s_calls % 100 == 0) {
         unsigned long long h[2][16];
         (void)hipStreamSynchronize(mpg_stream(stream));
         (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_env_tl), sizeof(h));
@@ -756,9 +693,8 @@ int step_store_reset_impl(int env_kind, int n, int obs_dim, float* state, const 
 extern "C" int mpg_env_step_store_reset(int env_kind, int n, int obs_dim, float* state, const float* action, int capacity, int next_idx,
                                         float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
                                         uint64_t seed, uint64_t ctr, float* obs_out, uint8_t* done_out, mpg_stream_t stream) {
-    PreDraw pd{};
-    return step_store_reset_impl(env_kind, n, obs_dim, state, action, capacity, next_idx, ring_obs, ring_act, ring_rew, ring_obs2,
-                                 ring_done, seed, ctr, obs_out, done_out, pd, stream);
+    return step_store_reset_impl(env_kind, n, obs_dim, state, action, capacity, next_idx,
+                                 RingPtrs{ring_obs, ring_act, ring_rew, ring_obs2, ring_done}, seed, ctr, obs_out, done_out, PreDraw{}, stream);
 }
 
 extern "C" int mpg_env_step_store_reset_draw(int env_kind, int n, int obs_dim, float* state, const float* action, int capacity,
@@ -767,16 +703,10 @@ extern "C" int mpg_env_step_store_reset_draw(int env_kind, int n, int obs_dim, f
                                              const mpg_replay_draw_t* draw, int rows, float* b_obs, float* b_act, float* b_rew,
                                              float* b_obs2, mpg_stream_t stream) {
     MPG_REQUIRE(env_kind == MPG_ENV_PATH_TRACKING && obs_dim == 6, "mpg_env_step_store_reset_draw: path-tracking env with obs_dim 6 only");
-    MPG_REQUIRE(draw && rows > 0 && b_obs && b_act && b_rew && b_obs2 && draw->n_storage > 0 && draw->n_storage <= capacity,
-                "mpg_env_step_store_reset_draw: incomplete draw");
     PreDraw pd{};
-    pd.rows = rows; pd.n_storage = draw->n_storage;
-    pd.k0 = (uint32_t)draw->seed; pd.k1 = (uint32_t)(draw->seed >> 32);
-    pd.c1 = (uint32_t)draw->ctr; pd.c2 = (uint32_t)(draw->ctr >> 32);
-    pd.o_idx = draw->idx_out; pd.o_done = draw->done_out;
-    pd.o_obs = b_obs; pd.o_act = b_act; pd.o_rew = b_rew; pd.o_obs2 = b_obs2;
-    return step_store_reset_impl(env_kind, n, obs_dim, state, action, capacity, next_idx, ring_obs, ring_act, ring_rew, ring_obs2,
-                                 ring_done, seed, ctr, obs_out, done_out, pd, stream);
+    if (int rc = make_predraw("mpg_env_step_store_reset_draw", draw, rows, b_obs, b_act, b_rew, b_obs2, capacity, pd)) return rc;
+    return step_store_reset_impl(env_kind, n, obs_dim, state, action, capacity, next_idx,
+                                 RingPtrs{ring_obs, ring_act, ring_rew, ring_obs2, ring_done}, seed, ctr, obs_out, done_out, pd, stream);
 }
 
 // worker.py:95-112 for the path-tracking env: mpg_policy_action + mpg_env_step_store_reset(_draw) as one launch (bit-identical actions,
@@ -806,32 +736,22 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
     MPG_REQUIRE(!cfg || cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_step: " MPG_NO_DOUBLE_PENDULUM_ENV);
     MPG_REQUIRE(cfg && cfg->env_kind == MPG_ENV_PATH_TRACKING && pt_obs_dim_ok(cfg->obs_dim) && cfg->act_dim == 2,
                 "mpg_worker_step: path-tracking env with obs_dim 6 .. 16 only");
-    MPG_REQUIRE(policy_params && n > 0 && state && obs_io && act_out && capacity >= n && next_idx >= 0 && next_idx < capacity && ring_obs &&
-                    ring_act && ring_rew && ring_obs2 && ring_done,
-                "mpg_worker_step: bad argument");
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    MPG_REQUIRE(policy_params && ring_ok(n, capacity, next_idx, ring) && state && obs_io && act_out, "mpg_worker_step: bad argument");
     // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_step: tanh policy with an action range");
     const bool wide = cfg->obs_dim > 6;
     // the rows are gathered six wide (predraw_row) for the fused gradient launch, which exists for six-entry observations only
     MPG_REQUIRE(!(draw && wide), "mpg_worker_step: the pre-gathered draw serves obs_dim 6 only (got obs_dim %d: pass draw = NULL)", cfg->obs_dim);
     PreDraw pd{};
-    if (draw) {
-        MPG_REQUIRE(rows > 0 && b_obs && b_act && b_rew && b_obs2 && draw->n_storage > 0 && draw->n_storage <= capacity,
-                    "mpg_worker_step: incomplete draw");
-        pd.rows = rows; pd.n_storage = draw->n_storage;
-        pd.k0 = (uint32_t)draw->seed; pd.k1 = (uint32_t)(draw->seed >> 32);
-        pd.c1 = (uint32_t)draw->ctr; pd.c2 = (uint32_t)(draw->ctr >> 32);
-        pd.o_idx = draw->idx_out; pd.o_done = draw->done_out;
-        pd.o_obs = b_obs; pd.o_act = b_act; pd.o_rew = b_rew; pd.o_obs2 = b_obs2;
-    }
+    if (draw)
+        if (int rc = make_predraw("mpg_worker_step", draw, rows, b_obs, b_act, b_rew, b_obs2, capacity, pd)) return rc;
     pd.env_blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
-    RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
     const int blocks = pd.env_blocks + (pd.rows + mlp::NTHREAD - 1) / mlp::NTHREAD;
     hipStream_t s = mpg_stream(stream);
 #define MPG_WORKER_LAUNCH(PK, IN)                                                                                                        \
     hipLaunchKernelGGL((k_policy_step_store_reset<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, ring, \
-                       capacity, next_idx, (uint32_t)env_seed, (uint32_t)(env_seed >> 32), (uint32_t)env_ctr, (uint32_t)(env_ctr >> 32), \
-                       done_out, pd)
+                       capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out, pd)
     if (wide) {             // (pd.rows == 0: the grid is the policy groups)
         worker_policy::WideArgs pa;
         fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);

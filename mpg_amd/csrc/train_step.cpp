@@ -88,27 +88,50 @@ bool ctx_ok(const mpg_train_ctx_t* c) {
            (!c->prioritized || (c->per_sum && c->per_min && c->per_stamp && c->per_capacity >= c->ring_capacity && c->per_max_priority && c->b_weights));
 }
 
-// ---- worker.sample + replay_buffer.add_batch (optimizer.py:332-337, worker.py:91-119), the plain form (NADP, TD3) ----
+// ---- worker.sample + replay_buffer.add_batch (optimizer.py:332-337, worker.py:91-119) ----
 // worker.py:95-112 as one launch (mpg_worker_step): path-tracking env, six-entry observations.  mpg_worker_step serves obs_dim 7 .. 16
 // too; the driver does not take it there: its step time against the two launches at K = 3 / 10 has NOT been measured
 inline bool worker_step_fused(const mpg_train_ctx_t* c) {
     return c->cfg.env_kind == MPG_ENV_PATH_TRACKING && c->cfg.obs_dim == 6 && c->cfg.act_dim == 2;
 }
 
-int sample_and_add(mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
+// draws_now: MPG-v2 draws its minibatch right after the add.  The last env launch then gathers it in spare workgroups (the random
+// ring reads overlap the env's sub-steps) except the rows drawn from the slots that launch is writing (path-tracking env, six-entry
+// observations); *pre_gathered and *fresh_start tell the gradient launch so (written only then; NADP and TD3 pass draws_now = false).
+int sample_and_add(mpg_train_ctx_t* c, const float* policy, bool draws_now, bool* pre_gathered, int* fresh_start, mpg_stream_t s) {
     const int od = c->cfg.obs_dim, kind = c->cfg.env_kind;
     for (int it = 0; it < c->sample_iters; ++it) {
         MPG_REQUIRE(c->num_agent <= c->ring_capacity, "mpg_step_begin: ring smaller than one sample");
-        if (worker_step_fused(c)) {     // policy pass + env.step -> ring -> env.reset in one launch
+        const bool predraw = draws_now && it == c->sample_iters - 1 && kind == MPG_ENV_PATH_TRACKING && od == 6;
+        mpg_replay_draw_t pd = {};
+        if (predraw) {
+            pd.n_storage = std::min(c->ring_size + c->num_agent, c->ring_capacity);
+            pd.seed = c->replay_seed; pd.ctr = c->replay_times + 1;
+            pd.idx_out = c->idx; pd.done_out = c->b_done;
+            *pre_gathered = true;
+            *fresh_start = c->ring_next;
+        }
+        if (worker_step_fused(c)) {
+            // the policy pass, env.step -> ring slot (next + i) % capacity -> env.reset of the done agents (and the draw): one launch
             TRY(mpg_worker_step(&c->cfg, policy, c->num_agent, c->env_state, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr++,
                                 c->w_act, c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
-                                c->env_seed, c->env_ctr++, c->w_done, nullptr, 0, nullptr, nullptr, nullptr, nullptr, s));
+                                c->env_seed, c->env_ctr++, c->w_done, predraw ? &pd : nullptr, c->batch, c->b_obs, c->b_act, c->b_rew,
+                                c->b_obs2, s));
         } else {
-        TRY(mpg_policy_action(&c->cfg, policy, c->num_agent, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr++, c->w_act, s));
-        mpg_prof_begin(c->cfg.prof, 2, mpg_stream(s));
-        TRY(mpg_env_step_store_reset(kind, c->num_agent, od, c->env_state, c->w_act, c->ring_capacity, c->ring_next, c->ring_obs,
-                                     c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, c->env_seed, c->env_ctr++, c->w_obs, c->w_done, s));
-        mpg_prof_end(c->cfg.prof, 2, mpg_stream(s));
+            TRY(mpg_policy_action(&c->cfg, policy, c->num_agent, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr++, c->w_act, s));
+            // env.step -> ring slot (next + i) % capacity -> env.reset of the done agents, one launch
+            mpg_prof_begin(c->cfg.prof, 2, mpg_stream(s));
+            if (predraw) {
+                TRY(mpg_env_step_store_reset_draw(kind, c->num_agent, od, c->env_state, c->w_act, c->ring_capacity, c->ring_next,
+                                                  c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, c->env_seed,
+                                                  c->env_ctr++, c->w_obs, c->w_done, &pd, c->batch, c->b_obs, c->b_act, c->b_rew,
+                                                  c->b_obs2, s));
+            } else {
+                TRY(mpg_env_step_store_reset(kind, c->num_agent, od, c->env_state, c->w_act, c->ring_capacity, c->ring_next, c->ring_obs,
+                                             c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, c->env_seed, c->env_ctr++, c->w_obs,
+                                             c->w_done, s));
+            }
+            mpg_prof_end(c->cfg.prof, 2, mpg_stream(s));
         }
         if (c->learner_version == 4 && c->prioritized)       // new transitions enter at the max priority (buffer.py:127-136)
             TRY(mpg_per_add(c->per_sum, c->per_min, c->per_stamp, c->per_capacity, c->ring_capacity, c->ring_next, c->num_agent,
@@ -191,7 +214,7 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
     const float* policy = c->params + l.off[l.n_nets - 1];
     const float* policy_t = c->targets + l.off[l.n_nets - 1];
     if (!is_mpg(c)) {        // ---- NADP / TD3: sample, add, replay, gradients (optimizer.py:330-353) ----
-        if (iteration % c->sampling_interval == 0) TRY(sample_and_add(c, policy, s));
+        if (iteration % c->sampling_interval == 0) TRY(sample_and_add(c, policy, false, nullptr, nullptr, s));
         MPG_REQUIRE(c->ring_size > 0, "mpg_step_begin: empty replay ring");
         c->replay_times++;
         if (c->learner_version == 4 && c->prioritized) {
@@ -206,51 +229,11 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
         c->learner_counter++;
         return c->learner_version == 3 ? nadp_gradients(c, l, s) : td3_gradients(c, l, s);
     }
-    // ---- worker.sample + replay_buffer.add_batch (optimizer.py:332-337, worker.py:91-119) ----
-    // MPG-v2 draws its minibatch right after the add: the last env launch gathers it in spare workgroups (the random ring
-    // reads overlap the env's sub-steps) except the rows drawn from the slots that launch is writing
+    // ---- worker.sample + replay_buffer.add_batch; MPG-v2 draws its minibatch right after the add ----
     const bool draws_now = c->learner_version == 2 && c->learner_counter % c->num_batch_reuse == 0;
     bool pre_gathered = false;
     int fresh_start = 0;
-    if (iteration % c->sampling_interval == 0) {
-        for (int it = 0; it < c->sample_iters; ++it) {
-            MPG_REQUIRE(c->num_agent <= c->ring_capacity, "mpg_step_begin: ring smaller than one sample");
-            const bool predraw = draws_now && it == c->sample_iters - 1 && kind == MPG_ENV_PATH_TRACKING && od == 6;
-            mpg_replay_draw_t pd = {};
-            if (predraw) {
-                pd.n_storage = std::min(c->ring_size + c->num_agent, c->ring_capacity);
-                pd.seed = c->replay_seed; pd.ctr = c->replay_times + 1;
-                pd.idx_out = c->idx; pd.done_out = c->b_done;
-                pre_gathered = true;
-                fresh_start = c->ring_next;
-            }
-            if (worker_step_fused(c)) {
-                // the policy pass, env.step -> ring slot (next + i) % capacity -> env.reset of the done agents (and the draw): one launch
-                TRY(mpg_worker_step(&c->cfg, policy, c->num_agent, c->env_state, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr++,
-                                    c->w_act, c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2,
-                                    c->ring_done, c->env_seed, c->env_ctr++, c->w_done, predraw ? &pd : nullptr, c->batch, c->b_obs, c->b_act,
-                                    c->b_rew, c->b_obs2, s));
-            } else {
-                TRY(mpg_policy_action(&c->cfg, policy, c->num_agent, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr++,
-                                      c->w_act, s));
-                // env.step -> ring slot (next + i) % capacity -> env.reset of the done agents, one launch
-                mpg_prof_begin(c->cfg.prof, 2, mpg_stream(s));
-                if (predraw) {
-                    TRY(mpg_env_step_store_reset_draw(kind, c->num_agent, od, c->env_state, c->w_act, c->ring_capacity, c->ring_next,
-                                                      c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, c->env_seed,
-                                                      c->env_ctr++, c->w_obs, c->w_done, &pd, c->batch, c->b_obs, c->b_act, c->b_rew,
-                                                      c->b_obs2, s));
-                } else {
-                    TRY(mpg_env_step_store_reset(kind, c->num_agent, od, c->env_state, c->w_act, c->ring_capacity, c->ring_next,
-                                                 c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, c->env_seed,
-                                                 c->env_ctr++, c->w_obs, c->w_done, s));
-                }
-                mpg_prof_end(c->cfg.prof, 2, mpg_stream(s));
-            }
-            c->ring_next = (c->ring_next + c->num_agent) % c->ring_capacity;
-            c->ring_size = std::min(c->ring_size + c->num_agent, c->ring_capacity);
-        }
-    }
+    if (iteration % c->sampling_interval == 0) TRY(sample_and_add(c, policy, draws_now, &pre_gathered, &fresh_start, s));
     // ---- replay_buffer.replay (optimizer.py:340-341; buffer.py:70-91) ----
     MPG_REQUIRE(c->ring_size > 0, "mpg_step_begin: empty replay ring");
     c->replay_times++;

@@ -178,11 +178,16 @@ def test_worker_step_equals_policy_action_plus_env_step_store_reset(n, sigma, ca
     del wc
 
 
-def test_pre_gathered_draw_equals_the_draw_inside_the_gradient_launch():
+@pytest.mark.parametrize('via,n,cap,nxt', [('env', 64, 1000, 970), ('env', 65536, 1_000_000, 970_000), ('worker', 64, 1000, 970)])
+def test_pre_gathered_draw_equals_the_draw_inside_the_gradient_launch(via, n, cap, nxt):
     """mpg_env_step_store_reset_draw + mpg_mpg_gradients(draw.pre_gathered = 1) == mpg_env_step_store_reset +
     mpg_mpg_gradients(draw): same ring, same minibatch (indices, five columns), same targets and gradients, bit for bit -
     with a full ring whose fresh window wraps around the end, so that some drawn rows fall into the slots the env launch
-    is writing (those are left to the gradient launch)."""
+    is writing (those are left to the gradient launch).  The spare workgroups that gather the draw exist in three kernels:
+    via = 'env' at 64 agents is the four-lane env launch, at 65 536 agents (the smallest count that takes it) the one-lane
+    env launch, and via = 'worker' is mpg_worker_step with and without the draw (the policy is the third network of params).
+    In all three the fresh window is 6.6 % of the ring: of the 512 draws of key (77, 5) 35 fall into it (the oracle's
+    uniform_indices_philox gives the same count for both ring sizes)."""
     import ctypes
     import mpg_amd._lib as L
     from mpg_amd import ops
@@ -199,9 +204,11 @@ def test_pre_gathered_draw_equals_the_draw_inside_the_gradient_launch():
     def dev(x):
         return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).cuda()
 
-    n, cap, nxt, B = 64, 1000, 970, 512               # 970 + 64 wraps; ~6 % of the draws land in the fresh window
+    B = 512                                           # next + n wraps; ~6 % of the draws land in the fresh window
     rng = np.random.Generator(np.random.PCG64(11))
-    params = dev(np.concatenate([mlp_weights_flat(rng, 8, 1), mlp_weights_flat(rng, 8, 1), mlp_weights_flat(rng, 6, 4)]))
+    nets = [mlp_weights_flat(rng, 8, 1), mlp_weights_flat(rng, 8, 1), mlp_weights_flat(rng, 6, 4)]
+    params = dev(np.concatenate(nets))
+    policy = params[nets[0].size + nets[1].size:]
     targets = (params * 0.97).contiguous()
     act = dev(rng.uniform(-1.2, 1.2, (n, 2)))
     ring0 = [dev(rng.standard_normal((cap, 6)) * np.array([3, 1, .5, 1, .5, 300])), dev(rng.uniform(-1, 1, (cap, 2))),
@@ -213,20 +220,26 @@ def test_pre_gathered_draw_equals_the_draw_inside_the_gradient_launch():
 
     def run(pre):
         env = PathTrackingEnv(num_agent=n, seed=5)
-        env.reset()
+        wobs = env.reset().clone()
         ring = [t.clone() for t in ring0]
         out = dict(obs=torch.zeros(B, 6).cuda(), act=torch.zeros(B, 2).cuda(), rew=torch.zeros(B).cuda(), obs2=torch.zeros(B, 6).cuda(),
                    idx=torch.zeros(B, dtype=torch.int32).cuda(), done=torch.zeros(B).cuda(), y=torch.zeros(B).cuda(),
-                   grad=torch.zeros(params.numel()).cuda(), stats=torch.zeros(16).cuda(), wobs=torch.empty(n, 6).cuda())
+                   grad=torch.zeros(params.numel()).cuda(), stats=torch.zeros(16).cuda(),
+                   wobs=wobs if via == 'worker' else torch.empty(n, 6).cuda(), wact=torch.zeros(n, 2).cuda())
         d = Draw(cap, 77, 5, *[t.data_ptr() for t in ring], out['idx'].data_ptr(), out['done'].data_ptr(), 0, 0, 0, 0)
         env_args = [L.c_int(0), L.c_int(n), L.c_int(6), L.ptr(env._state), L.ptr(act), L.c_int(cap), L.c_int(nxt),
                     *[L.ptr(t) for t in ring], L.c_u64(env.seed), L.c_u64(env._ctr), L.ptr(out['wobs']), L.ptr(None)]
-        if pre:
-            L.call('mpg_env_step_store_reset_draw', *env_args, ctypes.byref(d), L.c_int(B), L.ptr(out['obs']), L.ptr(out['act']),
-                   L.ptr(out['rew']), L.ptr(out['obs2']), L.stream())
-            d.pre_gathered, d.capacity, d.fresh_start, d.fresh_count = 1, cap, nxt, n
+        batch = [L.c_int(B), L.ptr(out['obs']), L.ptr(out['act']), L.ptr(out['rew']), L.ptr(out['obs2'])]
+        if via == 'worker':                           # one launch either way; without the draw the gradient launch draws
+            L.call('mpg_worker_step', ctypes.byref(cfg), L.ptr(policy), L.c_int(n), L.ptr(env._state), L.ptr(out['wobs']), L.c_float(0.3),
+                   L.c_u64(11), L.c_u64(5), L.ptr(out['wact']), L.c_int(cap), L.c_int(nxt), *[L.ptr(t) for t in ring], L.c_u64(env.seed),
+                   L.c_u64(env._ctr), L.ptr(None), ctypes.byref(d) if pre else L.ptr(None), *batch, L.stream())
+        elif pre:
+            L.call('mpg_env_step_store_reset_draw', *env_args, ctypes.byref(d), *batch, L.stream())
         else:
             L.call('mpg_env_step_store_reset', *env_args, L.stream())
+        if pre:
+            d.pre_gathered, d.capacity, d.fresh_start, d.fresh_count = 1, cap, nxt, n
         ws = torch.empty(nb + 256, dtype=torch.uint8, device='cuda')
         L.call('mpg_mpg_gradients', ctypes.byref(cfg), L.c_int(2), L.ptr(params), L.ptr(targets), L.c_int(B), L.ptr(out['obs']),
                L.ptr(out['act']), L.ptr(out['rew']), L.ptr(out['obs2']), L.ptr(None), L.c_int(1), L.c_int(25), sel, L.c_int(2), w,

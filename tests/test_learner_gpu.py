@@ -563,13 +563,15 @@ def test_training_loop_with_look_ahead_observations(fused, K):
     pw.check_status()
 
 
-@pytest.mark.parametrize('alg', ['MPG-v2', 'MPG-v1', 'MPG-v2-sel0_5_25'])
+@pytest.mark.parametrize('alg', ['MPG-v2', 'MPG-v1', 'MPG-v2-sel0_5_25', 'MPG-v2-ring600'])
 def test_native_step_driver_equals_method_by_method_path(alg):
     """mpg_step_begin/_end enqueue the same launches as the python classes: after the same number of iterations the
     counters and the replay ring are identical, and parameters / Adam moments / targets agree to float32 rounding (the
     host-side scalars - rule-based weights, bias-corrected learning rates - are evaluated by libm in one path and by
     numpy in the other, which may differ in the last bit).  'MPG-v2-sel0_5_25': MPG-v2 with num_rollout_list_for_policy_update
-    [0, 5, 25] - the driver's own statement of the rule-based weights (train_step.cpp) for three slices."""
+    [0, 5, 25] - the driver's own statement of the rule-based weights (train_step.cpp) for three slices.  'MPG-v2-ring600': MPG-v2 with
+    a 600-slot ring for the 896 transitions the run samples (512 to start, then 2 x 64 at iterations 0, 3 and 6): the worker launch
+    that pre-gathers the draw at iteration 0 writes slots 576 .. 639, so its fresh window wraps around the end of the ring."""
     from mpg_amd.buffer import ReplayBuffer
     from mpg_amd.config import default_args
     from mpg_amd.learners import MPGLearner
@@ -577,12 +579,14 @@ def test_native_step_driver_equals_method_by_method_path(alg):
     from mpg_amd.policy import PolicyWithQs
     from mpg_amd.worker import OffPolicyWorker
 
-    extra = {}
+    extra, ring = {}, 1000
     if alg == 'MPG-v2-sel0_5_25':
         alg, extra = 'MPG-v2', dict(num_rollout_list_for_policy_update=[0, 5, 25])
+    if alg == 'MPG-v2-ring600':
+        alg, ring = 'MPG-v2', 600
 
     def run(fused):
-        args = default_args(alg, num_agent=64, batch_size=128, replay_batch_size=96, replay_starts=512, max_buffer_size=1000,
+        args = default_args(alg, num_agent=64, batch_size=128, replay_batch_size=96, replay_starts=512, max_buffer_size=ring,
                             num_batch_reuse=2 if alg == 'MPG-v1' else 1, **extra)
         worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
         learner = MPGLearner(PolicyWithQs, args)

@@ -1,7 +1,7 @@
 """mpg_worker_step with look-ahead observations (num_future_data = K > 0, obs_dim = 6 + K in 7 .. 16): the worker's policy pass on the
 16-wide first layer and the env step as ONE launch, against the two stand-alone calls (mpg_policy_action + mpg_env_step_store_reset) it
 replaces - bit for bit, like the six-wide launch in tests/test_env_gpu.py - and the native step driver, which takes that launch at
-K > 0 from both of its worker call sites, against the method-by-method path (whose python classes keep calling the two stand-alone
+K > 0 from both branches of mpg_step_begin, against the method-by-method path (whose python classes keep calling the two stand-alone
 entry points).  The refusals of the entry point need no GPU: every argument is validated before anything is enqueued."""
 import ctypes
 
@@ -150,8 +150,8 @@ def test_native_step_driver_equals_method_by_method_path_with_look_ahead():
 @pytest.mark.gpu
 def test_native_step_driver_equals_method_path_for_td3_with_look_ahead():
     """tests/test_config34_gpu.py::test_native_step_driver_equals_method_path_for_td3_and_nadp for TD3 (uniform replay) at
-    num_future_data = 3: the regression net for `sample_and_add`, the driver's other call site of the worker step.  Same assertions, same
-    tolerances."""
+    num_future_data = 3: the regression net for `sample_and_add` as the NADP / TD3 branch calls it (no draw request).  Same assertions,
+    same tolerances."""
     from mpg_amd.buffer import ReplayBuffer
     from mpg_amd.config import default_args
     from mpg_amd.learners import TD3Learner
