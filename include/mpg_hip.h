@@ -377,6 +377,15 @@ int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params, int n, flo
                     uint8_t* done_out /* nullable */, const mpg_replay_draw_t* draw /* nullable */, int rows, float* b_obs,
                     float* b_act, float* b_rew, float* b_obs2, mpg_stream_t stream);
 
+/* MPGLearner.sample / NDPGLearner.sample - learners/mpg_learner.py:109-124, learners/ndpg.py:99-114, PathTracking env, ONE launch:
+ * from obs0 [rows][obs_dim] take n real-env steps, the first with the replay action act0 [rows][2], the later ones with the ONLINE
+ * policy's deterministic action (no noise, no reset on done).  rewards [n][rows] RAW, last_obs [rows][obs_dim].  Bit-identical - the
+ * sticky status word included - to mpg_env_reset_from_obs followed by, for t < n, mpg_policy_action(explore_sigma 0) when t > 0 and
+ * mpg_env_step; no env state block, action or done array is needed.  obs_dim 6 .. 16, act_dim 2, 1 <= n < 32: MPG_EINVAL otherwise,
+ * for any other env and for a tanh policy with an action range. */
+int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
+                    float* rewards, float* last_obs, mpg_stream_t stream);
+
 size_t mpg_mpg_gradients_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select, int n_q);
 int mpg_mpg_gradients(const mpg_cfg_t* cfg, int n_q, const float* params, const float* target_params, int rows,
                       float* obs, float* act, float* rew, float* obs_tp1, const float* y_in,
@@ -413,6 +422,14 @@ size_t mpg_td3_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows);
 int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, const float* q2,
                         int rows, const float* obs, float inv_b_global, float* qmin_sum, float* qmin_sqsum,
                         float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
+/* NDPGLearner.policy_forward_and_backward  - learners/ndpg.py:174-186:
+ *   loss = -mean_B Q1(s~, pi(s~)); grad = flat policy gradient (unclipped, reduced over this GPU's rows, divisor B_global through
+ *   inv_b_global); q_sum / q_sqsum: sum and sum of squares of Q1 over the rows (value_mean / value_var, :180-182).  One critic
+ *   forward and one critic backward (mpg_td3_policy_grad runs two of each and refuses a null q2). */
+size_t mpg_dpg_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, int rows, const float* obs,
+                        float inv_b_global, float* q_sum, float* q_sqsum, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_by_global_norm + Keras Adam + Polyak (K7, K8) over the flat [net0 | net1 | ...] vectors
@@ -543,7 +560,10 @@ typedef struct {
     int learner_version;              /* 1: MPG-v1 (n-step real-env target), 2: MPG-v2 (clipped double-Q target),
                                          3: NADP (learners/nadp.py:209-241: networks [Q1 | policy]; n = the Q-target AND policy
                                             rollout horizon, n_select / select / eta / total_ite unused),
-                                         4: TD3 (learners/td3.py:150-188: networks [Q1 | Q2 | policy]; n, M, select unused) */
+                                         4: TD3 (learners/td3.py:150-188: networks [Q1 | Q2 | policy]; n, M, select unused),
+                                         5: NDPG (learners/ndpg.py:202-237: networks [Q1 | policy]; n = sample_num_in_learner, the
+                                            real-env n-step target of version 1 (mpg_env_rollout into l_rewards / l_obs) every
+                                            num_batch_reuse-th call; M, n_select / select / eta / total_ite unused) */
     int num_agent, sample_iters;      /* worker: sample_iters env steps of num_agent agents per sampling call */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];
@@ -575,7 +595,7 @@ typedef struct {
     float* norms;                     /* n_nets */
     float* clip_scratch;              /* n_nets * MPG_CLIP_PARTS floats */
     int* nonfinite;                   /* n_nets */
-    /* MPG-v1 only: the learner's own env for the n-step sampler (batch agents) */
+    /* MPG-v1: the learner's own env for the n-step sampler (batch agents).  NDPG (5): l_rewards [n][batch] and l_obs only */
     float *l_env_state, *l_obs, *l_act, *l_rewards;
     uint8_t *l_done, *l_done_intended;
     void *ws0, *ws1;

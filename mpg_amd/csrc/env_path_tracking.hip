@@ -109,6 +109,60 @@ __device__ __forceinline__ void group(const typename args_of<IN>::type& a, int r
     report_activation_range(a.status, zmax);
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
+
+// The same policy pass for a kernel that applies it to one group MANY times (k_env_rollout, below): `group` in two parts, beside it
+// rather than out of it (the worker launch's code stays as it is).  load: the policy's registers, once.  pass: one evaluation on the
+// group's observations sObs [16][od] that wave 0 left in LDS - the same single float32 product with obs_scale, the same device
+// functions on the same operands in the same order as `group` (so as mpg_policy_action without noise), the actions to sAct [16][2].
+// zmax / saw_nan accumulate over the passes; report() ORs them into the status word once.  pass() starts with the caller's LDS in
+// order (a workgroup barrier behind the writes of sObs) and ends with sAct written by wave 0's own lanes.
+template <bool PK, int IN>
+__device__ __forceinline__ void load(const typename args_of<IN>::type& a, const Lane& L, float (&w2)[128], SmallRegs<IN, 2>& r, float& b3v) {
+    const Net net = make_net(a.params, obs_dim_of(a), 4);
+    b3v = 0.f;
+    if (threadIdx.x < GROUP * 2) b3v = net.b3[threadIdx.x % 2];
+    load_small<IN, 2>(net, L, r);
+    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
+}
+template <int IN>
+__device__ __forceinline__ void pass(const typename args_of<IN>::type& a, int rows, long g, const float* sObs, float* smem, float* sAct,
+                                     const Lane& L, const float (&w2)[128], const SmallRegs<IN, 2>& r, float b3v, float& zmax,
+                                     bool& saw_nan) {
+    constexpr int OU = 2, XSW = xs_of<IN>();
+    const int od = obs_dim_of(a);
+    float* sA = smem;
+    float* sX = sA + A_IMG;
+    float* sPart = sX + GROUP * XSW;
+    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 and the rows beyond `rows` stay zero)
+        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
+        float xv = 0.f;
+        if (g * GROUP + row < rows && i < od) xv = sObs[row * od + i] * a.scale[i];
+        saw_nan |= xv != xv;
+        sX[threadIdx.x] = xv;
+    }
+    lds_barrier();
+    float pz = 0.f;
+    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
+    float h1[2][4], h2[2][4];
+    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    const int tid = threadIdx.x;
+    if (tid < GROUP * OU) {
+        const int row = (tid / OU) % GROUP, o = tid % OU;
+        float y = 0.f;
+        if (g * GROUP + row < rows) {
+            float z = out_preact(sPart, b3v, row, o);
+            y = a.out_tanh ? a.out_scale * tanhf(z) : z;
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sAct[tid] = y;
+    }
+}
+template <class A>
+__device__ __forceinline__ void report(const A& a, float zmax, bool saw_nan) {
+    report_activation_range(a.status, zmax);
+    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
+}
 }  // namespace worker_policy
 #pragma clang fp contract(off)
 
@@ -592,6 +646,67 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
                 worker_policy::obs_dim_of(pa));
 }
 
+// MPGLearner.sample / NDPGLearner.sample (mpg_learner.py:109-124, ndpg.py:99-114) in ONE launch: from obs0 take n real-env steps, the
+// first with the replay action act0, the later ones with the policy's deterministic action.  The stand-alone chain is
+// mpg_env_reset_from_obs + n x mpg_env_step + (n - 1) x mpg_policy_action = 2 n launches of one wave per CU each, every policy launch
+// fetching the weights again.  Here one 512-thread workgroup owns 16 rows for all n steps: the policy's registers are loaded once
+// (worker_policy::load), wave 0 - four lanes per row, step_agent<4> - builds the agents from obs0 as k_reset_from_obs does and keeps
+// them in registers, and per step the observations go from wave 0 to the policy pass and the actions back THROUGH LDS between
+// workgroup barriers.  Global memory is read in the prologue only (obs0, act0, weights) and written for rewards / last_obs only, never
+// read back.  No done flag has a consumer (k_step does not reset, neither sample() nor mpg_nstep_targets reads them).  Rewards, last
+// observations and the status word are bit-identical to the chain's: the same device functions on the same operands in the same
+// order (tests/test_ndpg_gpu.py).  IN as in k_policy_step_store_reset.
+template <bool PK, int IN>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename worker_policy::args_of<IN>::type pa, int rows, int n,
+                                                                  const float* __restrict__ obs0, const float* __restrict__ act0,
+                                                                  float* __restrict__ rewards, float* __restrict__ last_obs) {
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN>()];
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
+    __shared__ float sAct[mlp::GROUP * 2];
+    const int od = worker_policy::obs_dim_of(pa);
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<IN, 2> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
+    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    const int a_loc = threadIdx.x >> 2, q = threadIdx.x & 3, i = blockIdx.x * mlp::GROUP + a_loc;
+    const bool env_lane_on = threadIdx.x < 64 && i < rows;
+    Agent ag = {};
+    float2 an = make_float2(0.f, 0.f);
+    if (env_lane_on) {                                   // k_reset_from_obs: only the six base entries are read
+        const float* o = obs0 + (size_t)i * od;
+        const float dy = o[3], dphi = o[4];
+        const PathRef p = path_ref(o[5]);
+        ag.vx = o[0] + 20.f; ag.vy = o[1]; ag.r = o[2];
+        ag.y = dy + p.y;
+        ag.phi = dphi + p.phi;
+        ag.x = o[5]; ag.dy = dy; ag.dphi = dphi;
+        an = reinterpret_cast<const float2*>(act0)[i];
+    }
+    for (int t = 0; t < n; ++t) {
+        if (t > 0) {
+            mlp::lds_barrier();                          // sObs of step t - 1 is complete (and the previous pass's LDS is free)
+            worker_policy::pass<IN>(pa, rows, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+            if (threadIdx.x < 64) {                      // wave 0 wrote sAct itself: LDS is in order within a wave
+                __builtin_amdgcn_wave_barrier();
+                an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
+            }
+        }
+        if (env_lane_on) {
+            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
+            if (q == 0) rewards[(size_t)t * rows + i] = o.reward;
+            if (q == 1) {
+                if (t == n - 1) write_obs(last_obs, i, od, ag);
+                else write_obs(sObs, a_loc, od, ag);
+            }
+        }
+    }
+    worker_policy::report(pa, zmax, saw_nan);
+}
+
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
 // MPG_ENV_INVERTED_DOUBLE_PENDULUM names a differentiable model only (include/mpg_hip.h): every real-env entry point refuses it
@@ -767,5 +882,38 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
 #undef MPG_WORKER_LAUNCH
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_step");
+    return MPG_OK;
+}
+
+// mpg_learner.py:109-124 / ndpg.py:99-114 for the path-tracking env: mpg_env_reset_from_obs + n x (mpg_policy_action from the second
+// step on, mpg_env_step) as one launch (k_env_rollout: bit-identical rewards, last observations and status word).
+extern "C" int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
+                               float* rewards, float* last_obs, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_env_rollout: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_env_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 2, "mpg_env_rollout: act_dim 2 only (got %d)", cfg->act_dim);
+    MPG_REQUIRE(n >= 1 && n < 32, "mpg_env_rollout: 1 <= n < 32 steps (got %d)", n);
+    MPG_REQUIRE(rows > 0, "mpg_env_rollout: no rows");
+    MPG_REQUIRE(policy_params && obs0 && act0 && rewards && last_obs, "mpg_env_rollout: null pointer");
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_env_rollout: tanh policy with an action range");
+    const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+#define MPG_ROLLOUT_LAUNCH(PK, IN) \
+    hipLaunchKernelGGL((k_env_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs)
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, 0.f, 0, 0);
+        pa.obs_dim = cfg->obs_dim;
+        if (pa.pack) MPG_ROLLOUT_LAUNCH(true, 16); else MPG_ROLLOUT_LAUNCH(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, 0.f, 0, 0);
+        if (pa.pack) MPG_ROLLOUT_LAUNCH(true, 6); else MPG_ROLLOUT_LAUNCH(false, 6);
+    }
+#undef MPG_ROLLOUT_LAUNCH
+    MPG_CHECK_LAUNCH("mpg_env_rollout");
     return MPG_OK;
 }

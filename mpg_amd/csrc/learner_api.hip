@@ -143,6 +143,56 @@ __global__ void __launch_bounds__(1024) k_td3_dy_mb(int rows, const float* __res
     }
     if (threadIdx.x == 0) { part[blockIdx.x] = red[0][0]; part[ERR_PARTS + blockIdx.x] = red[1][0]; }
 }
+// n-step DPG policy loss pieces (ndpg.py:174-186): one critic, so dL/dq = -inv_b for every row; the sums of q and q^2 over the rows
+// (value_mean / value_var).  The one-block and the many-block form, like k_td3_dy / k_td3_dy_mb.
+__global__ void __launch_bounds__(1024) k_dpg_dy(int rows, const float* __restrict__ q, float inv_b, float* __restrict__ dy,
+                                                 float* __restrict__ q_sum, float* __restrict__ q_sqsum) {
+    __shared__ float red[2][1024];
+    float s = 0.f, s2 = 0.f;
+    for (int i = threadIdx.x; i < rows; i += 1024) {
+        const float m = q[i];
+        dy[i] = -inv_b;
+        s += m;
+        s2 += m * m;
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        q_sum[0] = red[0][0];
+        q_sqsum[0] = red[1][0];
+    }
+}
+__global__ void __launch_bounds__(1024) k_dpg_dy_mb(int rows, const float* __restrict__ q, float inv_b, float* __restrict__ dy,
+                                                    float* __restrict__ part) {
+    __shared__ float red[2][1024];
+    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
+    float s = 0.f, s2 = 0.f;
+    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
+        const float m = q[i];
+        dy[i] = -inv_b;
+        s += m;
+        s2 += m * m;
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { part[blockIdx.x] = red[0][0]; part[ERR_PARTS + blockIdx.x] = red[1][0]; }
+}
 // out0 = scale0 * sum_b part[b]; out1 (nullable) = scale1 * sum_b part[PARTS + b]
 __global__ void k_finish_parts(int n_part, const float* __restrict__ part, float scale0, float scale1, float* __restrict__ out0,
                                float* __restrict__ out1) {
@@ -229,6 +279,23 @@ Td3PolicyWs td3_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     w.qv1 = ar.take(rows); w.qv2 = ar.take(rows); w.dy1 = ar.take(rows); w.dy2 = ar.take(rows);
     w.dx1 = ar.take((size_t)rows * qin); w.dx2 = ar.take((size_t)rows * qin);
     w.ga = ar.take((size_t)rows * ad);
+    w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
+    w.parts = ar.take(2 * ERR_PARTS);
+    return w;
+}
+
+struct DpgPolicyWs {        // mpg_dpg_policy_grad: the single-critic half of Td3PolicyWs
+    float *hp1, *hp2, *h1, *h2, *dz1, *dz2, *a, *dz3, *qv, *dy, *dx, *slabs, *parts;
+};
+DpgPolicyWs dpg_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    DpgPolicyWs w;
+    w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
+    w.h1 = ar.take(stash_floats(rows)); w.h2 = ar.take(stash_floats(rows));
+    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
+    w.a = ar.take((size_t)rows * ad); w.dz3 = ar.take((size_t)rows * ad);
+    w.qv = ar.take(rows); w.dy = ar.take(rows);
+    w.dx = ar.take((size_t)rows * qin);
     w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
     w.parts = ar.take(2 * ERR_PARTS);
     return w;
@@ -438,6 +505,50 @@ extern "C" int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
     hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx1, w.dx2, w.ga);
     MPG_CHECK_LAUNCH("k_sum_action_grad");
     rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, w.ga, ad, w.a, ad, po.out_tanh, po.out_scale, w.hp1, w.hp2,
+                         thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
+    if (rc) return rc;
+    return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,
+                        thin ? w.dz1 : nullptr, thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+}
+
+extern "C" size_t mpg_dpg_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (!net_cfg_ok(cfg) || rows <= 0) return 0;
+    return measured(dpg_policy_ws, cfg, rows);
+}
+
+// NDPGLearner.policy_forward_and_backward, ndpg.py:174-186: mpg_td3_policy_grad with ONE critic - one critic forward, one critic
+// backward, and the policy's backward reads dQ/da straight out of the critic's input gradient (its last act_dim columns; there is no
+// second critic to add)
+extern "C" int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, int rows, const float* obs,
+                                   float inv_b_global, float* q_sum, float* q_sqsum, float* grad, void* ws, size_t ws_bytes,
+                                   mpg_stream_t stream) {
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && obs && q_sum && q_sqsum && grad && ws && rows > 0,
+                "mpg_dpg_policy_grad: bad argument");
+    Arena ar(ws, ws_bytes);
+    const DpgPolicyWs w = dpg_policy_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_dpg_policy_grad", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    const OutSpec po = policy_out(cfg);
+    const XSpec xp = policy_x(cfg, obs);
+    int rc = policy_forward(cfg, policy_params, rows, xp, po, w.a, w.hp1, w.hp2, s);        // ndpg.py:178
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs, w.a);
+    rc = critic_forward(cfg, q1, rows, xq, w.qv, w.h1, w.h2, s);                            // :179
+    if (rc) return rc;
+    const bool thin = backward_takes_thin(od, ad);        // (see mpg_q_loss_grad)
+    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 1.f, 1.f, q_sum, q_sqsum};
+    const bool mb = rows >= ERR_MB_MIN_ROWS;
+    if (mb) {
+        hipLaunchKernelGGL(k_dpg_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv, inv_b_global, w.dy, w.parts);
+        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, q_sum, q_sqsum);
+    } else
+    hipLaunchKernelGGL(k_dpg_dy, dim3(1), dim3(1024), 0, s, rows, w.qv, inv_b_global, w.dy, q_sum, q_sqsum);
+    MPG_CHECK_LAUNCH("k_dpg_dy");
+    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy, 1, nullptr, 0, 0, 1.f, w.h1, w.h2, nullptr, nullptr, nullptr, w.dx, qin, s);
+    if (rc) return rc;
+    // dL/da = the critic's input gradient at the action columns: rows of qin floats, from column od on
+    rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, w.dx + od, qin, w.a, ad, po.out_tanh, po.out_scale, w.hp1, w.hp2,
                          thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
     if (rc) return rc;
     return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,

@@ -76,13 +76,14 @@ inline bool exchanged(const mpg_train_ctx_t* c) { return c->world_size > 1 || c-
 inline bool is_mpg(const mpg_train_ctx_t* c) { return c->learner_version == 1 || c->learner_version == 2; }
 
 bool ctx_ok(const mpg_train_ctx_t* c) {
-    if (!c || c->learner_version < 1 || c->learner_version > 4) return false;
+    if (!c || c->learner_version < 1 || c->learner_version > 5) return false;
     const bool common = c->num_agent > 0 && c->batch > 0 && c->world_size > 0 && c->sampling_interval > 0 && c->num_batch_reuse > 0 &&
                         c->ring_capacity > 0 && c->params && c->targets && c->grad && c->ws0 && c->ws1;
     if (!common) return false;
     if (is_mpg(c))
         return c->n > 0 && c->M > 0 && c->n_select > 0 && c->n_select <= 4 && (c->learner_version == 2 ? 2 : 1) + 2 * c->n_select <= 8;
     if (c->learner_version == 3) return c->n > 0 && c->num_batch_reuse == 1;
+    if (c->learner_version == 5) return c->n > 0 && c->l_obs && c->l_rewards;       // no state block, no l_act / l_done*
     // TD3: the scratch block, and the trees when the replay is prioritized
     return c->scratch && c->num_batch_reuse == 1 &&
            (!c->prioritized || (c->per_sum && c->per_min && c->per_stamp && c->per_capacity >= c->ring_capacity && c->per_max_priority && c->b_weights));
@@ -187,16 +188,41 @@ int td3_gradients(mpg_train_ctx_t* c, const Layout& l, mpg_stream_t s) {
     return mpg_td3_policy_grad(&c->cfg, policy, q1, q2, B, c->b_obs, inv_b, stats + 2, stats + 3, c->grad + l.off[2], c->ws1, c->ws1_bytes, s);
 }
 
+// ---- NDPGLearner.compute_gradient, learners/ndpg.py:202-237 (networks [Q1 | policy]); the minibatch and its n-step real-env target
+//      (:57-72,127-151) every num_batch_reuse-th call ----
+int ndpg_gradients(mpg_train_ctx_t* c, const Layout& l, bool fresh, mpg_stream_t s) {
+    const int od = c->cfg.obs_dim, ad = c->cfg.act_dim;
+    const float* q1 = c->params;
+    const float* policy = c->params + l.off[1];
+    const float inv_b = 1.f / ((float)c->batch * (float)c->world_size);
+    float* stats = c->grad + l.n_grad;
+    if (fresh) {
+        TRY(mpg_replay_sample_uniform(c->ring_size, c->batch, c->replay_seed, c->replay_times, od, ad, c->ring_obs, c->ring_act,
+                                      c->ring_rew, c->ring_obs2, c->ring_done, c->idx, c->b_obs, c->b_act, c->b_rew, c->b_obs2,
+                                      c->b_done, s));
+        TRY(mpg_env_rollout(&c->cfg, policy, c->batch, c->n, c->b_obs, c->b_act, c->l_rewards, c->l_obs, s));
+        TRY(mpg_nstep_targets(&c->cfg, c->targets + l.off[1], c->targets, c->batch, c->n, c->l_rewards, c->l_obs, c->b_targets, c->ws0,
+                              c->ws0_bytes, s));
+    }
+    TRY(mpg_q_loss_grad(&c->cfg, q1, c->batch, c->b_obs, c->b_act, c->b_targets, inv_b, stats, c->grad + l.off[0], nullptr, c->ws0,
+                        c->ws0_bytes, s));
+    return mpg_dpg_policy_grad(&c->cfg, policy, q1, c->batch, c->b_obs, inv_b, stats + 2, stats + 3, c->grad + l.off[1], c->ws1,
+                               c->ws1_bytes, s);
+}
+
 }  // namespace
 
 extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, size_t* ws1) {
     MPG_REQUIRE(c && ws0 && ws1, "mpg_step_workspace_bytes: null pointer");
+    MPG_REQUIRE(c->learner_version >= 1 && c->learner_version <= 5, "mpg_step_workspace_bytes: unknown learner_version %d", c->learner_version);
     *ws0 = std::max(mpg_q_targets_workspace_bytes(&c->cfg, c->batch), mpg_q_loss_grad_workspace_bytes(&c->cfg, c->batch));
     if (c->learner_version == 3) {
         *ws0 = std::max(*ws0, mpg_rollout_q_target_workspace_bytes(&c->cfg, c->batch));
         *ws1 = mpg_rollout_pg_workspace_bytes(&c->cfg, c->batch, 1, c->n, 2, 1);
     } else if (c->learner_version == 4) {
         *ws1 = mpg_td3_policy_grad_workspace_bytes(&c->cfg, c->batch);
+    } else if (c->learner_version == 5) {
+        *ws1 = mpg_dpg_policy_grad_workspace_bytes(&c->cfg, c->batch);
     } else
     *ws1 = mpg_mpg_gradients_workspace_bytes(&c->cfg, c->batch, c->M, c->n, c->n_select, c->learner_version == 2 ? 2 : 1);
     MPG_REQUIRE(*ws0 && *ws1, "mpg_step_workspace_bytes: unsupported configuration");
@@ -213,10 +239,15 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
     const int od = c->cfg.obs_dim, ad = c->cfg.act_dim, kind = c->cfg.env_kind;
     const float* policy = c->params + l.off[l.n_nets - 1];
     const float* policy_t = c->targets + l.off[l.n_nets - 1];
-    if (!is_mpg(c)) {        // ---- NADP / TD3: sample, add, replay, gradients (optimizer.py:330-353) ----
+    if (!is_mpg(c)) {        // ---- NADP / TD3 / NDPG: sample, add, replay, gradients (optimizer.py:330-353) ----
         if (iteration % c->sampling_interval == 0) TRY(sample_and_add(c, policy, false, nullptr, nullptr, s));
         MPG_REQUIRE(c->ring_size > 0, "mpg_step_begin: empty replay ring");
         c->replay_times++;
+        if (c->learner_version == 5) {       // the batch is drawn on every num_batch_reuse-th call only (ndpg.py:203-204)
+            const bool fresh = c->learner_counter % c->num_batch_reuse == 0;
+            c->learner_counter++;
+            return ndpg_gradients(c, l, fresh, s);
+        }
         if (c->learner_version == 4 && c->prioritized) {
             TRY(mpg_per_sample_gather(c->per_sum, c->per_min, c->per_capacity, c->ring_size, c->batch, nullptr, c->replay_seed,
                                       c->replay_times, c->per_beta, c->idx, c->b_weights, od, ad, c->ring_obs, c->ring_act, c->ring_rew,

@@ -48,11 +48,11 @@ class TrainCtx(ctypes.Structure):
 class FusedMPGStep(object):
     """step(iteration) == SingleProcessOffPolicyOptimizer.step for (OffPolicyWorker, replay buffer, learner) sharing one
     PolicyWithQs: MPGLearner + ReplayBuffer (learner_version 1 / 2), NADPLearner + ReplayBuffer (3), TD3Learner + ReplayBuffer
-    or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included)."""
+    or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included), NDPGLearner + ReplayBuffer (5)."""
 
     def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
         from .buffer import PrioritizedReplayBuffer
-        from .learners import MPGLearner, NADPLearner, TD3Learner
+        from .learners import MPGLearner, NADPLearner, NDPGLearner, TD3Learner
         per = isinstance(rb, PrioritizedReplayBuffer)
         assert per == (learner.args.buffer_type != 'normal')
         assert learner.policy_with_value is worker.policy_with_value
@@ -71,6 +71,9 @@ class FusedMPGStep(object):
         elif type(learner) is NADPLearner:
             assert not per and learner.n_q == learner.n_pi and learner.num_batch_reuse == 1
             c.learner_version, c.n, c.M, c.n_select = 3, learner.n_pi, 1, 2
+        elif type(learner) is NDPGLearner:
+            assert not per
+            c.learner_version, c.n, c.M, c.n_select = 5, learner.sample_num_in_learner, 1, 1
         else:
             assert type(learner) is TD3Learner and learner.num_batch_reuse == 1
             c.learner_version, c.n, c.M, c.n_select = 4, 1, 1, 1
@@ -100,6 +103,8 @@ class FusedMPGStep(object):
             t.update(l_obs=torch.empty(B, od, **f), l_act=torch.empty(B, ad, **f), l_rewards=torch.empty(c.n, B, **f),
                      l_done=torch.ones(B, **u8), l_done_intended=torch.zeros(B, **u8))
             c.l_env_state = L.ptr(learner.env._state)
+        elif c.learner_version == 5:        # the one-launch sampler keeps its agents in registers: rewards and last observations only
+            t.update(l_obs=torch.empty(B, od, **f), l_rewards=torch.empty(c.n, B, **f))
         for k, v in t.items():
             setattr(c, k, L.ptr(v))
         c.env_state = L.ptr(worker.env._state)

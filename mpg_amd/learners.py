@@ -1,5 +1,5 @@
-"""Learners - device mirrors of learners/mpg_learner.py (MPGLearner), learners/nadp.py (NADPLearner) and
-learners/td3.py (TD3Learner): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
+"""Learners - device mirrors of learners/mpg_learner.py (MPGLearner), learners/nadp.py (NADPLearner),
+learners/td3.py (TD3Learner) and learners/ndpg.py (NDPGLearner): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
 (`set_weights`, `compute_gradient(batch5, rb, indexes, iteration)`, `get_stats`, `get_info_for_buffer`), same
 output order `q1 (+q2) + policy`.
 
@@ -378,4 +378,75 @@ class TD3Learner(_LearnerBase):
             return dict(q_loss1=stats[0], q_loss2=stats[1], policy_loss=-mean, value_mean=mean,
                         value_var=stats[3] / B - mean * mean, q_gradient_norm1=self.norms[0],
                         q_gradient_norm2=self.norms[1], policy_gradient_norm=self.norms[2])
+        return lazy
+
+
+class NDPGLearner(_LearnerBase):
+    """n-step DPG (learners/ndpg.py:23-237): the critic's target is MPG-v1's n-step REAL-env return (:127-151), the policy gradient
+    is one-step DPG through the single critic (:174-186).  Networks [Q1 | policy] (double_Q=False, target=True).
+    PathTracking-v0 with num_future_data 0 .. 10 only: the reference's other branch is a per-row loop over a one-agent gym env
+    (:78-98) for which it ships no parser, and the analytic cart-pole here is not pinned to MuJoCo."""
+
+    def __init__(self, policy_cls, args, device='cuda'):
+        if args.env_id != 'PathTracking-v0':
+            raise ValueError('NDPGLearner serves PathTracking-v0 only (got env_id %r): the reference samples every other env row by '
+                             'row from a one-agent gym env (ndpg.py:78-98) and ships no parser for it' % (args.env_id,))
+        if not 0 <= int(args.num_future_data) <= PathTrackingEnv.MAX_FUTURE:
+            raise ValueError('NDPGLearner: num_future_data in [0, %d] (got %r)' % (PathTrackingEnv.MAX_FUTURE, args.num_future_data))
+        super().__init__(policy_cls, args, device)
+        assert self.policy_with_value.names == ['Q1', 'policy'], 'NDPG trains [Q1 | policy]: double_Q=False, target=True'
+        self.sample_num_in_learner = args.sample_num_in_learner
+
+    def sample(self, start_obs, start_action):
+        """ndpg.py:99-114: n real-env steps, the first with the replay action, then the ONLINE policy without noise - one launch"""
+        pw = self.policy_with_value
+        rewards, last_obs = ops.env_rollout(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
+        return {'all_rewards': rewards, 'last_obs': last_obs}
+
+    def compute_n_step_target(self):
+        """ndpg.py:127-151: target policy and Q1_target at the LAST observation only"""
+        pw, b = self.policy_with_value, self.batch_data
+        ro = self.sample(b['batch_obs'], b['batch_actions'])
+        return ops.nstep_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), ro['all_rewards'], ro['last_obs'])
+
+    def compute_td_error(self):
+        """ndpg.py:116-125 (signed)."""
+        pw, b = self.policy_with_value, self.batch_data
+        y1 = ops.q_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), None, b['batch_rewards'], b['batch_obs_tp1'])
+        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
+
+    def get_batch_data(self, batch_data, rb, indexes):
+        self._get_batch(batch_data)
+        self.batch_data['batch_targets'] = self.compute_n_step_target()
+        if self.args.buffer_type != 'normal':
+            self.info_for_buffer.update(dict(td_error=self.compute_td_error(), rb=rb, indexes=indexes))
+
+    def compute_gradient(self, batch_data, rb, indexes, iteration):
+        """ndpg.py:202-237"""
+        if self.counter % self.num_batch_reuse == 0:
+            self.get_batch_data(batch_data, rb, indexes)
+        self.counter += 1
+        if self.args.buffer_type != 'normal':                  # :206-207: the priorities follow the critic within a reused batch
+            self.info_for_buffer.update(dict(td_error=self.compute_td_error()))
+        pw, b = self.policy_with_value, self.batch_data
+        rows = b['batch_obs'].shape[0]
+        inv_b = 1.0 / (rows * D.world_size())
+        stats = self.flat[self.n_grad:]
+        ops.q_loss_grad(self.cfg, pw.net('Q1'), b['batch_obs'], b['batch_actions'], b['batch_targets'], inv_b_global=inv_b,
+                        grad_out=self.grad('Q1'), loss_out=stats[0:1])                               # :162-172
+        ops.dpg_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), b['batch_obs'], inv_b_global=inv_b,
+                            grad_out=self.grad('policy'), stats_out=stats[2:4])                      # :174-186
+        out = self._finish(iteration, float(self.args.gradient_clip_norm))
+        self._lazy_stats = self._native_lazy_stats(iteration)
+        return out
+
+    def _native_lazy_stats(self, iteration):
+        stats, B = self.flat[self.n_grad:], self.batch_size * D.world_size()
+
+        def lazy():        # evaluated only when get_stats() is called: no elementwise launches in the training loop
+            mean = stats[2] / B
+            # (mb_targets_mean: this process's batch, like the reference's np.mean(mb_targets))
+            return dict(q_loss=stats[0], policy_loss=-mean, value_mean=mean, value_var=stats[3] / B - mean * mean,
+                        mb_targets_mean=self.batch_data['batch_targets'].mean(), q_gradient_norm=self.norms[0],
+                        policy_gradient_norm=self.norms[1])
         return lazy

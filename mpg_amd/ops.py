@@ -279,6 +279,17 @@ def nstep_targets(cfg, policy_t, q1t, rewards, last_obs):
     return y
 
 
+def env_rollout(cfg, policy_params, obs0, act0, n):
+    """mpg_env_rollout: n real-env steps from (obs0, act0), later actions from the policy without noise, ONE launch.
+    Returns (rewards [n, rows] RAW, last_obs [rows, obs_dim])."""
+    rows, dev = obs0.shape[0], obs0.device
+    rewards = torch.empty(int(n), rows, dtype=torch.float32, device=dev)
+    last_obs = torch.empty(rows, cfg.obs_dim, dtype=torch.float32, device=dev)
+    L.call('mpg_env_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)),
+           L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
+    return rewards, last_obs
+
+
 def q_loss_grad(cfg, q_params, obs, act, y, inv_b_global=None, grad_out=None, loss_out=None, want_td=False):
     rows = obs.shape[0]
     dev = obs.device
@@ -389,6 +400,18 @@ def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out
     L.call('mpg_td3_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)),
            L.c_int(rows), L.ptr(_f32(obs)), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
            L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad), *ws, L.stream())
+    return stats, grad
+
+
+def dpg_policy_grad(cfg, policy_params, q1, obs, inv_b_global=None, grad_out=None, stats_out=None):
+    """mpg_dpg_policy_grad: -mean Q1(s~, pi(s~)) and its policy gradient.  Returns (stats = [q_sum, q_sqsum], grad)."""
+    rows, dev = obs.shape[0], obs.device
+    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
+    stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.float32, device=dev)
+    ws = _ws(dev, 1, 'mpg_dpg_policy_grad_workspace_bytes', cfg, rows)
+    L.call('mpg_dpg_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.c_int(rows), L.ptr(_f32(obs)),
+           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad),
+           *ws, L.stream())
     return stats, grad
 
 

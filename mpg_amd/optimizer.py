@@ -36,12 +36,13 @@ class SingleProcessOffPolicyOptimizer(object):
         self._fused = None
         if fused:
             from .buffer import PrioritizedReplayBuffer
-            from .learners import MPGLearner, NADPLearner, TD3Learner
+            from .learners import MPGLearner, NADPLearner, NDPGLearner, TD3Learner
             per = isinstance(replay_buffer, PrioritizedReplayBuffer)
             normal = getattr(args, 'buffer_type', 'normal') == 'normal'
             ok = (type(learner) is MPGLearner and not per and normal and not learner.deriv_interval_policy) or \
                  (type(learner) is NADPLearner and not per and normal and learner.num_batch_reuse == 1 and learner.n_q == learner.n_pi) or \
-                 (type(learner) is TD3Learner and per == (not normal) and learner.num_batch_reuse == 1)
+                 (type(learner) is TD3Learner and per == (not normal) and learner.num_batch_reuse == 1) or \
+                 (type(learner) is NDPGLearner and not per and normal)
             if ok:
                 from .fused import FusedMPGStep
                 self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
