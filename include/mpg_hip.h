@@ -238,7 +238,8 @@ typedef struct {
 } mpg_cfg_t;
 
 /* MLPNet.call  - model.py:39-43:  y[rows][out_used] = act(ELU(ELU(x W1 + b1) W2 + b2) W3 + b3)[:, :out_used].
- * x [rows][in_dim] (supported (in_dim, out_used): (6,2) (8,1) (4,1) (5,1) (6,1)); the first n_scaled input
+ * x [rows][in_dim] (supported (in_dim, out_used): (6,2) (8,1) (4,1) (5,1) (6,1), the look-ahead widths, and (6..16, 4):
+ * all four logits of the PathTracking policy head); the first n_scaled input
  * columns are multiplied by in_scale[] (host array, may be NULL). */
 int mpg_mlp_forward(const float* params, int in_dim, int out_dim, int out_used, int out_act, int rows,
                     const float* x, const float* in_scale, int n_scaled, float* y,
@@ -430,6 +431,40 @@ int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const 
 size_t mpg_dpg_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows);
 int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, int rows, const float* obs,
                         float inv_b_global, float* q_sum, float* q_sqsum, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
+/* ---- SAC with a fixed temperature (learners/sac.py; policy.py:179-204 with action_range None: no bijector) ----
+ * The stochastic policy is a diagonal Gaussian over the FOUR logits of the PathTracking policy: mean = logits[:, :2],
+ * log_std = clip(logits[:, 2:], -5, 1).  Every entry point below takes the caller's standard-normal draws eps [rows][2]
+ * (mpg_normal_fill; no generator runs inside) and refuses, before any launch, with MPG_EINVAL and its own name in the message: null
+ * pointers, rows <= 0, act_dim != 2 or env_kind != MPG_ENV_PATH_TRACKING ("Gaussian head without an action range only": the
+ * pendulum's action_range 3 is a tanh-affine bijector, policy.py:183-190), action_range > 0, alpha < 0 or not finite; a workspace
+ * one byte short is MPG_EWORKSPACE with both sizes.  The queries answer 0 for what the entry points refuse. */
+
+/* PolicyWithQs.compute_action / compute_target_action, stochastic branch  - policy.py:193-217 (act_dist.sample(),
+ * act_dist.log_prob):  act_out [rows][2] = mean + sigma * eps, sigma the correctly rounded float32 exp(log_std), product and sum rounded separately,
+ * logp_out [rows] = sum_k (-0.5 eps_k^2 - log_std_k - 0.5 log(2 pi)), logits_out [rows][4] (nullable) the policy's output on
+ * obs*obs_scale (policy_out_act applied to all four, as MLPNet does). */
+size_t mpg_policy_sample_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_policy_sample(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
+                      float* logp_out, float* logits_out /* nullable */, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
+/* SACLearner.compute_clipped_double_q_target  - learners/sac.py:67-80:
+ *   y = (rew+shift)*scale + gamma * (min(Q1t, Q2t)(s~', a') - alpha * logp'),  (a', logp') sampled from `policy` at s~' with eps
+ *   (the reference samples from the ONLINE policy here, sac.py:71: pass the online parameters). */
+size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                    const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
+/* SACLearner.policy_forward_and_backward  - learners/sac.py:119-136:
+ *   loss = mean_B (alpha * logp - min(Q1,Q2)(s~, a)),  (a, logp) sampled with eps; grad = flat policy gradient over all four
+ *   output columns (unclipped, reduced over this GPU's rows, divisor B_global through inv_b_global).  qmin_sum / qmin_sqsum / logp_sum:
+ *   sums over the rows of min-Q, its square and logp (value_mean, value_var, policy_entropy = -mean logp, policy_loss =
+ *   alpha * mean logp - value_mean; sac.py:128-132).  A log-std logit outside [-5, 1] has zero gradient (clip_by_value; the
+ *   bounds themselves pass it). */
+size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                        const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                        float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_by_global_norm + Keras Adam + Polyak (K7, K8) over the flat [net0 | net1 | ...] vectors

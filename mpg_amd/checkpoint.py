@@ -48,7 +48,9 @@ def state_of(optimizer):
         format_version=FORMAT_VERSION, learner_cls=type(ln).__name__, buffer_cls=type(rb).__name__, names=list(pw.names),
         learner_version=getattr(ln.args, 'learner_version', None),
         optimizer=dict(iteration=optimizer.iteration, num_sampled_steps=optimizer.num_sampled_steps),
-        policy=dict(opt_steps={k: int(v) for k, v in pw.opt_steps.items()}),
+        # (sample_ctr: the stochastic policy's own stream of draws; absent for a deterministic policy)
+        policy=dict(opt_steps={k: int(v) for k, v in pw.opt_steps.items()},
+                    **({'sample_ctr': int(pw._sample_ctr)} if not getattr(pw, 'deterministic_policy', True) else {})),
         worker=dict(seed=w.seed, noise_ctr=w._noise_ctr, env_seed=w.env.seed, env_ctr=w.env._ctr, num_sample=w.num_sample,
                     sample_times=w.sample_times, iteration=w.iteration, env_initialised=bool(w.env._initialised)),
         learner=dict(seed=ln.seed, counter=ln.counter),
@@ -89,6 +91,8 @@ def load_checkpoint(path, optimizer):
     for k in ('params', 'targets', 'm', 'v', 'nonfinite'):
         put(getattr(pw, k), 'policy/' + k)
     pw.opt_steps = {k: int(v) for k, v in meta['policy']['opt_steps'].items()}
+    if 'sample_ctr' in meta['policy']:
+        pw._sample_ctr = int(meta['policy']['sample_ctr'])
     pw.refresh_weight_cache()
     put(w.env._state, 'worker/env_state')
     m = meta['worker']

@@ -240,6 +240,99 @@ __global__ void k_sum_action_grad(int rows, int od, int ad, const float* __restr
     ga[i] = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
 }
 
+// ---- Gaussian policy head (policy.py:179-204 with action_range None: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))), no
+// bijector) on the four logits of the policy pass, one thread per row ---------------------------------------------------------------
+constexpr float LOG_STD_MIN = -5.f, LOG_STD_MAX = 1.f, HALF_LOG_2PI = 0.91893853320467274f;
+// sigma = exp(log_std) as the CORRECTLY ROUNDED float32 exponential (the double-precision exp, rounded once): the float32 library exp is
+// within an ulp of it and its last bit differs between compiler versions, while a sample must be reproducible from logits_out by anyone
+// (two values per row: the double-precision pipe is not on any hot path here)
+__device__ __forceinline__ float sigma_of(float clipped_log_std) { return (float)exp((double)clipped_log_std); }
+// a * b + c with the product and the sum rounded separately, whatever the translation unit's contraction mode (the __fmul_rn / __fadd_rn
+// intrinsics are plain operators here and fuse)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return p + c;
+}
+// act = mean + sigma * eps with the product and the sum rounded separately (the same bits as the two-op expression a caller forms
+// from logits_out); returns the row's log-density.  z, the standardised sample of the density, is eps ITSELF: TFP forms
+// (a - mean) / sigma, which in exact arithmetic is eps and in float32 is eps with two more roundings - against the float64 run of the
+// reference, where that expression returns eps to 1e-16, eps is the nearer of the two.
+__device__ __forceinline__ float gauss_row(int ad, const float* __restrict__ l, const float* __restrict__ e, float* __restrict__ a) {
+    float lp = 0.f;
+    for (int k = 0; k < ad; ++k) {
+        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), sigma = sigma_of(ls), z = e[k];
+        a[k] = mul_then_add(sigma, z, l[k]);
+        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
+    }
+    return lp;
+}
+// logits [rows][2 ad], eps [rows][ad] -> act [rows][ad], logp [rows]; logp_sum (nullable): sum of logp over the rows (one block, fixed order)
+__global__ void __launch_bounds__(1024) k_gauss_head(int rows, int ad, const float* __restrict__ logits, const float* __restrict__ eps,
+                                                     float* __restrict__ act, float* __restrict__ logp, float* __restrict__ logp_sum) {
+    __shared__ float red[1024];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < rows; i += 1024) {
+        const float lp = gauss_row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
+        logp[i] = lp;
+        s += lp;
+    }
+    if (!logp_sum) return;                      // (uniform)
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) logp_sum[0] = red[0];
+}
+// the many-block form (k_td3_dy_mb): block b leaves the sum of its run of rows in part[b] (part nullable: no sum wanted)
+__global__ void __launch_bounds__(1024) k_gauss_head_mb(int rows, int ad, const float* __restrict__ logits, const float* __restrict__ eps,
+                                                        float* __restrict__ act, float* __restrict__ logp, float* __restrict__ part) {
+    __shared__ float red[1024];
+    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
+    float s = 0.f;
+    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
+        const float lp = gauss_row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
+        logp[i] = lp;
+        s += lp;
+    }
+    if (!part) return;
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// soft target (sac.py:78-79): y = (rew + shift) * scale + gamma * (min(q1, q2) - alpha * logp)
+__global__ void k_sac_combine(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
+                              const float* __restrict__ logp, float alpha, float shift, float scale, float gamma, float* __restrict__ y) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    y[i] = (rew[i] + shift) * scale + gamma * (fminf(q1[i], q2[i]) - alpha * logp[i]);
+}
+
+// dL/dlogits [rows][2 ad] of loss = mean(alpha * logp - qmin) (sac.py:128) with a = mean + sigma * eps, logp = sum(-0.5 eps^2 - log_std - c):
+// ga_k = dx1[row][od + k] + dx2[row][od + k] is d(-inv_b qmin)/da_k (the critics' input gradients under k_td3_dy's dy);
+// mean column k: ga_k; log-std column k: ga_k sigma_k eps_k - alpha inv_b, and ZERO where the clip is active - strictly outside
+// [-5, 1]: clip_by_value passes the gradient at the bounds themselves (the stand-in's clamp, and TF's own rule)
+__global__ void k_sac_dlogits(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
+                              const float* __restrict__ eps, const float* __restrict__ logits, float alpha, float inv_b,
+                              float* __restrict__ dlogits) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * ad) return;
+    const int row = i / ad, k = i % ad;
+    const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
+    const float raw = logits[(long)row * 2 * ad + ad + k];
+    const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
+    const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
+    dlogits[(long)row * 2 * ad + k] = ga;
+    dlogits[(long)row * 2 * ad + ad + k] = inside ? ga * sigma * eps[i] - alpha * inv_b : 0.f;
+}
+
 // ---- workspaces: one description each (host_glue.h Arena) ----------------------------------------------------------
 struct QTargetsWs {        // mpg_q_targets, mpg_td3_targets, mpg_nstep_targets (which leaves q2 unused)
     float *a, *q1, *q2;
@@ -299,6 +392,79 @@ DpgPolicyWs dpg_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
     w.parts = ar.take(2 * ERR_PARTS);
     return w;
+}
+
+struct PolicySampleWs {    // mpg_policy_sample
+    float* logits;
+};
+PolicySampleWs policy_sample_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    PolicySampleWs w;
+    w.logits = ar.take((size_t)rows * 2 * cfg->act_dim);
+    return w;
+}
+
+struct SacTargetsWs {      // mpg_sac_targets
+    float *logits, *a, *logp, *q1, *q2;
+};
+SacTargetsWs sac_targets_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    SacTargetsWs w;
+    w.logits = ar.take((size_t)rows * 2 * cfg->act_dim);
+    w.a = ar.take((size_t)rows * cfg->act_dim);
+    w.logp = ar.take(rows); w.q1 = ar.take(rows); w.q2 = ar.take(rows);
+    return w;
+}
+
+struct SacPolicyWs {       // mpg_sac_policy_grad: Td3PolicyWs with the logits, logp and the four-column output gradient
+    float *hp1, *hp2, *h11, *h12, *h21, *h22, *dz1, *dz2, *logits, *a, *logp, *dlogits, *dz3, *qv1, *qv2, *dy1, *dy2, *dx1, *dx2, *slabs,
+        *parts, *lparts;
+};
+SacPolicyWs sac_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    SacPolicyWs w;
+    w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
+    w.h11 = ar.take(stash_floats(rows)); w.h12 = ar.take(stash_floats(rows));
+    w.h21 = ar.take(stash_floats(rows)); w.h22 = ar.take(stash_floats(rows));
+    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
+    w.logits = ar.take((size_t)rows * 2 * ad); w.a = ar.take((size_t)rows * ad); w.logp = ar.take(rows);
+    w.dlogits = ar.take((size_t)rows * 2 * ad); w.dz3 = ar.take((size_t)rows * 2 * ad);
+    w.qv1 = ar.take(rows); w.qv2 = ar.take(rows); w.dy1 = ar.take(rows); w.dy2 = ar.take(rows);
+    w.dx1 = ar.take((size_t)rows * qin); w.dx2 = ar.take((size_t)rows * qin);
+    w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
+    w.parts = ar.take(2 * ERR_PARTS); w.lparts = ar.take(2 * ERR_PARTS);
+    return w;
+}
+
+// The refusals the three Gaussian-head entry points (and their workspace queries) share, in the order include/mpg_hip.h lists them.
+// `entry` names the caller in every message; MPG_OK when the call may proceed.
+int gauss_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
+    MPG_REQUIRE(cfg && pointers, "%s: null pointer", entry);
+    MPG_REQUIRE(rows > 0, "%s: rows must be positive (got %d)", entry, rows);
+    MPG_REQUIRE(cfg->act_dim == 2 && cfg->env_kind == MPG_ENV_PATH_TRACKING,
+                "%s: Gaussian head without an action range only (act_dim 2 on PathTracking; got act_dim %d, env_kind %d)", entry,
+                cfg->act_dim, cfg->env_kind);
+    MPG_REQUIRE(!(cfg->action_range > 0.f), "%s: Gaussian head without an action range only (got action_range %g)", entry,
+                (double)cfg->action_range);
+    MPG_REQUIRE(net_cfg_ok(cfg), "%s: unsupported observation width %d", entry, cfg->obs_dim);
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
+    return MPG_OK;
+}
+
+// all four logits of the policy (MLPNet's output activation on every column, no action range), optional stashes
+int policy_logits(const mpg_cfg_t* c, const float* params, int rows, const float* obs, float* logits, float* h1, float* h2, hipStream_t s) {
+    OutSpec o = linear_out();
+    o.out_tanh = c->policy_out_act == MPG_ACT_TANH;
+    return launch_forward(c, params, c->obs_dim, 2 * c->act_dim, 2 * c->act_dim, rows, policy_x(c, obs), o, logits, 2 * c->act_dim, h1, h2, s);
+}
+// the head on `logits`: act, logp and (nullable) the sum of logp - one block below ERR_MB_MIN_ROWS, ERR_PARTS blocks + the finish above
+int gauss_head(const mpg_cfg_t* c, int rows, const float* logits, const float* eps, float* act, float* logp, float* logp_sum, float* parts,
+               hipStream_t s) {
+    if (rows >= ERR_MB_MIN_ROWS) {
+        hipLaunchKernelGGL(k_gauss_head_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, c->act_dim, logits, eps, act, logp, logp_sum ? parts : nullptr);
+        if (logp_sum) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, parts, 1.f, 0.f, logp_sum, (float*)nullptr);
+    } else
+        hipLaunchKernelGGL(k_gauss_head, dim3(1), dim3(1024), 0, s, rows, c->act_dim, logits, eps, act, logp, logp_sum);
+    MPG_CHECK_LAUNCH("k_gauss_head");
+    return MPG_OK;
 }
 
 }  // namespace
@@ -553,4 +719,99 @@ extern "C" int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
     if (rc) return rc;
     return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,
                         thin ? w.dz1 : nullptr, thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+}
+
+extern "C" size_t mpg_policy_sample_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (gauss_refusal("mpg_policy_sample_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(policy_sample_ws, cfg, rows);
+}
+
+extern "C" int mpg_policy_sample(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
+                                 float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = gauss_refusal("mpg_policy_sample", cfg, policy && obs && eps && act_out && logp_out && ws, rows, 0.f);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const PolicySampleWs w = policy_sample_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_policy_sample", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    float* logits = logits_out ? logits_out : w.logits;
+    rc = policy_logits(cfg, policy, rows, obs, logits, nullptr, nullptr, s);
+    if (rc) return rc;
+    return gauss_head(cfg, rows, logits, eps, act_out, logp_out, nullptr, nullptr, s);
+}
+
+extern "C" size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (gauss_refusal("mpg_sac_targets_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(sac_targets_ws, cfg, rows);
+}
+
+extern "C" int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                               const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes,
+                               mpg_stream_t stream) {
+    int rc = gauss_refusal("mpg_sac_targets", cfg, policy && q1t && q2t && rew && obs_tp1 && eps && y && ws, rows, alpha);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_sac_targets", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);          // sac.py:71
+    if (rc) return rc;
+    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s);
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);                     // :73
+    if (rc) return rc;
+    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);                     // :74
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sac_combine, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, alpha, cfg->rew_shift,
+                       cfg->rew_scale, cfg->gamma, y);                                      // :78-79
+    MPG_CHECK_LAUNCH("k_sac_combine");
+    return MPG_OK;
+}
+
+extern "C" size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (gauss_refusal("mpg_sac_policy_grad_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(sac_policy_ws, cfg, rows);
+}
+
+// mpg_td3_policy_grad with the sampled action in place of the mean: the policy pass keeps all four logits, the head samples, the
+// critics' input gradients come back as in TD3 (the same dy kernel: the gradient flows through the smaller critic), k_sac_dlogits
+// turns them into the four-column output gradient, and the policy's backward / weight gradient run in their four-output form
+extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                                   const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                                   float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = gauss_refusal("mpg_sac_policy_grad", cfg, policy && q1 && q2 && obs && eps && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
+                           rows, alpha);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const SacPolicyWs w = sac_policy_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_sac_policy_grad", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, out_tanh = cfg->policy_out_act == MPG_ACT_TANH;
+    rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);                  // sac.py:123
+    if (rc) return rc;
+    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs, w.a);
+    rc = critic_forward(cfg, q1, rows, xq, w.qv1, w.h11, w.h12, s);                         // :124
+    if (rc) return rc;
+    rc = critic_forward(cfg, q2, rows, xq, w.qv2, w.h21, w.h22, s);                         // :125
+    if (rc) return rc;
+    if (rows >= ERR_MB_MIN_ROWS) {                                                          // :126, :131-132
+        hipLaunchKernelGGL(k_td3_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, w.parts);
+        hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, qmin_sum, qmin_sqsum);
+    } else
+        hipLaunchKernelGGL(k_td3_dy, dim3(1), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, qmin_sum, qmin_sqsum);
+    MPG_CHECK_LAUNCH("k_td3_dy");
+    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy1, 1, nullptr, 0, 0, 1.f, w.h11, w.h12, nullptr, nullptr, nullptr, w.dx1, qin, s);
+    if (rc) return rc;
+    rc = launch_backward(cfg, q2, qin, 1, 1, rows, w.dy2, 1, nullptr, 0, 0, 1.f, w.h21, w.h22, nullptr, nullptr, nullptr, w.dx2, qin, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sac_dlogits, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx1, w.dx2, eps, w.logits, alpha,
+                       inv_b_global, w.dlogits);
+    MPG_CHECK_LAUNCH("k_sac_dlogits");
+    rc = launch_backward(cfg, policy, od, 2 * ad, 2 * ad, rows, w.dlogits, 2 * ad, w.logits, 2 * ad, out_tanh, 1.f, w.hp1, w.hp2, w.dz1, w.dz2,
+                         w.dz3, nullptr, 0, s);
+    if (rc) return rc;
+    return launch_wgrad(cfg, od, 2 * ad, 2 * ad, rows, policy_x(cfg, obs), w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s);
 }

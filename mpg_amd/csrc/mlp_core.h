@@ -33,7 +33,12 @@ template <int IN>
 __host__ __device__ constexpr int xs_of() { return IN <= 8 ? 8 : (IN <= 16 ? 16 : 24); }
 template <int IN>
 __host__ __device__ constexpr int l1_steps() { return IN <= 8 ? 2 : (IN <= 16 ? 4 : 6); }
-constexpr int MAXOUT = 2;      // outputs ever *used* (policy mean: act_dim <= 2; critic: 1)
+// Row stride of the LDS blocks indexed by used output (sPart [NWAVE][16][stride], sD3 [stride][16]) for a kernel built for OU
+// used outputs: 2 for OU <= 2 (policy mean: act_dim <= 2; critic: 1), 4 for the four-logit Gaussian head (mean | log-std,
+// policy.py:179-204).  MAXOUT is the stride of every kernel that is built for OU <= 2 only (sweeps, worker, fused kernels).
+template <int OU>
+__host__ __device__ constexpr int out_stride() { return OU <= 2 ? 2 : 4; }
+constexpr int MAXOUT = out_stride<2>();
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -525,7 +530,7 @@ __device__ __forceinline__ void stash_load(const float* __restrict__ base, long 
 }
 
 // ---- forward through the two hidden layers + partial output layer for one row group ---------------------
-// sX  [16][XS]  inputs (already scaled), sA the LDS A image, sPart [NWAVE][16][MAXOUT] output partials.
+// sX  [16][XS]  inputs (already scaled), sA the LDS A image, sPart [NWAVE][16][out_stride<OU>()] output partials.
 // On return h1/h2 hold this lane's C-layout activations and sPart the per-wave partial sums of h2*W3 (no bias);
 // the caller must have synchronised sX before the call and may read sPart right after (ends on a barrier).
 template <int IN, int OU, bool FINAL_BARRIER = true, StashStore ST = StashStore::plain>
@@ -572,7 +577,12 @@ __device__ __forceinline__ void forward_group(const float* sX, float* sA, float*
             asm volatile("v_add_f32_dpp %0, %1, %1 " MODS " row_mask:0xf bank_mask:0xf" : "=v"(p[o][j]) : "v"(p[o][j]));
         // the first stage's operands come from ordinary fmas the scheduler could place right in front of a DPP read:
         // one wait that depends on ALL of them (so every producer is ahead of it) covers the whole stage
-        if constexpr (OU == 2)
+        static_assert(OU == 1 || OU == 2 || OU == 4, "the wait below names every p[o][j]");
+        if constexpr (OU == 4)
+            asm volatile("s_nop 1" : "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[0][2]), "+v"(p[0][3]), "+v"(p[1][0]), "+v"(p[1][1]),
+                         "+v"(p[1][2]), "+v"(p[1][3]), "+v"(p[2][0]), "+v"(p[2][1]), "+v"(p[2][2]), "+v"(p[2][3]), "+v"(p[OU - 1][0]),
+                         "+v"(p[OU - 1][1]), "+v"(p[OU - 1][2]), "+v"(p[OU - 1][3]));
+        else if constexpr (OU == 2)
             asm volatile("s_nop 1" : "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[0][2]), "+v"(p[0][3]), "+v"(p[OU - 1][0]),
                          "+v"(p[OU - 1][1]), "+v"(p[OU - 1][2]), "+v"(p[OU - 1][3]));
         else
@@ -584,7 +594,7 @@ __device__ __forceinline__ void forward_group(const float* sX, float* sA, float*
 #pragma unroll
             for (int o = 0; o < OU; ++o)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sPart[(L.wave * GROUP + L.row(j)) * MAXOUT + o] = p[o][j];
+                for (int j = 0; j < 4; ++j) sPart[(L.wave * GROUP + L.row(j)) * out_stride<OU>() + o] = p[o][j];
         }
     }
     MPG_STAMP_AT(4);
@@ -625,7 +635,12 @@ __device__ __forceinline__ void forward_group2(const float* sXa, const float* sX
         _Pragma("unroll") for (int o = 0; o < OU; ++o)           \
         _Pragma("unroll") for (int j = 0; j < 4; ++j)            \
             asm volatile("v_add_f32_dpp %0, %1, %1 " MODS " row_mask:0xf bank_mask:0xf" : "=v"(p[o][j]) : "v"(p[o][j]));
-        if constexpr (OU == 2)
+        static_assert(OU == 1 || OU == 2 || OU == 4, "the wait below names every p[o][j]");
+        if constexpr (OU == 4)
+            asm volatile("s_nop 1" : "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[0][2]), "+v"(p[0][3]), "+v"(p[1][0]), "+v"(p[1][1]),
+                         "+v"(p[1][2]), "+v"(p[1][3]), "+v"(p[2][0]), "+v"(p[2][1]), "+v"(p[2][2]), "+v"(p[2][3]), "+v"(p[OU - 1][0]),
+                         "+v"(p[OU - 1][1]), "+v"(p[OU - 1][2]), "+v"(p[OU - 1][3]));
+        else if constexpr (OU == 2)
             asm volatile("s_nop 1" : "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[0][2]), "+v"(p[0][3]), "+v"(p[OU - 1][0]),
                          "+v"(p[OU - 1][1]), "+v"(p[OU - 1][2]), "+v"(p[OU - 1][3]));
         else
@@ -637,7 +652,7 @@ __device__ __forceinline__ void forward_group2(const float* sXa, const float* sX
 #pragma unroll
             for (int o = 0; o < OU; ++o)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sPart[(L.wave * GROUP + L.row(j)) * MAXOUT + o] = p[o][j];
+                for (int j = 0; j < 4; ++j) sPart[(L.wave * GROUP + L.row(j)) * out_stride<OU>() + o] = p[o][j];
         }
     };
     layer1(sXa, sAa, h1a);
@@ -654,11 +669,12 @@ __device__ __forceinline__ void forward_group2(const float* sXa, const float* sX
     lds_barrier();
 }
 
-// sum of the 8 per-wave partials + bias for (row, o)
+// sum of the 8 per-wave partials + bias for (row, o); OS: the block's stride (out_stride of the kernel's OU)
+template <int OS = MAXOUT>
 __device__ __forceinline__ float out_preact(const float* sPart, float bias, int row, int o) {
     float z = bias;
 #pragma unroll
-    for (int w = 0; w < NWAVE; ++w) z += sPart[(w * GROUP + row) * MAXOUT + o];
+    for (int w = 0; w < NWAVE; ++w) z += sPart[(w * GROUP + row) * OS + o];
     return z;
 }
 // same sum as a depth-3 tree (the rollout's serial chain: 3 dependent adds instead of 8)
@@ -669,7 +685,7 @@ __device__ __forceinline__ float out_preact_tree(const float* sPart, float bias,
     return (((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]))) + bias;
 }
 
-// sD3 [MAXOUT][16]: dL/dz3 of the used outputs, OUTPUT-major so that the four rows a lane needs (4 rg .. 4 rg + 3) are
+// sD3 [out_stride<OU>()][16]: dL/dz3 of the used outputs, OUTPUT-major so that the four rows a lane needs (4 rg .. 4 rg + 3) are
 // one aligned 16-byte read per output and pair up for packed fmas without register shuffles
 __device__ __forceinline__ int d3_index(int row, int o) { return o * GROUP + row; }
 
@@ -690,7 +706,7 @@ __device__ __forceinline__ void row_exponents(const float* sD3, const Lane& L, i
 }
 
 // ---- backward through the hidden layers for one row group ---------------------------------------------
-// sD3 [16][MAXOUT] holds dL/dz3 (pre-activation of the used outputs).  h1/h2: this lane's stashed activations.
+// sD3 [out_stride<OU>()][16] holds dL/dz3 (pre-activation of the used outputs).  h1/h2: this lane's stashed activations.
 // Produces dz2 and dz1 (C layout).  If WANT_DX, leaves per-wave partial sums of dz1*W1^T in sPartX
 // [NWAVE][16][XS] and ends on a barrier; the caller reduces them.
 // first half: dz2 = (dz3 W3^T) * ELU'(h2) into the LDS A image (ends on the barrier that publishes it)

@@ -26,8 +26,8 @@ struct FwdArgs {
 // pair rides in the first one's barrier waits and LDS round trips.  Same arithmetic per group (bit-identical results).
 template <int IN, int OU, bool PK, int G2>
 __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
-    constexpr int XSW = xs_of<IN>();
-    __shared__ __attribute__((aligned(16))) float smem[G2 * (A_IMG + GROUP * XSW + NWAVE * GROUP * MAXOUT)];
+    constexpr int XSW = xs_of<IN>(), OS = out_stride<OU>();
+    __shared__ __attribute__((aligned(16))) float smem[G2 * (A_IMG + GROUP * XSW + NWAVE * GROUP * OS)];
     float* sA = smem;
     float* sX = sA + G2 * A_IMG;
     float* sPart = sX + G2 * GROUP * XSW;
@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
         if (threadIdx.x < G2 * GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
         float h1[G2][2][4], h2[G2][2][4];
         if constexpr (G2 == 2)
-            forward_group2<IN, OU>(sX, sX + GROUP * XSW, sA, sA + A_IMG, sPart, sPart + NWAVE * GROUP * MAXOUT, L, w2, r, h1[0], h2[0], h1[1],
+            forward_group2<IN, OU>(sX, sX + GROUP * XSW, sA, sA + A_IMG, sPart, sPart + NWAVE * GROUP * OS, L, w2, r, h1[0], h2[0], h1[1],
                                    h2[1], &zmax);
         else
             forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1[0], h2[0], nullptr, 0, nullptr, &zmax);
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
             const int g2 = tid / (GROUP * OU), row = (tid / OU) % GROUP, o = tid % OU;
             const long gr = (u * G2 + g2) * GROUP + row;
             if (gr < a.rows) {
-                float z = out_preact(sPart + g2 * NWAVE * GROUP * MAXOUT, b3v, row, o);
+                float z = out_preact<OS>(sPart + g2 * NWAVE * GROUP * OS, b3v, row, o);
                 float y = a.out_tanh ? a.out_scale * tanhf(z) : z;
                 y += pz;
                 if (a.sigma > 0.f) {   // OffPolicyWorker.sample: action += N(0, sigma), worker.py:97-98
@@ -127,7 +127,8 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
 
-#define MPG_DISPATCH_NET(in_dim, ou, CALL)                                    \
+// the shapes built for at most two used outputs (every pass), ...
+#define MPG_DISPATCH_NET2_(in_dim, ou, CALL)                                  \
     if ((in_dim) == 6 && (ou) == 2) { CALL(6, 2); }                           \
     else if ((in_dim) == 8 && (ou) == 1) { CALL(8, 1); }                      \
     else if ((in_dim) == 4 && (ou) == 1) { CALL(4, 1); }                      \
@@ -137,11 +138,22 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
     else if ((in_dim) > 8 && (in_dim) <= 16 && (ou) == 1) { CALL(16, 1); }    \
     else if ((in_dim) == 7 && (ou) == 2) { CALL(16, 2); }                     \
     else if ((in_dim) == 8 && (ou) == 2) { CALL(16, 2); }                     \
-    else if ((in_dim) > 16 && (in_dim) <= 24 && (ou) == 1) { CALL(24, 1); }   \
+    else if ((in_dim) > 16 && (in_dim) <= 24 && (ou) == 1) { CALL(24, 1); }
+#define MPG_DISPATCH_REFUSE_(in_dim, ou)                                      \
     else {                                                                    \
         mpg_set_error("unsupported network shape in=%d used-out=%d", (in_dim), (ou)); \
         return MPG_EINVAL;                                                    \
     }
+// ... and the four-logit policy head (mean | log-std of the PathTracking policy, obs_dim 6 .. 16) for the passes that have a
+// four-output form: forward, backward without dx and without THIN, the full weight gradient
+#define MPG_DISPATCH_NET(in_dim, ou, CALL)                                    \
+    MPG_DISPATCH_NET2_(in_dim, ou, CALL)                                      \
+    else if ((in_dim) == 6 && (ou) == 4) { CALL(6, 4); }                      \
+    else if ((in_dim) > 6 && (in_dim) <= 16 && (ou) == 4) { CALL(16, 4); }    \
+    MPG_DISPATCH_REFUSE_(in_dim, ou)
+#define MPG_DISPATCH_NET2(in_dim, ou, CALL)                                   \
+    MPG_DISPATCH_NET2_(in_dim, ou, CALL)                                      \
+    MPG_DISPATCH_REFUSE_(in_dim, ou)
 
 static int grid_for(long ngroups) { return (int)(ngroups < 256 ? ngroups : 256); }
 
@@ -202,13 +214,13 @@ struct BwdArgs {
 template <int IN, int OU, bool WANT_DX, bool PK, bool THIN = false>
 __global__ void __launch_bounds__(NTHREAD, 2) k_backward(const BwdArgs a) {
     static_assert(!THIN || (!WANT_DX && IN <= 8), "THIN is built for the base input widths, without dx");
-    constexpr int XSW = xs_of<IN>();
-    __shared__ __attribute__((aligned(16))) float smem[2 * A_IMG + GROUP * MAXOUT + NWAVE * GROUP * XSW];
+    constexpr int XSW = xs_of<IN>(), OS = out_stride<OU>();
+    __shared__ __attribute__((aligned(16))) float smem[2 * A_IMG + GROUP * OS + NWAVE * GROUP * XSW];
     __shared__ __attribute__((aligned(16))) float sXt[THIN ? 2 * GROUP * XSW : 4];      // network input of the group, two parities
     float* sA = smem;
     float* sA1 = sA + A_IMG;
     float* sD3 = sA1 + A_IMG;
-    float* sPartX = sD3 + GROUP * MAXOUT;
+    float* sPartX = sD3 + GROUP * OS;
     const Lane L;
     const Net net = make_net(a.params, a.in_dim, a.out_dim);
     float w2t[128];
@@ -490,7 +502,8 @@ static void launch_backward_thin(const BwdArgs& a, int grid, hipStream_t s) {
 }
 
 bool backward_takes_thin(int in_dim, int ou) {
-    return in_dim <= 8 && !(in_dim == 7 && ou == 2) && !(in_dim == 8 && ou == 2);
+    // (four used outputs: no THIN form is built - the head's gradient goes through the plain backward and the full k_wgrad)
+    return in_dim <= 8 && ou <= 2 && !(in_dim == 7 && ou == 2) && !(in_dim == 8 && ou == 2);
 }
 int backward_thin_parts(int rows) { return grid_for((rows + GROUP - 1) / GROUP); }
 
@@ -513,11 +526,11 @@ int launch_backward(const mpg_cfg_t* cfg, const float* params, int in_dim, int o
 #define CALL(I, O)                                                                                                \
     if (a.pack) hipLaunchKernelGGL((k_backward<I, O, true, true>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, a); \
     else hipLaunchKernelGGL((k_backward<I, O, true, false>), dim3(grid_for(ngroups)), dim3(NTHREAD), 0, s, a)
-        MPG_DISPATCH_NET(in_dim, ou, CALL)
+        MPG_DISPATCH_NET2(in_dim, ou, CALL)
 #undef CALL
     } else if (thin_part) {
 #define CALL(I, O) launch_backward_thin<I, O>(a, grid_for(ngroups), s)
-        MPG_DISPATCH_NET(in_dim, ou, CALL)
+        MPG_DISPATCH_NET2(in_dim, ou, CALL)
 #undef CALL
     } else {
 #define CALL(I, O)                                                                                                 \
@@ -538,7 +551,8 @@ int launch_backward(const mpg_cfg_t* cfg, const float* params, int in_dim, int o
 // by 8 workgroups; k_sum_parts sums the chunk slabs in a fixed order (deterministic, no float atomics).
 // -------------------------------------------------------------------------------------------------------
 template <int IN, int OU>
-__global__ void __launch_bounds__(NTHREAD, IN <= 8 ? 4 : 2) k_wgrad(const WgradArgs a) {      // (16-wide: 80 KB of LDS, one workgroup per CU anyway)
+// (four outputs: 56 KB of LDS, two workgroups per CU at the most - at the four-workgroup register cap the 8-input form spills)
+__global__ void __launch_bounds__(NTHREAD, IN <= 8 && OU <= 2 ? 4 : 2) k_wgrad(const WgradArgs a) {      // (16-wide: 80 KB of LDS, one workgroup per CU anyway)
     __shared__ __attribute__((aligned(16))) float sRed[NWAVE * wgrad_nq<IN, OU>() * 64];
     int chunk, sl;
     wgrad_map(blockIdx.x, gridDim.x >> 3, chunk, sl);
@@ -593,7 +607,7 @@ int launch_wgrad(const mpg_cfg_t* cfg, int in_dim, int out_dim, int ou, int rows
     if (w2_only) {
 #ifdef MPG_SPLIT
 #define CALL(I, O) launch_wgrad_w2<I, O>(a, nch, s)
-        MPG_DISPATCH_NET(in_dim, ou, CALL)
+        MPG_DISPATCH_NET2(in_dim, ou, CALL)
 #undef CALL
 #endif
     } else {

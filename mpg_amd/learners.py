@@ -1,5 +1,5 @@
 """Learners - device mirrors of learners/mpg_learner.py (MPGLearner), learners/nadp.py (NADPLearner),
-learners/td3.py (TD3Learner) and learners/ndpg.py (NDPGLearner): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
+learners/td3.py (TD3Learner), learners/ndpg.py (NDPGLearner) and learners/sac.py (SACLearner, fixed temperature): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
 (`set_weights`, `compute_gradient(batch5, rb, indexes, iteration)`, `get_stats`, `get_info_for_buffer`), same
 output order `q1 (+q2) + policy`.
 
@@ -449,4 +449,90 @@ class NDPGLearner(_LearnerBase):
             return dict(q_loss=stats[0], policy_loss=-mean, value_mean=mean, value_var=stats[3] / B - mean * mean,
                         mb_targets_mean=self.batch_data['batch_targets'].mean(), q_gradient_norm=self.norms[0],
                         policy_gradient_norm=self.norms[1])
+        return lazy
+
+
+class SACLearner(_LearnerBase):
+    """Soft actor-critic with a fixed temperature (learners/sac.py:21-219): networks [Q1 | Q2 | policy], the policy a diagonal
+    Gaussian over its four logits (policy.py:179-204, no action range).  PathTracking-v0 only; alpha = 'auto' is not built.
+    Every draw is the library's Philox stream keyed by (learner seed, call counter): two per gradient call - the action at s' for the
+    target (from the ONLINE policy, sac.py:71) and the action of the policy loss (:123) - and one more, from the TARGET policy, for a
+    prioritized buffer's td error (:88)."""
+
+    def __init__(self, policy_cls, args, device='cuda'):
+        if getattr(args, 'alpha', None) == 'auto':
+            raise ValueError("SACLearner: alpha = 'auto' (AlphaModel, its Adam, target_entropy) is not built; pass a fixed alpha such as "
+                             "the reference's default 0.03")
+        if getattr(args, 'deterministic_policy', True):
+            raise ValueError('SACLearner needs deterministic_policy=False (built_SAC_parser, train_script.py:672-792)')
+        if args.env_id != 'PathTracking-v0':
+            raise ValueError('SACLearner serves PathTracking-v0 only (got env_id %r): the pendulum\'s action_range is a tanh-affine '
+                             'bijector whose log-density correction is not built' % (args.env_id,))
+        super().__init__(policy_cls, args, device)
+        assert self.policy_with_value.names == ['Q1', 'Q2', 'policy'], 'SAC trains [Q1 | Q2 | policy]: double_Q=True, target=True'
+
+    @property
+    def alpha(self):
+        return self.policy_with_value.alpha
+
+    def _draw(self, rows, ctr, stream=0):
+        ad = self.cfg.act_dim
+        return ops.normal_fill(rows * ad, self.seed + stream, ctr, self.device).view(rows, ad)
+
+    def compute_clipped_double_q_target(self, eps_target=None):
+        """sac.py:67-80"""
+        pw, b = self.policy_with_value, self.batch_data
+        if eps_target is None:
+            eps_target = self._draw(b['batch_obs'].shape[0], 2 * (self.counter + 1))
+        return ops.sac_targets(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'], b['batch_obs_tp1'],
+                               eps_target, self.alpha)
+
+    def compute_td_error(self, eps=None, ctr=None):
+        """sac.py:82-91 (signed): r~ + gamma Q1_target(s', a') - Q1(s, a), a' its own draw from the TARGET policy - the soft target's
+        launch sequence with the target policy, one critic in both places and alpha 0 (0 * logp is an exact zero).
+        ctr: the draw's counter in the learner's second stream (default 2 * counter: the call from get_batch_data)"""
+        pw, b = self.policy_with_value, self.batch_data
+        if eps is None:
+            eps = self._draw(b['batch_obs'].shape[0], 2 * self.counter if ctr is None else ctr, stream=1)
+        y1 = ops.sac_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), pw.net('Q1', True), b['batch_rewards'],
+                             b['batch_obs_tp1'], eps, 0.0)
+        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
+
+    def get_batch_data(self, batch_data, rb, indexes, eps_target=None):
+        self._get_batch(batch_data)
+        self.batch_data['batch_targets'] = self.compute_clipped_double_q_target(eps_target)
+        if self.args.buffer_type != 'normal':
+            self.info_for_buffer.update(dict(td_error=self.compute_td_error(), rb=rb, indexes=indexes))
+
+    def compute_gradient(self, batch_data, rb, indexes, iteration, eps_target=None, eps_policy=None):
+        """sac.py:169-219; output order q1 + q2 + policy"""
+        if self.counter % self.num_batch_reuse == 0:
+            self.get_batch_data(batch_data, rb, indexes, eps_target)
+        self.counter += 1
+        if self.args.buffer_type != 'normal':                  # :173-174: the priorities follow the critic within a reused batch
+            self.info_for_buffer.update(dict(td_error=self.compute_td_error(ctr=2 * self.counter - 1)))
+        pw, b = self.policy_with_value, self.batch_data
+        rows = b['batch_obs'].shape[0]
+        inv_b = 1.0 / (rows * D.world_size())
+        stats = self.flat[self.n_grad:]
+        for i, nm in enumerate(('Q1', 'Q2')):                                                          # :102-117
+            ops.q_loss_grad(self.cfg, pw.net(nm), b['batch_obs'], b['batch_actions'], b['batch_targets'], inv_b_global=inv_b,
+                            grad_out=self.grad(nm), loss_out=stats[i:i + 1])
+        if eps_policy is None:
+            eps_policy = self._draw(rows, 2 * self.counter + 1)
+        ops.sac_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha,
+                            inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5])    # :119-136
+        out = self._finish(iteration, float(self.args.gradient_clip_norm))
+        self._lazy_stats = self._native_lazy_stats(iteration)
+        return out
+
+    def _native_lazy_stats(self, iteration):
+        stats, B, alpha = self.flat[self.n_grad:], self.batch_size * D.world_size(), self.alpha
+
+        def lazy():        # evaluated only when get_stats() is called: no elementwise launches in the training loop
+            mean, logp = stats[2] / B, stats[4] / B
+            # (mb_targets_mean: this process's batch, like the reference's np.mean(mb_targets))
+            return dict(q_loss1=stats[0], q_loss2=stats[1], policy_loss=alpha * logp - mean, policy_entropy=-logp,
+                        mb_targets_mean=self.batch_data['batch_targets'].mean(), value_mean=mean, value_var=stats[3] / B - mean * mean,
+                        q_gradient_norm1=self.norms[0], q_gradient_norm2=self.norms[1], policy_gradient_norm=self.norms[2])
         return lazy

@@ -415,6 +415,43 @@ def dpg_policy_grad(cfg, policy_params, q1, obs, inv_b_global=None, grad_out=Non
     return stats, grad
 
 
+def policy_sample(cfg, policy_params, obs, eps, want_logits=False):
+    """mpg_policy_sample: (act, logp[, logits]) of the Gaussian policy on the caller's standard-normal draws eps [rows, act_dim]
+    (PolicyWithQs.compute_action, stochastic branch, policy.py:200-204)"""
+    rows, dev = obs.shape[0], obs.device
+    act = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
+    logp = torch.empty(rows, dtype=torch.float32, device=dev)
+    logits = torch.empty(rows, 2 * cfg.act_dim, dtype=torch.float32, device=dev) if want_logits else None
+    ws = _ws(dev, 0, 'mpg_policy_sample_workspace_bytes', cfg, rows)
+    L.call('mpg_policy_sample', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.ptr(_f32(obs)), L.ptr(_f32(eps)),
+           L.ptr(act), L.ptr(logp), L.ptr(logits), *ws, L.stream())
+    return (act, logp, logits) if want_logits else (act, logp)
+
+
+def sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
+    """mpg_sac_targets: y = (rew + shift) * scale + gamma * (min(Q1t, Q2t)(s', a') - alpha * logp'), (a', logp') sampled from
+    `policy` - the ONLINE one in the reference, sac.py:71 - with eps"""
+    rows = obs_tp1.shape[0]
+    y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
+    ws = _ws(obs_tp1.device, 0, 'mpg_sac_targets_workspace_bytes', cfg, rows)
+    L.call('mpg_sac_targets', ctypes.byref(cfg), L.ptr(_f32(policy)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows), L.ptr(_f32(rew)),
+           L.ptr(_f32(obs_tp1)), L.ptr(_f32(eps)), L.c_float(alpha), L.ptr(y), *ws, L.stream())
+    return y
+
+
+def sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None):
+    """mpg_sac_policy_grad: mean(alpha * logp - min Q) and its policy gradient over all four output columns.
+    Returns (stats = [qmin_sum, qmin_sqsum, logp_sum], grad)."""
+    rows, dev = obs.shape[0], obs.device
+    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
+    stats = stats_out if stats_out is not None else torch.empty(3, dtype=torch.float32, device=dev)
+    ws = _ws(dev, 1, 'mpg_sac_policy_grad_workspace_bytes', cfg, rows)
+    L.call('mpg_sac_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)), L.c_int(rows),
+           L.ptr(_f32(obs)), L.ptr(_f32(eps)), L.c_float(alpha), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
+           L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(stats[2:3]), L.ptr(grad), *ws, L.stream())
+    return stats, grad
+
+
 def mpg_gradients_supported(cfg, rows, M, n, n_select, n_q):
     """whether mpg_mpg_gradients serves these sizes: its workspace query answers 0 for what the entry point refuses"""
     return L.lib().mpg_mpg_gradients_workspace_bytes(ctypes.byref(cfg), *[L.c_int(int(v)) for v in (rows, M, n, n_select, n_q)]) != 0

@@ -1,4 +1,5 @@
-"""PolicyWithQs - device-resident mirror of policy.py:19-245 (deterministic policy branch).
+"""PolicyWithQs - device-resident mirror of policy.py:19-245: the deterministic policy branch, and the stochastic one (a diagonal
+Gaussian over the four logits, policy.py:179-204) with a fixed temperature `alpha` and no action range.
 
 All networks live in ONE flat float32 tensor in the order of the reference's `self.models`
 (policy.py:72-86): Q1, (Q2,) policy; the target nets in a second flat tensor in the same order; Adam moments
@@ -61,9 +62,26 @@ class PolicyWithQs(object):
                  double_Q=True, target=True, tau=0.005, delay_update=2, deterministic_policy=True, action_range=None,
                  policy_out_activation='tanh', env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift=0.,
                  gamma=0.98, value_num_hidden_units=256, policy_num_hidden_units=256, policy_only=False,
-                 device='cuda', seed=0, init_seed=0, **kwargs):
+                 device='cuda', seed=0, init_seed=0, alpha=None, **kwargs):
         assert value_num_hidden_units == 256 and policy_num_hidden_units == 256, 'kernels are built for 2x256 nets'
-        assert deterministic_policy and not policy_only and target, 'hot-path scope: deterministic actor-critic with targets'
+        assert not policy_only and target, 'hot-path scope: actor-critic with targets'
+        self.deterministic_policy = bool(deterministic_policy)
+        self.alpha = None
+        if not self.deterministic_policy:
+            # the stochastic branch (SAC): a float temperature, the Gaussian head without a bijector (include/mpg_hip.h)
+            if isinstance(alpha, str):
+                raise ValueError("alpha = %r: the learned temperature (AlphaModel, target_entropy) is not built; pass a fixed alpha such "
+                                 "as the reference's default 0.03" % (alpha,))
+            if alpha is None or not (math.isfinite(float(alpha)) and float(alpha) >= 0.):
+                raise ValueError('a stochastic policy needs a finite alpha >= 0 (got %r)' % (alpha,))
+            if action_range is not None:
+                raise ValueError('a stochastic policy with an action_range (%r) is not built: its tanh-affine bijector changes the '
+                                 'log-density (policy.py:183-190)' % (action_range,))
+            if act_dim != 2 or env_id != 'PathTracking-v0':
+                raise ValueError('the stochastic policy is built for PathTracking-v0 with act_dim 2 (got env_id %r, act_dim %r)'
+                                 % (env_id, act_dim))
+            self.alpha = float(alpha)
+            self.sample_seed, self._sample_ctr = int(seed) * 7919 + 104729, 0      # the policy's own stream of draws (compute_action without eps)
         self.device = torch.device(device)
         self.double_Q, self.tau, self.delay_update = bool(double_Q), float(tau), int(delay_update)
         self.cfg = ops.make_cfg(env_id, obs_scale=obs_scale, rew_scale=rew_scale, rew_shift=rew_shift, gamma=gamma,
@@ -170,13 +188,30 @@ class PolicyWithQs(object):
         self.refresh_weight_cache()
 
     # ---- forward helpers ----
-    def compute_action(self, obs):
-        """policy.py:193-204: returns (action, logp=0.).  obs is the PROCESSED obs in the reference; here the 'scale'
-        preprocessing is fused into the kernel, so pass RAW obs."""
-        return ops.policy_action(self.cfg, self.net('policy'), obs), 0.
+    def compute_action(self, obs, eps=None):
+        """policy.py:193-204: returns (action, logp=0.), or (sampled actions, logps) with a stochastic policy - on the standard-normal
+        draws `eps` [rows, act_dim], or on the policy's own (seed, counter) stream.  obs is the PROCESSED obs in the reference; here
+        the 'scale' preprocessing is fused into the kernel, so pass RAW obs."""
+        return self._act(False, obs, eps)
 
-    def compute_target_action(self, obs):
-        return ops.policy_action(self.cfg, self.net('policy', True), obs), 0.
+    def compute_target_action(self, obs, eps=None):
+        return self._act(True, obs, eps)
+
+    def _act(self, target, obs, eps):
+        if self.deterministic_policy:
+            return ops.policy_action(self.cfg, self.net('policy', target), obs), 0.
+        if eps is None:
+            eps = self.draw(obs.shape[0])
+        return ops.policy_sample(self.cfg, self.net('policy', target), obs, eps)
+
+    def draw(self, rows):
+        """the next [rows, act_dim] standard normals of the policy's own stream (mpg_normal_fill keyed by (sample_seed, counter))"""
+        self._sample_ctr += 1
+        return ops.normal_fill(rows * self.act_dim, self.sample_seed, self._sample_ctr, self.device).view(rows, self.act_dim)
+
+    def compute_mode(self, obs):
+        """policy.py:173-177: the mean (what the evaluator acts with)"""
+        return ops.policy_action(self.cfg, self.net('policy'), obs)
 
     def _q(self, name, target, obs, act):
         x = torch.cat([obs, act], 1).contiguous()

@@ -62,8 +62,15 @@ class OffPolicyWorker(object):
         iters = max(1, self.batch_size // self.num_agent)
         for _ in range(iters):
             obs = self.obs
-            action = ops.policy_action(pw.cfg, pw.net('policy'), obs, explore_sigma=float(self.explore_sigma or 0.),
-                                       seed=self.seed, ctr=self._noise_ctr)
+            if getattr(pw, 'deterministic_policy', True):
+                action = ops.policy_action(pw.cfg, pw.net('policy'), obs, explore_sigma=float(self.explore_sigma or 0.),
+                                           seed=self.seed, ctr=self._noise_ctr)
+            else:
+                # stochastic policy: the action IS the sample (worker.py:96), un-clipped; explore_sigma noise only if it is set (:97-98)
+                n = obs.shape[0] * pw.act_dim
+                action, _ = pw.compute_action(obs, ops.normal_fill(n, self.seed, self._noise_ctr, self.device).view(obs.shape[0], pw.act_dim))
+                if self.explore_sigma is not None:
+                    action.add_(ops.normal_fill(n, self.seed + 1, self._noise_ctr, self.device).view_as(action), alpha=float(self.explore_sigma))
             self._noise_ctr += 1
             obs_tp1, reward, done, _ = self.env.step(action)          # fresh tensors every call (never aliased later)
             for lst, x in zip(out, (obs, action, reward, obs_tp1, done)):
