@@ -43,155 +43,100 @@ __global__ void k_nstep(int rows, int n, const float* __restrict__ rewards, cons
     y[i] = acc + powf(gamma, (float)n) * q[i];
 }
 
-// err = q - y; dz3 = err * inv_b; td (nullable) = err; loss_sum += 0.5 * inv_b * sum err^2 (one block, fixed order)
-__global__ void __launch_bounds__(1024) k_q_err(int rows, const float* __restrict__ q, const float* __restrict__ y,
-                                                float inv_b, float* __restrict__ dz3, float* __restrict__ td,
-                                                float* __restrict__ loss_sum) {
-    __shared__ float red[1024];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < rows; i += 1024) {
-        const float e = q[i] - y[i];
-        dz3[i] = e * inv_b;
-        if (td) td[i] = e;
-        s += e * e;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_sum[0] = 0.5f * inv_b * red[0];
-}
-
-// TD3 policy loss pieces (td3.py:120-134): qmin = min(q1, q2); dL/dq_i = -inv_b where q_i is the smaller one
-// (tf.reduce_min routes the gradient to the minimum; exact ties go to Q1).  One block, fixed-order sums.
-__global__ void __launch_bounds__(1024) k_td3_dy(int rows, const float* __restrict__ q1, const float* __restrict__ q2,
-                                                 float inv_b, float* __restrict__ dy1, float* __restrict__ dy2,
-                                                 float* __restrict__ qmin_sum, float* __restrict__ qmin_sqsum) {
-    __shared__ float red[2][1024];
-    float s = 0.f, s2 = 0.f;
-    for (int i = threadIdx.x; i < rows; i += 1024) {
-        const bool first = q1[i] <= q2[i];
-        const float m = first ? q1[i] : q2[i];
-        dy1[i] = first ? -inv_b : 0.f;
-        dy2[i] = first ? 0.f : -inv_b;
-        s += m;
-        s2 += m * m;
-    }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = s2;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        qmin_sum[0] = red[0][0];
-        qmin_sqsum[0] = red[1][0];
-    }
-}
-
-// Large batches (TD3 at B = 65 536: the one-block forms above walk 64 rows per thread, 18 - 34 us each): the same element-wise
-// work over a grid, block b leaving the sums of its contiguous run of rows in part[b] (+ part[PARTS + b]); k_finish_parts adds the
-// partials in block order.  Fixed order at both levels: deterministic.
+// ---- row sums: the element-wise pass of a loss over the rows of a batch together with the one or two sums it reports ----------------
+// A row body carries its pointers and scalars, NS (the number of sums), SUM_OPTIONAL (whether a null destination means "no sum
+// wanted"), scale0() (what the finished first sum is multiplied by; the second is reported as it is) and operator()(i, s): the stores
+// of row i and its terms added into s[NS].
 constexpr int ERR_PARTS = 64;
-__global__ void __launch_bounds__(1024) k_q_err_mb(int rows, const float* __restrict__ q, const float* __restrict__ y, float inv_b,
-                                                   float* __restrict__ dz3, float* __restrict__ td, float* __restrict__ part) {
-    __shared__ float red[1024];
-    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
-    float s = 0.f;
-    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
+constexpr int ERR_MB_MIN_ROWS = 8192;          // below: the one-block form (one launch instead of two)
+
+// critic loss: err = q - y; dz3 = err * inv_b; td (nullable) = err; the sum of err^2, finished as the loss 0.5 * inv_b * sum
+struct QErrRow {
+    const float *__restrict__ q, *__restrict__ y;
+    float inv_b;
+    float *__restrict__ dz3, *__restrict__ td;
+    static constexpr int NS = 1;
+    static constexpr bool SUM_OPTIONAL = false;
+    __host__ __device__ float scale0() const { return 0.5f * inv_b; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
         const float e = q[i] - y[i];
         dz3[i] = e * inv_b;
         if (td) td[i] = e;
-        s += e * e;
+        s[0] += e * e;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-__global__ void __launch_bounds__(1024) k_td3_dy_mb(int rows, const float* __restrict__ q1, const float* __restrict__ q2, float inv_b,
-                                                    float* __restrict__ dy1, float* __restrict__ dy2, float* __restrict__ part) {
-    __shared__ float red[2][1024];
-    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
-    float s = 0.f, s2 = 0.f;
-    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
+};
+// TD3 policy loss pieces (td3.py:120-134): qmin = min(q1, q2); dL/dq_i = -inv_b where q_i is the smaller one (tf.reduce_min routes
+// the gradient to the minimum; exact ties go to Q1); the sums of qmin and qmin^2 (value_mean / value_var)
+struct Td3DyRow {
+    const float *__restrict__ q1, *__restrict__ q2;
+    float inv_b;
+    float *__restrict__ dy1, *__restrict__ dy2;
+    static constexpr int NS = 2;
+    static constexpr bool SUM_OPTIONAL = false;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
         const bool first = q1[i] <= q2[i];
         const float m = first ? q1[i] : q2[i];
         dy1[i] = first ? -inv_b : 0.f;
         dy2[i] = first ? 0.f : -inv_b;
-        s += m;
-        s2 += m * m;
+        s[0] += m;
+        s[1] += m * m;
     }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = s2;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[blockIdx.x] = red[0][0]; part[ERR_PARTS + blockIdx.x] = red[1][0]; }
-}
-// n-step DPG policy loss pieces (ndpg.py:174-186): one critic, so dL/dq = -inv_b for every row; the sums of q and q^2 over the rows
-// (value_mean / value_var).  The one-block and the many-block form, like k_td3_dy / k_td3_dy_mb.
-__global__ void __launch_bounds__(1024) k_dpg_dy(int rows, const float* __restrict__ q, float inv_b, float* __restrict__ dy,
-                                                 float* __restrict__ q_sum, float* __restrict__ q_sqsum) {
-    __shared__ float red[2][1024];
-    float s = 0.f, s2 = 0.f;
-    for (int i = threadIdx.x; i < rows; i += 1024) {
+};
+// n-step DPG policy loss pieces (ndpg.py:174-186): one critic, so dL/dq = -inv_b for every row; the sums of q and q^2
+struct DpgDyRow {
+    const float* __restrict__ q;
+    float inv_b;
+    float* __restrict__ dy;
+    static constexpr int NS = 2;
+    static constexpr bool SUM_OPTIONAL = false;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
         const float m = q[i];
         dy[i] = -inv_b;
-        s += m;
-        s2 += m * m;
+        s[0] += m;
+        s[1] += m * m;
     }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = s2;
+};
+
+// Thread t of a block walks the rows t, t + 1024, ... of the block's run; a 1024-wide tree (512 -> 1) adds the threads' sums.  Fixed
+// order at every level: deterministic.
+// One block (MB false): the run is all rows, and the finished sums go to out0[0] (and out1[0]).
+// Many blocks (MB true; TD3 at B = 65 536: the one-block form walks 64 rows per thread, 18 - 34 us): block b takes a contiguous run of
+// rows and leaves its sums in out0[b] (and out0[ERR_PARTS + b]), out0 being the partials buffer that k_finish_parts, or the FinishJob
+// block of the weight-gradient summation launch (mlp_kernels.hip), adds up in block order.
+template <class Row, bool MB>
+__global__ void __launch_bounds__(1024) k_row_sums(int rows, const Row row, float* __restrict__ out0, float* __restrict__ out1) {
+    constexpr int NS = Row::NS;
+    __shared__ float red[NS][1024];
+    int r0 = 0, r1 = rows;
+    if constexpr (MB) {
+        const int per = (rows + gridDim.x - 1) / gridDim.x;
+        r0 = blockIdx.x * per;
+        r1 = min(rows, r0 + per);
+    }
+    float s[NS] = {};
+    for (int i = r0 + threadIdx.x; i < r1; i += 1024) row(i, s);
+    if (Row::SUM_OPTIONAL && !out0) return;          // (uniform)
+#pragma unroll
+    for (int k = 0; k < NS; ++k) red[k][threadIdx.x] = s[k];
     __syncthreads();
     for (int w = 512; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        q_sum[0] = red[0][0];
-        q_sqsum[0] = red[1][0];
-    }
-}
-__global__ void __launch_bounds__(1024) k_dpg_dy_mb(int rows, const float* __restrict__ q, float inv_b, float* __restrict__ dy,
-                                                    float* __restrict__ part) {
-    __shared__ float red[2][1024];
-    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
-    float s = 0.f, s2 = 0.f;
-    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
-        const float m = q[i];
-        dy[i] = -inv_b;
-        s += m;
-        s2 += m * m;
-    }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = s2;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        if constexpr (MB) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) out0[k * ERR_PARTS + blockIdx.x] = red[k][0];
+        } else {
+            out0[0] = row.scale0() * red[0][0];
+            if (NS > 1) out1[0] = red[1][0];
         }
-        __syncthreads();
     }
-    if (threadIdx.x == 0) { part[blockIdx.x] = red[0][0]; part[ERR_PARTS + blockIdx.x] = red[1][0]; }
 }
 // out0 = scale0 * sum_b part[b]; out1 (nullable) = scale1 * sum_b part[PARTS + b]
 __global__ void k_finish_parts(int n_part, const float* __restrict__ part, float scale0, float scale1, float* __restrict__ out0,
@@ -206,7 +151,24 @@ __global__ void k_finish_parts(int n_part, const float* __restrict__ part, float
         out1[0] = scale1 * s;
     }
 }
-constexpr int ERR_MB_MIN_ROWS = 8192;          // below: the one-block forms (one launch instead of two)
+// The row sums of `row` over `rows` rows into out0 (and out1): one block below ERR_MB_MIN_ROWS; from there on ERR_PARTS blocks leave
+// their partials in `parts` and the finish follows - as k_finish_parts, or, where the caller has a launch_wgrad coming that can carry
+// it, as the FinishJob written to *carried (left as it is otherwise: start it zeroed and pass it on if its `part` is set).
+template <class Row>
+int launch_row_sums(const char* name, const Row& row, int rows, float* parts, float* out0, float* out1, FinishJob* carried, hipStream_t s) {
+    if (rows >= ERR_MB_MIN_ROWS) {
+        const FinishJob fin{parts, ERR_PARTS, ERR_PARTS, row.scale0(), Row::NS > 1 ? 1.f : 0.f, out0, out1};
+        hipLaunchKernelGGL((k_row_sums<Row, true>), dim3(ERR_PARTS), dim3(1024), 0, s, rows, row, out0 ? parts : nullptr, (float*)nullptr);
+        if (carried)
+            *carried = fin;
+        else if (out0)
+            hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, fin.n_part, fin.part, fin.scale0, fin.scale1, fin.out0, fin.out1);
+    } else {
+        hipLaunchKernelGGL((k_row_sums<Row, false>), dim3(1), dim3(1024), 0, s, rows, row, out0, out1);
+    }
+    MPG_CHECK_LAUNCH(name);
+    return MPG_OK;
+}
 
 // out[i] ~ N(0, 1): Philox4x32-10(key = seed, counter = (i / 4, ctr)), Box-Muller on two of the four words per pair of outputs
 __global__ void k_normal_fill(int n, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, float* __restrict__ out) {
@@ -267,45 +229,20 @@ __device__ __forceinline__ float gauss_row(int ad, const float* __restrict__ l, 
     }
     return lp;
 }
-// logits [rows][2 ad], eps [rows][ad] -> act [rows][ad], logp [rows]; logp_sum (nullable): sum of logp over the rows (one block, fixed order)
-__global__ void __launch_bounds__(1024) k_gauss_head(int rows, int ad, const float* __restrict__ logits, const float* __restrict__ eps,
-                                                     float* __restrict__ act, float* __restrict__ logp, float* __restrict__ logp_sum) {
-    __shared__ float red[1024];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < rows; i += 1024) {
+// logits [rows][2 ad], eps [rows][ad] -> act [rows][ad], logp [rows]; the sum of logp over the rows, where one is wanted
+struct GaussRow {
+    int ad;
+    const float *__restrict__ logits, *__restrict__ eps;
+    float *__restrict__ act, *__restrict__ logp;
+    static constexpr int NS = 1;
+    static constexpr bool SUM_OPTIONAL = true;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
         const float lp = gauss_row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
         logp[i] = lp;
-        s += lp;
+        s[0] += lp;
     }
-    if (!logp_sum) return;                      // (uniform)
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) logp_sum[0] = red[0];
-}
-// the many-block form (k_td3_dy_mb): block b leaves the sum of its run of rows in part[b] (part nullable: no sum wanted)
-__global__ void __launch_bounds__(1024) k_gauss_head_mb(int rows, int ad, const float* __restrict__ logits, const float* __restrict__ eps,
-                                                        float* __restrict__ act, float* __restrict__ logp, float* __restrict__ part) {
-    __shared__ float red[1024];
-    const int per = (rows + gridDim.x - 1) / gridDim.x, r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
-    float s = 0.f;
-    for (int i = r0 + threadIdx.x; i < r1; i += 1024) {
-        const float lp = gauss_row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
-        logp[i] = lp;
-        s += lp;
-    }
-    if (!part) return;
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
+};
 
 // soft target (sac.py:78-79): y = (rew + shift) * scale + gamma * (min(q1, q2) - alpha * logp)
 __global__ void k_sac_combine(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
@@ -316,7 +253,7 @@ __global__ void k_sac_combine(int n, const float* __restrict__ rew, const float*
 }
 
 // dL/dlogits [rows][2 ad] of loss = mean(alpha * logp - qmin) (sac.py:128) with a = mean + sigma * eps, logp = sum(-0.5 eps^2 - log_std - c):
-// ga_k = dx1[row][od + k] + dx2[row][od + k] is d(-inv_b qmin)/da_k (the critics' input gradients under k_td3_dy's dy);
+// ga_k = dx1[row][od + k] + dx2[row][od + k] is d(-inv_b qmin)/da_k (the critics' input gradients under Td3DyRow's dy);
 // mean column k: ga_k; log-std column k: ga_k sigma_k eps_k - alpha inv_b, and ZERO where the clip is active - strictly outside
 // [-5, 1]: clip_by_value passes the gradient at the bounds themselves (the stand-in's clamp, and TF's own rule)
 __global__ void k_sac_dlogits(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
@@ -358,37 +295,24 @@ QLossWs q_loss_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     return w;
 }
 
-struct Td3PolicyWs {
-    float *hp1, *hp2, *h11, *h12, *h21, *h22, *dz1, *dz2, *a, *dz3, *qv1, *qv2, *dy1, *dy2, *dx1, *dx2, *ga, *slabs, *parts;
+// mpg_td3_policy_grad (two critics), mpg_dpg_policy_grad (one) and mpg_sac_policy_grad (two, with the Gaussian head): each takes only
+// what it uses.  g is the policy's output gradient where a kernel forms it - the two critics' summed action gradients, or the head's
+// four columns; with one critic the critic's dx serves as it is.
+struct PolicyGradWs {
+    float *hp1, *hp2, *h1[2], *h2[2], *dz1, *dz2, *logits, *a, *logp, *g, *dz3, *qv[2], *dy[2], *dx[2], *slabs, *parts, *lparts;
 };
-Td3PolicyWs td3_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    Td3PolicyWs w;
+PolicyGradWs policy_grad_ws(Arena& ar, const mpg_cfg_t* cfg, int rows, int n_q, bool gauss) {
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, ou = gauss ? 2 * ad : ad;
+    PolicyGradWs w = {};
     w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
-    w.h11 = ar.take(stash_floats(rows)); w.h12 = ar.take(stash_floats(rows));
-    w.h21 = ar.take(stash_floats(rows)); w.h22 = ar.take(stash_floats(rows));
+    for (int k = 0; k < n_q; ++k) { w.h1[k] = ar.take(stash_floats(rows)); w.h2[k] = ar.take(stash_floats(rows)); }
     w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
-    w.a = ar.take((size_t)rows * ad); w.dz3 = ar.take((size_t)rows * ad);
-    w.qv1 = ar.take(rows); w.qv2 = ar.take(rows); w.dy1 = ar.take(rows); w.dy2 = ar.take(rows);
-    w.dx1 = ar.take((size_t)rows * qin); w.dx2 = ar.take((size_t)rows * qin);
-    w.ga = ar.take((size_t)rows * ad);
-    w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
-    w.parts = ar.take(2 * ERR_PARTS);
-    return w;
-}
-
-struct DpgPolicyWs {        // mpg_dpg_policy_grad: the single-critic half of Td3PolicyWs
-    float *hp1, *hp2, *h1, *h2, *dz1, *dz2, *a, *dz3, *qv, *dy, *dx, *slabs, *parts;
-};
-DpgPolicyWs dpg_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    DpgPolicyWs w;
-    w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
-    w.h1 = ar.take(stash_floats(rows)); w.h2 = ar.take(stash_floats(rows));
-    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
-    w.a = ar.take((size_t)rows * ad); w.dz3 = ar.take((size_t)rows * ad);
-    w.qv = ar.take(rows); w.dy = ar.take(rows);
-    w.dx = ar.take((size_t)rows * qin);
+    if (gauss) { w.logits = ar.take((size_t)rows * 2 * ad); w.logp = ar.take(rows); w.lparts = ar.take(2 * ERR_PARTS); }
+    w.a = ar.take((size_t)rows * ad); w.dz3 = ar.take((size_t)rows * ou);
+    for (int k = 0; k < n_q; ++k) w.qv[k] = ar.take(rows);
+    for (int k = 0; k < n_q; ++k) w.dy[k] = ar.take(rows);
+    for (int k = 0; k < n_q; ++k) w.dx[k] = ar.take((size_t)rows * qin);
+    if (n_q == 2) w.g = ar.take((size_t)rows * ou);
     w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
     w.parts = ar.take(2 * ERR_PARTS);
     return w;
@@ -414,26 +338,6 @@ SacTargetsWs sac_targets_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     return w;
 }
 
-struct SacPolicyWs {       // mpg_sac_policy_grad: Td3PolicyWs with the logits, logp and the four-column output gradient
-    float *hp1, *hp2, *h11, *h12, *h21, *h22, *dz1, *dz2, *logits, *a, *logp, *dlogits, *dz3, *qv1, *qv2, *dy1, *dy2, *dx1, *dx2, *slabs,
-        *parts, *lparts;
-};
-SacPolicyWs sac_policy_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    SacPolicyWs w;
-    w.hp1 = ar.take(stash_floats(rows)); w.hp2 = ar.take(stash_floats(rows));
-    w.h11 = ar.take(stash_floats(rows)); w.h12 = ar.take(stash_floats(rows));
-    w.h21 = ar.take(stash_floats(rows)); w.h22 = ar.take(stash_floats(rows));
-    w.dz1 = ar.take(stash_floats(rows)); w.dz2 = ar.take(stash_floats(rows));
-    w.logits = ar.take((size_t)rows * 2 * ad); w.a = ar.take((size_t)rows * ad); w.logp = ar.take(rows);
-    w.dlogits = ar.take((size_t)rows * 2 * ad); w.dz3 = ar.take((size_t)rows * 2 * ad);
-    w.qv1 = ar.take(rows); w.qv2 = ar.take(rows); w.dy1 = ar.take(rows); w.dy2 = ar.take(rows);
-    w.dx1 = ar.take((size_t)rows * qin); w.dx2 = ar.take((size_t)rows * qin);
-    w.slabs = ar.take(wgrad_workspace_floats(rows, od, 2 * ad));
-    w.parts = ar.take(2 * ERR_PARTS); w.lparts = ar.take(2 * ERR_PARTS);
-    return w;
-}
-
 // The refusals the three Gaussian-head entry points (and their workspace queries) share, in the order include/mpg_hip.h lists them.
 // `entry` names the caller in every message; MPG_OK when the call may proceed.
 int gauss_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
@@ -455,16 +359,72 @@ int policy_logits(const mpg_cfg_t* c, const float* params, int rows, const float
     o.out_tanh = c->policy_out_act == MPG_ACT_TANH;
     return launch_forward(c, params, c->obs_dim, 2 * c->act_dim, 2 * c->act_dim, rows, policy_x(c, obs), o, logits, 2 * c->act_dim, h1, h2, s);
 }
-// the head on `logits`: act, logp and (nullable) the sum of logp - one block below ERR_MB_MIN_ROWS, ERR_PARTS blocks + the finish above
+// the head on `logits`: act, logp and (nullable) the sum of logp
 int gauss_head(const mpg_cfg_t* c, int rows, const float* logits, const float* eps, float* act, float* logp, float* logp_sum, float* parts,
                hipStream_t s) {
-    if (rows >= ERR_MB_MIN_ROWS) {
-        hipLaunchKernelGGL(k_gauss_head_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, c->act_dim, logits, eps, act, logp, logp_sum ? parts : nullptr);
-        if (logp_sum) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, parts, 1.f, 0.f, logp_sum, (float*)nullptr);
-    } else
-        hipLaunchKernelGGL(k_gauss_head, dim3(1), dim3(1024), 0, s, rows, c->act_dim, logits, eps, act, logp, logp_sum);
-    MPG_CHECK_LAUNCH("k_gauss_head");
-    return MPG_OK;
+    return launch_row_sums("k_row_sums<GaussRow>", GaussRow{c->act_dim, logits, eps, act, logp}, rows, parts, logp_sum, nullptr, nullptr, s);
+}
+
+// The policy gradient through the critic(s), td3.py:120-134 / ndpg.py:174-186 / sac.py:119-136: policy forward (eps: all four logits and
+// the head's sample in place of the mean), the critics' forwards, dL/dq and the statistic sums, the critics' backwards down to dx, the
+// policy's output gradient, the policy's backward and weight gradient.  q2 null: one critic (DPG), whose dx is dQ/da as it stands; eps
+// (with alpha, logp_sum) non-null: the Gaussian head, two critics only (SAC).
+int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                const float* eps, float alpha, float inv_b, float* q_sum, float* q_sqsum, float* logp_sum, float* grad, void* ws,
+                size_t ws_bytes, mpg_stream_t stream) {
+    const int n_q = q2 ? 2 : 1;
+    Arena ar(ws, ws_bytes);
+    const PolicyGradWs w = policy_grad_ws(ar, cfg, rows, n_q, eps != nullptr);
+    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, ou = eps ? 2 * ad : ad;
+    const OutSpec po = policy_out(cfg);        // (the head has no action range: the plain output activation on all four columns)
+    const XSpec xp = policy_x(cfg, obs);
+    const float* const q[2] = {q1, q2};
+    int rc;
+    if (eps) {
+        rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);
+        if (rc) return rc;
+        rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
+    } else {
+        rc = policy_forward(cfg, policy, rows, xp, po, w.a, w.hp1, w.hp2, s);
+    }
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs, w.a);
+    for (int k = 0; k < n_q; ++k) {
+        rc = critic_forward(cfg, q[k], rows, xq, w.qv[k], w.h1[k], w.h2[k], s);
+        if (rc) return rc;
+    }
+    // (see mpg_q_loss_grad; four used outputs have no thin form, so the head's sums are finished by k_finish_parts)
+    const bool thin = backward_takes_thin(od, ou);
+    FinishJob fin = {};
+    rc = n_q == 2 ? launch_row_sums("k_row_sums<Td3DyRow>", Td3DyRow{w.qv[0], w.qv[1], inv_b, w.dy[0], w.dy[1]}, rows, w.parts, q_sum, q_sqsum,
+                                    thin ? &fin : nullptr, s)
+                  : launch_row_sums("k_row_sums<DpgDyRow>", DpgDyRow{w.qv[0], inv_b, w.dy[0]}, rows, w.parts, q_sum, q_sqsum,
+                                    thin ? &fin : nullptr, s);
+    if (rc) return rc;
+    for (int k = 0; k < n_q; ++k) {
+        rc = launch_backward(cfg, q[k], qin, 1, 1, rows, w.dy[k], 1, nullptr, 0, 0, 1.f, w.h1[k], w.h2[k], nullptr, nullptr, nullptr, w.dx[k], qin, s);
+        if (rc) return rc;
+    }
+    // dL/d(policy output): one critic - its input gradient at the action columns (rows of qin floats, from column od on)
+    const float* g = w.dx[0] + od;
+    int ldg = qin;
+    if (n_q == 2) {
+        if (eps)
+            hipLaunchKernelGGL(k_sac_dlogits, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits, alpha,
+                               inv_b, w.g);
+        else
+            hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], w.g);
+        MPG_CHECK_LAUNCH(eps ? "k_sac_dlogits" : "k_sum_action_grad");
+        g = w.g;
+        ldg = ou;
+    }
+    rc = launch_backward(cfg, policy, od, 2 * ad, ou, rows, g, ldg, eps ? w.logits : w.a, ou, po.out_tanh, po.out_scale, w.hp1, w.hp2,
+                         thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
+    if (rc) return rc;
+    return launch_wgrad(cfg, od, 2 * ad, ou, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b, grad, w.slabs, s, thin, thin ? w.dz1 : nullptr,
+                        thin ? backward_thin_parts(rows) : 0, fin.part ? &fin : nullptr);
 }
 
 }  // namespace
@@ -614,26 +574,21 @@ extern "C" int mpg_q_loss_grad(const mpg_cfg_t* cfg, const float* q_params, int 
     // the thin parameter gradients ride in the backward launch (mlp_launch.h): its per-workgroup partials live where the dz1 stash
     // would (never larger), the weight-gradient launch reads h1 and dz2 only
     const bool thin = backward_takes_thin(in, 1);
-    // large batches: the loss partials of the 64-block error kernel are added up by one extra block of the gradient's summation launch
-    // (round 5; k_finish_parts' arithmetic) when that launch exists (thin), by k_finish_parts otherwise
-    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 0.5f * inv_b_global, 0.f, loss_sum, nullptr};
-    const bool mb = rows >= ERR_MB_MIN_ROWS;
-    if (mb) {
-        hipLaunchKernelGGL(k_q_err_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.q, y, inv_b_global, w.dz3, td, w.parts);
-        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 0.5f * inv_b_global, 0.f, loss_sum, (float*)nullptr);
-    } else
-    hipLaunchKernelGGL(k_q_err, dim3(1), dim3(1024), 0, s, rows, w.q, y, inv_b_global, w.dz3, td, loss_sum);
-    MPG_CHECK_LAUNCH("k_q_err");
+    // large batches: the loss partials of the many-block form are added up by one extra block of the gradient's summation launch
+    // (k_finish_parts' arithmetic) when that launch exists (thin), by k_finish_parts otherwise
+    FinishJob fin = {};
+    rc = launch_row_sums("k_row_sums<QErrRow>", QErrRow{w.q, y, inv_b_global, w.dz3, td}, rows, w.parts, loss_sum, nullptr, thin ? &fin : nullptr, s);
+    if (rc) return rc;
     rc = launch_backward(cfg, q_params, in, 1, 1, rows, w.dz3, 1, nullptr, 0, 0, 1.f, w.h1, w.h2, thin ? nullptr : w.dz1, w.dz2, nullptr, nullptr, 0, s,
                          thin ? &xq : nullptr, thin ? w.dz1 : nullptr);
     if (rc) return rc;
     return launch_wgrad(cfg, in, 1, 1, rows, xq, w.h1, w.h2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin, thin ? w.dz1 : nullptr,
-                        thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+                        thin ? backward_thin_parts(rows) : 0, fin.part ? &fin : nullptr);
 }
 
 extern "C" size_t mpg_td3_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
     if (!net_cfg_ok(cfg) || rows <= 0) return 0;
-    return measured(td3_policy_ws, cfg, rows);
+    return measured(policy_grad_ws, cfg, rows, 2, false);
 }
 
 extern "C" int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_params, const float* q1, const float* q2,
@@ -641,45 +596,13 @@ extern "C" int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
                                    float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
     MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && q2 && obs && qmin_sum && qmin_sqsum && grad && ws && rows > 0,
                 "mpg_td3_policy_grad: bad argument");
-    Arena ar(ws, ws_bytes);
-    const Td3PolicyWs w = td3_policy_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_td3_policy_grad", ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    const OutSpec po = policy_out(cfg);
-    const XSpec xp = policy_x(cfg, obs);
-    int rc = policy_forward(cfg, policy_params, rows, xp, po, w.a, w.hp1, w.hp2, s);        // td3.py:123
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs, w.a);
-    rc = critic_forward(cfg, q1, rows, xq, w.qv1, w.h11, w.h12, s);                         // :124
-    if (rc) return rc;
-    rc = critic_forward(cfg, q2, rows, xq, w.qv2, w.h21, w.h22, s);                         // :125
-    if (rc) return rc;
-    const bool thin = backward_takes_thin(od, ad);        // (see mpg_q_loss_grad)
-    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 1.f, 1.f, qmin_sum, qmin_sqsum};
-    const bool mb = rows >= ERR_MB_MIN_ROWS;
-    if (mb) {
-        hipLaunchKernelGGL(k_td3_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, w.parts);
-        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, qmin_sum, qmin_sqsum);
-    } else
-    hipLaunchKernelGGL(k_td3_dy, dim3(1), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, qmin_sum, qmin_sqsum);
-    MPG_CHECK_LAUNCH("k_td3_dy");
-    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy1, 1, nullptr, 0, 0, 1.f, w.h11, w.h12, nullptr, nullptr, nullptr, w.dx1, qin, s);
-    if (rc) return rc;
-    rc = launch_backward(cfg, q2, qin, 1, 1, rows, w.dy2, 1, nullptr, 0, 0, 1.f, w.h21, w.h22, nullptr, nullptr, nullptr, w.dx2, qin, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx1, w.dx2, w.ga);
-    MPG_CHECK_LAUNCH("k_sum_action_grad");
-    rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, w.ga, ad, w.a, ad, po.out_tanh, po.out_scale, w.hp1, w.hp2,
-                         thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
-    if (rc) return rc;
-    return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,
-                        thin ? w.dz1 : nullptr, thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+    return policy_grad("mpg_td3_policy_grad", cfg, policy_params, q1, q2, rows, obs, nullptr, 0.f, inv_b_global, qmin_sum, qmin_sqsum, nullptr,
+                       grad, ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_dpg_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
     if (!net_cfg_ok(cfg) || rows <= 0) return 0;
-    return measured(dpg_policy_ws, cfg, rows);
+    return measured(policy_grad_ws, cfg, rows, 1, false);
 }
 
 // NDPGLearner.policy_forward_and_backward, ndpg.py:174-186: mpg_td3_policy_grad with ONE critic - one critic forward, one critic
@@ -690,35 +613,8 @@ extern "C" int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
                                    mpg_stream_t stream) {
     MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && obs && q_sum && q_sqsum && grad && ws && rows > 0,
                 "mpg_dpg_policy_grad: bad argument");
-    Arena ar(ws, ws_bytes);
-    const DpgPolicyWs w = dpg_policy_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_dpg_policy_grad", ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
-    const OutSpec po = policy_out(cfg);
-    const XSpec xp = policy_x(cfg, obs);
-    int rc = policy_forward(cfg, policy_params, rows, xp, po, w.a, w.hp1, w.hp2, s);        // ndpg.py:178
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs, w.a);
-    rc = critic_forward(cfg, q1, rows, xq, w.qv, w.h1, w.h2, s);                            // :179
-    if (rc) return rc;
-    const bool thin = backward_takes_thin(od, ad);        // (see mpg_q_loss_grad)
-    FinishJob fin{w.parts, ERR_PARTS, ERR_PARTS, 1.f, 1.f, q_sum, q_sqsum};
-    const bool mb = rows >= ERR_MB_MIN_ROWS;
-    if (mb) {
-        hipLaunchKernelGGL(k_dpg_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv, inv_b_global, w.dy, w.parts);
-        if (!thin) hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, q_sum, q_sqsum);
-    } else
-    hipLaunchKernelGGL(k_dpg_dy, dim3(1), dim3(1024), 0, s, rows, w.qv, inv_b_global, w.dy, q_sum, q_sqsum);
-    MPG_CHECK_LAUNCH("k_dpg_dy");
-    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy, 1, nullptr, 0, 0, 1.f, w.h1, w.h2, nullptr, nullptr, nullptr, w.dx, qin, s);
-    if (rc) return rc;
-    // dL/da = the critic's input gradient at the action columns: rows of qin floats, from column od on
-    rc = launch_backward(cfg, policy_params, od, 2 * ad, ad, rows, w.dx + od, qin, w.a, ad, po.out_tanh, po.out_scale, w.hp1, w.hp2,
-                         thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
-    if (rc) return rc;
-    return launch_wgrad(cfg, od, 2 * ad, ad, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s, thin,
-                        thin ? w.dz1 : nullptr, thin ? backward_thin_parts(rows) : 0, (mb && thin) ? &fin : nullptr);
+    return policy_grad("mpg_dpg_policy_grad", cfg, policy_params, q1, nullptr, rows, obs, nullptr, 0.f, inv_b_global, q_sum, q_sqsum, nullptr, grad,
+                       ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_policy_sample_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
@@ -771,11 +667,11 @@ extern "C" int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const 
 
 extern "C" size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
     if (gauss_refusal("mpg_sac_policy_grad_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(sac_policy_ws, cfg, rows);
+    return measured(policy_grad_ws, cfg, rows, 2, true);
 }
 
 // mpg_td3_policy_grad with the sampled action in place of the mean: the policy pass keeps all four logits, the head samples, the
-// critics' input gradients come back as in TD3 (the same dy kernel: the gradient flows through the smaller critic), k_sac_dlogits
+// critics' input gradients come back as in TD3 (the same dy rows: the gradient flows through the smaller critic), k_sac_dlogits
 // turns them into the four-column output gradient, and the policy's backward / weight gradient run in their four-output form
 extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
                                    const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
@@ -783,35 +679,6 @@ extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, co
     int rc = gauss_refusal("mpg_sac_policy_grad", cfg, policy && q1 && q2 && obs && eps && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
                            rows, alpha);
     if (rc) return rc;
-    Arena ar(ws, ws_bytes);
-    const SacPolicyWs w = sac_policy_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_sac_policy_grad", ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, out_tanh = cfg->policy_out_act == MPG_ACT_TANH;
-    rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);                  // sac.py:123
-    if (rc) return rc;
-    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs, w.a);
-    rc = critic_forward(cfg, q1, rows, xq, w.qv1, w.h11, w.h12, s);                         // :124
-    if (rc) return rc;
-    rc = critic_forward(cfg, q2, rows, xq, w.qv2, w.h21, w.h22, s);                         // :125
-    if (rc) return rc;
-    if (rows >= ERR_MB_MIN_ROWS) {                                                          // :126, :131-132
-        hipLaunchKernelGGL(k_td3_dy_mb, dim3(ERR_PARTS), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, w.parts);
-        hipLaunchKernelGGL(k_finish_parts, dim3(1), dim3(128), 0, s, ERR_PARTS, w.parts, 1.f, 1.f, qmin_sum, qmin_sqsum);
-    } else
-        hipLaunchKernelGGL(k_td3_dy, dim3(1), dim3(1024), 0, s, rows, w.qv1, w.qv2, inv_b_global, w.dy1, w.dy2, qmin_sum, qmin_sqsum);
-    MPG_CHECK_LAUNCH("k_td3_dy");
-    rc = launch_backward(cfg, q1, qin, 1, 1, rows, w.dy1, 1, nullptr, 0, 0, 1.f, w.h11, w.h12, nullptr, nullptr, nullptr, w.dx1, qin, s);
-    if (rc) return rc;
-    rc = launch_backward(cfg, q2, qin, 1, 1, rows, w.dy2, 1, nullptr, 0, 0, 1.f, w.h21, w.h22, nullptr, nullptr, nullptr, w.dx2, qin, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sac_dlogits, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx1, w.dx2, eps, w.logits, alpha,
-                       inv_b_global, w.dlogits);
-    MPG_CHECK_LAUNCH("k_sac_dlogits");
-    rc = launch_backward(cfg, policy, od, 2 * ad, 2 * ad, rows, w.dlogits, 2 * ad, w.logits, 2 * ad, out_tanh, 1.f, w.hp1, w.hp2, w.dz1, w.dz2,
-                         w.dz3, nullptr, 0, s);
-    if (rc) return rc;
-    return launch_wgrad(cfg, od, 2 * ad, 2 * ad, rows, policy_x(cfg, obs), w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b_global, grad, w.slabs, s);
+    return policy_grad("mpg_sac_policy_grad", cfg, policy, q1, q2, rows, obs, eps, alpha, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
+                       ws_bytes, stream);
 }

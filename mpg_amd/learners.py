@@ -98,9 +98,25 @@ class _LearnerBase(object):
         self.batch_data = {k: f32(batch_data[i])
                            for i, k in enumerate(('batch_obs', 'batch_actions', 'batch_rewards', 'batch_obs_tp1', 'batch_dones'))}
 
-    def _finish(self, iteration, clip):
-        """all-reduce, clip per network, expose the reference's list view."""
-        pw = self.policy_with_value
+    def compute_td_error(self):
+        """mpg_learner.py:136-144, td3.py:83-92, ndpg.py:116-125 (signed): the plain Q1 target - Q1(s, a)."""
+        pw, b = self.policy_with_value, self.batch_data
+        y1 = ops.q_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), None, b['batch_rewards'], b['batch_obs_tp1'])
+        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
+
+    def _begin(self, batch_data, rb, indexes, *noise):
+        """the opening of every compute_gradient: a new batch (get_batch_data, with the caller's draws) unless the last one is reused;
+        the call is counted.  Returns (networks, batch, rows, 1 / B_global, the statistics slots behind the gradients)."""
+        if self.counter % self.num_batch_reuse == 0:
+            self.get_batch_data(batch_data, rb, indexes, *noise)
+        self.counter += 1
+        rows = self.batch_data['batch_obs'].shape[0]
+        return self.policy_with_value, self.batch_data, rows, 1.0 / (rows * D.world_size()), self.flat[self.n_grad:]
+
+    def _finish(self, iteration, lazy_stats=None):
+        """the close of every compute_gradient: all-reduce, clip per network, expose the reference's list view; the statistics
+        (lazy_stats, default _native_lazy_stats) are evaluated when get_stats() asks."""
+        pw, clip = self.policy_with_value, float(self.args.gradient_clip_norm)
         D.all_reduce_sum_(self.flat)
         if self._views is None:
             self.flat_grad = self.flat[:self.n_grad]
@@ -110,6 +126,7 @@ class _LearnerBase(object):
         ops.clip_by_global_norm(self.flat_grad, pw.sizes, clip, norms_out=self.norms, nonfinite=pw.nonfinite,
                                 scratch=self.clip_scratch)
         self.stats['iteration'] = iteration
+        self._lazy_stats = (lazy_stats or self._native_lazy_stats)(iteration)
         return self._views
 
 
@@ -171,12 +188,6 @@ class MPGLearner(_LearnerBase):
         ro = self.sample(b['batch_obs'], b['batch_actions'])
         return ops.nstep_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), ro['all_rewards'], ro['last_obs'])
 
-    def compute_td_error(self):
-        """mpg_learner.py:136-144 (signed)."""
-        pw, b = self.policy_with_value, self.batch_data
-        y1 = ops.q_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), None, b['batch_rewards'], b['batch_obs_tp1'])
-        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
-
     def get_batch_data(self, batch_data, rb, indexes):
         self._get_batch(batch_data)
         if self.args.learner_version == 'MPG-v1':
@@ -196,13 +207,7 @@ class MPGLearner(_LearnerBase):
         """mpg_learner.py:401-455.  Returns the list [q1 (6 arrays) (+ q2) + policy (6 arrays)] of device tensors
         (views of one flat buffer, also available as `self.flat_grad`).  eps: optional [n, M*B] standard-normal model
         noise (parity tests); by default it is drawn inside the rollout kernel."""
-        if self.counter % self.num_batch_reuse == 0:
-            self.get_batch_data(batch_data, rb, indexes)
-        self.counter += 1
-        pw, b = self.policy_with_value, self.batch_data
-        rows = b['batch_obs'].shape[0]
-        world = D.world_size()
-        inv_b = 1.0 / (rows * world)
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes)
         select = self.num_rollout_list_for_policy_update
         ws = rule_based_weights(iteration, self.args.rule_based_bias_total_ite, self.args.eta, select)
         n = max(select)
@@ -210,25 +215,20 @@ class MPGLearner(_LearnerBase):
             select, ws = select + [0], np.append(ws, np.float32(0.0))
         if self.deriv_interval_policy:
             # every rollout step goes through pi_theta (full BPTT, mpg_learner.py:247-248): the fine-grained entry points
-            stats = self.flat[self.n_grad:]
             for i, nm in enumerate(n for n in pw.names if n != 'policy'):
                 ops.q_loss_grad(self.cfg, pw.net(nm), b['batch_obs'], b['batch_actions'], b['batch_targets'],
                                 inv_b_global=inv_b, grad_out=self.grad(nm), loss_out=stats[i:i + 1])
             ops.rollout_pg(self.cfg, pw.net('policy'), pw.net('Q1'), b['batch_obs'], eps, select, ws, M=self.M,
                            inv_b_global=inv_b, all_steps_param_grad=True, grad_out=self.grad('policy'),
                            stats_out=stats[2:2 + 2 * len(select)], n=n, noise_seed=self.seed, noise_ctr=self.counter)
-            out = self._finish(iteration, float(self.args.gradient_clip_norm))
-            self._lazy_stats = self._mpg_lazy_stats(iteration)
-            return out
+            return self._finish(iteration, self._mpg_lazy_stats)
         # one native call: critic losses/gradients + model rollout + mixed policy gradient (5 launches); the targets
         # were computed by get_batch_data (the reference caches them per batch, mpg_learner.py:402-403)
         ops.mpg_gradients(self.cfg, len(pw.names) - 1, pw.params, pw.targets, b['batch_obs'], b['batch_actions'],
                           b['batch_rewards'], b['batch_obs_tp1'], b['batch_targets'], select, ws, self.flat[:self.n_grad],
-                          self.flat[self.n_grad:], b['batch_targets'], M=self.M, n=n, eps=eps, noise_seed=self.seed,
+                          stats, b['batch_targets'], M=self.M, n=n, eps=eps, noise_seed=self.seed,
                           noise_ctr=self.counter, inv_b_global=inv_b)
-        out = self._finish(iteration, float(self.args.gradient_clip_norm))
-        self._lazy_stats = self._mpg_lazy_stats(iteration)
-        return out
+        return self._finish(iteration, self._mpg_lazy_stats)
 
     def _native_lazy_stats(self, iteration):
         """what the native step driver leaves in the statistics slots, as get_stats() reports it"""
@@ -275,14 +275,7 @@ class NADPLearner(_LearnerBase):
 
     def compute_gradient(self, batch_data, rb, indexes, iteration, eps_q=None, eps_pi=None):
         """nadp.py:209-241"""
-        if self.counter % self.num_batch_reuse == 0:
-            self.get_batch_data(batch_data, rb, indexes)
-        self.counter += 1
-        pw, b = self.policy_with_value, self.batch_data
-        rows = b['batch_obs'].shape[0]
-        world = D.world_size()
-        inv_b = 1.0 / (rows * world)
-        stats = self.flat[self.n_grad:]
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes)
         targets = ops.rollout_q_target(self.cfg, pw.net('policy'), pw.net('Q1', True), b['batch_obs'], b['batch_actions'],
                                        eps_q, n=self.n_q, noise_seed=self.seed, noise_ctr=2 * self.counter)   # nadp.py:87-126
         self.batch_data['batch_targets'] = targets
@@ -292,9 +285,7 @@ class NADPLearner(_LearnerBase):
         ops.rollout_pg(self.cfg, pw.net('policy'), pw.net('Q1'), b['batch_obs'], eps_pi, [0, self.n_pi], [0.0, 1.0], M=1,
                        inv_b_global=inv_b, all_steps_param_grad=True, grad_out=self.grad('policy'), stats_out=stats[2:6],
                        n=self.n_pi, noise_seed=self.seed, noise_ctr=2 * self.counter + 1)
-        out = self._finish(iteration, float(self.args.gradient_clip_norm))
-        self._lazy_stats = self._native_lazy_stats(iteration)
-        return out
+        return self._finish(iteration)
 
     def _native_lazy_stats(self, iteration):
         """evaluated only when get_stats() is called: no elementwise launches in the training loop"""
@@ -321,12 +312,6 @@ class TD3Learner(_LearnerBase):
         (learner seed, the gradient step this batch is fetched for) - the numbers the native step driver draws"""
         return ops.normal_fill(rows * self.cfg.act_dim, self.seed, self.counter + 1, self.device).view(rows, self.cfg.act_dim)
 
-    def compute_td_error(self):
-        """td3.py:83-92 (signed)."""
-        pw, b = self.policy_with_value, self.batch_data
-        y1 = ops.q_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), None, b['batch_rewards'], b['batch_obs_tp1'])
-        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
-
     def get_batch_data(self, batch_data, rb, indexes, smooth_eps=None):
         self._get_batch(batch_data)
         self._y1 = None
@@ -349,14 +334,7 @@ class TD3Learner(_LearnerBase):
 
     def compute_gradient(self, batch_data, rb, indexes, iteration, smooth_eps=None):
         """td3.py:150-188"""
-        if self.counter % self.num_batch_reuse == 0:
-            self.get_batch_data(batch_data, rb, indexes, smooth_eps)
-        self.counter += 1
-        pw, b = self.policy_with_value, self.batch_data
-        rows = b['batch_obs'].shape[0]
-        world = D.world_size()
-        inv_b = 1.0 / (rows * world)
-        stats = self.flat[self.n_grad:]
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes, smooth_eps)
         for i, nm in enumerate(('Q1', 'Q2')):
             pending = nm == 'Q1' and getattr(self, '_y1', None) is not None
             td = ops.q_loss_grad(self.cfg, pw.net(nm), b['batch_obs'], b['batch_actions'], b['batch_targets'], inv_b_global=inv_b,
@@ -366,9 +344,7 @@ class TD3Learner(_LearnerBase):
                 self._y1 = None
         ops.td3_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], inv_b_global=inv_b,
                             grad_out=self.grad('policy'), stats_out=stats[2:4])
-        out = self._finish(iteration, float(self.args.gradient_clip_norm))
-        self._lazy_stats = self._native_lazy_stats(iteration)
-        return out
+        return self._finish(iteration)
 
     def _native_lazy_stats(self, iteration):
         stats, B = self.flat[self.n_grad:], self.batch_size * D.world_size()
@@ -409,12 +385,6 @@ class NDPGLearner(_LearnerBase):
         ro = self.sample(b['batch_obs'], b['batch_actions'])
         return ops.nstep_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), ro['all_rewards'], ro['last_obs'])
 
-    def compute_td_error(self):
-        """ndpg.py:116-125 (signed)."""
-        pw, b = self.policy_with_value, self.batch_data
-        y1 = ops.q_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), None, b['batch_rewards'], b['batch_obs_tp1'])
-        return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
-
     def get_batch_data(self, batch_data, rb, indexes):
         self._get_batch(batch_data)
         self.batch_data['batch_targets'] = self.compute_n_step_target()
@@ -423,22 +393,14 @@ class NDPGLearner(_LearnerBase):
 
     def compute_gradient(self, batch_data, rb, indexes, iteration):
         """ndpg.py:202-237"""
-        if self.counter % self.num_batch_reuse == 0:
-            self.get_batch_data(batch_data, rb, indexes)
-        self.counter += 1
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes)
         if self.args.buffer_type != 'normal':                  # :206-207: the priorities follow the critic within a reused batch
             self.info_for_buffer.update(dict(td_error=self.compute_td_error()))
-        pw, b = self.policy_with_value, self.batch_data
-        rows = b['batch_obs'].shape[0]
-        inv_b = 1.0 / (rows * D.world_size())
-        stats = self.flat[self.n_grad:]
         ops.q_loss_grad(self.cfg, pw.net('Q1'), b['batch_obs'], b['batch_actions'], b['batch_targets'], inv_b_global=inv_b,
                         grad_out=self.grad('Q1'), loss_out=stats[0:1])                               # :162-172
         ops.dpg_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), b['batch_obs'], inv_b_global=inv_b,
                             grad_out=self.grad('policy'), stats_out=stats[2:4])                      # :174-186
-        out = self._finish(iteration, float(self.args.gradient_clip_norm))
-        self._lazy_stats = self._native_lazy_stats(iteration)
-        return out
+        return self._finish(iteration)
 
     def _native_lazy_stats(self, iteration):
         stats, B = self.flat[self.n_grad:], self.batch_size * D.world_size()
@@ -506,15 +468,9 @@ class SACLearner(_LearnerBase):
 
     def compute_gradient(self, batch_data, rb, indexes, iteration, eps_target=None, eps_policy=None):
         """sac.py:169-219; output order q1 + q2 + policy"""
-        if self.counter % self.num_batch_reuse == 0:
-            self.get_batch_data(batch_data, rb, indexes, eps_target)
-        self.counter += 1
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes, eps_target)
         if self.args.buffer_type != 'normal':                  # :173-174: the priorities follow the critic within a reused batch
             self.info_for_buffer.update(dict(td_error=self.compute_td_error(ctr=2 * self.counter - 1)))
-        pw, b = self.policy_with_value, self.batch_data
-        rows = b['batch_obs'].shape[0]
-        inv_b = 1.0 / (rows * D.world_size())
-        stats = self.flat[self.n_grad:]
         for i, nm in enumerate(('Q1', 'Q2')):                                                          # :102-117
             ops.q_loss_grad(self.cfg, pw.net(nm), b['batch_obs'], b['batch_actions'], b['batch_targets'], inv_b_global=inv_b,
                             grad_out=self.grad(nm), loss_out=stats[i:i + 1])
@@ -522,9 +478,7 @@ class SACLearner(_LearnerBase):
             eps_policy = self._draw(rows, 2 * self.counter + 1)
         ops.sac_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha,
                             inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5])    # :119-136
-        out = self._finish(iteration, float(self.args.gradient_clip_norm))
-        self._lazy_stats = self._native_lazy_stats(iteration)
-        return out
+        return self._finish(iteration)
 
     def _native_lazy_stats(self, iteration):
         stats, B, alpha = self.flat[self.n_grad:], self.batch_size * D.world_size(), self.alpha

@@ -392,27 +392,25 @@ def rollout_q_estimation(cfg, policy_params, q1t, obs0, act0, eps, select, M=1, 
     return y
 
 
-def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out=None, stats_out=None):
+def _policy_grad(name, cfg, policy_params, critics, obs, extra, n_stats, inv_b_global, grad_out, stats_out):
+    """the mpg_*_policy_grad call: (cfg, policy, critics..., rows, obs, extra..., inv_b, one pointer per statistic, grad, workspace)"""
     rows, dev = obs.shape[0], obs.device
     grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
-    stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _ws(dev, 1, 'mpg_td3_policy_grad_workspace_bytes', cfg, rows)
-    L.call('mpg_td3_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)),
-           L.c_int(rows), L.ptr(_f32(obs)), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
-           L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad), *ws, L.stream())
+    stats = stats_out if stats_out is not None else torch.empty(n_stats, dtype=torch.float32, device=dev)
+    ws = _ws(dev, 1, name + '_workspace_bytes', cfg, rows)
+    L.call(name, ctypes.byref(cfg), L.ptr(_f32(policy_params)), *[L.ptr(_f32(q)) for q in critics], L.c_int(rows), L.ptr(_f32(obs)), *extra,
+           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), *[L.ptr(stats[i:i + 1]) for i in range(n_stats)],
+           L.ptr(grad), *ws, L.stream())
     return stats, grad
+
+
+def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out=None, stats_out=None):
+    return _policy_grad('mpg_td3_policy_grad', cfg, policy_params, (q1, q2), obs, (), 2, inv_b_global, grad_out, stats_out)
 
 
 def dpg_policy_grad(cfg, policy_params, q1, obs, inv_b_global=None, grad_out=None, stats_out=None):
     """mpg_dpg_policy_grad: -mean Q1(s~, pi(s~)) and its policy gradient.  Returns (stats = [q_sum, q_sqsum], grad)."""
-    rows, dev = obs.shape[0], obs.device
-    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
-    stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _ws(dev, 1, 'mpg_dpg_policy_grad_workspace_bytes', cfg, rows)
-    L.call('mpg_dpg_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.c_int(rows), L.ptr(_f32(obs)),
-           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad),
-           *ws, L.stream())
-    return stats, grad
+    return _policy_grad('mpg_dpg_policy_grad', cfg, policy_params, (q1,), obs, (), 2, inv_b_global, grad_out, stats_out)
 
 
 def policy_sample(cfg, policy_params, obs, eps, want_logits=False):
@@ -442,14 +440,8 @@ def sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
 def sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None):
     """mpg_sac_policy_grad: mean(alpha * logp - min Q) and its policy gradient over all four output columns.
     Returns (stats = [qmin_sum, qmin_sqsum, logp_sum], grad)."""
-    rows, dev = obs.shape[0], obs.device
-    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
-    stats = stats_out if stats_out is not None else torch.empty(3, dtype=torch.float32, device=dev)
-    ws = _ws(dev, 1, 'mpg_sac_policy_grad_workspace_bytes', cfg, rows)
-    L.call('mpg_sac_policy_grad', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)), L.c_int(rows),
-           L.ptr(_f32(obs)), L.ptr(_f32(eps)), L.c_float(alpha), L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows),
-           L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(stats[2:3]), L.ptr(grad), *ws, L.stream())
-    return stats, grad
+    return _policy_grad('mpg_sac_policy_grad', cfg, policy_params, (q1, q2), obs, (L.ptr(_f32(eps)), L.c_float(alpha)), 3, inv_b_global,
+                        grad_out, stats_out)
 
 
 def mpg_gradients_supported(cfg, rows, M, n, n_select, n_q):

@@ -146,7 +146,7 @@ def q_loss_reference(seed, B, K):
 
 @pytest.mark.parametrize('B,cut,K', NET_SHAPES)
 def test_q_loss_grad_shards(engine, B, cut, K):
-    """k_q_err (one block) and k_q_err_mb + the finish job (k_finish_parts where the backward is not thin, K = 3; the extra block of
+    """k_row_sums<QErrRow>: the one-block form, and the many-block form + the finish job (k_finish_parts where the backward is not thin, K = 3; the extra block of
     the weight-gradient launch's summation where it is, K = 0).  td is unscaled: a shard's td equals the same rows of the unsharded
     call bit for bit.  Loss bar: test_q_loss_grad_vs_oracle_autograd_ragged (rtol 2e-5)."""
     c, ref = net_case(100 + B + K, B, K), q_loss_reference(100 + B + K, B, K)
@@ -188,7 +188,7 @@ def dpg_reference(seed, B, K, two_critics):
 
 @pytest.mark.parametrize('B,cut,K', NET_SHAPES)
 def test_td3_policy_grad_shards(engine, B, cut, K):
-    """k_td3_dy and k_td3_dy_mb.  The statistic sums as the learner reports them (value_mean = sum / B, value_var = sqsum / B - mean^2)
+    """k_row_sums<Td3DyRow>, one block and many.  The statistic sums as the learner reports them (value_mean = sum / B, value_var = sqsum / B - mean^2)
     at the bars of test_td3_compute_gradient_vs_golden (rtol 1e-4 atol 1e-7; value_var rtol 2e-3)."""
     c, ref = net_case(200 + B + K, B, K), dpg_reference(200 + B + K, B, K, True)
     cfg = ops.make_cfg(obs_dim=c['od'], obs_scale=c['scale'])
@@ -214,7 +214,7 @@ def test_td3_policy_grad_shards(engine, B, cut, K):
 
 @pytest.mark.parametrize('B,cut,K', NET_SHAPES)
 def test_dpg_policy_grad_shards(engine, B, cut, K):
-    """k_dpg_dy and k_dpg_dy_mb.  q_sum / q_sqsum at the bar of test_dpg_policy_grad_vs_float64_autograd_and_vs_the_td3_entry_point
+    """k_row_sums<DpgDyRow>, one block and many.  q_sum / q_sqsum at the bar of test_dpg_policy_grad_vs_float64_autograd_and_vs_the_td3_entry_point
     (1e-6 relative)."""
     c, ref = net_case(300 + B + K, B, K), dpg_reference(300 + B + K, B, K, False)
     cfg = ops.make_cfg(obs_dim=c['od'], obs_scale=c['scale'])
@@ -247,7 +247,7 @@ def sac_reference(seed, B, K):
 
 @pytest.mark.parametrize('B,cut,K', NET_SHAPES)
 def test_sac_policy_grad_shards(engine, B, cut, K):
-    """the head's - alpha * inv_b term (k_sac_dlogits), k_td3_dy / k_td3_dy_mb under it, and the three statistic sums at the bars of
+    """the head's - alpha * inv_b term (k_sac_dlogits), k_row_sums<Td3DyRow> (one block and many) under it, and the three statistic sums at the bars of
     test_sac_targets_and_policy_grad_vs_float64_autograd"""
     c = net_case(400 + B + K, B, K)
     r32, r64 = sac_reference(400 + B + K, B, K)
