@@ -378,6 +378,24 @@ int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params, int n, flo
                     uint8_t* done_out /* nullable */, const mpg_replay_draw_t* draw /* nullable */, int rows, float* b_obs,
                     float* b_act, float* b_rew, float* b_obs2, mpg_stream_t stream);
 
+/* OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head below,
+ * no explore_sigma) as ONE launch for the path-tracking env, obs_dim 6 .. 16, act_dim 2.  Bit-identical - actions, log-densities,
+ * every ring row, env state, next observations, done flags and the sticky status word - to
+ *   mpg_normal_fill(2 n, sample_seed, sample_ctr, eps);
+ *   mpg_policy_sample(cfg, policy_params, n, obs_io, eps, act_out, logp_out, NULL, ...);
+ *   mpg_env_step_store_reset(MPG_ENV_PATH_TRACKING, n, obs_dim, state, act_out, capacity, next_idx, ring..., env_seed, env_ctr,
+ *                            obs_io, done_out);
+ * row r draws elements 2 r and 2 r + 1 of that stream inside the launch (no eps array exists).  There is no pre-gathered minibatch
+ * draw and no explore_sigma.  Refused before any launch with MPG_EINVAL and "mpg_worker_sample_step" in the message: everything
+ * mpg_policy_sample refuses (null pointers - logp_out alone may be null -, n <= 0, act_dim != 2, another env, action_range > 0, an
+ * unsupported width), a ring that mpg_worker_step refuses (capacity < n, next_idx outside [0, capacity)), and env_kind 2 with the
+ * text of the other real-env entry points. */
+int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_params, int n, float* state, float* obs_io,
+                           uint64_t sample_seed, uint64_t sample_ctr, float* act_out, float* logp_out /* nullable */,
+                           int capacity, int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2,
+                           uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out /* nullable */,
+                           mpg_stream_t stream);
+
 /* MPGLearner.sample / NDPGLearner.sample - learners/mpg_learner.py:109-124, learners/ndpg.py:99-114, PathTracking env, ONE launch:
  * from obs0 [rows][obs_dim] take n real-env steps, the first with the replay action act0 [rows][2], the later ones with the ONLINE
  * policy's deterministic action (no noise, no reset on done).  rewards [n][rows] RAW, last_obs [rows][obs_dim].  Bit-identical - the
@@ -598,7 +616,12 @@ typedef struct {
                                          4: TD3 (learners/td3.py:150-188: networks [Q1 | Q2 | policy]; n, M, select unused),
                                          5: NDPG (learners/ndpg.py:202-237: networks [Q1 | policy]; n = sample_num_in_learner, the
                                             real-env n-step target of version 1 (mpg_env_rollout into l_rewards / l_obs) every
-                                            num_batch_reuse-th call; M, n_select / select / eta / total_ite unused) */
+                                            num_batch_reuse-th call; M, n_select / select / eta / total_ite unused),
+                                         7: SAC, fixed temperature (learners/sac.py:169-219: networks [Q1 | Q2 | policy], uniform
+                                            replay; n, M, select, smooth_* unused).  Served by mpg_sac_step_begin, which carries the
+                                            temperature as an argument (this struct gains no field: the ABI version stays 10);
+                                            mpg_step_begin refuses it and names that function.  6 is not assigned: it stays refused
+                                            everywhere (mpg_step_workspace_bytes, mpg_step_begin, mpg_sac_step_begin) */
     int num_agent, sample_iters;      /* worker: sample_iters env steps of num_agent agents per sampling call */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];
@@ -645,7 +668,11 @@ typedef struct {
     double per_alpha, per_beta, per_eps;
     float* b_weights;                 /* [batch] IS weights of the draw (buffer.py:146-160; the TD3 loss does not use them) */
     float* scratch;                   /* max(batch * (act_dim + 3), 2 * num_agent) floats: smoothing noise | y1 | td | priority errors
-                                         (and the index / priority pairs of a ring add) */
+                                         (and the index / priority pairs of a ring add).
+                                         SAC (learner_version 7): max(batch * act_dim, num_agent * (act_dim + 1)) floats - the
+                                         learner's draws [batch][act_dim]; the second size is room for a worker's draws
+                                         [num_agent][act_dim] and log-densities [num_agent], which the one-launch worker step
+                                         the driver takes (mpg_worker_sample_step) forms in registers and does not store */
     /* scheduling option (round 5, ABI 9; MPG only, optional) */
     void* critics_ready_event;        /* hipEvent_t, nullable: see mpg_grad_opts_t (the caller overlaps the critics' exchange) */
     mpg_grad_opts_t grad_opts;        /* storage for cfg.grad_opts during mpg_step_begin */
@@ -661,6 +688,19 @@ typedef struct {
 int mpg_step_workspace_bytes(const mpg_train_ctx_t* ctx, size_t* ws0_bytes, size_t* ws1_bytes);
 int mpg_step_begin(mpg_train_ctx_t* ctx, int iteration, mpg_stream_t stream);
 int mpg_step_end(mpg_train_ctx_t* ctx, int iteration, mpg_stream_t stream);
+
+/* mpg_step_begin for learner_version 7 - SingleProcessOffPolicyOptimizer.step with SACLearner.compute_gradient (sac.py:169-219) on a
+ * uniform replay ring, through the entry points above only and with the counters advanced as the Python classes advance them:
+ *   [every sampling_interval-th iteration, sample_iters x: the stochastic worker step keyed by (worker_seed, noise_ctr++) and
+ *    (env_seed, env_ctr++) -> ring];  replay_times++;  on every num_batch_reuse-th call: mpg_replay_sample_uniform,
+ *   mpg_normal_fill(batch * act_dim, learner_seed, 2 * (learner_counter + 1)), mpg_sac_targets with the ONLINE policy and both target
+ *   critics into b_targets;  learner_counter++;  mpg_q_loss_grad for Q1 and Q2 (statistics 0, 1);
+ *   mpg_normal_fill(batch * act_dim, learner_seed, 2 * learner_counter + 1);  mpg_sac_policy_grad (statistics 2 .. 4: the sums of
+ *   min-Q, its square and logp).  Gradients are scaled by 1 / (batch * world_size).  mpg_step_end follows as for every version.
+ * ws0 / ws1: mpg_step_workspace_bytes (ws0: the larger of the mpg_sac_targets and mpg_q_loss_grad workspaces; ws1:
+ * mpg_sac_policy_grad's).  Refused with MPG_EINVAL before anything is enqueued: a learner_version other than 7, an incomplete context
+ * (scratch included), prioritized != 0, explore_sigma != 0, alpha negative or not finite, env_kind 2. */
+int mpg_sac_step_begin(mpg_train_ctx_t* ctx, float alpha, int iteration, mpg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 // environment's op-by-op arithmetic: the pragma is lexical, the environment code below is back under "off".
 #pragma clang fp contract(fast)
 #include "mlp_core.h"
+#include "gauss_head.h"
 
 namespace worker_policy {
 using namespace mlp;
@@ -48,8 +49,9 @@ template <> struct args_of<16> { typedef WideArgs type; };
 __device__ __forceinline__ constexpr int obs_dim_of(const Args&) { return 6; }
 __device__ __forceinline__ int obs_dim_of(const WideArgs& a) { return a.obs_dim; }
 
-template <int IN>
-__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * xs_of<IN>() + NWAVE * GROUP * MAXOUT; }
+// (OU: the used outputs the pass is built for - two: the deterministic action; four: the Gaussian head's logits)
+template <int IN, int OU = 2>
+__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * xs_of<IN>() + NWAVE * GROUP * out_stride<OU>(); }
 
 // One 16-row group of mpg_policy_action: k_forward<6, 2, PK, 1> or k_forward<16, 2, PK, 1> (mlp_kernels.hip) for unit g - the same
 // device functions on the same operands in the same order, so the actions are bit-identical to the stand-alone launch's (tests:
@@ -105,6 +107,78 @@ __device__ __forceinline__ void group(const typename args_of<IN>::type& a, int r
             act_out[gr * OU + o] = y;
         }
         sAct[tid] = y;
+    }
+    report_activation_range(a.status, zmax);
+    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
+}
+
+// One 16-row group of mpg_policy_sample on the worker's own draw: k_forward<6, 4, PK, 1> or k_forward<16, 4, PK, 1> for unit g as
+// policy_logits launches it (the output activation on all four columns, no action range) - the same device functions on the same
+// operands in the same order, the same row_poison, activation-range and NaN reporting - and then k_row_sums<GaussRow>'s row body
+// (gauss::gauss_row) on eps = elements 2 gr, 2 gr + 1 of the stream mpg_normal_fill writes for (a.k0 .. a.c2).  The four logits
+// of a row are formed by lanes 4 row .. 4 row + 3 of wave 0 - the lanes that step the row's agent afterwards - and go through sLogit
+// [16][4] to the first of them, which draws, samples and leaves the action in act_out, the log-density in logp_out (nullable) and the
+// action in sAct [16][2] for the env lanes: LDS is in order within a wave.  a.sigma and a.out_scale are not read.
+template <bool PK, int IN>
+__device__ __forceinline__ void sample_group(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g,
+                                             float* smem, float* sLogit, float* sAct, float* __restrict__ act_out,
+                                             float* __restrict__ logp_out) {
+    static_assert(IN == 6 || IN == 16, "the worker launch is built for six-entry observations and for the 16-wide first layer");
+    constexpr int OU = 4, XSW = xs_of<IN>(), OS = out_stride<OU>();
+    static_assert(GROUP * OU == 64, "the four logits of every row of a group are formed by one wave");
+    const int od = obs_dim_of(a);              // a constant at IN = 6
+    float* sA = smem;
+    float* sX = sA + A_IMG;
+    float* sPart = sX + GROUP * XSW;
+    const Lane L;
+    const Net net = make_net(a.params, od, OU);
+    float w2[128];
+    SmallRegs<IN, OU> r;
+    float xv = 0.f;
+    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 stay zero)
+        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
+        const long gr = g * GROUP + row;
+        if (gr < rows && i < od) xv = obs[gr * od + i] * a.scale[i];
+    }
+    float b3v = 0.f;
+    if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
+    float zmax = 0.f;
+    bool saw_nan = false;
+    load_small<IN, OU>(net, L, r);
+    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
+    saw_nan |= xv != xv;
+    if (threadIdx.x < GROUP * XSW) sX[threadIdx.x] = xv;
+    lds_barrier();
+    float pz = 0.f;
+    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
+    float h1[2][4], h2[2][4];
+    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    const int tid = threadIdx.x;
+    if (tid < GROUP * OU) {
+        const int row = tid / OU, o = tid % OU;
+        const long gr = g * GROUP + row;
+        float y = 0.f;
+        if (gr < rows) {
+            float z = out_preact<OS>(sPart, b3v, row, o);
+            y = a.out_tanh ? tanhf(z) : z;
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sLogit[tid] = y;
+        __builtin_amdgcn_wave_barrier();
+        if (o == 0) {
+            float act[2] = {0.f, 0.f};
+            if (gr < rows) {
+                float eps[2];
+                gauss::normal_pair((uint32_t)(gr >> 1), (int)(gr & 1), a.k0, a.k1, a.c1, a.c2, eps[0], eps[1]);
+                const float lp = gauss::gauss_row(2, sLogit + row * OU, eps, act);
+                act_out[gr * 2] = act[0];
+                act_out[gr * 2 + 1] = act[1];
+                if (logp_out) logp_out[gr] = lp;
+            }
+            sAct[2 * row] = act[0];
+            sAct[2 * row + 1] = act[1];
+        }
     }
     report_activation_range(a.status, zmax);
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
@@ -646,6 +720,34 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
                 worker_policy::obs_dim_of(pa));
 }
 
+// OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head, no
+// explore_sigma) in ONE launch: mpg_normal_fill + mpg_policy_sample (k_forward<IN, 4>, k_row_sums<GaussRow>) + mpg_env_step_store_reset
+// are four launches of at most one wave per CU each; here a 512-thread workgroup runs the four-logit policy pass of a 16-agent group,
+// wave 0 draws and samples (worker_policy::sample_group) and then steps those agents with env_lane<4>, exactly as in
+// k_policy_step_store_reset.  No spare workgroups: there is no pre-gathered draw.  IN as in k_policy_step_store_reset.
+template <bool PK, int IN>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_sample_step_store_reset(const typename worker_policy::args_of<IN>::type pa,
+                                                                                     int n, float* __restrict__ st,
+                                                                                     float* __restrict__ obs_io, float* __restrict__ act_out,
+                                                                                     float* __restrict__ logp_out, RingPtrs ring,
+                                                                                     int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                                                     uint32_t c1, uint32_t c2,
+                                                                                     uint8_t* __restrict__ done_out) {
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN, 4>()];
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    __shared__ float sLogit[mlp::GROUP * 4];
+    __shared__ float sAct[mlp::GROUP * 2];
+    worker_policy::sample_group<PK, IN>(pa, n, obs_io, blockIdx.x, smem, sLogit, sAct, act_out, logp_out);
+    if (threadIdx.x >= 64) return;                     // the env lanes: wave 0, four lanes per agent (it wrote sAct itself: LDS is in
+    __builtin_amdgcn_wave_barrier();                   // order within a wave)
+    const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
+    if (i >= n) return;
+    const Agent ag = load_agent(st, n, i);
+    const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
+    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_io, done_out,
+                worker_policy::obs_dim_of(pa));
+}
+
 // MPGLearner.sample / NDPGLearner.sample (mpg_learner.py:109-124, ndpg.py:99-114) in ONE launch: from obs0 take n real-env steps, the
 // first with the replay action act0, the later ones with the policy's deterministic action.  The stand-alone chain is
 // mpg_env_reset_from_obs + n x mpg_env_step + (n - 1) x mpg_policy_action = 2 n launches of one wave per CU each, every policy launch
@@ -882,6 +984,44 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
 #undef MPG_WORKER_LAUNCH
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_step");
+    return MPG_OK;
+}
+
+// worker.py:68-79 (stochastic policy, explore_sigma unset) for the path-tracking env: mpg_normal_fill(2 n, sample_seed, sample_ctr) +
+// mpg_policy_sample + mpg_env_step_store_reset as one launch (bit-identical actions, log-densities, ring rows, states, observations,
+// done flags and status word)
+extern "C" int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_params, int n, float* state, float* obs_io,
+                                      uint64_t sample_seed, uint64_t sample_ctr, float* act_out, float* logp_out, int capacity, int next_idx,
+                                      float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
+                                      uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
+    MPG_REQUIRE(!cfg || cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_sample_step: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    // what mpg_policy_sample refuses (its logp_out may be null here), then what mpg_worker_step asks of the ring
+    if (int rc = gauss::gauss_refusal("mpg_worker_sample_step", cfg, policy_params && state && obs_io && act_out && ring.obs &&
+                                           ring.act && ring.rew && ring.obs2 && ring.done, n, 0.f))
+        return rc;
+    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "mpg_worker_sample_step: bad ring (capacity %d < n %d, or next_idx %d outside it)",
+                capacity, n, next_idx);
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+#define MPG_WORKER_LAUNCH(PK, IN)                                                                                                         \
+    hipLaunchKernelGGL((k_policy_sample_step_store_reset<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, \
+                       logp_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out)
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, 0.f, sample_seed, sample_ctr);
+        pa.obs_dim = cfg->obs_dim;
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_LAUNCH(true, 16); else MPG_WORKER_LAUNCH(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, 0.f, sample_seed, sample_ctr);
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_LAUNCH(true, 6); else MPG_WORKER_LAUNCH(false, 6);
+    }
+#undef MPG_WORKER_LAUNCH
+    mpg_prof_end(mpg_prof_of(cfg), 2, s);
+    MPG_CHECK_LAUNCH("mpg_worker_sample_step");
     return MPG_OK;
 }
 

@@ -1,0 +1,74 @@
+// Gaussian policy head (policy.py:179-204 with action_range None: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))), no bijector)
+// on the four logits of the policy pass, and the element function of the library's standard-normal stream.  Shared by the two
+// translation units that evaluate the head - learner_api.hip (k_row_sums<GaussRow>, k_sac_dlogits) and env_path_tracking.hip (the
+// stochastic worker launch) - which must agree bit for bit: include it where contraction is allowed (env_path_tracking.hip: inside
+// its `#pragma clang fp contract(fast)` block), so that both compile these expressions under the same rule.
+#pragma once
+#include <math.h>
+
+#include "mpg_common.h"
+
+namespace gauss {
+
+constexpr float LOG_STD_MIN = -5.f, LOG_STD_MAX = 1.f, HALF_LOG_2PI = 0.91893853320467274f;
+// sigma = exp(log_std) as the CORRECTLY ROUNDED float32 exponential (the double-precision exp, rounded once): the float32 library exp is
+// within an ulp of it and its last bit differs between compiler versions, while a sample must be reproducible from logits_out by anyone
+// (two values per row: the double-precision pipe is not on any hot path here)
+__device__ __forceinline__ float sigma_of(float clipped_log_std) { return (float)exp((double)clipped_log_std); }
+// a * b + c with the product and the sum rounded separately, whatever the translation unit's contraction mode (the __fmul_rn / __fadd_rn
+// intrinsics are plain operators here and fuse)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return p + c;
+}
+// act = mean + sigma * eps with the product and the sum rounded separately (the same bits as the two-op expression a caller forms
+// from logits_out); returns the row's log-density.  z, the standardised sample of the density, is eps ITSELF: TFP forms
+// (a - mean) / sigma, which in exact arithmetic is eps and in float32 is eps with two more roundings - against the float64 run of the
+// reference, where that expression returns eps to 1e-16, eps is the nearer of the two.
+__device__ __forceinline__ float gauss_row(int ad, const float* __restrict__ l, const float* __restrict__ e, float* __restrict__ a) {
+    float lp = 0.f;
+    for (int k = 0; k < ad; ++k) {
+        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), sigma = sigma_of(ls), z = e[k];
+        a[k] = mul_then_add(sigma, z, l[k]);
+        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
+    }
+    return lp;
+}
+
+// Elements 4 q + 2 pair and 4 q + 2 pair + 1 of the stream mpg_normal_fill writes for (key, counter): Philox block q, Box-Muller on
+// the words (v[0], v[1]) (pair 0) or (v[2], v[3]) (pair 1) - the cosine for the even element, the sine for the odd one.  k_normal_fill
+// (learner_api.hip) states the same operations for a whole block; tests/test_sac_native_gpu.py compares the two bit for bit.
+// The logarithm and the root are the builtins themselves, not the library's logf / sqrtf: those are wrappers that the HIP headers
+// define ahead of any pragma, so the backend would expand them under the translation unit's own contraction mode (the last step of
+// the logarithm's expansion is a product and a sum that fuse under one mode and not under the other), while a builtin called HERE is
+// expanded under the mode in force here - which is k_normal_fill's.
+constexpr uint32_t NORMAL_STREAM_TAG = 0x6e6f726du;
+__device__ __forceinline__ void normal_pair(uint32_t q, int pair, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, float& z_even,
+                                            float& z_odd) {
+    const Philox4 p = philox4x32_10(q, c1, c2, NORMAL_STREAM_TAG, k0, k1);
+    const uint32_t a = pair ? p.v[2] : p.v[0], b = pair ? p.v[3] : p.v[1];     // selects: never a run-time index (mpg_common.h)
+    const float r = __builtin_sqrtf(-2.f * __builtin_logf(u01(a)));
+    float s, c;
+    sincosf(6.283185307179586f * u01(b), &s, &c);
+    z_even = r * c;
+    z_odd = r * s;
+}
+
+// The refusals the Gaussian-head entry points (and their workspace queries) share, in the order include/mpg_hip.h lists them.
+// `entry` names the caller in every message; MPG_OK when the call may proceed.  (The width test is what net_cfg_ok, host_glue.h,
+// leaves once act_dim is 2 and there is no action range.)
+inline int gauss_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
+    MPG_REQUIRE(cfg && pointers, "%s: null pointer", entry);
+    MPG_REQUIRE(rows > 0, "%s: rows must be positive (got %d)", entry, rows);
+    MPG_REQUIRE(cfg->act_dim == 2 && cfg->env_kind == MPG_ENV_PATH_TRACKING,
+                "%s: Gaussian head without an action range only (act_dim 2 on PathTracking; got act_dim %d, env_kind %d)", entry,
+                cfg->act_dim, cfg->env_kind);
+    MPG_REQUIRE(!(cfg->action_range > 0.f), "%s: Gaussian head without an action range only (got action_range %g)", entry,
+                (double)cfg->action_range);
+    MPG_REQUIRE(cfg->obs_dim >= 6 && cfg->obs_dim <= 16, "%s: unsupported observation width %d", entry, cfg->obs_dim);
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
+    return MPG_OK;
+}
+
+}  // namespace gauss

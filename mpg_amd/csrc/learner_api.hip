@@ -1,8 +1,10 @@
 // C-ABI entry points built from the generic network kernels: policy actions, critic targets, critic loss +
 // gradient.  (The fused n-step rollout lives in rollout_kernels.hip, the optimizer in optim_kernels.hip.)
+#include "gauss_head.h"
 #include "host_glue.h"
 
 using namespace mlp;
+using namespace gauss;
 
 namespace {
 
@@ -171,6 +173,7 @@ int launch_row_sums(const char* name, const Row& row, int rows, float* parts, fl
 }
 
 // out[i] ~ N(0, 1): Philox4x32-10(key = seed, counter = (i / 4, ctr)), Box-Muller on two of the four words per pair of outputs
+// (gauss_head.h normal_pair restates one pair of it for the worker launch that draws its own)
 __global__ void k_normal_fill(int n, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, float* __restrict__ out) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;          // one Philox draw = four normals
     if (4 * q >= n) return;
@@ -202,33 +205,8 @@ __global__ void k_sum_action_grad(int rows, int od, int ad, const float* __restr
     ga[i] = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
 }
 
-// ---- Gaussian policy head (policy.py:179-204 with action_range None: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))), no
-// bijector) on the four logits of the policy pass, one thread per row ---------------------------------------------------------------
-constexpr float LOG_STD_MIN = -5.f, LOG_STD_MAX = 1.f, HALF_LOG_2PI = 0.91893853320467274f;
-// sigma = exp(log_std) as the CORRECTLY ROUNDED float32 exponential (the double-precision exp, rounded once): the float32 library exp is
-// within an ulp of it and its last bit differs between compiler versions, while a sample must be reproducible from logits_out by anyone
-// (two values per row: the double-precision pipe is not on any hot path here)
-__device__ __forceinline__ float sigma_of(float clipped_log_std) { return (float)exp((double)clipped_log_std); }
-// a * b + c with the product and the sum rounded separately, whatever the translation unit's contraction mode (the __fmul_rn / __fadd_rn
-// intrinsics are plain operators here and fuse)
-__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return p + c;
-}
-// act = mean + sigma * eps with the product and the sum rounded separately (the same bits as the two-op expression a caller forms
-// from logits_out); returns the row's log-density.  z, the standardised sample of the density, is eps ITSELF: TFP forms
-// (a - mean) / sigma, which in exact arithmetic is eps and in float32 is eps with two more roundings - against the float64 run of the
-// reference, where that expression returns eps to 1e-16, eps is the nearer of the two.
-__device__ __forceinline__ float gauss_row(int ad, const float* __restrict__ l, const float* __restrict__ e, float* __restrict__ a) {
-    float lp = 0.f;
-    for (int k = 0; k < ad; ++k) {
-        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), sigma = sigma_of(ls), z = e[k];
-        a[k] = mul_then_add(sigma, z, l[k]);
-        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
-    }
-    return lp;
-}
+// ---- Gaussian policy head (gauss_head.h: the clip bounds, sigma_of, gauss_row) on the four logits of the policy pass, one thread per
+// row ---------------------------------------------------------------------------------------------------------------------------
 // logits [rows][2 ad], eps [rows][ad] -> act [rows][ad], logp [rows]; the sum of logp over the rows, where one is wanted
 struct GaussRow {
     int ad;
@@ -336,21 +314,6 @@ SacTargetsWs sac_targets_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     w.a = ar.take((size_t)rows * cfg->act_dim);
     w.logp = ar.take(rows); w.q1 = ar.take(rows); w.q2 = ar.take(rows);
     return w;
-}
-
-// The refusals the three Gaussian-head entry points (and their workspace queries) share, in the order include/mpg_hip.h lists them.
-// `entry` names the caller in every message; MPG_OK when the call may proceed.
-int gauss_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
-    MPG_REQUIRE(cfg && pointers, "%s: null pointer", entry);
-    MPG_REQUIRE(rows > 0, "%s: rows must be positive (got %d)", entry, rows);
-    MPG_REQUIRE(cfg->act_dim == 2 && cfg->env_kind == MPG_ENV_PATH_TRACKING,
-                "%s: Gaussian head without an action range only (act_dim 2 on PathTracking; got act_dim %d, env_kind %d)", entry,
-                cfg->act_dim, cfg->env_kind);
-    MPG_REQUIRE(!(cfg->action_range > 0.f), "%s: Gaussian head without an action range only (got action_range %g)", entry,
-                (double)cfg->action_range);
-    MPG_REQUIRE(net_cfg_ok(cfg), "%s: unsupported observation width %d", entry, cfg->obs_dim);
-    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
-    return MPG_OK;
 }
 
 // all four logits of the policy (MLPNet's output activation on every column, no action range), optional stashes

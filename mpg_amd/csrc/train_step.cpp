@@ -19,7 +19,7 @@ Layout layout(const mpg_train_ctx_t* c) {
     Layout l;
     l.q_size = net_size(c->cfg.obs_dim + c->cfg.act_dim, 1);
     l.p_size = net_size(c->cfg.obs_dim, 2 * c->cfg.act_dim);
-    l.n_nets = (c->learner_version == 2 || c->learner_version == 4) ? 3 : 2;        // MPG-v2 / TD3: double Q
+    l.n_nets = (c->learner_version == 2 || c->learner_version == 4 || c->learner_version == 7) ? 3 : 2;        // MPG-v2 / TD3 / SAC: double Q
     int o = 0;
     for (int k = 0; k < l.n_nets; ++k) {
         l.sizes[k] = k == l.n_nets - 1 ? l.p_size : l.q_size;
@@ -76,7 +76,7 @@ inline bool exchanged(const mpg_train_ctx_t* c) { return c->world_size > 1 || c-
 inline bool is_mpg(const mpg_train_ctx_t* c) { return c->learner_version == 1 || c->learner_version == 2; }
 
 bool ctx_ok(const mpg_train_ctx_t* c) {
-    if (!c || c->learner_version < 1 || c->learner_version > 5) return false;
+    if (!c || c->learner_version < 1 || (c->learner_version > 5 && c->learner_version != 7)) return false;
     const bool common = c->num_agent > 0 && c->batch > 0 && c->world_size > 0 && c->sampling_interval > 0 && c->num_batch_reuse > 0 &&
                         c->ring_capacity > 0 && c->params && c->targets && c->grad && c->ws0 && c->ws1;
     if (!common) return false;
@@ -84,6 +84,7 @@ bool ctx_ok(const mpg_train_ctx_t* c) {
         return c->n > 0 && c->M > 0 && c->n_select > 0 && c->n_select <= 4 && (c->learner_version == 2 ? 2 : 1) + 2 * c->n_select <= 8;
     if (c->learner_version == 3) return c->n > 0 && c->num_batch_reuse == 1;
     if (c->learner_version == 5) return c->n > 0 && c->l_obs && c->l_rewards;       // no state block, no l_act / l_done*
+    if (c->learner_version == 7) return c->scratch != nullptr;                       // SAC: the draws' block
     // TD3: the scratch block, and the trees when the replay is prioritized
     return c->scratch && c->num_batch_reuse == 1 &&
            (!c->prioritized || (c->per_sum && c->per_min && c->per_stamp && c->per_capacity >= c->ring_capacity && c->per_max_priority && c->b_weights));
@@ -210,11 +211,62 @@ int ndpg_gradients(mpg_train_ctx_t* c, const Layout& l, bool fresh, mpg_stream_t
                                c->ws1_bytes, s);
 }
 
+// ---- SAC (learner_version 7): worker.py:68-79 with a stochastic policy + replay_buffer.add_batch ----
+// The draw, the policy pass, the Gaussian head, env.step -> ring slot (next + i) % capacity -> env.reset of the done agents: ONE launch
+// (mpg_worker_sample_step) at every width.  Against the three calls it replaces (mpg_normal_fill, mpg_policy_sample,
+// mpg_env_step_store_reset: four launches, bit-identical) it measured faster at 8 and at 4096 agents with obs_dim 6 and 9
+// (tools/bench_sac_native.py), which is the rule for taking it.
+int sac_sample_and_add(mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
+    const int n = c->num_agent;
+    MPG_REQUIRE(n <= c->ring_capacity, "mpg_sac_step_begin: ring smaller than one sample");
+    for (int it = 0; it < c->sample_iters; ++it) {
+        // (the log-densities have no consumer: worker.py:96 drops them)
+        TRY(mpg_worker_sample_step(&c->cfg, policy, n, c->env_state, c->w_obs, c->worker_seed, c->noise_ctr++, c->w_act, nullptr,
+                                   c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
+                                   c->env_seed, c->env_ctr++, c->w_done, s));
+        c->ring_next = (c->ring_next + n) % c->ring_capacity;
+        c->ring_size = std::min(c->ring_size + n, c->ring_capacity);
+    }
+    return MPG_OK;
+}
+
+// ---- SACLearner.compute_gradient, learners/sac.py:169-219 (networks [Q1 | Q2 | policy]); the minibatch and its soft target
+//      (:67-80) every num_batch_reuse-th call.  Draws: counters 2 (k + 1) for the target of call k, 2 k + 1 for the policy loss after
+//      the counter's increment, as SACLearner._draw ----
+int sac_gradients(mpg_train_ctx_t* c, const Layout& l, float alpha, bool fresh, mpg_stream_t s) {
+    const int od = c->cfg.obs_dim, ad = c->cfg.act_dim, B = c->batch;
+    const float *q1 = c->params, *q2 = c->params + l.off[1], *policy = c->params + l.off[2];
+    const float *q1t = c->targets, *q2t = c->targets + l.off[1];
+    const float inv_b = 1.f / ((float)B * (float)c->world_size);
+    float* stats = c->grad + l.n_grad;
+    float* eps = c->scratch;                          // [B][ad]
+    if (fresh) {
+        TRY(mpg_replay_sample_uniform(c->ring_size, B, c->replay_seed, c->replay_times, od, ad, c->ring_obs, c->ring_act, c->ring_rew,
+                                      c->ring_obs2, c->ring_done, c->idx, c->b_obs, c->b_act, c->b_rew, c->b_obs2, c->b_done, s));
+        TRY(mpg_normal_fill(B * ad, c->learner_seed, 2 * (c->learner_counter + 1), eps, s));
+        TRY(mpg_sac_targets(&c->cfg, policy, q1t, q2t, B, c->b_rew, c->b_obs2, eps, alpha, c->b_targets, c->ws0, c->ws0_bytes, s));
+    }
+    c->learner_counter++;
+    TRY(mpg_q_loss_grad(&c->cfg, q1, B, c->b_obs, c->b_act, c->b_targets, inv_b, stats, c->grad + l.off[0], nullptr, c->ws0, c->ws0_bytes, s));
+    TRY(mpg_q_loss_grad(&c->cfg, q2, B, c->b_obs, c->b_act, c->b_targets, inv_b, stats + 1, c->grad + l.off[1], nullptr, c->ws0,
+                        c->ws0_bytes, s));
+    TRY(mpg_normal_fill(B * ad, c->learner_seed, 2 * c->learner_counter + 1, eps, s));
+    return mpg_sac_policy_grad(&c->cfg, policy, q1, q2, B, c->b_obs, eps, alpha, inv_b, stats + 2, stats + 3, stats + 4, c->grad + l.off[2],
+                               c->ws1, c->ws1_bytes, s);
+}
+
 }  // namespace
 
 extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, size_t* ws1) {
     MPG_REQUIRE(c && ws0 && ws1, "mpg_step_workspace_bytes: null pointer");
-    MPG_REQUIRE(c->learner_version >= 1 && c->learner_version <= 5, "mpg_step_workspace_bytes: unknown learner_version %d", c->learner_version);
+    MPG_REQUIRE((c->learner_version >= 1 && c->learner_version <= 5) || c->learner_version == 7,
+                "mpg_step_workspace_bytes: unknown learner_version %d", c->learner_version);
+    if (c->learner_version == 7) {       // SAC: soft targets / critic loss; the Gaussian-head policy gradient
+        *ws0 = std::max(mpg_sac_targets_workspace_bytes(&c->cfg, c->batch), mpg_q_loss_grad_workspace_bytes(&c->cfg, c->batch));
+        *ws1 = mpg_sac_policy_grad_workspace_bytes(&c->cfg, c->batch);
+        MPG_REQUIRE(*ws0 && *ws1, "mpg_step_workspace_bytes: unsupported configuration");
+        return MPG_OK;
+    }
     *ws0 = std::max(mpg_q_targets_workspace_bytes(&c->cfg, c->batch), mpg_q_loss_grad_workspace_bytes(&c->cfg, c->batch));
     if (c->learner_version == 3) {
         *ws0 = std::max(*ws0, mpg_rollout_q_target_workspace_bytes(&c->cfg, c->batch));
@@ -230,6 +282,8 @@ extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, s
 }
 
 extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
+    MPG_REQUIRE(!c || c->learner_version != 7,
+                "mpg_step_begin: learner_version 7 (SAC) takes its temperature as an argument: call mpg_sac_step_begin");
     MPG_REQUIRE(ctx_ok(c), "mpg_step_begin: incomplete context");
     // the driver's first act is the worker's sample on the REAL env, which this model does not have: refused before anything is enqueued
     MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
@@ -316,6 +370,26 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
                                      draw_in_gradients ? &draw : nullptr, c->ws1, c->ws1_bytes, s);
     c->cfg.grad_opts = nullptr;
     return rc;
+}
+
+extern "C" int mpg_sac_step_begin(mpg_train_ctx_t* c, float alpha, int iteration, mpg_stream_t s) {
+    MPG_REQUIRE(c, "mpg_sac_step_begin: null context");
+    MPG_REQUIRE(c->learner_version == 7, "mpg_sac_step_begin: learner_version 7 (SAC) only (got %d)", c->learner_version);
+    MPG_REQUIRE(ctx_ok(c), "mpg_sac_step_begin: incomplete context");
+    MPG_REQUIRE(!c->prioritized, "mpg_sac_step_begin: a prioritized replay buffer is not served (prioritized = %d)", c->prioritized);
+    MPG_REQUIRE(c->explore_sigma == 0.f, "mpg_sac_step_begin: explore_sigma on top of the stochastic policy is not served (got %g)",
+                (double)c->explore_sigma);
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "mpg_sac_step_begin: alpha must be finite and not negative (got %g)",
+                (double)alpha);
+    MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
+                "mpg_sac_step_begin: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
+                "samples it) does not serve this model");
+    const Layout l = layout(c);
+    if (iteration % c->sampling_interval == 0) TRY(sac_sample_and_add(c, c->params + l.off[2], s));
+    MPG_REQUIRE(c->ring_size > 0, "mpg_sac_step_begin: empty replay ring");
+    c->replay_times++;
+    const bool fresh = c->learner_counter % c->num_batch_reuse == 0;     // the batch is drawn on every num_batch_reuse-th call only
+    return sac_gradients(c, l, alpha, fresh, s);
 }
 
 extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {

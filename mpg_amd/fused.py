@@ -48,11 +48,12 @@ class TrainCtx(ctypes.Structure):
 class FusedMPGStep(object):
     """step(iteration) == SingleProcessOffPolicyOptimizer.step for (OffPolicyWorker, replay buffer, learner) sharing one
     PolicyWithQs: MPGLearner + ReplayBuffer (learner_version 1 / 2), NADPLearner + ReplayBuffer (3), TD3Learner + ReplayBuffer
-    or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included), NDPGLearner + ReplayBuffer (5)."""
+    or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included), NDPGLearner + ReplayBuffer (5),
+    SACLearner + ReplayBuffer without explore_sigma (7: mpg_sac_step_begin, which takes the learner's fixed alpha)."""
 
     def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
         from .buffer import PrioritizedReplayBuffer
-        from .learners import MPGLearner, NADPLearner, NDPGLearner, TD3Learner
+        from .learners import MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
         per = isinstance(rb, PrioritizedReplayBuffer)
         assert per == (learner.args.buffer_type != 'normal')
         assert learner.policy_with_value is worker.policy_with_value
@@ -74,6 +75,9 @@ class FusedMPGStep(object):
         elif type(learner) is NDPGLearner:
             assert not per
             c.learner_version, c.n, c.M, c.n_select = 5, learner.sample_num_in_learner, 1, 1
+        elif type(learner) is SACLearner:
+            assert not per and worker.explore_sigma is None
+            c.learner_version, c.n, c.M, c.n_select = 7, 1, 1, 1
         else:
             assert type(learner) is TD3Learner and learner.num_batch_reuse == 1
             c.learner_version, c.n, c.M, c.n_select = 4, 1, 1, 1
@@ -114,6 +118,9 @@ class FusedMPGStep(object):
         c.params, c.targets, c.adam_m, c.adam_v = L.ptr(pw.params), L.ptr(pw.targets), L.ptr(pw.m), L.ptr(pw.v)
         c.grad, c.norms, c.nonfinite = L.ptr(learner.flat), L.ptr(learner.norms), L.ptr(pw.nonfinite)
         c.clip_scratch = L.ptr(learner.clip_scratch)
+        if c.learner_version == 7:          # the learner's draws (the size include/mpg_hip.h documents for this version)
+            self.scratch = torch.empty(max(B * ad, n * (ad + 1)) + 64, **f)
+            c.scratch = L.ptr(self.scratch)
         if c.learner_version == 4:
             self.scratch = torch.empty(max(B * (ad + 3), 2 * n) + 64, **f)
             c.scratch = L.ptr(self.scratch)
@@ -199,7 +206,11 @@ class FusedMPGStep(object):
         try:
             if slot is not None:
                 c.grad = slot.data_ptr()
-            L.check(self._lib.mpg_step_begin(self._ref, ctypes.c_int(iteration), s), 'mpg_step_begin')
+            if c.learner_version == 7:       # the temperature travels as an argument (mpg_train_ctx_t has no field for it)
+                L.check(self._lib.mpg_sac_step_begin(self._ref, ctypes.c_float(self.learner.alpha), ctypes.c_int(iteration), s),
+                        'mpg_sac_step_begin')
+            else:
+                L.check(self._lib.mpg_step_begin(self._ref, ctypes.c_int(iteration), s), 'mpg_step_begin')
             if c.grads_exchanged:
                 # the ONE exchange step, timed under the caller's kernel timer (slot 8, HIP events on the launch stream: bench.py's
                 # `exchange_ms`) - a null or stopped timer makes both calls no-ops

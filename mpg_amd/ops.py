@@ -426,6 +426,24 @@ def policy_sample(cfg, policy_params, obs, eps, want_logits=False):
     return (act, logp, logits) if want_logits else (act, logp)
 
 
+def worker_sample_step(cfg, policy_params, state, obs_io, sample_seed, sample_ctr, ring, capacity, next_idx, env_seed, env_ctr,
+                       want_logp=True, done_out=None):
+    """mpg_worker_sample_step: OffPolicyWorker.sample's inner body for a stochastic policy in ONE launch - the draw
+    (mpg_normal_fill(2 n, sample_seed, sample_ctr)), mpg_policy_sample and mpg_env_step_store_reset.  obs_io [n, obs_dim] holds the
+    current observations and receives the next ones; ring = (obs, act, rew, obs2, done) arrays of `capacity` rows, written at
+    (next_idx + i) % capacity.  Returns (act [n, 2], logp [n] or None)."""
+    n, dev = obs_io.shape[0], obs_io.device
+    act = torch.empty(n, cfg.act_dim, dtype=torch.float32, device=dev)
+    logp = torch.empty(n, dtype=torch.float32, device=dev) if want_logp else None
+    r_obs, r_act, r_rew, r_obs2, r_done = ring
+    assert r_done.dtype == torch.uint8 and (done_out is None or done_out.dtype == torch.uint8)
+    L.call('mpg_worker_sample_step', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.ptr(_f32(state)), L.ptr(_f32(obs_io)),
+           L.c_u64(sample_seed), L.c_u64(sample_ctr), L.ptr(act), L.ptr(logp), L.c_int(int(capacity)), L.c_int(int(next_idx)),
+           L.ptr(_f32(r_obs)), L.ptr(_f32(r_act)), L.ptr(_f32(r_rew)), L.ptr(_f32(r_obs2)), L.ptr(r_done), L.c_u64(env_seed),
+           L.c_u64(env_ctr), L.ptr(done_out), L.stream())
+    return act, logp
+
+
 def sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
     """mpg_sac_targets: y = (rew + shift) * scale + gamma * (min(Q1t, Q2t)(s', a') - alpha * logp'), (a', logp') sampled from
     `policy` - the ONLINE one in the reference, sac.py:71 - with eps"""

@@ -18,7 +18,13 @@ def quiesce_gc():
 
 class SingleProcessOffPolicyOptimizer(object):
     def __init__(self, worker, learner, replay_buffer, evaluator, args, sampling_interval=10, fused=True,
-                 always_exchange=False):
+                 always_exchange=False, native_sac=False):
+        if native_sac:
+            # SAC's native step (mpg_sac_step_begin) is taken on request only; a request it cannot serve is an error - raised before
+            # anything is sampled - never a silent fall-back to the method path
+            reason = self._native_sac_refusal(worker, learner, replay_buffer, args)
+            if reason:
+                raise ValueError('native_sac=True: ' + reason)
         self.args = args
         self.worker, self.learner, self.replay_buffer, self.evaluator = worker, learner, replay_buffer, evaluator
         self.num_sampled_steps = 0
@@ -34,7 +40,10 @@ class SingleProcessOffPolicyOptimizer(object):
         # native step driver (mpg_step_begin/_end) when the stock MPG components are plugged in; otherwise the
         # method-by-method path below, which computes the same thing
         self._fused = None
-        if fused:
+        if native_sac:
+            from .fused import FusedMPGStep
+            self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
+        elif fused:
             from .buffer import PrioritizedReplayBuffer
             from .learners import MPGLearner, NADPLearner, NDPGLearner, TD3Learner
             per = isinstance(replay_buffer, PrioritizedReplayBuffer)
@@ -46,6 +55,19 @@ class SingleProcessOffPolicyOptimizer(object):
             if ok:
                 from .fused import FusedMPGStep
                 self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
+
+    @staticmethod
+    def _native_sac_refusal(worker, learner, replay_buffer, args):
+        """why mpg_sac_step_begin does not serve this stack, or None"""
+        from .buffer import PrioritizedReplayBuffer
+        from .learners import SACLearner
+        if type(learner) is not SACLearner:
+            return 'the learner is %s, not SACLearner (every other learner takes the native step by default)' % type(learner).__name__
+        if isinstance(replay_buffer, PrioritizedReplayBuffer) or getattr(args, 'buffer_type', 'normal') != 'normal':
+            return 'a prioritized replay buffer is not served by the native SAC step (uniform ReplayBuffer only)'
+        if worker.explore_sigma is not None:
+            return 'explore_sigma (%r) on top of the stochastic policy is not served by the native SAC step' % (worker.explore_sigma,)
+        return None
 
     def set_profiler(self, prof):
         """attach an ops.Profiler (or None) to every cfg this optimizer launches with"""
