@@ -324,6 +324,23 @@ int mpg_rollout_pg(const mpg_cfg_t* cfg, const float* policy_params, const float
                    uint64_t noise_seed, uint64_t noise_ctr, float inv_b_global, int all_steps_param_grad, float* ret_sum, float* ret_sqsum, float* grad,
                    void* ws, size_t ws_bytes, mpg_stream_t stream);
 
+/* AMPCLearner.model_rollout_for_policy_update + policy_forward_and_backward  - learners/ampc.py:73-96: the policy-only learner.
+ * n policy evaluations and model steps from obs0 (M copies tiled inside, like mpg_rollout_pg), NO critic and no policy
+ * evaluation at the last observation; every step goes through pi_theta.  The rewards are summed WITHOUT a discount whatever
+ * cfg->gamma holds (ampc.py:83; the parser's gamma = 1 only reaches the Preprocessor).
+ *   eps    [n][M*rows] standard-normal model noise, or NULL: Philox4x32-10 keyed by (noise_seed, noise_ctr, step, trajectory)
+ * Outputs
+ *   ret_sum [1], ret_sqsum [1]: sum over this GPU's rows of the M-mean reward sum and of its square
+ *   grad    flat policy gradient of  -inv_b_global / M * sum(rewards_sum), reduced over this GPU's rows, NOT clipped.
+ * Needs rows*M % 16 == 0 and 0 < n < 32; all three models of mpg_rollout_pg.  Composed from that entry point's launches: the
+ * forward sweep with the single slice n, k_ampc_returns (the sums, and zeros where the reverse sweep reads the critic's input
+ * gradient), the reverse sweep, the weight-gradient launch over n + 1 steps (the last one contributes exact zeros).
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+size_t mpg_ampc_pg_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n);
+int mpg_ampc_pg(const mpg_cfg_t* cfg, const float* policy_params, int rows, int M, int n, const float* obs0, const float* eps,
+                uint64_t noise_seed, uint64_t noise_ctr, float inv_b_global, float* ret_sum, float* ret_sqsum, float* grad,
+                void* ws, size_t ws_bytes, mpg_stream_t stream);
+
 /* MPGLearner.compute_gradient without the clip, as one entry point  - learners/mpg_learner.py:401-431:
  * target (when y_in == NULL: clipped double-Q target from target_params, :126-134), critic losses and gradients of
  * the n_q (1: MPG-v1, 2: MPG-v2) critics (:326-354), n-step model rollout + mixed policy gradient (:226-286,356-365).

@@ -1,5 +1,5 @@
 """Default hyper-parameters = the reference's argparse defaults (train_scripts/train_script.py:177-306 MPG,
-:431-549 NDPG, :551-670 TD3, :672-792 SAC; train_scripts/train_script4mujoco.py:296-411 NADP on InvertedPendulumConti-v0), under the same names,
+:57-175 AMPC, :431-549 NDPG, :551-670 TD3, :672-792 SAC; train_scripts/train_script4mujoco.py:296-411 NADP on InvertedPendulumConti-v0), under the same names,
 so `Namespace` objects are interchangeable with the reference's `args`."""
 import argparse
 
@@ -15,7 +15,7 @@ def default_args(alg='MPG-v2', env_id=None, **overrides):
         num_rollout_list_for_q_estimation=[] if alg.startswith('MPG') else [25],
         eta=0.1, rule_based_bias_total_ite=9000, gamma=0.98, gradient_clip_norm=3.,
         num_batch_reuse=10 if alg in ('MPG-v1', 'NDPG') else 1,
-        batch_size=512, explore_sigma=None if alg in ('NADP', 'NDPG', 'SAC') else 0.1,
+        batch_size=512, explore_sigma=None if alg in ('NADP', 'NDPG', 'SAC', 'AMPC') else 0.1,
         max_buffer_size=500000, replay_starts=3000, replay_batch_size=256, replay_alpha=0.6, replay_beta=0.4,
         obs_dim=4 if pend else 6, act_dim=1 if pend else 2,
         value_model_cls='MLP', value_num_hidden_layers=2, value_num_hidden_units=256, value_hidden_activation='elu',
@@ -34,6 +34,9 @@ def default_args(alg='MPG-v2', env_id=None, **overrides):
         # the reference ships no parser for this env: the single pendulum's NADP settings with this env's dimensions, unit scales and
         # a = tanh(mean) (ops.make_cfg: this project's choice)
         d.update(num_agent=1, obs_dim=11, act_dim=1, policy_out_activation='linear', action_range=1., obs_scale=[1.] * 11, rew_scale=1.)
+    if alg == 'AMPC':
+        # built_AMPC_parser: the policy alone - no critic, no target (their settings are None); gamma = 1 reaches the Preprocessor only
+        d.update(gamma=1., policy_only=True, double_Q=False, target=False, tau=None, delay_update=None)
     d.update(overrides)
     if not pend and d['num_future_data'] and 'obs_dim' not in overrides:       # train_script.py:146-147, 794-811
         d['obs_dim'] = 6 + d['num_future_data']

@@ -91,6 +91,39 @@ __global__ void __launch_bounds__(1024) k_returns(int rows, int M, int n_sel, co
     }
 }
 
+// AMPC (learners/ampc.py:73-87): no critic.  ret[b] = mean over the M copies of the undiscounted reward sum G_n; one workgroup sums
+// them and their squares over this GPU's rows in a fixed order (block 0), and every workgroup zero-fills gxq - the block the
+// reverse sweep reads as dL/d(critic input) at the single slice n: with zeros there the sweep starts from a zero adjoint.
+__global__ void __launch_bounds__(1024) k_ampc_returns(int rows, int M, long n_gxq, const float* __restrict__ GK,
+                                                       float* __restrict__ gxq, float* __restrict__ ret_sum,
+                                                       float* __restrict__ ret_sqsum) {
+    for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < n_gxq; i += (long)gridDim.x * 1024) gxq[i] = 0.f;
+    if (blockIdx.x != 0) return;
+    __shared__ float red[2][1024];
+    float s = 0.f, s2 = 0.f;
+    for (int b = threadIdx.x; b < rows; b += 1024) {
+        float m = 0.f;
+        for (int mm = 0; mm < M; ++mm) m += GK[(long)mm * rows + b];
+        m /= (float)M;
+        s += m;
+        s2 += m * m;
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ret_sum[0] = red[0][0];
+        ret_sqsum[0] = red[1][0];
+    }
+}
+
 // y = G_n + gamma^n * Q   (nadp.py:117-126)
 __global__ void k_gq(int n, const float* __restrict__ G, const float* __restrict__ Q, float gpow, float* __restrict__ y) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -165,6 +198,28 @@ PgWs pg_ws(Arena& ar, const mpg_cfg_t* cfg, int rows, int M, int n, int n_sel, i
     w.slabs = ar.take(wgrad_workspace_floats((int)(T * stash_floats(R) / H), od, 2 * ad));
     w.thin_part = thin_in_sweep(cfg, M, stash_all) ? ar.take((size_t)256 * thin_floats(od, 2 * ad)) : nullptr;
     w.XW = wide_inputs_needed(cfg, M, stash_all) ? ar.take((size_t)T * R * od) : nullptr;
+    return w;
+}
+
+struct AmpcWs {            // mpg_ampc_pg: the rollout's part of PgWs at one slice and n + 1 stashed steps; nothing of the critic's
+    float *H1, *H2, *SA, *XQ, *GK, *GXQ, *DZ1, *DZ2, *DZ3, *slabs;
+    float *thin_part, *XW;   // null when absent
+};
+AmpcWs ampc_ws(Arena& ar, const mpg_cfg_t* cfg, int rows, int M, int n) {
+    const long R = (long)rows * M;
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    const int T = n + 1;
+    AmpcWs w;
+    w.H1 = ar.take((size_t)T * stash_floats(R)); w.H2 = ar.take((size_t)T * stash_floats(R));
+    w.SA = ar.take((size_t)T * R * SAW);
+    w.XQ = ar.take((size_t)R * qin);             // (the forward sweep writes the slice's critic input; nothing reads it)
+    w.GK = ar.take((size_t)R);
+    w.GXQ = ar.take((size_t)R * qin);
+    w.DZ1 = ar.take((size_t)T * stash_floats(R)); w.DZ2 = ar.take((size_t)T * stash_floats(R));
+    w.DZ3 = ar.take((size_t)T * R * ad);
+    w.slabs = ar.take(wgrad_workspace_floats((int)(T * stash_floats(R) / H), od, 2 * ad));
+    w.thin_part = thin_in_sweep(cfg, M, 1) ? ar.take((size_t)256 * thin_floats(od, 2 * ad)) : nullptr;
+    w.XW = wide_inputs_needed(cfg, M, 1) ? ar.take((size_t)T * R * od) : nullptr;
     return w;
 }
 
@@ -285,6 +340,34 @@ int run_rollout_bwd(const mpg_cfg_t* cfg, const float* policy_params, int rows, 
     return launch_rollout_bwd(ba, cfg->env_kind, ngroups, n, s, cfg->prof);
 }
 
+// the policy's weight gradient from the stashes of T steps (1: step 0 only; n + 1: every step), shared by mpg_rollout_pg and mpg_ampc_pg
+int run_rollout_wgrad(const mpg_cfg_t* cfg, int rows, int M, int T, const float* obs0, const float* H1, const float* H2, const float* SA,
+                      float* XW, const float* DZ1, const float* DZ2, const float* DZ3, float* slabs, float* thin_part, float inv_b_global,
+                      float* grad, hipStream_t s) {
+    const long R = (long)rows * M;
+    const int od = cfg->obs_dim, ad = cfg->act_dim;
+    // the first layer's input of every stashed step: the (obs | action) records hold the six base entries; with look-ahead entries
+    // (obs_dim > 6) it is the caller's batch itself (M == 1, step 0 only) or written out by k_wide_inputs
+    XSpec xs = policy_x(cfg, SA);
+    xs.ld0 = SAW;
+    if (od > 6) xs = policy_x(cfg, obs0);
+    if (XW && cfg->env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM) {     // the model's features, not copies of an entry
+        launch_feature_inputs_double_pendulum(T, R, rows, obs0, SA, XW, s);
+        MPG_CHECK_LAUNCH("k_feature_inputs");
+        xs = policy_x(cfg, XW);
+    } else if (XW) {
+        const long nx = (long)T * R * od;
+        hipLaunchKernelGGL(k_wide_inputs, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, T, R, rows, od, PathTracking::OBS,
+                           PathTracking::FUT_SRC, obs0, SA, XW);
+        MPG_CHECK_LAUNCH("k_wide_inputs");
+        xs = policy_x(cfg, XW);
+    }
+    // (with thin_part: dW2 from the chunk slabs, the thin parts from the sweep's per-workgroup partials, summed in one launch)
+    const int n_part = (int)std::min<long>(256, (R + GROUP - 1) / GROUP);
+    return launch_wgrad(cfg, od, 2 * ad, ad, (int)(T * R), xs, H1, H2, DZ1, DZ2, DZ3, inv_b_global / (float)M, grad, slabs, s,
+                        thin_part != nullptr, thin_part, thin_part ? n_part : 0);
+}
+
 }  // namespace
 
 extern "C" size_t mpg_rollout_pg_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select,
@@ -336,27 +419,54 @@ extern "C" int mpg_rollout_pg(const mpg_cfg_t* cfg, const float* policy_params, 
     if (rc) return rc;
 
     // ---- policy weight gradient from the stashes (step 0 only, or every step for NADP) ----
-    const int T = all_steps_param_grad ? n + 1 : 1;
-    // the first layer's input of every stashed step: the (obs | action) records hold the six base entries; with look-ahead entries
-    // (obs_dim > 6) it is the caller's batch itself (M == 1, step 0 only) or written out by k_wide_inputs
-    XSpec xs = policy_x(cfg, a.SA);
-    xs.ld0 = SAW;
-    if (od > 6) xs = policy_x(cfg, obs0);
-    if (a.XW && cfg->env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM) {     // the model's features, not copies of an entry
-        launch_feature_inputs_double_pendulum(T, R, rows, obs0, a.SA, a.XW, s);
-        MPG_CHECK_LAUNCH("k_feature_inputs");
-        xs = policy_x(cfg, a.XW);
-    } else if (a.XW) {
-        const long nx = (long)T * R * od;
-        hipLaunchKernelGGL(k_wide_inputs, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, T, R, rows, od, PathTracking::OBS,
-                           PathTracking::FUT_SRC, obs0, a.SA, a.XW);
-        MPG_CHECK_LAUNCH("k_wide_inputs");
-        xs = policy_x(cfg, a.XW);
-    }
-    // (with thin_part: dW2 from the chunk slabs, the thin parts from the sweep's per-workgroup partials, summed in one launch)
-    const int n_part = (int)std::min<long>(256, (R + GROUP - 1) / GROUP);
-    return launch_wgrad(cfg, od, 2 * ad, ad, (int)(T * R), xs, a.H1, a.H2, a.DZ1, a.DZ2, a.DZ3, inv_b_global / (float)M, grad, a.slabs, s,
-                        thin_part != nullptr, thin_part, thin_part ? n_part : 0);
+    return run_rollout_wgrad(cfg, rows, M, all_steps_param_grad ? n + 1 : 1, obs0, a.H1, a.H2, a.SA, a.XW, a.DZ1, a.DZ2, a.DZ3, a.slabs,
+                             thin_part, inv_b_global, grad, s);
+}
+
+extern "C" size_t mpg_ampc_pg_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n) {
+    if (!rollout_cfg_ok(cfg) || rows <= 0 || M <= 0 || n <= 0 || n >= MAXN || ((long)rows * M) % GROUP != 0) return 0;
+    return measured(ampc_ws, cfg, rows, M, n);
+}
+
+extern "C" int mpg_ampc_pg(const mpg_cfg_t* cfg, const float* policy_params, int rows, int M, int n, const float* obs0, const float* eps,
+                           uint64_t noise_seed, uint64_t noise_ctr, float inv_b_global, float* ret_sum, float* ret_sqsum, float* grad,
+                           void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    MPG_REQUIRE(rollout_cfg_ok(cfg), "mpg_ampc_pg: unsupported cfg (obs/act dims, env_kind)");
+    MPG_REQUIRE(policy_params && obs0 && ret_sum && ret_sqsum && grad && ws, "mpg_ampc_pg: null pointer");
+    MPG_REQUIRE(rows > 0 && M > 0, "mpg_ampc_pg: no rows (rows %d, M %d)", rows, M);
+    MPG_REQUIRE(n > 0 && n < MAXN, "mpg_ampc_pg: horizon out of range: 0 < n < %d (got %d)", MAXN, n);
+    const long R = (long)rows * M;
+    MPG_REQUIRE(R % GROUP == 0, "mpg_ampc_pg: every step is differentiated through the policy: needs rows*M %% 16 == 0 (got %ld)", R);
+    Arena ar(ws, ws_bytes);
+    const AmpcWs a = ampc_ws(ar, cfg, rows, M, n);
+    if (!ar.fits()) return workspace_too_small("mpg_ampc_pg", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad;
+    // (the THIN reverse sweep is a packed-image kernel: without the caller's weight cache the thin parts stay in the wgrad launch)
+    float* thin_part = a.thin_part;
+    if (thin_part && !weight_cache_lookup(cfg, make_net(policy_params, od, 2 * ad).W2, 1)) thin_part = nullptr;
+
+    // ---- forward sweep, the single slice n, discount 1 (ampc.py:79-83) ----
+    mpg_cfg_t undiscounted = *cfg;
+    undiscounted.gamma = 1.f;
+    int rc = run_rollout_fwd(&undiscounted, policy_params, rows, M, n, &n, 1, obs0, nullptr, eps, noise_seed, noise_ctr, a.H1, a.H2, a.SA, a.XQ,
+                             a.GK, s, cfg->prof);
+    if (rc) return rc;
+
+    // ---- the sums of -policy_loss (:85); zeros for the critic's input gradient ----
+    const long n_gxq = R * qin;
+    hipLaunchKernelGGL(k_ampc_returns, dim3((unsigned)std::min<long>(64, (n_gxq + 1023) / 1024)), dim3(1024), 0, s, rows, M, n_gxq, a.GK,
+                       a.GXQ, ret_sum, ret_sqsum);
+    MPG_CHECK_LAUNCH("k_ampc_returns");
+
+    // ---- reverse sweep: dL/d(raw reward_t) = -inv_b_global / M * rew_scale at every step ----
+    float rho[MAXN];
+    for (int t = 0; t < MAXN; ++t) rho[t] = t < n ? -(inv_b_global / (float)M) * cfg->rew_scale : 0.f;
+    rc = run_rollout_bwd(cfg, policy_params, rows, M, n, &n, 1, rho, a.H1, a.H2, a.SA, a.GXQ, 1, a.DZ1, a.DZ2, a.DZ3, s, thin_part);
+    if (rc) return rc;
+
+    // ---- policy weight gradient over the n + 1 stashed steps (the adjoint of step n is zero: it adds exact zeros) ----
+    return run_rollout_wgrad(cfg, rows, M, n + 1, obs0, a.H1, a.H2, a.SA, a.XW, a.DZ1, a.DZ2, a.DZ3, a.slabs, thin_part, inv_b_global, grad, s);
 }
 
 extern "C" size_t mpg_rollout_q_target_workspace_bytes(const mpg_cfg_t* cfg, int rows) {

@@ -1,5 +1,6 @@
 """Learners - device mirrors of learners/mpg_learner.py (MPGLearner), learners/nadp.py (NADPLearner),
-learners/td3.py (TD3Learner), learners/ndpg.py (NDPGLearner) and learners/sac.py (SACLearner, fixed temperature): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
+learners/td3.py (TD3Learner), learners/ndpg.py (NDPGLearner), learners/sac.py (SACLearner, fixed temperature) and learners/ampc.py
+(AMPCLearner, the policy alone): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
 (`set_weights`, `compute_gradient(batch5, rb, indexes, iteration)`, `get_stats`, `get_info_for_buffer`), same
 output order `q1 (+q2) + policy`.
 
@@ -292,6 +293,38 @@ class NADPLearner(_LearnerBase):
         stats, B = self.flat[self.n_grad:], self.batch_size * D.world_size()
         return lambda: dict(q_loss=stats[0], policy_loss=-stats[3] / B, value_mean=stats[2] / B,
                             q_gradient_norm=self.norms[0], policy_gradient_norm=self.norms[1])
+
+
+class AMPCLearner(_LearnerBase):
+    """Approximate MPC (learners/ampc.py:22-122): the policy alone.  The loss is minus the mean UNDISCOUNTED reward sum of an
+    n-step model rollout from the batch's observations, M copies each, every step through pi_theta (:73-87); no critic, no target,
+    a fresh batch on every call (:105-107).  Networks [policy] (policy_only=True)."""
+
+    def __init__(self, policy_cls, args, device='cuda'):
+        if not getattr(args, 'policy_only', False):
+            raise ValueError('AMPCLearner needs policy_only=True (built_AMPC_parser, train_script.py:57-175): it trains the policy alone '
+                             'and its gradient list has no critic entries')
+        super().__init__(policy_cls, args, device)
+        assert self.policy_with_value.names == ['policy'], 'AMPC trains [policy]'
+        self.M = int(args.M)
+        self.n = int(args.num_rollout_list_for_policy_update[0])
+        self.num_batch_reuse = 1                                # :105-107: get_batch_data on every call
+
+    def get_batch_data(self, batch_data, rb, indexes):
+        self._get_batch(batch_data)
+
+    def compute_gradient(self, batch_data, rb, indexes, iteration, eps=None):
+        """ampc.py:105-122.  eps: optional [n, M*B] standard-normal model noise (parity tests); by default it is drawn inside the
+        rollout kernel, keyed by (learner seed, call counter)."""
+        pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes)
+        ops.ampc_pg(self.cfg, pw.net('policy'), b['batch_obs'], eps, M=self.M, inv_b_global=inv_b, grad_out=self.grad('policy'),
+                    stats_out=stats[0:2], n=self.n, noise_seed=self.seed, noise_ctr=2 * self.counter + 1)
+        return self._finish(iteration)
+
+    def _native_lazy_stats(self, iteration):
+        """evaluated only when get_stats() is called (pg_time: the reference's wall-clock timer; nothing here synchronises to take one)"""
+        stats, B = self.flat[self.n_grad:], self.batch_size * D.world_size()
+        return lambda: dict(pg_time=None, policy_loss=-stats[0] / B, policy_gradient_norm=self.norms[0])
 
 
 class TD3Learner(_LearnerBase):

@@ -325,6 +325,23 @@ def rollout_pg(cfg, policy_params, q1_params, obs0, eps, select, w, M=1, inv_b_g
     return stats[:ns], stats[ns:], grad
 
 
+def ampc_pg(cfg, policy_params, obs0, eps, M=1, inv_b_global=None, grad_out=None, stats_out=None, n=None, noise_seed=0, noise_ctr=0):
+    """mpg_ampc_pg: n-step model rollout without a critic, every step through the policy, no discount.  Returns (ret_sum [1],
+    ret_sqsum [1], grad).  eps=None draws the model noise inside the kernel (Philox(noise_seed, noise_ctr)); then pass n."""
+    rows, dev = obs0.shape[0], obs0.device
+    if eps is not None:
+        n = eps.shape[0]
+        assert eps.shape[1] == rows * M
+    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
+    stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.float32, device=dev)
+    ws = _ws(dev, 1, 'mpg_ampc_pg_workspace_bytes', cfg, rows, M, n)
+    L.call('mpg_ampc_pg', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(M), L.c_int(n), L.ptr(_f32(obs0)),
+           L.ptr(_f32(eps) if eps is not None else None), L.c_u64(noise_seed), L.c_u64(noise_ctr),
+           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), L.ptr(stats[0:1]), L.ptr(stats[1:2]), L.ptr(grad), *ws,
+           L.stream())
+    return stats[0:1], stats[1:2], grad
+
+
 CLIP_PARTS = 272          # MPG_CLIP_PARTS (include/mpg_hip.h)
 
 

@@ -64,7 +64,12 @@ class PolicyWithQs(object):
                  gamma=0.98, value_num_hidden_units=256, policy_num_hidden_units=256, policy_only=False,
                  device='cuda', seed=0, init_seed=0, alpha=None, **kwargs):
         assert value_num_hidden_units == 256 and policy_num_hidden_units == 256, 'kernels are built for 2x256 nets'
-        assert not policy_only and target, 'hot-path scope: actor-critic with targets'
+        self.policy_only = bool(policy_only)
+        # policy_only (AMPC, policy.py:72-75,125-127): the policy is the one model, no target; double_Q / target / tau / delay_update /
+        # alpha are None in built_AMPC_parser and are not looked at
+        assert self.policy_only or target, 'hot-path scope: actor-critic with targets, or policy_only'
+        if self.policy_only:
+            double_Q, tau, delay_update = False, 0., 1
         self.deterministic_policy = bool(deterministic_policy)
         self.alpha = None
         if not self.deterministic_policy:
@@ -87,7 +92,7 @@ class PolicyWithQs(object):
         self.cfg = ops.make_cfg(env_id, obs_scale=obs_scale, rew_scale=rew_scale, rew_shift=rew_shift, gamma=gamma,
                                 policy_out_activation=policy_out_activation, action_range=action_range, obs_dim=obs_dim)
         self.obs_dim, self.act_dim = obs_dim, act_dim
-        self.names = ['Q1', 'Q2', 'policy'] if self.double_Q else ['Q1', 'policy']      # policy.py:72-86
+        self.names = ['policy'] if self.policy_only else (['Q1', 'Q2', 'policy'] if self.double_Q else ['Q1', 'policy'])      # policy.py:72-86
         self.dims = {'Q1': (obs_dim + act_dim, 1), 'Q2': (obs_dim + act_dim, 1), 'policy': (obs_dim, 2 * act_dim)}
         self.sizes = [ops.net_size(*self.dims[n]) for n in self.names]
         self.offsets = np.cumsum([0] + self.sizes)
@@ -96,6 +101,8 @@ class PolicyWithQs(object):
         gen = torch.Generator().manual_seed(init_seed)
         flat = torch.cat([init_mlp_flat(gen, *self.dims[n]) for n in self.names])
         self.params = flat.to(self.device)
+        # (policy_only: there is no target model; the copy is never read or updated - it keeps the flat state, the weight cache pair and
+        # the checkpoint format those of every other stack)
         self.targets = self.params.clone()                                             # policy.py:60,68
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
@@ -110,6 +117,9 @@ class PolicyWithQs(object):
 
     # ---- weight cache (packed register images of the hidden kernels; caller-owned, see include/mpg_hip.h) ----
     def _bind_weight_cache(self):
+        self.wc_params = self.wc_targets = None
+        if self.device.type != 'cuda':       # a stack on the host holds weights and optimizer state only: every kernel needs the device
+            return
         dims = [self.dims[n] for n in self.names]
         self.wc_params = ops.WeightCache(self.params, dims, status=self.status)
         self.wc_targets = ops.WeightCache(self.targets, dims, status=self.status)
@@ -139,8 +149,9 @@ class PolicyWithQs(object):
 
     def refresh_weight_cache(self):
         """call after writing params/targets by anything other than apply_gradients"""
-        self.wc_params.pack()
-        self.wc_targets.pack()
+        if self.wc_params is not None:
+            self.wc_params.pack()
+            self.wc_targets.pack()
 
     def sync_from_rank0(self):
         """Data-parallel start-up: every replica takes rank 0's parameters / targets / optimizer state."""
@@ -168,11 +179,12 @@ class PolicyWithQs(object):
         """[models..., target_models...] each a list of 6 arrays (policy.py:112-114).  COPIES, like Keras' get_weights():
         writing into them does not touch the live parameters (whose packed images would otherwise go stale)."""
         return [self._as_list(self.net(n).clone(), n) for n in self.names] + \
-               [self._as_list(self.net(n, True).clone(), n) for n in self.names]
+               [self._as_list(self.net(n, True).clone(), n) for n in self.names if not self.policy_only]
 
     def set_weights(self, weights):
         """policy.py:116-121"""
         k = len(self.names)
+        assert not self.policy_only or len(weights) == 1, 'a policy-only stack has one model and no target (policy.py:72-75)'
         for i, w in enumerate(weights):
             name = self.names[i % k]
             dst = self.net(name, target=i >= k)
@@ -241,11 +253,11 @@ class PolicyWithQs(object):
         delayed = int(iteration) % self.delay_update == 0
         lr_t, do_adam, do_polyak = [], [], []
         for n in self.names:
-            upd = (n != 'policy') or delayed
+            upd = (n != 'policy') or delayed or self.policy_only           # policy.py:125-127: the policy's Adam on every call
             t = self.opt_steps[n] + 1
             lr_t.append(adam_step_size(self.schedules[n], self.opt_steps[n]))
             do_adam.append(int(upd))
-            do_polyak.append(int(delayed))
+            do_polyak.append(int(delayed and not self.policy_only))
             if upd:
                 self.opt_steps[n] = t
         ops.adam_polyak(self.params, self.m, self.v, self.targets, grads, self.sizes, lr_t, do_adam, do_polyak, self.tau,
