@@ -501,6 +501,52 @@ int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* 
                         const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
                         float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
 
+/* ---- SAC with the LEARNED temperature (alpha = 'auto': AlphaModel, its Adam and target_entropy; learners/sac.py:138-148,
+ * policy.py:136-143) ----
+ * The temperature lives on the device and is read there: no entry point below takes alpha from the host, so a training loop never
+ * waits for it.  alpha = exp(log_alpha) is formed as the correctly rounded float32 exponential (the double-precision exp rounded once,
+ * the rule of sigma above): np.float32(np.exp(np.float64(log_alpha))) on the host is the same bits.
+ *
+ * mpg_sac_alpha_t: HOST struct, caller-owned.  state: DEVICE array of 8 floats -
+ *   [0] log_alpha   [1] Adam m   [2] Adam v   [3] alpha at the last mpg_sac_alpha_update with do_clip   [4] alpha_loss there
+ *   [5] the temperature gradient's norm |g| before the clip   [6] 1.0 where that gradient was not finite, else 0.0   [7] 0
+ * lr: PolynomialDecay(lr0, decay_steps, lr_end) of the temperature's own Adam; opt_steps: that Adam's step counter. */
+typedef struct {
+    float* state;
+    float target_entropy;
+    float lr[3];
+    long long opt_steps;
+} mpg_sac_alpha_t;
+
+/* mpg_sac_targets / mpg_sac_policy_grad with const float* log_alpha (device: state + 0) in place of float alpha.  Same workspaces
+ * (mpg_sac_targets_workspace_bytes, mpg_sac_policy_grad_workspace_bytes), same refusals under their own names (alpha's excepted),
+ * y / grad / qmin_sum / qmin_sqsum / logp_sum bit for bit those of the host-alpha entry points given the same alpha.
+ * mpg_sac_policy_grad_auto also evaluates the temperature's loss alpha_loss = mean(-log_alpha (logp_alpha + target_entropy))
+ * (sac.py:138-148), logp_alpha the head's log-density under a further draw eps_alpha [rows][2] on the SAME logits (the reference's third
+ * compute_action runs the same policy on the same observations: only the noise differs, so there is no third network pass and no
+ * further launch):  alpha_grad[0] = -inv_b_global * sum_rows(logp_alpha + target_entropy), this GPU's share of d alpha_loss / d log_alpha
+ * (unclipped; shares of unequal shards add up to the full-batch gradient).  The policy gradient does not flow into log_alpha.
+ * Refused besides: a target_entropy that is not finite. */
+int mpg_sac_targets_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                         const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
+                         mpg_stream_t stream);
+int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                             const float* eps, const float* log_alpha, const float* eps_alpha, float target_entropy, float inv_b_global,
+                             float* qmin_sum, float* qmin_sqsum, float* logp_sum, float* alpha_grad, float* grad, void* ws,
+                             size_t ws_bytes, mpg_stream_t stream);
+
+/* The temperature's scalar step, one small launch.  g: DEVICE, the reduced gradient (the sum of every GPU's alpha_grad).
+ * do_clip (SACLearner.compute_gradient): state[3] = alpha, state[4] = alpha_loss = log_alpha * g, state[5] = |g|, state[6] = its
+ *   non-finite flag; g[0] = g * clip * min(1 / |g|, 1 / clip) in place (tf.clip_by_global_norm of the one-element list).
+ * do_adam (PolicyWithQs.apply_gradients): one Keras-form Adam step on (log_alpha, m, v) - mpg_adam_polyak's arithmetic, the step size
+ *   from lr and opt_steps as for the networks - with a ZERO gradient if any of the n_skip_flags device ints is set or state[6] is
+ *   (optimizer.py:357-361 zeroes every gradient if any is NaN); opt_steps advances by one either way.
+ * Both: the two in that order (the native step's one launch); the same bits as two calls.
+ * Refused with MPG_EINVAL, each with its own text: a null struct, a null state, a null g, neither do_clip nor do_adam, clip <= 0 with
+ * do_clip, n_skip_flags > 0 behind a null pointer, a negative opt_steps. */
+int mpg_sac_alpha_update(mpg_sac_alpha_t* a, float* g, float clip, int do_clip, int do_adam, const int* skip_flags /* nullable */,
+                         int n_skip_flags, mpg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * clip_by_global_norm + Keras Adam + Polyak (K7, K8) over the flat [net0 | net1 | ...] vectors
  * ---------------------------------------------------------------------------------------------- */
@@ -689,7 +735,9 @@ typedef struct {
                                          SAC (learner_version 7): max(batch * act_dim, num_agent * (act_dim + 1)) floats - the
                                          learner's draws [batch][act_dim]; the second size is room for a worker's draws
                                          [num_agent][act_dim] and log-densities [num_agent], which the one-launch worker step
-                                         the driver takes (mpg_worker_sample_step) forms in registers and does not store */
+                                         the driver takes (mpg_worker_sample_step) forms in registers and does not store.
+                                         With the learned temperature (mpg_sac_auto_step_begin): max(2 * batch * act_dim, that) - the
+                                         draw of the temperature's loss [batch][act_dim] behind the learner's */
     /* scheduling option (round 5, ABI 9; MPG only, optional) */
     void* critics_ready_event;        /* hipEvent_t, nullable: see mpg_grad_opts_t (the caller overlaps the critics' exchange) */
     mpg_grad_opts_t grad_opts;        /* storage for cfg.grad_opts during mpg_step_begin */
@@ -718,6 +766,19 @@ int mpg_step_end(mpg_train_ctx_t* ctx, int iteration, mpg_stream_t stream);
  * mpg_sac_policy_grad's).  Refused with MPG_EINVAL before anything is enqueued: a learner_version other than 7, an incomplete context
  * (scratch included), prioritized != 0, explore_sigma != 0, alpha negative or not finite, env_kind 2. */
 int mpg_sac_step_begin(mpg_train_ctx_t* ctx, float alpha, int iteration, mpg_stream_t stream);
+
+/* The same step with the LEARNED temperature (mpg_sac_alpha_t above; SACLearner with alpha = 'auto').
+ * mpg_sac_auto_step_begin: mpg_sac_step_begin with mpg_sac_targets_auto / mpg_sac_policy_grad_auto on a->state (alpha is read on the
+ *   device) and a->target_entropy, and one more draw for the temperature's loss, mpg_normal_fill(batch * act_dim, learner_seed + 2,
+ *   learner_counter) after the counter's increment, into scratch + batch * act_dim.  The gradient buffer is
+ *   [grads | the temperature's gradient | statistics]: grad[n_grad] is this GPU's share, the statistics start at grad + n_grad + 1, and
+ *   the ONE exchange covers them all.  Refusals: those of mpg_sac_step_begin (alpha's excepted) under this name, a null struct, a null
+ *   state, a target_entropy that is not finite - each with its own text, before anything is enqueued or counted.
+ * mpg_sac_auto_step_end: mpg_step_end, then mpg_sac_alpha_update(a, grad + n_grad, ctx->clip, do_clip = 1,
+ *   do_adam = (iteration % delay_update == 0), ctx->nonfinite, n_nets): one more launch; a->opt_steps advances with the policy's.
+ *   Refusals: a null context, a learner_version other than 7, a null struct, a null state, an incomplete context. */
+int mpg_sac_auto_step_begin(mpg_train_ctx_t* ctx, const mpg_sac_alpha_t* a, int iteration, mpg_stream_t stream);
+int mpg_sac_auto_step_end(mpg_train_ctx_t* ctx, mpg_sac_alpha_t* a, int iteration, mpg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ steps (every random draw on the path is Philox(seed, counter), every reduction h
 Wire format: one uncompressed `.npz` (zip of `.npy`, readable without this package):
   meta                     JSON (utf-8 bytes): format version, class names, names of the networks, scalars / counters
   policy/{params,targets,m,v,nonfinite}      flat float32 in the reference's Keras order Q1,(Q2),policy
+  policy/alpha_state                         SAC with the learned temperature only: log_alpha, its Adam moments, the last snapshot
   worker/{env_state,obs,done}                SoA env state [8, num_agent], last observation, done mask
   learner/batch_*                            the minibatch cached across `num_batch_reuse` calls (+ its targets)
   learner/noise_gen                          torch generator state of the host-drawn noise stream (NADP / TD3)
@@ -33,6 +34,8 @@ def state_of(optimizer):
     w, ln, rb = optimizer.worker, optimizer.learner, optimizer.replay_buffer
     pw = w.policy_with_value
     arrays = {'policy/' + k: _np(getattr(pw, k)) for k in ('params', 'targets', 'm', 'v', 'nonfinite')}
+    if getattr(pw, 'auto_alpha', False):
+        arrays['policy/alpha_state'] = _np(pw.alpha_state)
     arrays.update({'worker/env_state': _np(w.env._state), 'worker/obs': _np(w.obs), 'worker/done': _np(w.env.done)})
     for k, v in ln.batch_data.items():
         arrays['learner/' + k] = _np(v)
@@ -50,7 +53,8 @@ def state_of(optimizer):
         optimizer=dict(iteration=optimizer.iteration, num_sampled_steps=optimizer.num_sampled_steps),
         # (sample_ctr: the stochastic policy's own stream of draws; absent for a deterministic policy)
         policy=dict(opt_steps={k: int(v) for k, v in pw.opt_steps.items()},
-                    **({'sample_ctr': int(pw._sample_ctr)} if not getattr(pw, 'deterministic_policy', True) else {})),
+                    **({'sample_ctr': int(pw._sample_ctr)} if not getattr(pw, 'deterministic_policy', True) else {}),
+                    **({'alpha_opt_steps': pw.alpha_opt_steps} if getattr(pw, 'auto_alpha', False) else {})),
         worker=dict(seed=w.seed, noise_ctr=w._noise_ctr, env_seed=w.env.seed, env_ctr=w.env._ctr, num_sample=w.num_sample,
                     sample_times=w.sample_times, iteration=w.iteration, env_initialised=bool(w.env._initialised)),
         learner=dict(seed=ln.seed, counter=ln.counter),
@@ -93,6 +97,11 @@ def load_checkpoint(path, optimizer):
     pw.opt_steps = {k: int(v) for k, v in meta['policy']['opt_steps'].items()}
     if 'sample_ctr' in meta['policy']:
         pw._sample_ctr = int(meta['policy']['sample_ctr'])
+    if getattr(pw, 'auto_alpha', False) != ('policy/alpha_state' in z.files):
+        raise ValueError('checkpoint and run differ in the temperature: one learns it (alpha = \'auto\'), the other does not')
+    if getattr(pw, 'auto_alpha', False):
+        put(pw.alpha_state, 'policy/alpha_state')
+        pw.alpha_desc.opt_steps = int(meta['policy']['alpha_opt_steps'])
     pw.refresh_weight_cache()
     put(w.env._state, 'worker/env_state')
     m = meta['worker']

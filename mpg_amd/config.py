@@ -22,7 +22,7 @@ def default_args(alg='MPG-v2', env_id=None, **overrides):
         value_lr_schedule=[8e-5, 100000, 8e-6],
         policy_model_cls='MLP', policy_num_hidden_layers=2, policy_num_hidden_units=256, policy_hidden_activation='elu',
         policy_out_activation='linear' if (pend or alg == 'SAC') else 'tanh', policy_lr_schedule=[3e-5, 100000, 3e-6],
-        # SAC: the fixed temperature of built_SAC_parser; 'auto' (AlphaModel, target_entropy) is not built
+        # SAC: the fixed temperature of built_SAC_parser; alpha='auto' learns it and needs target_entropy=... beside it (the parser adds it then)
         alpha=0.03 if alg == 'SAC' else None, alpha_lr_schedule=[8e-5, 100000, 8e-6] if alg == 'SAC' else None,
         policy_only=False, double_Q=alg in ('MPG-v2', 'TD3', 'SAC'), target=True, tau=0.005,
         delay_update=1 if alg in ('NADP', 'NDPG', 'SAC') else 2, deterministic_policy=alg != 'SAC', action_range=3. if pend else None,

@@ -35,6 +35,19 @@ __device__ __forceinline__ float gauss_row(int ad, const float* __restrict__ l, 
     }
     return lp;
 }
+// the log-density alone of the same head under another draw `e` (no action written): gauss_row's terms in gauss_row's order, so that
+// on the same draw it returns gauss_row's bits (the temperature's gradient, sac.py:138-148, needs logp of a draw nobody acts with)
+__device__ __forceinline__ float gauss_logp(int ad, const float* __restrict__ l, const float* __restrict__ e) {
+    float lp = 0.f;
+    for (int k = 0; k < ad; ++k) {
+        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), z = e[k];
+        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
+    }
+    return lp;
+}
+// alpha = exp(log_alpha) of the learned temperature, under sigma_of's rule and for its reason: the correctly rounded float32
+// exponential, which anyone can re-form on the host bit for bit
+__device__ __forceinline__ float alpha_of(const float* __restrict__ log_alpha) { return (float)exp((double)*log_alpha); }
 
 // Elements 4 q + 2 pair and 4 q + 2 pair + 1 of the stream mpg_normal_fill writes for (key, counter): Philox block q, Box-Muller on
 // the words (v[0], v[1]) (pair 0) or (v[2], v[3]) (pair 1) - the cosine for the even element, the sine for the odd one.  k_normal_fill

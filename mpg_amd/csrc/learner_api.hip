@@ -51,6 +51,17 @@ __global__ void k_nstep(int rows, int n, const float* __restrict__ rewards, cons
 // of row i and its terms added into s[NS].
 constexpr int ERR_PARTS = 64;
 constexpr int ERR_MB_MIN_ROWS = 8192;          // below: the one-block form (one launch instead of two)
+// a row body may also carry scale1(), what its finished SECOND sum is multiplied by (GaussRow2); without one it is reported as it is
+template <class Row, class = void>
+struct Scale1 {
+    static constexpr bool ANY = false;
+    static float of(const Row&) { return 1.f; }
+};
+template <class Row>
+struct Scale1<Row, decltype((void)&Row::scale1)> {
+    static constexpr bool ANY = true;
+    static float of(const Row& r) { return r.scale1(); }
+};
 
 // critic loss: err = q - y; dz3 = err * inv_b; td (nullable) = err; the sum of err^2, finished as the loss 0.5 * inv_b * sum
 struct QErrRow {
@@ -136,7 +147,8 @@ __global__ void __launch_bounds__(1024) k_row_sums(int rows, const Row row, floa
             for (int k = 0; k < NS; ++k) out0[k * ERR_PARTS + blockIdx.x] = red[k][0];
         } else {
             out0[0] = row.scale0() * red[0][0];
-            if (NS > 1) out1[0] = red[1][0];
+            if constexpr (Scale1<Row>::ANY) out1[0] = row.scale1() * red[1][0];
+            else if (NS > 1) out1[0] = red[1][0];
         }
     }
 }
@@ -159,7 +171,7 @@ __global__ void k_finish_parts(int n_part, const float* __restrict__ part, float
 template <class Row>
 int launch_row_sums(const char* name, const Row& row, int rows, float* parts, float* out0, float* out1, FinishJob* carried, hipStream_t s) {
     if (rows >= ERR_MB_MIN_ROWS) {
-        const FinishJob fin{parts, ERR_PARTS, ERR_PARTS, row.scale0(), Row::NS > 1 ? 1.f : 0.f, out0, out1};
+        const FinishJob fin{parts, ERR_PARTS, ERR_PARTS, row.scale0(), Row::NS > 1 ? Scale1<Row>::of(row) : 0.f, out0, out1};
         hipLaunchKernelGGL((k_row_sums<Row, true>), dim3(ERR_PARTS), dim3(1024), 0, s, rows, row, out0 ? parts : nullptr, (float*)nullptr);
         if (carried)
             *carried = fin;
@@ -222,11 +234,44 @@ struct GaussRow {
     }
 };
 
+// GaussRow for the policy draw and, in the same pass over the same logits, the temperature's share of the batch (sac.py:138-148): the
+// head's log-density under a SECOND draw eps_alpha (the reference's third compute_action: the same policy on the same observations,
+// only the noise differs - so no third network pass), with target_entropy added per row.  The second sum is finished as
+// -inv_b * sum_rows(logp_alpha + target_entropy): this rank's share of d alpha_loss / d log_alpha.  The clipped log-std of a NaN logit
+// is a bound (fmaxf / fminf return the other operand), so logp_alpha is finite whatever the policy produced.
+struct GaussRow2 {
+    int ad;
+    const float *__restrict__ logits, *__restrict__ eps, *__restrict__ eps_alpha;
+    float target_entropy, inv_b;
+    float *__restrict__ act, *__restrict__ logp;
+    static constexpr int NS = 2;
+    static constexpr bool SUM_OPTIONAL = false;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __host__ __device__ float scale1() const { return -inv_b; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
+        const float* l = logits + (size_t)i * 2 * ad;
+        const float lp = gauss_row(ad, l, eps + (size_t)i * ad, act + (size_t)i * ad);
+        logp[i] = lp;
+        s[0] += lp;
+        s[1] += gauss_logp(ad, l, eps_alpha + (size_t)i * ad) + target_entropy;
+    }
+};
+
 // soft target (sac.py:78-79): y = (rew + shift) * scale + gamma * (min(q1, q2) - alpha * logp)
 __global__ void k_sac_combine(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
                               const float* __restrict__ logp, float alpha, float shift, float scale, float gamma, float* __restrict__ y) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    y[i] = (rew[i] + shift) * scale + gamma * (fminf(q1[i], q2[i]) - alpha * logp[i]);
+}
+
+// the same with the learned temperature read on the device (alpha_of, gauss_head.h): a sibling, so that k_sac_combine keeps its code
+__global__ void k_sac_combine_auto(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
+                                   const float* __restrict__ logp, const float* __restrict__ log_alpha, float shift, float scale, float gamma,
+                                   float* __restrict__ y) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float alpha = alpha_of(log_alpha);
     y[i] = (rew[i] + shift) * scale + gamma * (fminf(q1[i], q2[i]) - alpha * logp[i]);
 }
 
@@ -239,6 +284,22 @@ __global__ void k_sac_dlogits(int rows, int od, int ad, const float* __restrict_
                               float* __restrict__ dlogits) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * ad) return;
+    const int row = i / ad, k = i % ad;
+    const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
+    const float raw = logits[(long)row * 2 * ad + ad + k];
+    const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
+    const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
+    dlogits[(long)row * 2 * ad + k] = ga;
+    dlogits[(long)row * 2 * ad + ad + k] = inside ? ga * sigma * eps[i] - alpha * inv_b : 0.f;
+}
+
+// k_sac_dlogits with the learned temperature read on the device (the policy's gradient does not flow into log_alpha, sac.py:127-128)
+__global__ void k_sac_dlogits_auto(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
+                                   const float* __restrict__ eps, const float* __restrict__ logits, const float* __restrict__ log_alpha,
+                                   float inv_b, float* __restrict__ dlogits) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * ad) return;
+    const float alpha = alpha_of(log_alpha);
     const int row = i / ad, k = i % ad;
     const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
     const float raw = logits[(long)row * 2 * ad + ad + k];
@@ -331,10 +392,16 @@ int gauss_head(const mpg_cfg_t* c, int rows, const float* logits, const float* e
 // The policy gradient through the critic(s), td3.py:120-134 / ndpg.py:174-186 / sac.py:119-136: policy forward (eps: all four logits and
 // the head's sample in place of the mean), the critics' forwards, dL/dq and the statistic sums, the critics' backwards down to dx, the
 // policy's output gradient, the policy's backward and weight gradient.  q2 null: one critic (DPG), whose dx is dQ/da as it stands; eps
-// (with alpha, logp_sum) non-null: the Gaussian head, two critics only (SAC).
+// (with alpha, logp_sum) non-null: the Gaussian head, two critics only (SAC).  `at` non-null: the learned temperature - alpha is
+// exp(*at->log_alpha) read on the device, and the head's pass also sums the temperature's gradient into at->alpha_grad (GaussRow2).
+struct AutoTemp {
+    const float *log_alpha, *eps_alpha;
+    float target_entropy;
+    float* alpha_grad;
+};
 int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
                 const float* eps, float alpha, float inv_b, float* q_sum, float* q_sqsum, float* logp_sum, float* grad, void* ws,
-                size_t ws_bytes, mpg_stream_t stream) {
+                size_t ws_bytes, mpg_stream_t stream, const AutoTemp* at = nullptr) {
     const int n_q = q2 ? 2 : 1;
     Arena ar(ws, ws_bytes);
     const PolicyGradWs w = policy_grad_ws(ar, cfg, rows, n_q, eps != nullptr);
@@ -348,7 +415,10 @@ int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, co
     if (eps) {
         rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);
         if (rc) return rc;
-        rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
+        rc = at ? launch_row_sums("k_row_sums<GaussRow2>",
+                                  GaussRow2{cfg->act_dim, w.logits, eps, at->eps_alpha, at->target_entropy, inv_b, w.a, w.logp}, rows, w.lparts,
+                                  logp_sum, at->alpha_grad, nullptr, s)
+                : gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
     } else {
         rc = policy_forward(cfg, policy, rows, xp, po, w.a, w.hp1, w.hp2, s);
     }
@@ -374,7 +444,10 @@ int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, co
     const float* g = w.dx[0] + od;
     int ldg = qin;
     if (n_q == 2) {
-        if (eps)
+        if (at)
+            hipLaunchKernelGGL(k_sac_dlogits_auto, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits,
+                               at->log_alpha, inv_b, w.g);
+        else if (eps)
             hipLaunchKernelGGL(k_sac_dlogits, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits, alpha,
                                inv_b, w.g);
         else
@@ -644,4 +717,43 @@ extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, co
     if (rc) return rc;
     return policy_grad("mpg_sac_policy_grad", cfg, policy, q1, q2, rows, obs, eps, alpha, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
                        ws_bytes, stream);
+}
+
+// ---- the learned temperature (alpha = 'auto'): the two entry points above with alpha = exp(*log_alpha) read on the device ----
+extern "C" int mpg_sac_targets_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                                    const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
+                                    mpg_stream_t stream) {
+    int rc = gauss_refusal("mpg_sac_targets_auto", cfg, policy && q1t && q2t && rew && obs_tp1 && eps && log_alpha && y && ws, rows, 0.f);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small("mpg_sac_targets_auto", ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);
+    if (rc) return rc;
+    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s);
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);
+    if (rc) return rc;
+    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sac_combine_auto, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, log_alpha, cfg->rew_shift,
+                       cfg->rew_scale, cfg->gamma, y);
+    MPG_CHECK_LAUNCH("k_sac_combine_auto");
+    return MPG_OK;
+}
+
+extern "C" int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                                        const float* eps, const float* log_alpha, const float* eps_alpha, float target_entropy,
+                                        float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum, float* alpha_grad, float* grad,
+                                        void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = gauss_refusal("mpg_sac_policy_grad_auto", cfg,
+                           policy && q1 && q2 && obs && eps && log_alpha && eps_alpha && qmin_sum && qmin_sqsum && logp_sum && alpha_grad && grad && ws,
+                           rows, 0.f);
+    if (rc) return rc;
+    MPG_REQUIRE(std::isfinite(target_entropy), "mpg_sac_policy_grad_auto: target_entropy must be finite (got %g)", (double)target_entropy);
+    const AutoTemp at{log_alpha, eps_alpha, target_entropy, alpha_grad};
+    return policy_grad("mpg_sac_policy_grad_auto", cfg, policy, q1, q2, rows, obs, eps, 0.f, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
+                       ws_bytes, stream, &at);
 }

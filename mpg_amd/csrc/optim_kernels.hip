@@ -4,6 +4,7 @@
 // Reference: learners/mpg_learner.py:415-431 (clip), policy.py:123-171 (apply_gradients, update_*_target),
 // optimizer.py:357-361 (NaN guard).  Adam follows TensorFlow's ApplyAdam functor:
 //   m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  w -= lr_t * m / (sqrt(v) + eps),  lr_t = lr sqrt(1-b2^t)/(1-b1^t).
+#include "adam_schedule.h"
 #include "mlp_core.h"   // net_size, wcache_w2_offset
 
 
@@ -357,6 +358,55 @@ extern "C" int mpg_adam_polyak(float* w, float* m, float* v, float* target, cons
     hipLaunchKernelGGL(k_adam_polyak, dim3((maxn + 255) / 256, n_seg), dim3(256), 0, mpg_stream(stream), sg, w, m, v,
                        target, grad, tau, skip_flags, skip_flags ? n_skip_flags : 0);
     MPG_CHECK_LAUNCH("k_adam_polyak");
+    return MPG_OK;
+}
+
+namespace {
+// ---- the learned temperature of SAC (learners/sac.py:138-148, policy.py:136-143): one scalar, one thread ----------------------------
+// state: [0] log_alpha, [1] Adam m, [2] Adam v, [3] alpha at the last gradient call, [4] alpha_loss there, [5] the gradient's norm
+// before the clip, [6] 1.0 where that gradient was not finite, [7] unused.
+// do_clip (compute_gradient): the snapshot for the statistics - alpha = exp(log_alpha) under the kernels' own rule, alpha_loss =
+// mean(-log_alpha (logp + target_entropy)) = log_alpha * g - then tf.clip_by_global_norm of the one-element list: norm |g|,
+// g * clip * min(1 / |g|, 1 / clip), written back in place.
+// do_adam (apply_gradients): adam_update on (log_alpha, m, v) - k_adam_polyak's arithmetic - with a zero gradient if any skip flag is
+// set or the temperature's own gradient was not finite (optimizer.py:357-361 zeroes the whole list).
+__global__ void k_sac_alpha_update(float* __restrict__ state, float* __restrict__ g, float clip, int do_clip, int do_adam, float lr_t,
+                                   const int* __restrict__ skip, int n_skip) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float gv = g[0];
+    if (do_clip) {
+        const float la = state[0], nrm = fabsf(gv);
+        state[3] = (float)exp((double)la);
+        state[4] = la * gv;
+        state[5] = nrm;
+        state[6] = isfinite(nrm) ? 0.f : 1.f;
+        gv *= clip * fminf(1.f / nrm, 1.f / clip);
+        g[0] = gv;
+    }
+    if (do_adam) {
+        bool bad = state[6] != 0.f;
+        for (int q = 0; q < n_skip; ++q) bad |= skip[q] != 0;
+        float wj = state[0], mj = state[1], vj = state[2];
+        adam_update(bad ? 0.f : gv, lr_t, mj, vj, wj);
+        state[0] = wj; state[1] = mj; state[2] = vj;
+    }
+}
+}  // namespace
+
+extern "C" int mpg_sac_alpha_update(mpg_sac_alpha_t* a, float* g, float clip, int do_clip, int do_adam, const int* skip_flags, int n_skip_flags,
+                                    mpg_stream_t stream) {
+    MPG_REQUIRE(a, "mpg_sac_alpha_update: null temperature struct");
+    MPG_REQUIRE(a->state, "mpg_sac_alpha_update: null temperature state");
+    MPG_REQUIRE(g, "mpg_sac_alpha_update: null gradient");
+    MPG_REQUIRE(do_clip || do_adam, "mpg_sac_alpha_update: nothing to do (do_clip and do_adam both 0)");
+    MPG_REQUIRE(!do_clip || clip > 0.f, "mpg_sac_alpha_update: the clip norm must be positive (got %g)", (double)clip);
+    MPG_REQUIRE(n_skip_flags >= 0 && (skip_flags || n_skip_flags == 0), "mpg_sac_alpha_update: %d skip flags behind a null pointer", n_skip_flags);
+    MPG_REQUIRE(a->opt_steps >= 0, "mpg_sac_alpha_update: negative step counter (%lld)", a->opt_steps);
+    const float lr_t = do_adam ? adam_step_size(a->lr, a->opt_steps) : 0.f;
+    hipLaunchKernelGGL(k_sac_alpha_update, dim3(1), dim3(64), 0, mpg_stream(stream), a->state, g, clip, do_clip, do_adam, lr_t, skip_flags,
+                       skip_flags ? n_skip_flags : 0);
+    MPG_CHECK_LAUNCH("k_sac_alpha_update");
+    if (do_adam) a->opt_steps += 1;
     return MPG_OK;
 }
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "adam_schedule.h"
 #include "mpg_common.h"
 
 namespace {
@@ -47,23 +48,7 @@ void rule_based_weights(int ite, int total_ite, float eta, const int* select, in
     for (int k = 0; k < ns; ++k) w[k] /= sum;
 }
 
-// PolynomialDecay (policy.py:54,62) and the ApplyAdam step size AS TENSORFLOW FORMS THEM: every operand a float32 tensor
-// (schedule in the dtype of the initial rate; beta^t = pow of the float32 hyper-parameter; alpha = lr sqrt(1 - b2^t) / (1 - b1^t)
-// in float32).  float32(0.999) is 1.3e-8 above 0.999, which puts alpha 6.7e-6 below the real-number formula for the first
-// thousands of steps - found in round 6 when the reference's own PolicyWithQs.apply_gradients first ran against this path.
-// beta^t: double-precision pow of the float32 operand rounded once = the correctly rounded powf.
-float polynomial_decay(const float* sched, long long step) {
-    const float lr0 = sched[0], S = sched[1], lr_end = sched[2];
-    const float p = std::min((float)step, S) / S;
-    return (lr0 - lr_end) * (1.f - p) + lr_end;
-}
-
-float adam_step_size(const float* sched, long long steps_done) {
-    const float lr = polynomial_decay(sched, steps_done);
-    const double t = (double)(steps_done + 1);
-    const float b1p = (float)std::pow((double)0.9f, t), b2p = (float)std::pow((double)0.999f, t);
-    return lr * std::sqrt(1.f - b2p) / (1.f - b1p);
-}
+// (polynomial_decay, adam_step_size: adam_schedule.h)
 
 #define TRY(call)            \
     do {                     \
@@ -216,9 +201,9 @@ int ndpg_gradients(mpg_train_ctx_t* c, const Layout& l, bool fresh, mpg_stream_t
 // (mpg_worker_sample_step) at every width.  Against the three calls it replaces (mpg_normal_fill, mpg_policy_sample,
 // mpg_env_step_store_reset: four launches, bit-identical) it measured faster at 8 and at 4096 agents with obs_dim 6 and 9
 // (tools/bench_sac_native.py), which is the rule for taking it.
-int sac_sample_and_add(mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
+int sac_sample_and_add(const char* entry, mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
     const int n = c->num_agent;
-    MPG_REQUIRE(n <= c->ring_capacity, "mpg_sac_step_begin: ring smaller than one sample");
+    MPG_REQUIRE(n <= c->ring_capacity, "%s: ring smaller than one sample", entry);
     for (int it = 0; it < c->sample_iters; ++it) {
         // (the log-densities have no consumer: worker.py:96 drops them)
         TRY(mpg_worker_sample_step(&c->cfg, policy, n, c->env_state, c->w_obs, c->worker_seed, c->noise_ctr++, c->w_act, nullptr,
@@ -232,25 +217,37 @@ int sac_sample_and_add(mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) 
 
 // ---- SACLearner.compute_gradient, learners/sac.py:169-219 (networks [Q1 | Q2 | policy]); the minibatch and its soft target
 //      (:67-80) every num_batch_reuse-th call.  Draws: counters 2 (k + 1) for the target of call k, 2 k + 1 for the policy loss after
-//      the counter's increment, as SACLearner._draw ----
-int sac_gradients(mpg_train_ctx_t* c, const Layout& l, float alpha, bool fresh, mpg_stream_t s) {
+//      the counter's increment, as SACLearner._draw.
+//      at non-null: the learned temperature - alpha is read on the device (at->state), the _auto entry points run, the third draw (stream
+//      learner_seed + 2, the counter after its increment) goes into the second half of the scratch block, the temperature's gradient
+//      into grad[n_grad] and the statistics one float further on: [grads | alpha grad | stats] ----
+int sac_gradients(mpg_train_ctx_t* c, const Layout& l, float alpha, const mpg_sac_alpha_t* at, bool fresh, mpg_stream_t s) {
     const int od = c->cfg.obs_dim, ad = c->cfg.act_dim, B = c->batch;
     const float *q1 = c->params, *q2 = c->params + l.off[1], *policy = c->params + l.off[2];
     const float *q1t = c->targets, *q2t = c->targets + l.off[1];
     const float inv_b = 1.f / ((float)B * (float)c->world_size);
-    float* stats = c->grad + l.n_grad;
+    float* stats = c->grad + l.n_grad + (at ? 1 : 0);
     float* eps = c->scratch;                          // [B][ad]
     if (fresh) {
         TRY(mpg_replay_sample_uniform(c->ring_size, B, c->replay_seed, c->replay_times, od, ad, c->ring_obs, c->ring_act, c->ring_rew,
                                       c->ring_obs2, c->ring_done, c->idx, c->b_obs, c->b_act, c->b_rew, c->b_obs2, c->b_done, s));
         TRY(mpg_normal_fill(B * ad, c->learner_seed, 2 * (c->learner_counter + 1), eps, s));
-        TRY(mpg_sac_targets(&c->cfg, policy, q1t, q2t, B, c->b_rew, c->b_obs2, eps, alpha, c->b_targets, c->ws0, c->ws0_bytes, s));
+        if (at)
+            TRY(mpg_sac_targets_auto(&c->cfg, policy, q1t, q2t, B, c->b_rew, c->b_obs2, eps, at->state, c->b_targets, c->ws0, c->ws0_bytes, s));
+        else
+            TRY(mpg_sac_targets(&c->cfg, policy, q1t, q2t, B, c->b_rew, c->b_obs2, eps, alpha, c->b_targets, c->ws0, c->ws0_bytes, s));
     }
     c->learner_counter++;
     TRY(mpg_q_loss_grad(&c->cfg, q1, B, c->b_obs, c->b_act, c->b_targets, inv_b, stats, c->grad + l.off[0], nullptr, c->ws0, c->ws0_bytes, s));
     TRY(mpg_q_loss_grad(&c->cfg, q2, B, c->b_obs, c->b_act, c->b_targets, inv_b, stats + 1, c->grad + l.off[1], nullptr, c->ws0,
                         c->ws0_bytes, s));
     TRY(mpg_normal_fill(B * ad, c->learner_seed, 2 * c->learner_counter + 1, eps, s));
+    if (at) {
+        float* eps_alpha = eps + (size_t)B * ad;
+        TRY(mpg_normal_fill(B * ad, c->learner_seed + 2, c->learner_counter, eps_alpha, s));
+        return mpg_sac_policy_grad_auto(&c->cfg, policy, q1, q2, B, c->b_obs, eps, at->state, eps_alpha, at->target_entropy, inv_b, stats + 2,
+                                        stats + 3, stats + 4, c->grad + l.n_grad, c->grad + l.off[2], c->ws1, c->ws1_bytes, s);
+    }
     return mpg_sac_policy_grad(&c->cfg, policy, q1, q2, B, c->b_obs, eps, alpha, inv_b, stats + 2, stats + 3, stats + 4, c->grad + l.off[2],
                                c->ws1, c->ws1_bytes, s);
 }
@@ -372,24 +369,48 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
     return rc;
 }
 
-extern "C" int mpg_sac_step_begin(mpg_train_ctx_t* c, float alpha, int iteration, mpg_stream_t s) {
-    MPG_REQUIRE(c, "mpg_sac_step_begin: null context");
-    MPG_REQUIRE(c->learner_version == 7, "mpg_sac_step_begin: learner_version 7 (SAC) only (got %d)", c->learner_version);
-    MPG_REQUIRE(ctx_ok(c), "mpg_sac_step_begin: incomplete context");
-    MPG_REQUIRE(!c->prioritized, "mpg_sac_step_begin: a prioritized replay buffer is not served (prioritized = %d)", c->prioritized);
-    MPG_REQUIRE(c->explore_sigma == 0.f, "mpg_sac_step_begin: explore_sigma on top of the stochastic policy is not served (got %g)",
+namespace {
+// what mpg_sac_step_begin and mpg_sac_auto_step_begin refuse alike, under the caller's name
+int sac_begin_refusal(const char* entry, const mpg_train_ctx_t* c) {
+    MPG_REQUIRE(c, "%s: null context", entry);
+    MPG_REQUIRE(c->learner_version == 7, "%s: learner_version 7 (SAC) only (got %d)", entry, c->learner_version);
+    MPG_REQUIRE(ctx_ok(c), "%s: incomplete context", entry);
+    MPG_REQUIRE(!c->prioritized, "%s: a prioritized replay buffer is not served (prioritized = %d)", entry, c->prioritized);
+    MPG_REQUIRE(c->explore_sigma == 0.f, "%s: explore_sigma on top of the stochastic policy is not served (got %g)", entry,
                 (double)c->explore_sigma);
-    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "mpg_sac_step_begin: alpha must be finite and not negative (got %g)",
-                (double)alpha);
+    return MPG_OK;
+}
+int sac_begin_env_refusal(const char* entry, const mpg_train_ctx_t* c) {
     MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
-                "mpg_sac_step_begin: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
-                "samples it) does not serve this model");
+                "%s: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
+                "samples it) does not serve this model", entry);
+    return MPG_OK;
+}
+int sac_begin(const char* entry, mpg_train_ctx_t* c, float alpha, const mpg_sac_alpha_t* at, int iteration, mpg_stream_t s) {
     const Layout l = layout(c);
-    if (iteration % c->sampling_interval == 0) TRY(sac_sample_and_add(c, c->params + l.off[2], s));
-    MPG_REQUIRE(c->ring_size > 0, "mpg_sac_step_begin: empty replay ring");
+    if (iteration % c->sampling_interval == 0) TRY(sac_sample_and_add(entry, c, c->params + l.off[2], s));
+    MPG_REQUIRE(c->ring_size > 0, "%s: empty replay ring", entry);
     c->replay_times++;
     const bool fresh = c->learner_counter % c->num_batch_reuse == 0;     // the batch is drawn on every num_batch_reuse-th call only
-    return sac_gradients(c, l, alpha, fresh, s);
+    return sac_gradients(c, l, alpha, at, fresh, s);
+}
+}  // namespace
+
+extern "C" int mpg_sac_step_begin(mpg_train_ctx_t* c, float alpha, int iteration, mpg_stream_t s) {
+    TRY(sac_begin_refusal("mpg_sac_step_begin", c));
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "mpg_sac_step_begin: alpha must be finite and not negative (got %g)",
+                (double)alpha);
+    TRY(sac_begin_env_refusal("mpg_sac_step_begin", c));
+    return sac_begin("mpg_sac_step_begin", c, alpha, nullptr, iteration, s);
+}
+
+extern "C" int mpg_sac_auto_step_begin(mpg_train_ctx_t* c, const mpg_sac_alpha_t* a, int iteration, mpg_stream_t s) {
+    TRY(sac_begin_refusal("mpg_sac_auto_step_begin", c));
+    MPG_REQUIRE(a, "mpg_sac_auto_step_begin: null temperature struct");
+    MPG_REQUIRE(a->state, "mpg_sac_auto_step_begin: null temperature state");
+    MPG_REQUIRE(std::isfinite(a->target_entropy), "mpg_sac_auto_step_begin: target_entropy must be finite (got %g)", (double)a->target_entropy);
+    TRY(sac_begin_env_refusal("mpg_sac_auto_step_begin", c));
+    return sac_begin("mpg_sac_auto_step_begin", c, 0.f, a, iteration, s);
 }
 
 extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
@@ -418,4 +439,20 @@ extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
                                         lr_t, do_adam, do_polyak, c->tau, c->norms, c->nonfinite, c->cfg.wcache[0], c->cfg.wcache[1], s);
     mpg_prof_end(c->cfg.prof, 9, mpg_stream(s));
     return rc;
+}
+
+// mpg_step_end for the learned temperature: the networks' clip + Adam + Polyak as for every version (the segments end where the
+// temperature's gradient begins), then the temperature's one launch - its clip and snapshot, and its Adam step together with the
+// policy's (policy.py:136-143), with a zero gradient if a network's gradient was not finite (ctx->nonfinite, written by the launch before)
+extern "C" int mpg_sac_auto_step_end(mpg_train_ctx_t* c, mpg_sac_alpha_t* a, int iteration, mpg_stream_t s) {
+    MPG_REQUIRE(c, "mpg_sac_auto_step_end: null context");
+    MPG_REQUIRE(c->learner_version == 7, "mpg_sac_auto_step_end: learner_version 7 (SAC) only (got %d)", c->learner_version);
+    MPG_REQUIRE(a, "mpg_sac_auto_step_end: null temperature struct");
+    MPG_REQUIRE(a->state, "mpg_sac_auto_step_end: null temperature state");
+    MPG_REQUIRE(ctx_ok(c) && c->norms && c->nonfinite && c->adam_m && c->adam_v && c->clip_scratch, "mpg_sac_auto_step_end: incomplete context");
+    MPG_REQUIRE(c->clip > 0.f && a->opt_steps >= 0, "mpg_sac_auto_step_end: clip norm %g / temperature step counter %lld", (double)c->clip,
+                a->opt_steps);
+    const Layout l = layout(c);
+    TRY(mpg_step_end(c, iteration, s));
+    return mpg_sac_alpha_update(a, c->grad + l.n_grad, c->clip, 1, iteration % c->delay_update == 0 ? 1 : 0, c->nonfinite, l.n_nets, s);
 }

@@ -49,7 +49,8 @@ class FusedMPGStep(object):
     """step(iteration) == SingleProcessOffPolicyOptimizer.step for (OffPolicyWorker, replay buffer, learner) sharing one
     PolicyWithQs: MPGLearner + ReplayBuffer (learner_version 1 / 2), NADPLearner + ReplayBuffer (3), TD3Learner + ReplayBuffer
     or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included), NDPGLearner + ReplayBuffer (5),
-    SACLearner + ReplayBuffer without explore_sigma (7: mpg_sac_step_begin, which takes the learner's fixed alpha)."""
+    SACLearner + ReplayBuffer without explore_sigma (7: mpg_sac_step_begin, which takes the learner's fixed alpha, or with
+    alpha = 'auto' the pair mpg_sac_auto_step_begin / mpg_sac_auto_step_end on the policy's device-resident temperature)."""
 
     def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
         from .buffer import PrioritizedReplayBuffer
@@ -119,7 +120,8 @@ class FusedMPGStep(object):
         c.grad, c.norms, c.nonfinite = L.ptr(learner.flat), L.ptr(learner.norms), L.ptr(pw.nonfinite)
         c.clip_scratch = L.ptr(learner.clip_scratch)
         if c.learner_version == 7:          # the learner's draws (the size include/mpg_hip.h documents for this version)
-            self.scratch = torch.empty(max(B * ad, n * (ad + 1)) + 64, **f)
+            self.auto_alpha = bool(getattr(learner, 'auto_alpha', False))
+            self.scratch = torch.empty(max((2 if self.auto_alpha else 1) * B * ad, n * (ad + 1)) + 64, **f)
             c.scratch = L.ptr(self.scratch)
         if c.learner_version == 4:
             self.scratch = torch.empty(max(B * (ad + 3), 2 * n) + 64, **f)
@@ -206,7 +208,10 @@ class FusedMPGStep(object):
         try:
             if slot is not None:
                 c.grad = slot.data_ptr()
-            if c.learner_version == 7:       # the temperature travels as an argument (mpg_train_ctx_t has no field for it)
+            if c.learner_version == 7 and self.auto_alpha:       # the learned temperature: read on the device, never here
+                L.check(self._lib.mpg_sac_auto_step_begin(self._ref, ctypes.byref(self.pw.alpha_desc), ctypes.c_int(iteration), s),
+                        'mpg_sac_auto_step_begin')
+            elif c.learner_version == 7:     # the temperature travels as an argument (mpg_train_ctx_t has no field for it)
                 L.check(self._lib.mpg_sac_step_begin(self._ref, ctypes.c_float(self.learner.alpha), ctypes.c_int(iteration), s),
                         'mpg_sac_step_begin')
             else:
@@ -238,5 +243,10 @@ class FusedMPGStep(object):
             c.grad = flat.data_ptr()
             if slot is not None and not c.clip_partials_ready:
                 D.release_slot(flat.numel())
-        L.check(self._lib.mpg_step_end(self._ref, ctypes.c_int(iteration), s), 'mpg_step_end')
+        if c.learner_version == 7 and self.auto_alpha:
+            # (the temperature's step counter lives in the policy's own struct: nothing to pull or push)
+            L.check(self._lib.mpg_sac_auto_step_end(self._ref, ctypes.byref(self.pw.alpha_desc), ctypes.c_int(iteration), s),
+                    'mpg_sac_auto_step_end')
+        else:
+            L.check(self._lib.mpg_step_end(self._ref, ctypes.c_int(iteration), s), 'mpg_step_end')
         self.push()

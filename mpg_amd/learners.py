@@ -1,5 +1,5 @@
 """Learners - device mirrors of learners/mpg_learner.py (MPGLearner), learners/nadp.py (NADPLearner),
-learners/td3.py (TD3Learner), learners/ndpg.py (NDPGLearner), learners/sac.py (SACLearner, fixed temperature) and learners/ampc.py
+learners/td3.py (TD3Learner), learners/ndpg.py (NDPGLearner), learners/sac.py (SACLearner, fixed or learned temperature) and learners/ampc.py
 (AMPCLearner, the policy alone): same constructor signature `(policy_cls, args)`, same methods the optimizer calls
 (`set_weights`, `compute_gradient(batch5, rb, indexes, iteration)`, `get_stats`, `get_info_for_buffer`), same
 output order `q1 (+q2) + policy`.
@@ -448,16 +448,21 @@ class NDPGLearner(_LearnerBase):
 
 
 class SACLearner(_LearnerBase):
-    """Soft actor-critic with a fixed temperature (learners/sac.py:21-219): networks [Q1 | Q2 | policy], the policy a diagonal
-    Gaussian over its four logits (policy.py:179-204, no action range).  PathTracking-v0 only; alpha = 'auto' is not built.
+    """Soft actor-critic (learners/sac.py:21-219): networks [Q1 | Q2 | policy], the policy a diagonal Gaussian over its four logits
+    (policy.py:179-204, no action range).  PathTracking-v0 only.
     Every draw is the library's Philox stream keyed by (learner seed, call counter): two per gradient call - the action at s' for the
     target (from the ONLINE policy, sac.py:71) and the action of the policy loss (:123) - and one more, from the TARGET policy, for a
-    prioritized buffer's td error (:88)."""
+    prioritized buffer's td error (:88).
+    alpha = 'auto' (with args.target_entropy): the temperature is learned (:138-148).  It stays on the device - the kernels read
+    log_alpha there, nothing in the step reads it on the host - its loss takes a third draw (stream seed + 2, the call counter), its
+    gradient travels as one more float between the networks' gradients and the statistics ([grads | alpha grad | stats]: one
+    all-reduce), and compute_gradient returns it as the 19th array."""
 
     def __init__(self, policy_cls, args, device='cuda'):
-        if getattr(args, 'alpha', None) == 'auto':
-            raise ValueError("SACLearner: alpha = 'auto' (AlphaModel, its Adam, target_entropy) is not built; pass a fixed alpha such as "
-                             "the reference's default 0.03")
+        self.auto_alpha = getattr(args, 'alpha', None) == 'auto'
+        if self.auto_alpha and getattr(args, 'target_entropy', None) is None:
+            raise ValueError("SACLearner: alpha = 'auto' needs args.target_entropy (the reference's parser adds it with 'auto' only, "
+                             "train_script.py:672-792; sac.py:144 reads it): default_args('SAC', alpha='auto', target_entropy=-2.)")
         if getattr(args, 'deterministic_policy', True):
             raise ValueError('SACLearner needs deterministic_policy=False (built_SAC_parser, train_script.py:672-792)')
         if args.env_id != 'PathTracking-v0':
@@ -465,6 +470,10 @@ class SACLearner(_LearnerBase):
                              'bijector whose log-density correction is not built' % (args.env_id,))
         super().__init__(policy_cls, args, device)
         assert self.policy_with_value.names == ['Q1', 'Q2', 'policy'], 'SAC trains [Q1 | Q2 | policy]: double_Q=True, target=True'
+        self.n_net_grad = self.n_grad
+        if self.auto_alpha:          # one more gradient float behind the networks'; the statistics follow it
+            self.n_grad += 1
+            self.flat = torch.zeros(self.n_grad + N_STATS, dtype=torch.float32, device=self.device)
 
     @property
     def alpha(self):
@@ -479,6 +488,9 @@ class SACLearner(_LearnerBase):
         pw, b = self.policy_with_value, self.batch_data
         if eps_target is None:
             eps_target = self._draw(b['batch_obs'].shape[0], 2 * (self.counter + 1))
+        if self.auto_alpha:
+            return ops.sac_targets_auto(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'],
+                                        b['batch_obs_tp1'], eps_target, pw.log_alpha)
         return ops.sac_targets(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'], b['batch_obs_tp1'],
                                eps_target, self.alpha)
 
@@ -499,8 +511,8 @@ class SACLearner(_LearnerBase):
         if self.args.buffer_type != 'normal':
             self.info_for_buffer.update(dict(td_error=self.compute_td_error(), rb=rb, indexes=indexes))
 
-    def compute_gradient(self, batch_data, rb, indexes, iteration, eps_target=None, eps_policy=None):
-        """sac.py:169-219; output order q1 + q2 + policy"""
+    def compute_gradient(self, batch_data, rb, indexes, iteration, eps_target=None, eps_policy=None, eps_alpha=None):
+        """sac.py:169-219; output order q1 + q2 + policy (+ the temperature's gradient, a 0-d array, with alpha = 'auto')"""
         pw, b, rows, inv_b, stats = self._begin(batch_data, rb, indexes, eps_target)
         if self.args.buffer_type != 'normal':                  # :173-174: the priorities follow the critic within a reused batch
             self.info_for_buffer.update(dict(td_error=self.compute_td_error(ctr=2 * self.counter - 1)))
@@ -509,17 +521,37 @@ class SACLearner(_LearnerBase):
                             grad_out=self.grad(nm), loss_out=stats[i:i + 1])
         if eps_policy is None:
             eps_policy = self._draw(rows, 2 * self.counter + 1)
-        ops.sac_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha,
-                            inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5])    # :119-136
-        return self._finish(iteration)
+        if not self.auto_alpha:
+            ops.sac_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha,
+                                inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5])    # :119-136
+            return self._finish(iteration)
+        if eps_alpha is None:                                                                          # :139: the third draw
+            eps_alpha = self._draw(rows, self.counter, stream=2)
+        g_alpha = self.flat[self.n_net_grad:self.n_grad]
+        ops.sac_policy_grad_auto(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, pw.log_alpha,
+                                 eps_alpha, pw.target_entropy, inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5],
+                                 alpha_grad_out=g_alpha)                                               # :119-148
+        fresh = self._views is None
+        views = self._finish(iteration)
+        if fresh:
+            views.append(g_alpha.view(()))                                                             # :216: the last gradient
+        # the temperature's own clip (alone in its list, :146) and the snapshot the statistics read
+        ops.sac_alpha_update(pw.alpha_desc, g_alpha, clip=float(self.args.gradient_clip_norm), do_clip=True)
+        return views
 
     def _native_lazy_stats(self, iteration):
         stats, B, alpha = self.flat[self.n_grad:], self.batch_size * D.world_size(), self.alpha
 
         def lazy():        # evaluated only when get_stats() is called: no elementwise launches in the training loop
             mean, logp = stats[2] / B, stats[4] / B
-            # (mb_targets_mean: this process's batch, like the reference's np.mean(mb_targets))
-            return dict(q_loss1=stats[0], q_loss2=stats[1], policy_loss=alpha * logp - mean, policy_entropy=-logp,
+            extra = {}
+            if self.auto_alpha:
+                # the snapshot mpg_sac_alpha_update took at the gradient call: alpha BEFORE the update that follows it (sac.py:189)
+                snap = self.policy_with_value.alpha_state
+                extra = dict(alpha=snap[ops.ALPHA_SNAPSHOT], alpha_loss=snap[ops.ALPHA_LOSS], alpha_gradient_norm=snap[ops.ALPHA_NORM],
+                             alpha_time=None)
+            a = extra['alpha'] if self.auto_alpha else alpha
+            return dict(extra, q_loss1=stats[0], q_loss2=stats[1], policy_loss=a * logp - mean, policy_entropy=-logp,
                         mb_targets_mean=self.batch_data['batch_targets'].mean(), value_mean=mean, value_var=stats[3] / B - mean * mean,
                         q_gradient_norm1=self.norms[0], q_gradient_norm2=self.norms[1], policy_gradient_norm=self.norms[2])
         return lazy

@@ -479,6 +479,51 @@ def sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=No
                         grad_out, stats_out)
 
 
+class SacAlphaStruct(ctypes.Structure):
+    """mpg_sac_alpha_t: the learned temperature of SAC - its device state block (8 floats: log_alpha, Adam m, Adam v, then the snapshot
+    of the last gradient call: alpha, alpha_loss, |g|, non-finite flag, 0), target_entropy, its Adam's schedule and step counter"""
+    _fields_ = [('state', ctypes.c_void_p), ('target_entropy', ctypes.c_float), ('lr', ctypes.c_float * 3),
+                ('opt_steps', ctypes.c_longlong)]
+
+
+ALPHA_STATE_FLOATS = 8
+ALPHA_LOG, ALPHA_M, ALPHA_V, ALPHA_SNAPSHOT, ALPHA_LOSS, ALPHA_NORM, ALPHA_NONFINITE = range(7)      # slots of the state block
+
+
+def sac_targets_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha):
+    """mpg_sac_targets_auto: mpg_sac_targets with alpha = exp(log_alpha[0]) read on the device (log_alpha: device tensor)"""
+    rows = obs_tp1.shape[0]
+    y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
+    ws = _ws(obs_tp1.device, 0, 'mpg_sac_targets_workspace_bytes', cfg, rows)
+    L.call('mpg_sac_targets_auto', ctypes.byref(cfg), L.ptr(_f32(policy)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows),
+           L.ptr(_f32(rew)), L.ptr(_f32(obs_tp1)), L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(y), *ws, L.stream())
+    return y
+
+
+def sac_policy_grad_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global=None, grad_out=None,
+                         stats_out=None, alpha_grad_out=None):
+    """mpg_sac_policy_grad_auto: mpg_sac_policy_grad with the device temperature, and this process's share of the temperature's
+    gradient -inv_b * sum(logp(eps_alpha) + target_entropy) from the same pass.  Returns (stats = [qmin_sum, qmin_sqsum, logp_sum],
+    grad, alpha_grad [1])."""
+    rows, dev = obs.shape[0], obs.device
+    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
+    stats = stats_out if stats_out is not None else torch.empty(3, dtype=torch.float32, device=dev)
+    ag = alpha_grad_out if alpha_grad_out is not None else torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _ws(dev, 1, 'mpg_sac_policy_grad_workspace_bytes', cfg, rows)
+    L.call('mpg_sac_policy_grad_auto', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)), L.c_int(rows),
+           L.ptr(_f32(obs)), L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(_f32(eps_alpha)), L.c_float(target_entropy),
+           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), *[L.ptr(stats[i:i + 1]) for i in range(3)], L.ptr(ag),
+           L.ptr(grad), *ws, L.stream())
+    return stats, grad, ag
+
+
+def sac_alpha_update(desc, g, clip=1.0, do_clip=False, do_adam=False, skip_flag=None):
+    """mpg_sac_alpha_update on the SacAlphaStruct `desc`: the clip of the reduced gradient g [1] (with the statistics' snapshot) and /
+    or one Adam step of log_alpha; desc.opt_steps advances with do_adam"""
+    L.call('mpg_sac_alpha_update', ctypes.byref(desc), L.ptr(_f32(g)), L.c_float(clip), L.c_int(int(do_clip)), L.c_int(int(do_adam)),
+           L.ptr(skip_flag), L.c_int(skip_flag.numel() if skip_flag is not None else 0), L.stream())
+
+
 def mpg_gradients_supported(cfg, rows, M, n, n_select, n_q):
     """whether mpg_mpg_gradients serves these sizes: its workspace query answers 0 for what the entry point refuses"""
     return L.lib().mpg_mpg_gradients_workspace_bytes(ctypes.byref(cfg), *[L.c_int(int(v)) for v in (rows, M, n, n_select, n_q)]) != 0

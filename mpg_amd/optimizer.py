@@ -20,7 +20,7 @@ class SingleProcessOffPolicyOptimizer(object):
     def __init__(self, worker, learner, replay_buffer, evaluator, args, sampling_interval=10, fused=True,
                  always_exchange=False, native_sac=False):
         if native_sac:
-            # SAC's native step (mpg_sac_step_begin) is taken on request only; a request it cannot serve is an error - raised before
+            # SAC's native step (mpg_sac_step_begin, or the mpg_sac_auto_step_* pair with alpha = 'auto') is taken on request only; a request it cannot serve is an error - raised before
             # anything is sampled - never a silent fall-back to the method path
             reason = self._native_sac_refusal(worker, learner, replay_buffer, args)
             if reason:

@@ -1,5 +1,6 @@
 """PolicyWithQs - device-resident mirror of policy.py:19-245: the deterministic policy branch, and the stochastic one (a diagonal
-Gaussian over the four logits, policy.py:179-204) with a fixed temperature `alpha` and no action range.
+Gaussian over the four logits, policy.py:179-204) with a fixed temperature `alpha`, or the learned one (alpha = 'auto': AlphaModel's
+log_alpha, its Adam and target_entropy, policy.py:45-52,136-143 - one block of eight device floats, `alpha_state`), and no action range.
 
 All networks live in ONE flat float32 tensor in the order of the reference's `self.models`
 (policy.py:72-86): Q1, (Q2,) policy; the target nets in a second flat tensor in the same order; Adam moments
@@ -62,7 +63,7 @@ class PolicyWithQs(object):
                  double_Q=True, target=True, tau=0.005, delay_update=2, deterministic_policy=True, action_range=None,
                  policy_out_activation='tanh', env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift=0.,
                  gamma=0.98, value_num_hidden_units=256, policy_num_hidden_units=256, policy_only=False,
-                 device='cuda', seed=0, init_seed=0, alpha=None, **kwargs):
+                 device='cuda', seed=0, init_seed=0, alpha=None, target_entropy=None, alpha_lr_schedule=None, **kwargs):
         assert value_num_hidden_units == 256 and policy_num_hidden_units == 256, 'kernels are built for 2x256 nets'
         self.policy_only = bool(policy_only)
         # policy_only (AMPC, policy.py:72-75,125-127): the policy is the one model, no target; double_Q / target / tau / delay_update /
@@ -72,12 +73,20 @@ class PolicyWithQs(object):
             double_Q, tau, delay_update = False, 0., 1
         self.deterministic_policy = bool(deterministic_policy)
         self.alpha = None
+        self.auto_alpha = False
         if not self.deterministic_policy:
-            # the stochastic branch (SAC): a float temperature, the Gaussian head without a bijector (include/mpg_hip.h)
+            # the stochastic branch (SAC): a float temperature or the learned one, the Gaussian head without a bijector (include/mpg_hip.h)
             if isinstance(alpha, str):
-                raise ValueError("alpha = %r: the learned temperature (AlphaModel, target_entropy) is not built; pass a fixed alpha such "
-                                 "as the reference's default 0.03" % (alpha,))
-            if alpha is None or not (math.isfinite(float(alpha)) and float(alpha) >= 0.):
+                if alpha != 'auto':
+                    raise ValueError("alpha = %r: a float, or 'auto' for the learned temperature" % (alpha,))
+                # (the reference's parser adds target_entropy only for 'auto', and sac.py:144 fails without it)
+                if target_entropy is None or not math.isfinite(float(target_entropy)):
+                    raise ValueError("alpha = 'auto': the learned temperature needs a finite target_entropy (got %r), e.g. -act_dim"
+                                     % (target_entropy,))
+                if alpha_lr_schedule is None or len(alpha_lr_schedule) != 3:
+                    alpha_lr_schedule = (8e-5, 100000, 8e-6)           # built_SAC_parser's default
+                self.auto_alpha = True
+            elif alpha is None or not (math.isfinite(float(alpha)) and float(alpha) >= 0.):
                 raise ValueError('a stochastic policy needs a finite alpha >= 0 (got %r)' % (alpha,))
             if action_range is not None:
                 raise ValueError('a stochastic policy with an action_range (%r) is not built: its tanh-affine bijector changes the '
@@ -85,7 +94,7 @@ class PolicyWithQs(object):
             if act_dim != 2 or env_id != 'PathTracking-v0':
                 raise ValueError('the stochastic policy is built for PathTracking-v0 with act_dim 2 (got env_id %r, act_dim %r)'
                                  % (env_id, act_dim))
-            self.alpha = float(alpha)
+            self.alpha = 'auto' if self.auto_alpha else float(alpha)
             self.sample_seed, self._sample_ctr = int(seed) * 7919 + 104729, 0      # the policy's own stream of draws (compute_action without eps)
         self.device = torch.device(device)
         self.double_Q, self.tau, self.delay_update = bool(double_Q), float(tau), int(delay_update)
@@ -114,6 +123,26 @@ class PolicyWithQs(object):
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.cfg.status = self.status.data_ptr()
         self._bind_weight_cache()
+        if self.auto_alpha:
+            # AlphaModel (policy.py:45-52): log_alpha starts at 0.  The block is read and written on the device only (ops.ALPHA_* name
+            # its slots); the struct beside it carries target_entropy, the schedule and the step counter of the temperature's own Adam
+            self.target_entropy = float(target_entropy)
+            self.alpha_state = torch.zeros(ops.ALPHA_STATE_FLOATS, dtype=torch.float32, device=self.device)
+            self.alpha_desc = ops.SacAlphaStruct()
+            self.alpha_desc.state = self.alpha_state.data_ptr() if self.device.type == 'cuda' else None
+            self.alpha_desc.target_entropy = self.target_entropy
+            for i in range(3):
+                self.alpha_desc.lr[i] = float(alpha_lr_schedule[i])
+            self.alpha_desc.opt_steps = 0
+
+    @property
+    def log_alpha(self):
+        """the one-element device view of the learned temperature's log (what the kernels read)"""
+        return self.alpha_state[ops.ALPHA_LOG:ops.ALPHA_LOG + 1]
+
+    @property
+    def alpha_opt_steps(self):
+        return int(self.alpha_desc.opt_steps)
 
     # ---- weight cache (packed register images of the hidden kernels; caller-owned, see include/mpg_hip.h) ----
     def _bind_weight_cache(self):
@@ -157,7 +186,7 @@ class PolicyWithQs(object):
         """Data-parallel start-up: every replica takes rank 0's parameters / targets / optimizer state."""
         import torch.distributed as dist
         if dist.is_initialized() and dist.get_world_size() > 1:
-            for t in (self.params, self.targets, self.m, self.v):
+            for t in (self.params, self.targets, self.m, self.v) + ((self.alpha_state,) if self.auto_alpha else ()):
                 dist.broadcast(t, src=0)
             self.refresh_weight_cache()
 
@@ -177,14 +206,22 @@ class PolicyWithQs(object):
 
     def get_weights(self):
         """[models..., target_models...] each a list of 6 arrays (policy.py:112-114).  COPIES, like Keras' get_weights():
-        writing into them does not touch the live parameters (whose packed images would otherwise go stale)."""
+        writing into them does not touch the live parameters (whose packed images would otherwise go stale).  With the learned
+        temperature the models are [Q1, Q2, policy, alpha_model] (policy.py:84-86): [log_alpha] sits between the two halves."""
         return [self._as_list(self.net(n).clone(), n) for n in self.names] + \
+               ([[self.log_alpha.clone().view(())]] if self.auto_alpha else []) + \
                [self._as_list(self.net(n, True).clone(), n) for n in self.names if not self.policy_only]
 
     def set_weights(self, weights):
         """policy.py:116-121"""
         k = len(self.names)
         assert not self.policy_only or len(weights) == 1, 'a policy-only stack has one model and no target (policy.py:72-75)'
+        if self.auto_alpha:
+            assert len(weights) > k and len(weights[k]) == 1, 'a learned-temperature stack lists [log_alpha] behind its networks'
+            la = weights[k][0]
+            la = torch.as_tensor(np.asarray(la.cpu() if isinstance(la, torch.Tensor) else la), dtype=torch.float32).reshape(1)
+            self.log_alpha.copy_(la.to(self.device))
+            weights = list(weights[:k]) + list(weights[k + 1:])
         for i, w in enumerate(weights):
             name = self.names[i % k]
             dst = self.net(name, target=i >= k)
@@ -246,11 +283,16 @@ class PolicyWithQs(object):
     # ---- optimizer ----
     def apply_gradients(self, iteration, grads):
         """policy.py:123-156: Adam on the critics every call; policy Adam + Polyak on all targets only when
-        iteration % delay_update == 0.  grads: flat tensor (or list of arrays) in the order Q1,(Q2),policy."""
+        iteration % delay_update == 0.  grads: flat tensor (or list of arrays) in the order Q1,(Q2),policy - with the learned
+        temperature its gradient comes last (sac.py:216), and its own Adam steps together with the policy's (policy.py:136-143)."""
         if not isinstance(grads, torch.Tensor):
             grads = torch.cat([torch.as_tensor(np.asarray(g.cpu() if isinstance(g, torch.Tensor) else g),
                                                dtype=torch.float32).reshape(-1) for g in grads]).to(self.device)
         delayed = int(iteration) % self.delay_update == 0
+        n_nets = int(self.offsets[-1])
+        if self.auto_alpha and grads.numel() < n_nets + 1:
+            raise ValueError("alpha = 'auto': the gradient list ends with the temperature's gradient (%d floats, got %d)"
+                             % (n_nets + 1, grads.numel()))
         lr_t, do_adam, do_polyak = [], [], []
         for n in self.names:
             upd = (n != 'policy') or delayed or self.policy_only           # policy.py:125-127: the policy's Adam on every call
@@ -262,17 +304,27 @@ class PolicyWithQs(object):
                 self.opt_steps[n] = t
         ops.adam_polyak(self.params, self.m, self.v, self.targets, grads, self.sizes, lr_t, do_adam, do_polyak, self.tau,
                         skip_flag=self.nonfinite, wc_w=self.wc_params, wc_target=self.wc_targets)
+        if self.auto_alpha and delayed:
+            # (optimizer.py:357-361: a non-finite gradient anywhere zeroes the whole list - the networks' flags reach the temperature;
+            # its own gradient is finite whatever the policy produced, csrc/learner_api.hip GaussRow2)
+            ops.sac_alpha_update(self.alpha_desc, grads[n_nets:n_nets + 1], do_adam=True, skip_flag=self.nonfinite)
 
     # ---- checkpoint (flat blob) ----
     def state_dict(self):
-        return dict(params=self.params.cpu(), targets=self.targets.cpu(), m=self.m.cpu(), v=self.v.cpu(),
-                    opt_steps=dict(self.opt_steps), names=list(self.names))
+        sd = dict(params=self.params.cpu(), targets=self.targets.cpu(), m=self.m.cpu(), v=self.v.cpu(),
+                  opt_steps=dict(self.opt_steps), names=list(self.names))
+        if self.auto_alpha:         # (a stack with a fixed temperature keeps the keys it had)
+            sd.update(alpha_state=self.alpha_state.cpu(), alpha_opt_steps=self.alpha_opt_steps)
+        return sd
 
     def load_state_dict(self, sd):
         assert sd['names'] == self.names
         for k in ('params', 'targets', 'm', 'v'):
             getattr(self, k).copy_(sd[k].to(self.device))
         self.opt_steps = dict(sd['opt_steps'])
+        if self.auto_alpha:
+            self.alpha_state.copy_(sd['alpha_state'].to(self.device))
+            self.alpha_desc.opt_steps = int(sd['alpha_opt_steps'])
         self.refresh_weight_cache()
 
     def save_weights(self, save_dir, iteration):

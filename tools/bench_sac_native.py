@@ -9,9 +9,13 @@ around the region, a synchronise at its end), the candidates alternating region 
   (b) one SAC step at the reference's worker defaults (8 agents, batch_size 512, sampling every 10th step), B = 256 and 4096: the
       native step (native_sac=True), the method-by-method path, and the native TD3 step.
 
+  (c) --auto: the learned temperature (alpha = 'auto', target_entropy -2) - the native step (mpg_sac_auto_step_begin / _end) beside the
+      native fixed-alpha step and the 'auto' method path, same settings, B = 256 and 4096.  No bar: the fixed-alpha native step of
+      the same run is the comparison (the 'auto' step adds one mpg_normal_fill and the temperature's one-thread launch).
+
 tools/bench_sac.py stays as the record of the method-path measurement.
 
-    python tools/bench_sac_native.py [--json out.json]          prints markdown tables (EXPERIMENTS.md)"""
+    python tools/bench_sac_native.py [--auto] [--json out.json]          prints markdown tables (EXPERIMENTS.md)"""
 import argparse
 import ctypes
 import json
@@ -112,7 +116,7 @@ def worker_case(n, od):
     return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb))
 
 
-def stack(alg, B, native):
+def stack(alg, B, native, auto=False):
     from mpg_amd.buffer import ReplayBuffer
     from mpg_amd.config import default_args
     from mpg_amd.learners import SACLearner, TD3Learner
@@ -120,7 +124,8 @@ def stack(alg, B, native):
     from mpg_amd.policy import PolicyWithQs
     from mpg_amd.worker import OffPolicyWorker
     # (the settings of tools/bench_sac.py: the same replay settings for both; TD3's own parser has delay_update 2: set to SAC's 1)
-    args = default_args(alg, replay_batch_size=B, replay_starts=max(3000, B), delay_update=1, nan_check_interval=10 ** 9)
+    more = dict(alpha='auto', target_entropy=-2.) if auto else {}
+    args = default_args(alg, replay_batch_size=B, replay_starts=max(3000, B), delay_update=1, nan_check_interval=10 ** 9, **more)
     assert (args.num_agent, args.batch_size) == (8, 512)
     worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
     learner = (SACLearner if alg == 'SAC' else TD3Learner)(PolicyWithQs, args)
@@ -130,12 +135,43 @@ def stack(alg, B, native):
     return opt
 
 
+def auto_leg(out):
+    from mpg_amd.optimizer import quiesce_gc
+    out['auto'] = []
+    print("| B | SAC 'auto' native, ms | SAC fixed alpha native, ms | SAC 'auto' method path, ms | auto / fixed (native) | method / native (auto) |"
+          '\n|---|---|---|---|---|---|', flush=True)
+    for B in (256, 4096):
+        opts = [stack('SAC', B, True, auto=True), stack('SAC', B, True), stack('SAC', B, False, auto=True)]
+        quiesce_gc()
+        for _ in range(WARMUP):
+            for o in opts:
+                o.step()
+        torch.cuda.synchronize()
+        t = [[], [], []]
+        for _ in range(REGIONS):                              # alternating: all three see the same machine
+            for k, o in enumerate(opts):
+                t[k].append(timed(o.step, REPS))
+        m = [statistics.median(x) for x in t]
+        out['auto'].append(dict(B=B, auto_native_ms=m[0], auto_native_range=(min(t[0]), max(t[0])), fixed_native_ms=m[1],
+                                fixed_native_range=(min(t[1]), max(t[1])), auto_method_ms=m[2], auto_method_range=(min(t[2]), max(t[2]))))
+        print('| %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f | %.2f |'
+              % (B, m[0], min(t[0]), max(t[0]), m[1], min(t[1]), max(t[1]), m[2], min(t[2]), max(t[2]), m[0] / m[1], m[2] / m[0]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--json', default=None)
+    ap.add_argument('--auto', action='store_true', help="the learned temperature's table only")
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_sac_native.py needs a GPU: nothing here is measured without one'
     from mpg_amd.optimizer import quiesce_gc
+    if a.auto:
+        out = {}
+        auto_leg(out)
+        if a.json:
+            with open(a.json, 'w') as fh:
+                json.dump(out, fh, indent=1)
+        return
     out = {'worker': [], 'step': []}
     print('| agents | obs_dim | (a) three calls, 4 launches, ms | (b) mpg_worker_sample_step, ms | (a) / (b) |\n|---|---|---|---|---|', flush=True)
     for od in (6, 9):
