@@ -305,6 +305,11 @@ int mpg_q_loss_grad(const mpg_cfg_t* cfg, const float* q_params, int rows, const
  * :186-194 where every step goes through pi_theta (needs rows*M % 16 == 0).
  *
  *   rows   B_local start states obs0 [rows][obs_dim]  (the M copies are tiled inside: trajectory = m*rows + b)
+ *          PathTracking start states are taken as they are, like the reference takes them: any v_x (the clamp to [1, 35],
+ *          path_tracking_env.py:289, applies to every state the MODEL produces, and the adjoint of v_x is zero across a clamped
+ *          step) and any heading error the float32 sine accepts - a start observation is NOT wrapped into (-pi, pi], every model
+ *          state is (:290-291).  Tested with v_x at both ends of the clamp and |heading error| up to 3.5
+ *          (tests/test_model_edges_gpu.py); the pendulum's angle is not range-limited.
  *   eps    [n][M*rows] standard-normal draws for the model's injected noise
  *          (path_tracking_env.py:119: dy += 0.5 + 0.01 eps; inverted_pendulum_model.py:61: p += 0.1 + 0.5 eps);
  *          NULL: drawn inside the kernel from Philox4x32-10 keyed by (noise_seed, noise_ctr, step, trajectory)

@@ -51,12 +51,12 @@ def make_model(cfg):
     return DP.DoublePendulumModelOracle() if cfg.env == DP.ENV_ID else O.make_model(cfg)
 
 
-def model_rollout_for_policy_update(cfg, nets, start_obses, eps):
+def model_rollout_for_policy_update(cfg, nets, start_obses, eps, model=None):
     """AMPCLearner.model_rollout_for_policy_update, ampc.py:73-87.  eps [n, M*B] standard normal (None: a model without noise).
-    Returns (policy_loss, rewards_sum [M*B])."""
+    model: a model object to roll instead of make_model(cfg) (tests/model_edge_inputs.py).  Returns (policy_loss, rewards_sum [M*B])."""
     dt = nets.dtype
     obses = start_obses.repeat(cfg.M, 1)                                     # :74
-    model = make_model(cfg)
+    model = make_model(cfg) if model is None else model
     model.reset(obses)                                                       # :75
     rsum = torch.zeros(obses.shape[0], dtype=dt)                             # :76
     for t in range(cfg.n):                                                   # :79
@@ -66,13 +66,13 @@ def model_rollout_for_policy_update(cfg, nets, start_obses, eps):
     return -rsum.mean(), rsum                                                # :85
 
 
-def compute_gradient(cfg, nets, batch_obs, eps, clip=True):
+def compute_gradient(cfg, nets, batch_obs, eps, clip=True, model=None):
     """AMPCLearner.compute_gradient, ampc.py:105-122.  Returns (the policy's 6 gradient arrays as numpy, stats with the un-clipped
     flat gradient and the per-trajectory reward sums)."""
     dt = nets.dtype
     obs = torch.as_tensor(np.asarray(batch_obs, dtype=np.float32)).to(dt)
     e = None if eps is None else torch.as_tensor(np.asarray(eps, dtype=np.float32)).to(dt)
-    loss, rsum = model_rollout_for_policy_update(cfg, nets, obs, e)
+    loss, rsum = model_rollout_for_policy_update(cfg, nets, obs, e, model=model)
     raw = list(torch.autograd.grad(loss, nets.w['policy']))
     pg, pn = O.clip_by_global_norm(raw, cfg.clip)
     stats = dict(policy_loss=loss.detach().numpy(), policy_gradient_norm=pn.numpy(), rewards_sum=rsum.detach().numpy(),
