@@ -552,6 +552,42 @@ int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const fl
 int mpg_sac_alpha_update(mpg_sac_alpha_t* a, float* g, float clip, int do_clip, int do_adam, const int* skip_flags /* nullable */,
                          int n_skip_flags, mpg_stream_t stream);
 
+/* ---- SAC with an action range: the tanh-squashed Gaussian head (policy.py:183-190: the same diagonal Gaussian wrapped in
+ * Chain([Affine(scale = action_range), Tanh()]); train_script4mujoco.py built_SAC_parser: InvertedPendulumConti-v0, action_range 3) ----
+ * The five entry points above with R = cfg->action_range > 0 and ad = act_dim, u_k = mean_k + sigma_k * eps_k formed as there:
+ *   act_k = R * tanh(u_k)
+ *   logp  = sum_k (-0.5 eps_k^2 - log_std_k - 0.5 log(2 pi)) - sum_k 2 (log 2 - u_k - softplus(-2 u_k)) - ad * log R
+ * (the Tanh bijector's forward_log_det_jacobian and Affine's; evaluated at u itself - TFP's bijector cache hands log_prob the x that
+ * produced the sample - not at atanh(act / R)).  logits_out [rows][2 ad] is the policy's plain output: the range never reaches it.
+ * The policy gradient of mean(alpha * logp - min Q): dL/du_k = ga_k R (1 - tanh(u_k)^2) + 2 alpha inv_b tanh(u_k), ga the critics'
+ * summed input gradient at the action; the mean column receives dL/du_k, the log-std column dL/du_k sigma_k eps_k - alpha inv_b, zero
+ * outside [-5, 1].  The _auto forms read alpha = exp(*log_alpha) on the device and sum the SQUASHED log-density under eps_alpha into
+ * alpha_grad; given the same alpha they return the fixed-alpha forms' bits.  Same arguments, launches and workspace layouts as the plain
+ * siblings (the _auto forms share the fixed-alpha queries); eps / eps_alpha are [rows][act_dim].
+ * Served: act_dim 2 on MPG_ENV_PATH_TRACKING with obs_dim 6 .. 16, and act_dim 1 with obs_dim 4 on MPG_ENV_INVERTED_PENDULUM.
+ * Refused before any launch with MPG_EINVAL, each with its own text under the entry point's name, prefilled outputs untouched: null
+ * pointers (logits_out alone may be null), rows <= 0, MPG_ENV_INVERTED_DOUBLE_PENDULUM, another act_dim / env_kind pair,
+ * action_range <= 0 or not finite, policy_out_act MPG_ACT_TANH together with the range, another observation width, alpha < 0 or not
+ * finite, a target_entropy that is not finite; a workspace one byte short is MPG_EWORKSPACE with both sizes.  The queries answer 0 for
+ * what the entry points refuse.  The plain entry points keep refusing every cfg with a range. */
+size_t mpg_policy_sample_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_policy_sample_squashed(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
+                               float* logp_out, float* logits_out /* nullable */, void* ws, size_t ws_bytes, mpg_stream_t stream);
+size_t mpg_sac_targets_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_sac_targets_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                             const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes, mpg_stream_t stream);
+size_t mpg_sac_policy_grad_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows);
+int mpg_sac_policy_grad_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                                 const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                                 float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
+int mpg_sac_targets_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                                  const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
+                                  mpg_stream_t stream);
+int mpg_sac_policy_grad_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows,
+                                      const float* obs, const float* eps, const float* log_alpha, const float* eps_alpha,
+                                      float target_entropy, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                                      float* alpha_grad, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * clip_by_global_norm + Keras Adam + Polyak (K7, K8) over the flat [net0 | net1 | ...] vectors
  * ---------------------------------------------------------------------------------------------- */

@@ -54,7 +54,9 @@ def state_of(optimizer):
         # (sample_ctr: the stochastic policy's own stream of draws; absent for a deterministic policy)
         policy=dict(opt_steps={k: int(v) for k, v in pw.opt_steps.items()},
                     **({'sample_ctr': int(pw._sample_ctr)} if not getattr(pw, 'deterministic_policy', True) else {}),
-                    **({'alpha_opt_steps': pw.alpha_opt_steps} if getattr(pw, 'auto_alpha', False) else {})),
+                    **({'alpha_opt_steps': pw.alpha_opt_steps} if getattr(pw, 'auto_alpha', False) else {}),
+                    # (the tanh-squashed head: written by a squashed stack only, so every other checkpoint keeps its meta)
+                    **({'squashed_head': True} if getattr(pw, 'squashed_head', False) else {})),
         worker=dict(seed=w.seed, noise_ctr=w._noise_ctr, env_seed=w.env.seed, env_ctr=w.env._ctr, num_sample=w.num_sample,
                     sample_times=w.sample_times, iteration=w.iteration, env_initialised=bool(w.env._initialised)),
         learner=dict(seed=ln.seed, counter=ln.counter),
@@ -102,6 +104,8 @@ def load_checkpoint(path, optimizer):
     if getattr(pw, 'auto_alpha', False):
         put(pw.alpha_state, 'policy/alpha_state')
         pw.alpha_desc.opt_steps = int(meta['policy']['alpha_opt_steps'])
+    if bool(meta['policy'].get('squashed_head', False)) != bool(getattr(pw, 'squashed_head', False)):
+        raise ValueError('checkpoint and run differ in the policy head: one is tanh-squashed (squashed_head=True), the other is not')
     pw.refresh_weight_cache()
     put(w.env._state, 'worker/env_state')
     m = meta['worker']

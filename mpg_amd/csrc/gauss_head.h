@@ -1,5 +1,5 @@
-// Gaussian policy head (policy.py:179-204 with action_range None: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))), no bijector)
-// on the four logits of the policy pass, and the element function of the library's standard-normal stream.  Shared by the two
+// Gaussian policy head (policy.py:179-204: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))); with action_range None no bijector,
+// with one the tanh-squashed sibling further down) on the 2 act_dim logits of the policy pass, and the element function of the library's standard-normal stream.  Shared by the two
 // translation units that evaluate the head - learner_api.hip (k_row_sums<GaussRow>, k_sac_dlogits) and env_path_tracking.hip (the
 // stochastic worker launch) - which must agree bit for bit: include it where contraction is allowed (env_path_tracking.hip: inside
 // its `#pragma clang fp contract(fast)` block), so that both compile these expressions under the same rule.
@@ -45,6 +45,50 @@ __device__ __forceinline__ float gauss_logp(int ad, const float* __restrict__ l,
     }
     return lp;
 }
+// ---- the tanh-squashed head (policy.py:183-190 with an action_range R: the same diagonal Gaussian under Chain([Affine(R), Tanh()])) ----
+// act = R tanh(u), u = mean + sigma * eps formed as gauss_row forms it;
+// logp = [gauss_row's sum] - sum_k 2 (log 2 - u_k - softplus(-2 u_k)) - ad log R: the Tanh bijector's published
+// forward_log_det_jacobian and Affine's.  The density is evaluated at u ITSELF, not at atanh(act / R): TFP's bijector cache returns the
+// x that produced y when log_prob is called on the tensor sample() returned - the decision of z = eps in gauss_row, for its reason
+// (and atanh of a saturated act is infinite where u is merely large).
+// tanh_ldj(u) = 2 (log 2 - u - softplus(-2 u)) = log(1 - tanh(u)^2), an even function: evaluated at |u|, where softplus(-2 |u|) =
+// log1p(exp(-2 |u|)) has an argument in (0, 1] - no overflow at any u, and no difference of two large terms on the negative side
+constexpr float LOG_2 = 0.69314718055994531f;
+__device__ __forceinline__ float tanh_ldj(float u) {
+    const float au = fabsf(u);
+    return 2.f * ((LOG_2 - au) - log1pf(expf(-2.f * au)));
+}
+// 1 - tanh(u)^2 = 4 e / (1 + e)^2 with e = exp(-2 |u|): no cancellation where tanh saturates
+__device__ __forceinline__ float sech2(float u) {
+    const float e = expf(-2.f * fabsf(u)), d = 1.f + e;
+    return 4.f * e / (d * d);
+}
+// log R of the Affine bijector as the correctly rounded float32 logarithm (sigma_of's rule), formed on the host
+inline float log_range(float range) { return (float)log((double)range); }
+// gauss_row under the bijectors: a[k] = range * tanh(u_k); returns the squashed log-density
+__device__ __forceinline__ float squash_row(int ad, float range, float log_r, const float* __restrict__ l, const float* __restrict__ e,
+                                            float* __restrict__ a) {
+    float lp = 0.f, ldj = 0.f;
+    for (int k = 0; k < ad; ++k) {
+        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), sigma = sigma_of(ls), z = e[k];
+        const float u = mul_then_add(sigma, z, l[k]);
+        a[k] = range * tanhf(u);
+        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
+        ldj += tanh_ldj(u);
+    }
+    return (lp - ldj) - (float)ad * log_r;
+}
+// the squashed log-density alone under another draw (gauss_logp's role): squash_row's terms in squash_row's order
+__device__ __forceinline__ float squash_logp(int ad, float log_r, const float* __restrict__ l, const float* __restrict__ e) {
+    float lp = 0.f, ldj = 0.f;
+    for (int k = 0; k < ad; ++k) {
+        const float ls = fminf(fmaxf(l[ad + k], LOG_STD_MIN), LOG_STD_MAX), sigma = sigma_of(ls), z = e[k];
+        lp += (-0.5f * z * z - ls) - HALF_LOG_2PI;
+        ldj += tanh_ldj(mul_then_add(sigma, z, l[k]));
+    }
+    return (lp - ldj) - (float)ad * log_r;
+}
+
 // alpha = exp(log_alpha) of the learned temperature, under sigma_of's rule and for its reason: the correctly rounded float32
 // exponential, which anyone can re-form on the host bit for bit
 __device__ __forceinline__ float alpha_of(const float* __restrict__ log_alpha) { return (float)exp((double)*log_alpha); }
@@ -80,6 +124,26 @@ inline int gauss_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers,
     MPG_REQUIRE(!(cfg->action_range > 0.f), "%s: Gaussian head without an action range only (got action_range %g)", entry,
                 (double)cfg->action_range);
     MPG_REQUIRE(cfg->obs_dim >= 6 && cfg->obs_dim <= 16, "%s: unsupported observation width %d", entry, cfg->obs_dim);
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
+    return MPG_OK;
+}
+
+// The refusals of the squashed entry points (mpg_*_squashed and their queries), each with a text of its own: PathTracking (act_dim 2,
+// obs_dim 6 .. 16) or the inverted pendulum (act_dim 1, obs_dim 4), a positive action range over a linear output.
+inline int squash_refusal(const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
+    MPG_REQUIRE(cfg && pointers, "%s: null pointer", entry);
+    MPG_REQUIRE(rows > 0, "%s: rows must be positive (got %d)", entry, rows);
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "%s: the squashed head is not built for the double pendulum (env_kind %d)",
+                entry, cfg->env_kind);
+    MPG_REQUIRE((cfg->act_dim == 2 && cfg->env_kind == MPG_ENV_PATH_TRACKING) || (cfg->act_dim == 1 && cfg->env_kind == MPG_ENV_INVERTED_PENDULUM),
+                "%s: squashed head on PathTracking (act_dim 2) or the inverted pendulum (act_dim 1) only (got act_dim %d, env_kind %d)", entry,
+                cfg->act_dim, cfg->env_kind);
+    MPG_REQUIRE(cfg->action_range > 0.f && cfg->action_range <= 3.4028234664e38f,
+                "%s: the squashed head needs a positive, finite action range (got action_range %g)", entry, (double)cfg->action_range);
+    MPG_REQUIRE(cfg->policy_out_act != MPG_ACT_TANH, "%s: a tanh output activation under an action range is not built (range * tanh(tanh(z)))",
+                entry);
+    MPG_REQUIRE(cfg->act_dim == 2 ? (cfg->obs_dim >= 6 && cfg->obs_dim <= 16) : cfg->obs_dim == 4, "%s: unsupported observation width %d", entry,
+                cfg->obs_dim);
     MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
     return MPG_OK;
 }

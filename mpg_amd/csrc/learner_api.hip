@@ -309,6 +309,63 @@ __global__ void k_sac_dlogits_auto(int rows, int od, int ad, const float* __rest
     dlogits[(long)row * 2 * ad + ad + k] = inside ? ga * sigma * eps[i] - alpha * inv_b : 0.f;
 }
 
+// ---- the tanh-squashed head (gauss_head.h squash_row): GaussRow / GaussRow2 / k_sac_dlogits under an action range.  Siblings, so that
+// every kernel above keeps its code; the bijectors' correction rides in the same launches ------------------------------------------------
+struct SquashRow {
+    int ad;
+    float range, log_r;
+    const float *__restrict__ logits, *__restrict__ eps;
+    float *__restrict__ act, *__restrict__ logp;
+    static constexpr int NS = 1;
+    static constexpr bool SUM_OPTIONAL = true;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
+        const float lp = squash_row(ad, range, log_r, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
+        logp[i] = lp;
+        s[0] += lp;
+    }
+};
+// (the temperature's sum takes the SQUASHED log-density under the further draw: the third compute_action goes through the same bijectors)
+struct SquashRow2 {
+    int ad;
+    float range, log_r;
+    const float *__restrict__ logits, *__restrict__ eps, *__restrict__ eps_alpha;
+    float target_entropy, inv_b;
+    float *__restrict__ act, *__restrict__ logp;
+    static constexpr int NS = 2;
+    static constexpr bool SUM_OPTIONAL = false;
+    __host__ __device__ float scale0() const { return 1.f; }
+    __host__ __device__ float scale1() const { return -inv_b; }
+    __device__ __forceinline__ void operator()(int i, float* s) const {
+        const float* l = logits + (size_t)i * 2 * ad;
+        const float lp = squash_row(ad, range, log_r, l, eps + (size_t)i * ad, act + (size_t)i * ad);
+        logp[i] = lp;
+        s[0] += lp;
+        s[1] += squash_logp(ad, log_r, l, eps_alpha + (size_t)i * ad) + target_entropy;
+    }
+};
+
+// k_sac_dlogits under the bijectors: a = R tanh(u), logp = ... - log(1 - tanh(u)^2) - log R with u = mean + sigma * eps, so
+// dL/du_k = ga_k R (1 - t_k^2) + 2 alpha inv_b t_k (t = tanh u); mean column: dL/du; log-std column: dL/du sigma eps - alpha inv_b, zero
+// where the clip is active.  AUTO: the learned temperature read on the device (alpha_of) - `alpha` is then not looked at.
+template <bool AUTO>
+__global__ void k_sac_dlogits_squashed(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
+                                       const float* __restrict__ eps, const float* __restrict__ logits, float alpha,
+                                       const float* __restrict__ log_alpha, float range, float inv_b, float* __restrict__ dlogits) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * ad) return;
+    if constexpr (AUTO) alpha = alpha_of(log_alpha);
+    const int row = i / ad, k = i % ad;
+    const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
+    const float raw = logits[(long)row * 2 * ad + ad + k];
+    const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
+    const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
+    const float u = mul_then_add(sigma, eps[i], logits[(long)row * 2 * ad + k]);
+    const float du = ga * range * sech2(u) + 2.f * alpha * inv_b * tanhf(u);
+    dlogits[(long)row * 2 * ad + k] = du;
+    dlogits[(long)row * 2 * ad + ad + k] = inside ? du * sigma * eps[i] - alpha * inv_b : 0.f;
+}
+
 // ---- workspaces: one description each (host_glue.h Arena) ----------------------------------------------------------
 struct QTargetsWs {        // mpg_q_targets, mpg_td3_targets, mpg_nstep_targets (which leaves q2 unused)
     float *a, *q1, *q2;
@@ -377,15 +434,22 @@ SacTargetsWs sac_targets_ws(Arena& ar, const mpg_cfg_t* cfg, int rows) {
     return w;
 }
 
-// all four logits of the policy (MLPNet's output activation on every column, no action range), optional stashes
-int policy_logits(const mpg_cfg_t* c, const float* params, int rows, const float* obs, float* logits, float* h1, float* h2, hipStream_t s) {
+// all 2 act_dim logits of the policy (MLPNet's output activation on every column; an action range never reaches them), optional stashes
+OutSpec logits_out(const mpg_cfg_t* c) {
     OutSpec o = linear_out();
     o.out_tanh = c->policy_out_act == MPG_ACT_TANH;
-    return launch_forward(c, params, c->obs_dim, 2 * c->act_dim, 2 * c->act_dim, rows, policy_x(c, obs), o, logits, 2 * c->act_dim, h1, h2, s);
+    return o;
 }
-// the head on `logits`: act, logp and (nullable) the sum of logp
+int policy_logits(const mpg_cfg_t* c, const float* params, int rows, const float* obs, float* logits, float* h1, float* h2, hipStream_t s) {
+    return launch_forward(c, params, c->obs_dim, 2 * c->act_dim, 2 * c->act_dim, rows, policy_x(c, obs), logits_out(c), logits, 2 * c->act_dim,
+                          h1, h2, s);
+}
+// the head on `logits`: act, logp and (nullable) the sum of logp; `squash`: under the bijectors of cfg->action_range
 int gauss_head(const mpg_cfg_t* c, int rows, const float* logits, const float* eps, float* act, float* logp, float* logp_sum, float* parts,
-               hipStream_t s) {
+               hipStream_t s, bool squash = false) {
+    if (squash)
+        return launch_row_sums("k_row_sums<SquashRow>", SquashRow{c->act_dim, c->action_range, log_range(c->action_range), logits, eps, act, logp},
+                               rows, parts, logp_sum, nullptr, nullptr, s);
     return launch_row_sums("k_row_sums<GaussRow>", GaussRow{c->act_dim, logits, eps, act, logp}, rows, parts, logp_sum, nullptr, nullptr, s);
 }
 
@@ -401,24 +465,33 @@ struct AutoTemp {
 };
 int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
                 const float* eps, float alpha, float inv_b, float* q_sum, float* q_sqsum, float* logp_sum, float* grad, void* ws,
-                size_t ws_bytes, mpg_stream_t stream, const AutoTemp* at = nullptr) {
+                size_t ws_bytes, mpg_stream_t stream, const AutoTemp* at = nullptr, bool squash = false) {
     const int n_q = q2 ? 2 : 1;
     Arena ar(ws, ws_bytes);
     const PolicyGradWs w = policy_grad_ws(ar, cfg, rows, n_q, eps != nullptr);
     if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
     const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, ou = eps ? 2 * ad : ad;
-    const OutSpec po = policy_out(cfg);        // (the head has no action range: the plain output activation on all four columns)
+    // (the backward of the logits pass undoes the logits' output rule - the plain activation on every column: with an action range
+    // policy_out is the DETERMINISTIC output rule, range * tanh on the mean, which the squashed head applies itself)
+    const OutSpec po = squash ? logits_out(cfg) : policy_out(cfg);
     const XSpec xp = policy_x(cfg, obs);
     const float* const q[2] = {q1, q2};
     int rc;
     if (eps) {
         rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);
         if (rc) return rc;
-        rc = at ? launch_row_sums("k_row_sums<GaussRow2>",
-                                  GaussRow2{cfg->act_dim, w.logits, eps, at->eps_alpha, at->target_entropy, inv_b, w.a, w.logp}, rows, w.lparts,
-                                  logp_sum, at->alpha_grad, nullptr, s)
-                : gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s);
+        if (at && squash)
+            rc = launch_row_sums("k_row_sums<SquashRow2>",
+                                 SquashRow2{cfg->act_dim, cfg->action_range, log_range(cfg->action_range), w.logits, eps, at->eps_alpha,
+                                            at->target_entropy, inv_b, w.a, w.logp},
+                                 rows, w.lparts, logp_sum, at->alpha_grad, nullptr, s);
+        else if (at)
+            rc = launch_row_sums("k_row_sums<GaussRow2>",
+                                 GaussRow2{cfg->act_dim, w.logits, eps, at->eps_alpha, at->target_entropy, inv_b, w.a, w.logp}, rows, w.lparts,
+                                 logp_sum, at->alpha_grad, nullptr, s);
+        else
+            rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s, squash);
     } else {
         rc = policy_forward(cfg, policy, rows, xp, po, w.a, w.hp1, w.hp2, s);
     }
@@ -444,7 +517,13 @@ int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, co
     const float* g = w.dx[0] + od;
     int ldg = qin;
     if (n_q == 2) {
-        if (at)
+        if (squash && at)
+            hipLaunchKernelGGL(k_sac_dlogits_squashed<true>, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps,
+                               w.logits, 0.f, at->log_alpha, cfg->action_range, inv_b, w.g);
+        else if (squash)
+            hipLaunchKernelGGL(k_sac_dlogits_squashed<false>, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps,
+                               w.logits, alpha, (const float*)nullptr, cfg->action_range, inv_b, w.g);
+        else if (at)
             hipLaunchKernelGGL(k_sac_dlogits_auto, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits,
                                at->log_alpha, inv_b, w.g);
         else if (eps)
@@ -658,18 +737,59 @@ extern "C" size_t mpg_policy_sample_workspace_bytes(const mpg_cfg_t* cfg, int ro
     return measured(policy_sample_ws, cfg, rows);
 }
 
-extern "C" int mpg_policy_sample(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
-                                 float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = gauss_refusal("mpg_policy_sample", cfg, policy && obs && eps && act_out && logp_out && ws, rows, 0.f);
+namespace {
+// the refusal of an entry point's family: the plain Gaussian head's, or the squashed one's
+int head_refusal(bool squash, const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
+    return squash ? squash_refusal(entry, cfg, pointers, rows, alpha) : gauss_refusal(entry, cfg, pointers, rows, alpha);
+}
+// mpg_policy_sample / mpg_policy_sample_squashed
+int policy_sample(const char* entry, bool squash, const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps,
+                  float* act_out, float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = head_refusal(squash, entry, cfg, policy && obs && eps && act_out && logp_out && ws, rows, 0.f);
     if (rc) return rc;
     Arena ar(ws, ws_bytes);
     const PolicySampleWs w = policy_sample_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_policy_sample", ws_bytes, ar.need);
+    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
     float* logits = logits_out ? logits_out : w.logits;
     rc = policy_logits(cfg, policy, rows, obs, logits, nullptr, nullptr, s);
     if (rc) return rc;
-    return gauss_head(cfg, rows, logits, eps, act_out, logp_out, nullptr, nullptr, s);
+    return gauss_head(cfg, rows, logits, eps, act_out, logp_out, nullptr, nullptr, s, squash);
+}
+// mpg_sac_targets and its _auto / _squashed forms (log_alpha non-null: the learned temperature, read on the device)
+int sac_targets(const char* entry, bool squash, const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
+                const float* rew, const float* obs_tp1, const float* eps, bool auto_alpha, float alpha, const float* log_alpha, float* y,
+                void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = head_refusal(squash, entry, cfg, policy && q1t && q2t && rew && obs_tp1 && eps && (log_alpha || !auto_alpha) && y && ws, rows,
+                          auto_alpha ? 0.f : alpha);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);          // sac.py:71
+    if (rc) return rc;
+    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s, squash);
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);                     // :73
+    if (rc) return rc;
+    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);                     // :74
+    if (rc) return rc;
+    if (auto_alpha)
+        hipLaunchKernelGGL(k_sac_combine_auto, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, log_alpha, cfg->rew_shift,
+                           cfg->rew_scale, cfg->gamma, y);
+    else
+        hipLaunchKernelGGL(k_sac_combine, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, alpha, cfg->rew_shift,
+                           cfg->rew_scale, cfg->gamma, y);                                  // :78-79
+    MPG_CHECK_LAUNCH(auto_alpha ? "k_sac_combine_auto" : "k_sac_combine");
+    return MPG_OK;
+}
+}  // namespace
+
+extern "C" int mpg_policy_sample(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
+                                 float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    return policy_sample("mpg_policy_sample", false, cfg, policy, rows, obs, eps, act_out, logp_out, logits_out, ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
@@ -680,25 +800,7 @@ extern "C" size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows
 extern "C" int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
                                const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes,
                                mpg_stream_t stream) {
-    int rc = gauss_refusal("mpg_sac_targets", cfg, policy && q1t && q2t && rew && obs_tp1 && eps && y && ws, rows, alpha);
-    if (rc) return rc;
-    Arena ar(ws, ws_bytes);
-    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_sac_targets", ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);          // sac.py:71
-    if (rc) return rc;
-    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s);
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
-    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);                     // :73
-    if (rc) return rc;
-    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);                     // :74
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sac_combine, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, alpha, cfg->rew_shift,
-                       cfg->rew_scale, cfg->gamma, y);                                      // :78-79
-    MPG_CHECK_LAUNCH("k_sac_combine");
-    return MPG_OK;
+    return sac_targets("mpg_sac_targets", false, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, false, alpha, nullptr, y, ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
@@ -723,25 +825,8 @@ extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, co
 extern "C" int mpg_sac_targets_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
                                     const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
                                     mpg_stream_t stream) {
-    int rc = gauss_refusal("mpg_sac_targets_auto", cfg, policy && q1t && q2t && rew && obs_tp1 && eps && log_alpha && y && ws, rows, 0.f);
-    if (rc) return rc;
-    Arena ar(ws, ws_bytes);
-    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_sac_targets_auto", ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);
-    if (rc) return rc;
-    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s);
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
-    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);
-    if (rc) return rc;
-    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sac_combine_auto, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, log_alpha, cfg->rew_shift,
-                       cfg->rew_scale, cfg->gamma, y);
-    MPG_CHECK_LAUNCH("k_sac_combine_auto");
-    return MPG_OK;
+    return sac_targets("mpg_sac_targets_auto", false, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, true, 0.f, log_alpha, y, ws, ws_bytes,
+                       stream);
 }
 
 extern "C" int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
@@ -756,4 +841,65 @@ extern "C" int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* polic
     const AutoTemp at{log_alpha, eps_alpha, target_entropy, alpha_grad};
     return policy_grad("mpg_sac_policy_grad_auto", cfg, policy, q1, q2, rows, obs, eps, 0.f, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
                        ws_bytes, stream, &at);
+}
+
+// ---- the tanh-squashed head (gauss_head.h squash_row): the five entry points above under cfg->action_range, on PathTracking or the
+// inverted pendulum.  The same launches as their plain siblings, the same workspaces described for the cfg's act_dim ----
+extern "C" size_t mpg_policy_sample_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (squash_refusal("mpg_policy_sample_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(policy_sample_ws, cfg, rows);
+}
+
+extern "C" int mpg_policy_sample_squashed(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps,
+                                          float* act_out, float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    return policy_sample("mpg_policy_sample_squashed", true, cfg, policy, rows, obs, eps, act_out, logp_out, logits_out, ws, ws_bytes, stream);
+}
+
+extern "C" size_t mpg_sac_targets_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (squash_refusal("mpg_sac_targets_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(sac_targets_ws, cfg, rows);
+}
+
+extern "C" int mpg_sac_targets_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
+                                        const float* rew, const float* obs_tp1, const float* eps, float alpha, float* y, void* ws,
+                                        size_t ws_bytes, mpg_stream_t stream) {
+    return sac_targets("mpg_sac_targets_squashed", true, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, false, alpha, nullptr, y, ws, ws_bytes,
+                       stream);
+}
+
+extern "C" int mpg_sac_targets_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
+                                             const float* rew, const float* obs_tp1, const float* eps, const float* log_alpha, float* y,
+                                             void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    return sac_targets("mpg_sac_targets_squashed_auto", true, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, true, 0.f, log_alpha, y, ws,
+                       ws_bytes, stream);
+}
+
+extern "C" size_t mpg_sac_policy_grad_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    if (squash_refusal("mpg_sac_policy_grad_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
+    return measured(policy_grad_ws, cfg, rows, 2, true);
+}
+
+// (the pendulum's two logits take the THIN backward like TD3's two actions; PathTracking's four the plain one, as mpg_sac_policy_grad)
+extern "C" int mpg_sac_policy_grad_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows,
+                                            const float* obs, const float* eps, float alpha, float inv_b_global, float* qmin_sum,
+                                            float* qmin_sqsum, float* logp_sum, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = squash_refusal("mpg_sac_policy_grad_squashed", cfg, policy && q1 && q2 && obs && eps && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
+                            rows, alpha);
+    if (rc) return rc;
+    return policy_grad("mpg_sac_policy_grad_squashed", cfg, policy, q1, q2, rows, obs, eps, alpha, inv_b_global, qmin_sum, qmin_sqsum, logp_sum,
+                       grad, ws, ws_bytes, stream, nullptr, true);
+}
+
+extern "C" int mpg_sac_policy_grad_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows,
+                                                 const float* obs, const float* eps, const float* log_alpha, const float* eps_alpha,
+                                                 float target_entropy, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                                                 float* alpha_grad, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = squash_refusal("mpg_sac_policy_grad_squashed_auto", cfg,
+                            policy && q1 && q2 && obs && eps && log_alpha && eps_alpha && qmin_sum && qmin_sqsum && logp_sum && alpha_grad && grad && ws,
+                            rows, 0.f);
+    if (rc) return rc;
+    MPG_REQUIRE(std::isfinite(target_entropy), "mpg_sac_policy_grad_squashed_auto: target_entropy must be finite (got %g)", (double)target_entropy);
+    const AutoTemp at{log_alpha, eps_alpha, target_entropy, alpha_grad};
+    return policy_grad("mpg_sac_policy_grad_squashed_auto", cfg, policy, q1, q2, rows, obs, eps, 0.f, inv_b_global, qmin_sum, qmin_sqsum, logp_sum,
+                       grad, ws, ws_bytes, stream, &at, true);
 }

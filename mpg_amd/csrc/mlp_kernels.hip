@@ -132,6 +132,7 @@ __global__ void __launch_bounds__(NTHREAD, 2) k_forward(const FwdArgs a) {
     if ((in_dim) == 6 && (ou) == 2) { CALL(6, 2); }                           \
     else if ((in_dim) == 8 && (ou) == 1) { CALL(8, 1); }                      \
     else if ((in_dim) == 4 && (ou) == 1) { CALL(4, 1); }                      \
+    else if ((in_dim) == 4 && (ou) == 2) { CALL(4, 2); }                      \
     else if ((in_dim) == 5 && (ou) == 1) { CALL(5, 1); }                      \
     else if ((in_dim) == 6 && (ou) == 1) { CALL(6, 1); }                      \
     else if ((in_dim) > 8 && (in_dim) <= 16 && (ou) == 2) { CALL(16, 2); }    \

@@ -449,7 +449,9 @@ class NDPGLearner(_LearnerBase):
 
 class SACLearner(_LearnerBase):
     """Soft actor-critic (learners/sac.py:21-219): networks [Q1 | Q2 | policy], the policy a diagonal Gaussian over its four logits
-    (policy.py:179-204, no action range).  PathTracking-v0 only.
+    (policy.py:179-204, no action range): PathTracking-v0.  With args.squashed_head the Gaussian sits under the tanh-affine bijectors of
+    args.action_range (policy.py:183-190; the mpg_*_squashed entry points): PathTracking-v0 with a range, and InvertedPendulumConti-v0
+    (built_SAC_parser of train_script4mujoco.py) - fixed or learned temperature, either buffer, any number of ranks.
     Every draw is the library's Philox stream keyed by (learner seed, call counter): two per gradient call - the action at s' for the
     target (from the ONLINE policy, sac.py:71) and the action of the policy loss (:123) - and one more, from the TARGET policy, for a
     prioritized buffer's td error (:88).
@@ -465,7 +467,12 @@ class SACLearner(_LearnerBase):
                              "train_script.py:672-792; sac.py:144 reads it): default_args('SAC', alpha='auto', target_entropy=-2.)")
         if getattr(args, 'deterministic_policy', True):
             raise ValueError('SACLearner needs deterministic_policy=False (built_SAC_parser, train_script.py:672-792)')
-        if args.env_id != 'PathTracking-v0':
+        # the tanh-squashed head (args.squashed_head, on request): PathTracking-v0 with an action_range, and InvertedPendulumConti-v0
+        self.squashed = bool(getattr(args, 'squashed_head', False))
+        if self.squashed and args.env_id not in ('PathTracking-v0', 'InvertedPendulumConti-v0'):
+            raise ValueError('SACLearner with squashed_head=True serves PathTracking-v0 and InvertedPendulumConti-v0 (got env_id %r)'
+                             % (args.env_id,))
+        if not self.squashed and args.env_id != 'PathTracking-v0':
             raise ValueError('SACLearner serves PathTracking-v0 only (got env_id %r): the pendulum\'s action_range is a tanh-affine '
                              'bijector whose log-density correction is not built' % (args.env_id,))
         super().__init__(policy_cls, args, device)
@@ -479,6 +486,9 @@ class SACLearner(_LearnerBase):
     def alpha(self):
         return self.policy_with_value.alpha
 
+    def _sac_targets(self, *a):
+        return (ops.sac_targets_squashed if self.squashed else ops.sac_targets)(*a)
+
     def _draw(self, rows, ctr, stream=0):
         ad = self.cfg.act_dim
         return ops.normal_fill(rows * ad, self.seed + stream, ctr, self.device).view(rows, ad)
@@ -490,8 +500,8 @@ class SACLearner(_LearnerBase):
             eps_target = self._draw(b['batch_obs'].shape[0], 2 * (self.counter + 1))
         if self.auto_alpha:
             return ops.sac_targets_auto(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'],
-                                        b['batch_obs_tp1'], eps_target, pw.log_alpha)
-        return ops.sac_targets(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'], b['batch_obs_tp1'],
+                                        b['batch_obs_tp1'], eps_target, pw.log_alpha, _squashed=self.squashed)
+        return self._sac_targets(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'], b['batch_obs_tp1'],
                                eps_target, self.alpha)
 
     def compute_td_error(self, eps=None, ctr=None):
@@ -501,7 +511,7 @@ class SACLearner(_LearnerBase):
         pw, b = self.policy_with_value, self.batch_data
         if eps is None:
             eps = self._draw(b['batch_obs'].shape[0], 2 * self.counter if ctr is None else ctr, stream=1)
-        y1 = ops.sac_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), pw.net('Q1', True), b['batch_rewards'],
+        y1 = self._sac_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), pw.net('Q1', True), b['batch_rewards'],
                              b['batch_obs_tp1'], eps, 0.0)
         return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
 
@@ -522,15 +532,16 @@ class SACLearner(_LearnerBase):
         if eps_policy is None:
             eps_policy = self._draw(rows, 2 * self.counter + 1)
         if not self.auto_alpha:
-            ops.sac_policy_grad(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha,
-                                inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5])    # :119-136
+            grad_fn = ops.sac_policy_grad_squashed if self.squashed else ops.sac_policy_grad
+            grad_fn(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha, inv_b_global=inv_b,
+                    grad_out=self.grad('policy'), stats_out=stats[2:5])                                    # :119-136
             return self._finish(iteration)
         if eps_alpha is None:                                                                          # :139: the third draw
             eps_alpha = self._draw(rows, self.counter, stream=2)
         g_alpha = self.flat[self.n_net_grad:self.n_grad]
         ops.sac_policy_grad_auto(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, pw.log_alpha,
                                  eps_alpha, pw.target_entropy, inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5],
-                                 alpha_grad_out=g_alpha)                                               # :119-148
+                                 alpha_grad_out=g_alpha, _squashed=self.squashed)                      # :119-148
         fresh = self._views is None
         views = self._finish(iteration)
         if fresh:

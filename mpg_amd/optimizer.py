@@ -65,6 +65,8 @@ class SingleProcessOffPolicyOptimizer(object):
             return 'the learner is %s, not SACLearner (every other learner takes the native step by default)' % type(learner).__name__
         if isinstance(replay_buffer, PrioritizedReplayBuffer) or getattr(args, 'buffer_type', 'normal') != 'normal':
             return 'a prioritized replay buffer is not served by the native SAC step (uniform ReplayBuffer only)'
+        if getattr(learner, 'squashed', False) or getattr(getattr(worker, 'policy_with_value', None), 'squashed_head', False):
+            return 'the tanh-squashed head (squashed_head=True) is not served by the native SAC step: build the optimizer without native_sac'
         if worker.explore_sigma is not None:
             return 'explore_sigma (%r) on top of the stochastic policy is not served by the native SAC step' % (worker.explore_sigma,)
         return None

@@ -1,6 +1,7 @@
 """PolicyWithQs - device-resident mirror of policy.py:19-245: the deterministic policy branch, and the stochastic one (a diagonal
 Gaussian over the four logits, policy.py:179-204) with a fixed temperature `alpha`, or the learned one (alpha = 'auto': AlphaModel's
-log_alpha, its Adam and target_entropy, policy.py:45-52,136-143 - one block of eight device floats, `alpha_state`), and no action range.
+log_alpha, its Adam and target_entropy, policy.py:45-52,136-143 - one block of eight device floats, `alpha_state`); without an action
+range, or - with squashed_head=True - under the tanh-affine bijectors of one (policy.py:183-190).
 
 All networks live in ONE flat float32 tensor in the order of the reference's `self.models`
 (policy.py:72-86): Q1, (Q2,) policy; the target nets in a second flat tensor in the same order; Adam moments
@@ -63,7 +64,8 @@ class PolicyWithQs(object):
                  double_Q=True, target=True, tau=0.005, delay_update=2, deterministic_policy=True, action_range=None,
                  policy_out_activation='tanh', env_id='PathTracking-v0', obs_scale=None, rew_scale=None, rew_shift=0.,
                  gamma=0.98, value_num_hidden_units=256, policy_num_hidden_units=256, policy_only=False,
-                 device='cuda', seed=0, init_seed=0, alpha=None, target_entropy=None, alpha_lr_schedule=None, **kwargs):
+                 device='cuda', seed=0, init_seed=0, alpha=None, target_entropy=None, alpha_lr_schedule=None, squashed_head=False,
+                 **kwargs):
         assert value_num_hidden_units == 256 and policy_num_hidden_units == 256, 'kernels are built for 2x256 nets'
         self.policy_only = bool(policy_only)
         # policy_only (AMPC, policy.py:72-75,125-127): the policy is the one model, no target; double_Q / target / tau / delay_update /
@@ -74,6 +76,9 @@ class PolicyWithQs(object):
         self.deterministic_policy = bool(deterministic_policy)
         self.alpha = None
         self.auto_alpha = False
+        # squashed_head (on request only): the Gaussian under the tanh-affine bijectors of an action_range (policy.py:183-190) - PathTracking
+        # with a range, or InvertedPendulumConti-v0 (built_SAC_parser of train_script4mujoco.py: action_range 3)
+        self.squashed_head = bool(squashed_head) and not self.deterministic_policy
         if not self.deterministic_policy:
             # the stochastic branch (SAC): a float temperature or the learned one, the Gaussian head without a bijector (include/mpg_hip.h)
             if isinstance(alpha, str):
@@ -88,10 +93,19 @@ class PolicyWithQs(object):
                 self.auto_alpha = True
             elif alpha is None or not (math.isfinite(float(alpha)) and float(alpha) >= 0.):
                 raise ValueError('a stochastic policy needs a finite alpha >= 0 (got %r)' % (alpha,))
-            if action_range is not None:
+            if self.squashed_head:
+                if action_range is None or not (math.isfinite(float(action_range)) and float(action_range) > 0.):
+                    raise ValueError('squashed_head=True needs a positive, finite action_range (got %r): without one the plain Gaussian '
+                                     'head serves' % (action_range,))
+                if policy_out_activation == 'tanh':
+                    raise ValueError('squashed_head=True with policy_out_activation=\'tanh\' is not built (range * tanh(tanh(z)))')
+                if (env_id, act_dim) not in (('PathTracking-v0', 2), ('InvertedPendulumConti-v0', 1)):
+                    raise ValueError('the squashed head is built for PathTracking-v0 with act_dim 2 and InvertedPendulumConti-v0 with '
+                                     'act_dim 1 (got env_id %r, act_dim %r)' % (env_id, act_dim))
+            elif action_range is not None:
                 raise ValueError('a stochastic policy with an action_range (%r) is not built: its tanh-affine bijector changes the '
                                  'log-density (policy.py:183-190)' % (action_range,))
-            if act_dim != 2 or env_id != 'PathTracking-v0':
+            elif act_dim != 2 or env_id != 'PathTracking-v0':
                 raise ValueError('the stochastic policy is built for PathTracking-v0 with act_dim 2 (got env_id %r, act_dim %r)'
                                  % (env_id, act_dim))
             self.alpha = 'auto' if self.auto_alpha else float(alpha)
@@ -251,7 +265,8 @@ class PolicyWithQs(object):
             return ops.policy_action(self.cfg, self.net('policy', target), obs), 0.
         if eps is None:
             eps = self.draw(obs.shape[0])
-        return ops.policy_sample(self.cfg, self.net('policy', target), obs, eps)
+        sample = ops.policy_sample_squashed if self.squashed_head else ops.policy_sample
+        return sample(self.cfg, self.net('policy', target), obs, eps)
 
     def draw(self, rows):
         """the next [rows, act_dim] standard normals of the policy's own stream (mpg_normal_fill keyed by (sample_seed, counter))"""
@@ -315,10 +330,14 @@ class PolicyWithQs(object):
                   opt_steps=dict(self.opt_steps), names=list(self.names))
         if self.auto_alpha:         # (a stack with a fixed temperature keeps the keys it had)
             sd.update(alpha_state=self.alpha_state.cpu(), alpha_opt_steps=self.alpha_opt_steps)
+        if self.squashed_head:      # (likewise: only a squashed stack writes the key)
+            sd.update(squashed_head=True)
         return sd
 
     def load_state_dict(self, sd):
         assert sd['names'] == self.names
+        if bool(sd.get('squashed_head', False)) != self.squashed_head:
+            raise ValueError('state and stack differ in the policy head: one is tanh-squashed (squashed_head=True), the other is not')
         for k in ('params', 'targets', 'm', 'v'):
             getattr(self, k).copy_(sd[k].to(self.device))
         self.opt_steps = dict(sd['opt_steps'])
