@@ -400,6 +400,26 @@ int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params, int n, flo
                     uint8_t* done_out /* nullable */, const mpg_replay_draw_t* draw /* nullable */, int rows, float* b_obs,
                     float* b_act, float* b_rew, float* b_obs2, mpg_stream_t stream);
 
+/* OffPolicyWorker.sample's loop (worker.py:91-119: `iters` = batch_size / num_agent iterations of policy -> + N(0, explore_sigma) ->
+ * env.step -> ring -> env.reset) as ONE launch for the path-tracking env, obs_dim 6 .. 16, act_dim 2: one workgroup keeps a 16-agent
+ * group's policy weights and agents in registers for all iterations; global memory is read at the start only (weights, state, obs_io)
+ * and written, never read back.  Everything these `iters` consecutive calls leave behind, it = 0 .. iters - 1,
+ *   mpg_worker_step(cfg, policy_params, n, state, obs_io, explore_sigma, noise_seed, noise_ctr + it, act_out, capacity,
+ *                   (next_idx + it * n) % capacity, ring..., env_seed, env_ctr + it, done_out, draw = NULL, ...);
+ * is bit-identical: state, obs_io [n][obs_dim] (the current observations in, those after the last iteration out), act_out [n][2] and
+ * done_out [n] (nullable) of the LAST iteration, every ring array - iteration `it` writes the slots (next_idx + it * n + i) % capacity -
+ * and the sticky status word.  The counters are 64-bit sums (the carry into the high word included).  There is no pre-gathered draw.
+ * Refused before any launch with MPG_EINVAL, "mpg_worker_rollout" and a text of its own each, the outputs untouched: what
+ * mpg_worker_step refuses (a null configuration, another env - env_kind 2 with the text of the other real-env entry points -, obs_dim
+ * outside 6 .. 16, act_dim != 2, a tanh policy with an action range, a null pointer other than done_out, n <= 0, capacity < n,
+ * next_idx outside [0, capacity)), iters < 1, iters > 1024 (what bounds one launch's run time; the reference's worker runs 64) and
+ * iters * n > capacity (two iterations would write one slot from different workgroups with no order between them).
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_worker_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                       float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx,
+                       float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
+                       uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
 /* OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head below,
  * no explore_sigma) as ONE launch for the path-tracking env, obs_dim 6 .. 16, act_dim 2.  Bit-identical - actions, log-densities,
  * every ring row, env state, next observations, done flags and the sticky status word - to
@@ -726,7 +746,12 @@ typedef struct {
                                             temperature as an argument (this struct gains no field: the ABI version stays 10);
                                             mpg_step_begin refuses it and names that function.  6 is not assigned: it stays refused
                                             everywhere (mpg_step_workspace_bytes, mpg_step_begin, mpg_sac_step_begin) */
-    int num_agent, sample_iters;      /* worker: sample_iters env steps of num_agent agents per sampling call */
+    int num_agent, sample_iters;      /* worker: sample_iters env steps of num_agent agents per sampling call.  mpg_step_begin issues
+                                         all of them but the one that pre-gathers MPG-v2's draw as ONE launch (mpg_worker_rollout,
+                                         bit-identical) where there are at least two, the ring holds them (iters * num_agent <=
+                                         ring_capacity) and the width's measurement says so (obs_dim 6), else one
+                                         mpg_worker_step each.  sample_iters < 0 (one more accepted value of this int: no layout
+                                         changed) asks for |sample_iters| steps with the chain KEPT: the A/B form of that measurement */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];
     float eta;                        /* rule_based_weights, mpg_learner.py:384-399 */

@@ -232,6 +232,26 @@ __device__ __forceinline__ void pass(const typename args_of<IN>::type& a, int ro
         sAct[tid] = y;
     }
 }
+// The exploration noise of `group` for a kernel that calls pass() (k_worker_rollout, below): lane tid < 32 of wave 0 takes its own
+// action back out of sAct, adds N(0, sigma) from the same Philox draw as `group` - row gr, output o, the 64-bit counter (c1, c2) -
+// tests the sum for NaN as `group` does (pass() tested the action before the noise: a NaN there is a NaN here) and puts it back for
+// the env lanes: LDS is in order within a wave.  Returns the action (0 beyond `rows`, as in sAct).
+__device__ __forceinline__ float explore(float sigma, int rows, long g, float* sAct, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2,
+                                         bool& saw_nan) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));              // (opaque: the lane's predicate is formed here, not held across the caller's loop)
+    const int row = (tid / 2) % GROUP, o = tid % 2;
+    const long gr = g * GROUP + row;
+    float y = sAct[tid];
+    if (gr < rows && sigma > 0.f) {   // OffPolicyWorker.sample: action += N(0, sigma), worker.py:97-98
+        Philox4 p = philox4x32_10((uint32_t)gr, c1, c2, 0x5eedu + (uint32_t)o, k0, k1);
+        float u1 = u01(p.v[0]), u2 = u01(p.v[1]);
+        y = add_gauss_noise(y, sigma, u1, u2);
+        saw_nan |= y != y;
+        sAct[tid] = y;
+    }
+    return y;
+}
 template <class A>
 __device__ __forceinline__ void report(const A& a, float zmax, bool saw_nan) {
     report_activation_range(a.status, zmax);
@@ -809,6 +829,114 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename 
     worker_policy::report(pa, zmax, saw_nan);
 }
 
+// k_worker_rollout (below): what wave 0 needs of the launch's arguments once per iteration.  They rest in LDS and are read where they
+// are used: held in scalar registers for the whole loop, beside the env's hoisted constants, they and the Philox key schedules
+// derived from them were spilled.
+struct RolloutEnvArgs {
+    RingPtrs ring;
+    float *st, *obs_io, *act_out;
+    uint8_t* done_out;
+    uint32_t k0, k1, nk0, nk1;     // env key, noise key
+    uint64_t env_ctr, noise_ctr;   // the counters of iteration 0
+    uint32_t capacity;
+};
+
+// OffPolicyWorker.sample's `iters` iterations (worker.py:91-119: policy -> + N(0, sigma) -> env.step -> ring -> env.reset) in ONE
+// launch: `iters` consecutive k_policy_step_store_reset launches with the noise and env counters and the ring position advancing by
+// one / one / n per launch.  Each of those fetches the policy's weights and the agents' state again; here one 512-thread workgroup owns
+// a 16-agent group for all iterations in the form of k_env_rollout: the policy's registers are loaded once (worker_policy::load),
+// wave 0 - four lanes per agent - reads the agents once and keeps them in registers, and per iteration the observations go from wave 0
+// to the policy pass and the actions back through LDS between workgroup barriers.  Per iteration `it` wave 0 does what env_lane<4>
+// does, in its order: ring row (obs, act) at slot (next_idx + it * n + i) % capacity, step_agent<4>, (obs2, rew, done), reset_agent
+// keyed (env key, env counter + it) if done, and the next observation - into sObs instead of obs_io.  State, obs_io, act_out and
+// done_out are written after the LAST iteration only (what the chain leaves behind).  Global memory is read in the prologue only
+// (weights, state, obs_io) and written, never read back; (noise / env) c1, c2: the counters of iteration 0, carried as 64-bit sums.
+// The host refuses iters * n > capacity: two iterations would write one ring slot from different workgroups.  Everything the chain
+// leaves is bit-identical: the same device functions on the same operands in the same order (tests/test_worker_rollout_gpu.py).
+// IN as in k_policy_step_store_reset.
+template <bool PK, int IN>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typename worker_policy::args_of<IN>::type pa, int n_launch,
+                                                                     int iters, float* st, float* obs_io, float* act_out, RingPtrs ring, int capacity,
+                                                                     int next_idx, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2,
+                                                                     uint8_t* done_out) {
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN>()];
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
+    __shared__ float sAct[mlp::GROUP * 2];
+    __shared__ RolloutEnvArgs sArg;
+    const int od_launch = worker_policy::obs_dim_of(pa);
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<IN, 2> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
+    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
+    Agent ag = {};
+    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
+    {   // the group's rows of obs_io (16 x od <= 256 floats)
+        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.ring = ring;
+        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
+        sArg.k0 = k0; sArg.k1 = k1; sArg.nk0 = pa.k0; sArg.nk1 = pa.k1;
+        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
+        sArg.noise_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        sArg.capacity = (uint32_t)capacity;
+    }
+    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    uint32_t slot = (uint32_t)(((long)next_idx + i_lane) % capacity);
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
+        worker_policy::pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+        if (threadIdx.x >= 64) continue;                 // wave 0 wrote sAct itself: LDS is in order within a wave
+        // The lane's place and the launch's sizes, opaque per iteration: what is derived from them - the predicates q == 0 .. 3 and
+        // i < n, row strides, the group's offset - is then formed where it is used and not held in scalar registers across the whole
+        // loop beside the env's hoisted constants, which left no room for them (tools/kernel_resources.py: no spilled register)
+        int q = q_lane, i = i_lane, od = od_launch, g = blockIdx.x, n = n_launch;
+        asm volatile("" : "+v"(q), "+v"(i), "+s"(g), "+s"(n));
+        if constexpr (IN == 16) asm volatile("" : "+s"(od));      // (a constant at IN = 6)
+        if (threadIdx.x < mlp::GROUP * 2) {
+            const uint64_t nc = sArg.noise_ctr + (uint64_t)it;
+            const float y = worker_policy::explore(pa.sigma, n, g, sAct, sArg.nk0, sArg.nk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
+            if (last && g * mlp::GROUP + (int)threadIdx.x / 2 < n) sArg.act_out[(size_t)g * mlp::GROUP * 2 + threadIdx.x] = y;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (i < n) {
+            const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
+            if (q == 0) {
+                write_obs(sArg.ring.obs, (int)slot, od, ag);             // obs before the step
+                reinterpret_cast<float2*>(sArg.ring.act)[slot] = an;
+            }
+            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
+            if (q == 1) {
+                write_obs(sArg.ring.obs2, (int)slot, od, ag);
+                sArg.ring.rew[slot] = o.reward;
+                sArg.ring.done[slot] = o.done ? 1 : 0;
+                uint8_t* const dn = sArg.done_out;
+                if (last && dn) dn[i] = o.done ? 1 : 0;
+            }
+            if (o.done) {
+                const uint64_t ec = sArg.env_ctr + (uint64_t)it;
+                reset_agent(ag, i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
+            }
+            if (last) {
+                if (q == 2) store_agent(sArg.st, n, i, ag);
+                if (q == 3) write_obs(sArg.obs_io, i, od, ag);
+            } else if (q == 3) {
+                write_obs(sObs, a_loc, od, ag);
+            }
+            slot += (uint32_t)n;
+            if (slot >= sArg.capacity) slot -= sArg.capacity;
+        }
+    }
+    worker_policy::report(pa, zmax, saw_nan);
+}
+
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
 // MPG_ENV_INVERTED_DOUBLE_PENDULUM names a differentiable model only (include/mpg_hip.h): every real-env entry point refuses it
@@ -984,6 +1112,54 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
 #undef MPG_WORKER_LAUNCH
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_step");
+    return MPG_OK;
+}
+
+// worker.py:91-119 for the path-tracking env: `iters` consecutive mpg_worker_step calls (draw = NULL; noise_ctr + it, ring position
+// (next_idx + it * n) % capacity, env_ctr + it) as one launch (k_worker_rollout: bit-identical state, observations, actions, done
+// flags, ring arrays and status word)
+extern "C" int mpg_worker_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                                  float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx,
+                                  float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
+                                  uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_worker_rollout: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_worker_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_worker_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 2, "mpg_worker_rollout: act_dim 2 only (got %d)", cfg->act_dim);
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_rollout: tanh policy with an action range");
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
+                "mpg_worker_rollout: null pointer");
+    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "mpg_worker_rollout: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n,
+                capacity, next_idx);
+    MPG_REQUIRE(iters >= 1, "mpg_worker_rollout: iters >= 1 (got %d)", iters);
+    // (what bounds one launch's run time; the reference's worker runs 64)
+    MPG_REQUIRE(iters <= 1024, "mpg_worker_rollout: iters <= 1024 (got %d)", iters);
+    // two iterations would write one slot from different workgroups with no order between them
+    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_rollout: iters * n = %ld transitions do not fit the ring's capacity %d",
+                (long)iters * n, capacity);
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+#define MPG_WORKER_ROLLOUT_LAUNCH(PK, IN)                                                                                                \
+    hipLaunchKernelGGL((k_worker_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring, \
+                       capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out)
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        pa.obs_dim = cfg->obs_dim;
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_ROLLOUT_LAUNCH(true, 16); else MPG_WORKER_ROLLOUT_LAUNCH(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_WORKER_ROLLOUT_LAUNCH(true, 6); else MPG_WORKER_ROLLOUT_LAUNCH(false, 6);
+    }
+#undef MPG_WORKER_ROLLOUT_LAUNCH
+    mpg_prof_end(mpg_prof_of(cfg), 2, s);
+    MPG_CHECK_LAUNCH("mpg_worker_rollout");
     return MPG_OK;
 }
 

@@ -82,14 +82,46 @@ inline bool worker_step_fused(const mpg_train_ctx_t* c) {
     return c->cfg.env_kind == MPG_ENV_PATH_TRACKING && c->cfg.obs_dim == 6 && c->cfg.act_dim == 2;
 }
 
+// worker.py:91-119, the iterations of one sample, as one launch (mpg_worker_rollout) instead of one mpg_worker_step each.  The rule
+// for taking it: per width, its median at or below the chain's at both measured sizes (tools/bench_worker_rollout.py).
+// A caller that passes sample_iters < 0 asks for |sample_iters| iterations on the chain (include/mpg_hip.h): the A/B switch of that
+// measurement and of tests/test_worker_rollout_gpu.py, which compares the two drivers bit for bit.
+inline bool worker_rollout_taken(const mpg_train_ctx_t* c) { return c->cfg.obs_dim == 6 && c->sample_iters > 0; }
+inline int sample_iters_of(const mpg_train_ctx_t* c) { return c->sample_iters < 0 ? -c->sample_iters : c->sample_iters; }
+
 // draws_now: MPG-v2 draws its minibatch right after the add.  The last env launch then gathers it in spare workgroups (the random
 // ring reads overlap the env's sub-steps) except the rows drawn from the slots that launch is writing (path-tracking env, six-entry
 // observations); *pre_gathered and *fresh_start tell the gradient launch so (written only then; NADP and TD3 pass draws_now = false).
 int sample_and_add(mpg_train_ctx_t* c, const float* policy, bool draws_now, bool* pre_gathered, int* fresh_start, mpg_stream_t s) {
-    const int od = c->cfg.obs_dim, kind = c->cfg.env_kind;
-    for (int it = 0; it < c->sample_iters; ++it) {
+    const int od = c->cfg.obs_dim, kind = c->cfg.env_kind, sample_iters = sample_iters_of(c);
+    int it = 0;
+    // The iterations before the one that pre-gathers the draw as ONE launch (mpg_worker_rollout: bit-identical to the loop below) when
+    // there are at least two of them (and at most the 1024 that launch takes) and the ring holds them all (iters * n <= capacity is what
+    // that launch asks: no slot written twice).  With one iteration - num_agent == batch, the benchmark's configuration - nothing changes.
+    {
+        const bool last_predraws = draws_now && kind == MPG_ENV_PATH_TRACKING && od == 6;
+        const int k = sample_iters - (last_predraws ? 1 : 0);
+        if (k >= 2 && k <= 1024 && (long)k * c->num_agent <= c->ring_capacity && worker_step_fused(c) && worker_rollout_taken(c)) {
+            const int n = c->num_agent;
+            TRY(mpg_worker_rollout(&c->cfg, policy, n, k, c->env_state, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr, c->w_act,
+                                   c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
+                                   c->env_seed, c->env_ctr, c->w_done, s));
+            c->noise_ctr += k;
+            c->env_ctr += k;
+            for (; it < k; ++it) {
+                // new transitions enter at the max priority (buffer.py:127-136), in iteration order: mpg_per_add reads no ring row and
+                // the worker's launch reads no tree
+                if (c->learner_version == 4 && c->prioritized)
+                    TRY(mpg_per_add(c->per_sum, c->per_min, c->per_stamp, c->per_capacity, c->ring_capacity, c->ring_next, n, c->per_alpha,
+                                    c->per_max_priority, reinterpret_cast<int*>(c->scratch), s));
+                c->ring_next = (c->ring_next + n) % c->ring_capacity;
+                c->ring_size = std::min(c->ring_size + n, c->ring_capacity);
+            }
+        }
+    }
+    for (; it < sample_iters; ++it) {
         MPG_REQUIRE(c->num_agent <= c->ring_capacity, "mpg_step_begin: ring smaller than one sample");
-        const bool predraw = draws_now && it == c->sample_iters - 1 && kind == MPG_ENV_PATH_TRACKING && od == 6;
+        const bool predraw = draws_now && it == sample_iters - 1 && kind == MPG_ENV_PATH_TRACKING && od == 6;
         mpg_replay_draw_t pd = {};
         if (predraw) {
             pd.n_storage = std::min(c->ring_size + c->num_agent, c->ring_capacity);
@@ -204,7 +236,7 @@ int ndpg_gradients(mpg_train_ctx_t* c, const Layout& l, bool fresh, mpg_stream_t
 int sac_sample_and_add(const char* entry, mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
     const int n = c->num_agent;
     MPG_REQUIRE(n <= c->ring_capacity, "%s: ring smaller than one sample", entry);
-    for (int it = 0; it < c->sample_iters; ++it) {
+    for (int it = 0; it < sample_iters_of(c); ++it) {      // (the sign: sample_and_add's chain-kept form; there is one form here)
         // (the log-densities have no consumer: worker.py:96 drops them)
         TRY(mpg_worker_sample_step(&c->cfg, policy, n, c->env_state, c->w_obs, c->worker_seed, c->noise_ctr++, c->w_act, nullptr,
                                    c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
@@ -335,8 +367,13 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
                                           c->ring_rew, c->ring_obs2, c->ring_done, c->idx, c->b_obs, c->b_act, c->b_rew, c->b_obs2,
                                           c->b_done, s));
             MPG_REQUIRE(c->l_env_state && c->l_obs && c->l_act && c->l_rewards && c->l_done, "mpg_step_begin: MPG-v1 needs the learner env buffers");
-            TRY(mpg_env_reset_from_obs(kind, c->batch, od, c->l_env_state, c->b_obs, s));
-            for (int t = 0; t < c->n; ++t) {
+            // one launch (mpg_env_rollout, bit-identical to the chain below: rewards, last observations, status word) where that entry
+            // point serves the configuration; the learner's env state, action and done buffers are not written then
+            const bool one_launch = kind == MPG_ENV_PATH_TRACKING && ad == 2 && c->n < 32 &&
+                                    !(c->cfg.policy_out_act == MPG_ACT_TANH && c->cfg.action_range > 0.f);
+            if (one_launch) TRY(mpg_env_rollout(&c->cfg, policy, c->batch, c->n, c->b_obs, c->b_act, c->l_rewards, c->l_obs, s));
+            else TRY(mpg_env_reset_from_obs(kind, c->batch, od, c->l_env_state, c->b_obs, s));
+            for (int t = 0; t < c->n && !one_launch; ++t) {
                 const float* act = c->b_act;
                 if (t > 0) {
                     TRY(mpg_policy_action(&c->cfg, policy, c->batch, c->l_obs, 0.f, 0, 0, c->l_act, s));

@@ -172,8 +172,12 @@ class MPGLearner(_LearnerBase):
                              b['batch_rewards'], b['batch_obs_tp1'])
 
     def sample(self, start_obs, start_action):
-        """mpg_learner.py:109-124: n real-env steps; first action from replay, then the ONLINE policy, no noise."""
+        """mpg_learner.py:109-124: n real-env steps; first action from replay, then the ONLINE policy, no noise.  One launch
+        (mpg_env_rollout, bit-identical to the chain below) for the horizons it serves (n < 32); the learner's env is not stepped then."""
         pw = self.policy_with_value
+        if self.sample_num_in_learner < 32:
+            rewards, last_obs = ops.env_rollout(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
+            return {'all_rewards': rewards, 'last_obs': last_obs}
         obs = start_obs
         self.env.reset(init_obs=obs)
         rewards = []

@@ -92,7 +92,7 @@ class SingleProcessOffPolicyOptimizer(object):
     def step(self):
         if self._fused is not None:
             if self.iteration % self.sampling_interval == 0:
-                self.num_sampled_steps += self.worker.num_agent * self._fused.c.sample_iters
+                self.num_sampled_steps += self.worker.num_agent * abs(self._fused.c.sample_iters)      # (< 0: the chain kept, include/mpg_hip.h)
             self._fused.step(self.iteration)
             self.learner._lazy_stats = self.learner._native_lazy_stats(self.iteration)
             self.iteration += 1

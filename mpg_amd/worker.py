@@ -57,9 +57,19 @@ class OffPolicyWorker(object):
 
     def sample(self):
         """-> (obs, act, RAW reward, obs', done) stacked over batch_size/num_agent env steps (worker.py:91-119)."""
+        iters = max(1, self.batch_size // self.num_agent)
+        batch = self._sample_one_launch(iters) if getattr(self.args, 'one_launch_sample', False) else self._sample_loop(iters)
+        self.num_sample += batch[0].shape[0]
+        self.sample_times += 1
+        # judge_is_nan (worker.py:95-107) runs inside the policy kernel: a NaN observation or action sets MPG_STATUS_NAN in the
+        # policy's status word; it is read (one host synchronisation) every `nan_check_interval` calls, not per step
+        if self.sample_times % self.nan_check_interval == 0:
+            self.policy_with_value.check_status()
+        return batch
+
+    def _sample_loop(self, iters):
         pw = self.policy_with_value
         out = [[], [], [], [], []]
-        iters = max(1, self.batch_size // self.num_agent)
         for _ in range(iters):
             obs = self.obs
             if getattr(pw, 'deterministic_policy', True):
@@ -77,14 +87,32 @@ class OffPolicyWorker(object):
                 lst.append(x)
             self.obs = self.env.reset()          # PathTracking: done is always 1, every agent is re-drawn; the pendulum
                                                  # re-draws the agents that fell (inverted_pendulum_conti.py:17-18)
-        batch = tuple(x[0] for x in out) if iters == 1 else tuple(torch.cat(x, 0) for x in out)
-        self.num_sample += batch[0].shape[0]
-        self.sample_times += 1
-        # judge_is_nan (worker.py:95-107) runs inside the policy kernel: a NaN observation or action sets MPG_STATUS_NAN in the
-        # policy's status word; it is read (one host synchronisation) every `nan_check_interval` calls, not per step
-        if self.sample_times % self.nan_check_interval == 0:
-            self.policy_with_value.check_status()
-        return batch
+        return tuple(x[0] for x in out) if iters == 1 else tuple(torch.cat(x, 0) for x in out)
+
+    def _sample_one_launch(self, iters):
+        """args.one_launch_sample = True: the same batch, observations, env state and counters as _sample_loop, bit for bit, from ONE
+        launch (mpg_worker_rollout) instead of three per iteration - the five output arrays [iters * n, .] are the launch's ring of
+        capacity iters * n at position 0.  Deterministic policy on PathTracking-v0 only.  env.done_intended is NOT refreshed on this
+        path (the launch does not form it; env.step does)."""
+        pw, env, n, dev = self.policy_with_value, self.env, self.num_agent, self.device
+        if not getattr(pw, 'deterministic_policy', True):
+            raise ValueError('one_launch_sample serves a deterministic policy only: the stochastic policy\'s loop form '
+                             '(mpg_worker_sample_step per iteration) is not built')
+        if env.kind != 0:
+            raise ValueError('one_launch_sample serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
+        rows, od = iters * n, env.obs_dim
+        f = dict(dtype=torch.float32, device=dev)
+        ring = (torch.empty(rows, od, **f), torch.empty(rows, pw.act_dim, **f), torch.empty(rows, **f), torch.empty(rows, od, **f),
+                torch.empty(rows, dtype=torch.uint8, device=dev))
+        obs_io = self.obs.clone()               # never write into a tensor already handed to the caller
+        done = torch.empty(n, dtype=torch.uint8, device=dev)
+        ops.worker_rollout(pw.cfg, pw.net('policy'), iters, env._state, obs_io, float(self.explore_sigma or 0.), self.seed, self._noise_ctr,
+                           ring, rows, 0, env.seed, env._ctr, done_out=done)
+        self._noise_ctr += iters
+        env._ctr += iters
+        env.obs, env.done, env.reward = obs_io, done, ring[2][rows - n:]
+        self.obs = obs_io
+        return ring
 
     def sample_with_count(self):
         batch = self.sample()

@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Times of one worker sample on the GPU, one process, medians of REGIONS timed regions after a warm-up (device events around REPS
+back-to-back samples, a synchronise at the end of every region):
+
+  (a) the sample as the chain of `iters` mpg_worker_step launches - what sample_and_add of train_step.cpp enqueues without the
+      one-launch form - enqueued by a C loop (tools/bench_worker_rollout_chain.c, compiled on first use), REPS samples per call into it;
+  (b) mpg_worker_rollout, the same sample as ONE launch (bit-identical: tests/test_worker_rollout_gpu.py; asserted here at the end);
+      cases (agents, iters, obs_dim) = (8, 64, 6), (256, 16, 6), (8, 64, 9), (256, 16, 9), explore_sigma 0.1, the packed weight
+      image, the two alternating region by region;
+  (c) one native step at the reference's worker defaults (num_agent 8, batch_size 512, sampling every 10th step), B = 256, for TD3
+      and MPG-v2: the driver as it decides, and the same driver with the chain kept (mpg_train_ctx_t.sample_iters < 0), alternating.
+
+The rule for the driver: it calls (b) for a width only if (b)'s median is at or below (a)'s at both sizes of that width.
+
+    python tools/bench_worker_rollout.py [--json out.json]          prints markdown tables (EXPERIMENTS.md)
+    python tools/bench_worker_rollout.py --steps-only [--tree DIR]  (c) alone; --tree: time another checkout's build (a parent commit)"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REGIONS, REPS, WARMUP = 7, 200, 5
+I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
+HERE = os.path.dirname(os.path.abspath(__file__))
+CASES = ((8, 64, 6), (256, 16, 6), (8, 64, 9), (256, 16, 9))
+
+
+class Side(ctypes.Structure):               # worker_side_t, tools/bench_worker_rollout_chain.c
+    _fields_ = [(k, ctypes.c_void_p) for k in ('state', 'obs', 'act', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'done')] + \
+               [('capacity', I), ('next_idx', I), ('ctr', U64)]
+
+
+def host_loops():
+    """tools/bench_worker_rollout_chain.c as a shared object beside it (rebuilt when the source is newer)"""
+    src, so = os.path.join(HERE, 'bench_worker_rollout_chain.c'), os.path.join(HERE, 'bench_worker_rollout_chain.so')
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        subprocess.check_call([os.environ.get('CC', 'cc'), '-O2', '-shared', '-fPIC', '-I' + os.path.join(HERE, '..', 'include'), src, '-o', so])
+    return ctypes.CDLL(so)
+
+
+def timed(fn, reps=REPS, batched=False):
+    """ms per call of one region: device events around `reps` calls (batched: fn(reps) issues them itself)"""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    if batched:
+        fn(reps)
+    else:
+        for _ in range(reps):
+            fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def sample_case(n, iters, od, sigma=0.1):
+    import numpy as np
+    import torch
+    from mpg_amd import _lib as L
+    from mpg_amd import ops
+    from mpg_amd.envs import PathTrackingEnv
+    from tests.golden_inputs import mlp_weights_flat
+    rng = np.random.Generator(np.random.PCG64(n + od))
+    dev = 'cuda'
+    cfg = ops.make_cfg(obs_dim=od)
+    pol = torch.as_tensor(mlp_weights_flat(rng, od, 4)).to(dev)
+    wc = ops.WeightCache(pol, [(od, 4)])
+    cfg.wcache[0] = wc.pointer
+    cap = 4 * iters * n + 3 * n                   # (the ring position wraps inside a sample now and then)
+    sides, keep = [], []
+    for _ in range(2):
+        env = PathTrackingEnv(num_agent=n, num_future_data=od - 6, seed=4)
+        t = dict(state=env._state, obs=env.reset().clone(), act=torch.empty(n, 2, device=dev), ring_obs=torch.zeros(cap, od, device=dev),
+                 ring_act=torch.zeros(cap, 2, device=dev), ring_rew=torch.zeros(cap, device=dev), ring_obs2=torch.zeros(cap, od, device=dev),
+                 ring_done=torch.zeros(cap, dtype=torch.uint8, device=dev), done=torch.zeros(n, dtype=torch.uint8, device=dev))
+        sd = Side(capacity=cap, next_idx=0, ctr=1)
+        for k, v in t.items():
+            setattr(sd, k, v.data_ptr())
+        sides.append((t, sd))
+        keep.append(env)
+    lib, s, c = L.lib(), L.stream(), ctypes.byref(cfg)
+    fp = lambda f: ctypes.cast(f, ctypes.c_void_p)
+    host = host_loops()
+
+    def chain(reps):
+        assert host.bench_chain(fp(lib.mpg_worker_step), c, L.ptr(pol), I(n), I(iters), F(sigma), ctypes.byref(sides[0][1]), s, I(reps)) == 0
+
+    def launch(reps):
+        assert host.bench_launch(fp(lib.mpg_worker_rollout), c, L.ptr(pol), I(n), I(iters), F(sigma), ctypes.byref(sides[1][1]), s, I(reps)) == 0
+    chain(WARMUP), launch(WARMUP)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(REGIONS):                                      # alternating: both see the same machine
+        ta.append(timed(chain, batched=True))
+        tb.append(timed(launch, batched=True))
+    torch.cuda.synchronize()
+    for k in sides[0][0]:                                         # the two did the same work: bit-identical at the end
+        a, b = sides[0][0][k], sides[1][0][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
+    del keep, wc
+    return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb))
+
+
+def stack(alg, chain=False):
+    from mpg_amd.buffer import ReplayBuffer
+    from mpg_amd.config import default_args
+    from mpg_amd.learners import MPGLearner, TD3Learner
+    from mpg_amd.optimizer import SingleProcessOffPolicyOptimizer
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    args = default_args(alg, nan_check_interval=10 ** 9)
+    assert (args.num_agent, args.batch_size, args.replay_batch_size) == (8, 512, 256)
+    worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+    learner = (TD3Learner if alg == 'TD3' else MPGLearner)(PolicyWithQs, args)
+    opt = SingleProcessOffPolicyOptimizer(worker, learner, ReplayBuffer(args, 0), None, args, sampling_interval=10)
+    assert opt._fused is not None and opt._fused.c.sample_iters == 64
+    if chain:
+        opt._fused.c.sample_iters = -64           # include/mpg_hip.h: the same iterations, one mpg_worker_step each
+    return opt
+
+
+def step_cases(out, ab):
+    import torch
+    from mpg_amd.optimizer import quiesce_gc
+    cases = [(a, chain) for a in ('TD3', 'MPG-v2') for chain in ((True, False) if ab else (False,))]
+    opts = [stack(a, chain) for a, chain in cases]
+    quiesce_gc()
+    for _ in range(40):
+        for o in opts:
+            o.step()
+    torch.cuda.synchronize()
+    t = [[] for _ in opts]
+    for _ in range(REGIONS):                                      # alternating; REPS a multiple of the sampling interval
+        for k, o in enumerate(opts):
+            t[k].append(timed(o.step, REPS))
+    print('\n| native step, num_agent 8, batch_size 512, sampling_interval 10, B = 256 | ms per step |\n|---|---|', flush=True)
+    for (a, chain), x in zip(cases, t):
+        form = ('chain kept (sample_iters < 0)' if chain else "the driver's own choice") if ab else 'as built'
+        out['step'].append(dict(alg=a, form=form, step_ms=statistics.median(x), step_range=(min(x), max(x))))
+        print('| %s, %s | %.4f (%.4f .. %.4f) |' % (a, form, statistics.median(x), min(x), max(x)), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--json', default=None)
+    ap.add_argument('--steps-only', action='store_true', help='the native step times alone')
+    ap.add_argument('--tree', default=None, help="another checkout of this project whose build is timed (with --steps-only)")
+    a = ap.parse_args()
+    assert not a.tree or a.steps_only, '--tree times the native steps of another checkout: pass --steps-only'
+    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else os.path.dirname(HERE))
+    import torch
+    assert torch.cuda.is_available(), 'bench_worker_rollout.py needs a GPU: nothing here is measured without one'
+    out = {'sample': [], 'step': []}
+    if not a.steps_only:
+        print('| agents | iters | obs_dim | (a) chain of mpg_worker_step, ms | (b) mpg_worker_rollout, ms | (a) / (b) |\n|---|---|---|---|---|---|', flush=True)
+        for n, iters, od in CASES:
+            ma, mb, ra, rb = sample_case(n, iters, od)
+            out['sample'].append(dict(agents=n, iters=iters, obs_dim=od, chain_ms=ma, chain_range=ra, launch_ms=mb, launch_range=rb))
+            print('| %d | %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f |' % (n, iters, od, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb),
+                  flush=True)
+    step_cases(out, ab=not a.tree)           # (another checkout may not know the chain-kept form)
+    if a.json:
+        with open(a.json, 'w') as fh:
+            json.dump(out, fh, indent=1)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,48 @@
+/* Host loops of tools/bench_worker_rollout.py: one worker sample as `iters` mpg_worker_step launches (what sample_and_add of
+ * train_step.cpp enqueues without the one-launch form) and as one mpg_worker_rollout launch, `reps` samples back to back, so that
+ * neither is charged an interpreter or a foreign-function call per launch.  The entry points come in as pointers (the tool resolves
+ * them in the engine's library), so this file links against nothing.
+ *
+ *   cc -O2 -shared -fPIC -Iinclude tools/bench_worker_rollout_chain.c -o tools/bench_worker_rollout_chain.so
+ *   (bench_worker_rollout.py does this itself) */
+#include "mpg_hip.h"
+
+typedef int (*step_fn)(const mpg_cfg_t*, const float*, int, float*, float*, float, uint64_t, uint64_t, float*, int, int, float*, float*,
+                       float*, float*, uint8_t*, uint64_t, uint64_t, uint8_t*, const mpg_replay_draw_t*, int, float*, float*, float*, float*,
+                       mpg_stream_t);
+typedef int (*rollout_fn)(const mpg_cfg_t*, const float*, int, int, float*, float*, float, uint64_t, uint64_t, float*, int, int, float*,
+                          float*, float*, float*, uint8_t*, uint64_t, uint64_t, uint8_t*, mpg_stream_t);
+
+/* one side's buffers and counters; both forms advance them alike */
+typedef struct {
+    float *state, *obs, *act;
+    float *ring_obs, *ring_act, *ring_rew, *ring_obs2;
+    uint8_t *ring_done, *done;
+    int capacity, next_idx;
+    uint64_t ctr;
+} worker_side_t;
+
+int bench_chain(step_fn worker_step, const mpg_cfg_t* cfg, const float* policy, int n, int iters, float sigma, worker_side_t* w,
+                mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = worker_step(cfg, policy, n, w->state, w->obs, sigma, 11, w->ctr, w->act, w->capacity, w->next_idx, w->ring_obs,
+                                 w->ring_act, w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, 0, 0, 0, 0, 0, 0, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
+
+int bench_launch(rollout_fn worker_rollout, const mpg_cfg_t* cfg, const float* policy, int n, int iters, float sigma, worker_side_t* w,
+                 mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r) {
+        int rc = worker_rollout(cfg, policy, n, iters, w->state, w->obs, sigma, 11, w->ctr, w->act, w->capacity, w->next_idx, w->ring_obs,
+                                w->ring_act, w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
+        if (rc) return rc;
+        w->ctr += (uint64_t)iters;
+        w->next_idx = (int)(((long)w->next_idx + (long)iters * n) % w->capacity);
+    }
+    return 0;
+}
