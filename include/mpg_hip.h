@@ -420,6 +420,27 @@ int mpg_worker_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, 
                        float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
                        uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
 
+/* The same for the pendulum's real env (MPG_ENV_INVERTED_PENDULUM, obs_dim 4, act_dim 1; the reference's pendulum worker runs ONE agent
+ * for 512 iterations per sample): one workgroup keeps a 16-agent group's policy weights in registers and one agent per lane for all
+ * iterations.  This env's done flag is real: an agent is carried across iterations until it falls and is re-drawn.  Everything these
+ * `iters` consecutive pairs leave behind, it = 0 .. iters - 1,
+ *   mpg_policy_action(cfg, policy_params, n, obs_io, explore_sigma, noise_seed, noise_ctr + it, act_out, stream);
+ *   mpg_env_step_store_reset(MPG_ENV_INVERTED_PENDULUM, n, 4, state, act_out, capacity, (next_idx + it * n) % capacity, ring...,
+ *                            env_seed, env_ctr + it, obs_io, done_out, stream);
+ * is bit-identical: state, obs_io [n][4] (the current observations in, those after the last iteration out), act_out [n][1] and
+ * done_out [n] (nullable) of the LAST iteration, every ring array - iteration `it` writes the slots (next_idx + it * n + i) % capacity -
+ * and the sticky status word.  The counters are 64-bit sums (the carry into the high word included).  Deterministic policy only
+ * (action_range * tanh(mean) where the cfg has an action range).
+ * Refused before any launch with MPG_EINVAL, "mpg_worker_rollout_pendulum" and a text of its own each, the outputs untouched: a null
+ * configuration, env_kind 2 (the text of the other real-env entry points), any other env that is not the pendulum, obs_dim != 4,
+ * act_dim != 1, a tanh policy with an action range, a null pointer other than done_out, n <= 0, capacity < n, next_idx outside
+ * [0, capacity), iters < 1, iters > 1024 and iters * n > capacity.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                                float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx,
+                                float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
+                                uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
 /* OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head below,
  * no explore_sigma) as ONE launch for the path-tracking env, obs_dim 6 .. 16, act_dim 2.  Bit-identical - actions, log-densities,
  * every ring row, env state, next observations, done flags and the sticky status word - to
@@ -750,7 +771,9 @@ typedef struct {
                                          all of them but the one that pre-gathers MPG-v2's draw as ONE launch (mpg_worker_rollout,
                                          bit-identical) where there are at least two, the ring holds them (iters * num_agent <=
                                          ring_capacity) and the width's measurement says so (obs_dim 6), else one
-                                         mpg_worker_step each.  sample_iters < 0 (one more accepted value of this int: no layout
+                                         mpg_worker_step each.  On the pendulum's real env (env_kind 1, obs_dim 4, act_dim 1) all of
+                                         them are ONE mpg_worker_rollout_pendulum under the same two conditions, else
+                                         mpg_policy_action + mpg_env_step_store_reset each.  sample_iters < 0 (one more accepted value of this int: no layout
                                          changed) asks for |sample_iters| steps with the chain KEPT: the A/B form of that measurement */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];

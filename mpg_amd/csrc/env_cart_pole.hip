@@ -13,7 +13,94 @@
 // reset: U(-0.01, 0.01) on all four (:21-25) from Philox(seed, ctr, agent).
 //
 // State block: rows 0..3 of the opaque [MPG_ENV_STATE_DIM][n] array (rows 4..7 unused).
+//
+// Also here, beside the device functions it steps the agents with: mpg_worker_rollout_pendulum, a worker sample's iterations on this
+// env in one launch (k_worker_rollout_pendulum).
 #include "env_internal.h"
+
+// The worker's policy pass rides in the one-launch worker sample (k_worker_rollout_pendulum, below).  The network engine is compiled
+// here as every other translation unit compiles it - contraction allowed - although this file is built with -ffp-contract=off for the
+// cart-pole's arithmetic (the step and the fused kernels must round identically): the pragma is lexical, the environment code below is
+// back under "off".
+#pragma clang fp contract(fast)
+#include "mlp_core.h"
+
+// worker_policy's load / pass / explore / report (env_path_tracking.hip) for the pendulum's policy: four inputs, ONE used output of the
+// two the network has (mean | log-std) - siblings, not a generalisation: the PathTracking kernels' code stays as it is.  The used
+// output of row `row` is formed by lane `row` of wave 0, the lane that holds the row's agent (S4, one lane per agent), so the action
+// goes from the pass to the noise to the env step in a register.
+namespace cp_worker_policy {
+using namespace mlp;
+constexpr int IN = 4, OU = 1, XSW = xs_of<IN>(), OS = out_stride<OU>();
+
+struct Args {
+    const float* params;       // policy network, Keras order
+    const float* pack;         // nullable: packed forward image of W2 (weight cache)
+    int* status;               // nullable: MPG_STATUS_* word of the caller
+    int out_tanh;
+    float out_scale, sigma;
+    uint32_t k0, k1, c1, c2;   // exploration-noise key and the counter of iteration 0
+    float scale[IN];           // obs_scale
+};
+
+__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * XSW + NWAVE * GROUP * OS; }
+
+// the policy's registers, once
+template <bool PK>
+__device__ __forceinline__ void load(const Args& a, const Lane& L, float (&w2)[128], SmallRegs<IN, OU>& r, float& b3v) {
+    const Net net = make_net(a.params, IN, 2);
+    b3v = 0.f;
+    if (threadIdx.x < GROUP * OU) b3v = net.b3[0];
+    load_small<IN, OU>(net, L, r);
+    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
+}
+// One evaluation on the group's observations sObs [16][4] in LDS: k_forward<4, 1, PK, 1> (mlp_kernels.hip) for unit g as
+// mpg_policy_action launches it - the same single float32 product with obs_scale, the same device functions on the same operands in
+// the same order, the same row_poison - WITHOUT the noise and the NaN test of the action (explore, below).  Returns row
+// threadIdx.x's action on the lanes threadIdx.x < 16 (0 beyond `rows` and on every other lane).  zmax / saw_nan accumulate over the
+// passes.  Starts with the caller's LDS in order (a workgroup barrier behind the writes of sObs).
+__device__ __forceinline__ float pass(const Args& a, int rows, long g, const float* sObs, float* smem, const Lane& L, const float (&w2)[128],
+                                      const SmallRegs<IN, OU>& r, float b3v, float& zmax, bool& saw_nan) {
+    float* sA = smem;
+    float* sX = sA + A_IMG;
+    float* sPart = sX + GROUP * XSW;
+    if (threadIdx.x < GROUP * XSW) {           // (columns 4 .. 7 and the rows beyond `rows` stay zero)
+        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
+        float xv = 0.f;
+        if (g * GROUP + row < rows && i < IN) xv = sObs[row * IN + i] * a.scale[i];
+        saw_nan |= xv != xv;
+        sX[threadIdx.x] = xv;
+    }
+    lds_barrier();
+    float pz = 0.f;
+    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
+    float h1[2][4], h2[2][4];
+    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    const int tid = threadIdx.x;
+    float y = 0.f;
+    if (tid < GROUP * OU && g * GROUP + tid < rows) {
+        float z = out_preact<OS>(sPart, b3v, tid, 0);
+        y = a.out_tanh ? a.out_scale * tanhf(z) : z;
+        y += pz;
+    }
+    return y;
+}
+// The exploration noise of k_forward on row gr's one output, from its Philox draw at the 64-bit counter (c1, c2), then its NaN test
+__device__ __forceinline__ float explore(float y, float sigma, long gr, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, bool& saw_nan) {
+    if (sigma > 0.f) {   // OffPolicyWorker.sample: action += N(0, sigma), worker.py:97-98
+        Philox4 p = philox4x32_10((uint32_t)gr, c1, c2, 0x5eedu, k0, k1);
+        float u1 = u01(p.v[0]), u2 = u01(p.v[1]);
+        y = add_gauss_noise(y, sigma, u1, u2);
+    }
+    saw_nan |= y != y;
+    return y;
+}
+__device__ __forceinline__ void report(const Args& a, float zmax, bool saw_nan) {
+    report_activation_range(a.status, zmax);
+    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
+}
+}  // namespace cp_worker_policy
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -150,7 +237,149 @@ __global__ void __launch_bounds__(64) k_cp_step_store_reset(int n, float* __rest
     write_obs(obs_out, i, s);
 }
 
+// k_worker_rollout_pendulum (below): what the env lanes need of the launch's arguments once per iteration.  They rest in LDS and are
+// read where they are used, as k_worker_rollout's do (env_path_tracking.hip): held in scalar registers for the whole loop beside the
+// policy's arguments and the Philox key schedules derived from them, eight of them were spilled (tools/kernel_resources.py).
+struct CpRolloutEnvArgs {
+    RingPtrs ring;
+    float *st, *obs_io, *act_out;
+    uint8_t* done_out;
+    uint32_t k0, k1, nk0, nk1;     // env key, noise key
+    uint64_t env_ctr, noise_ctr;   // the counters of iteration 0
+    uint32_t capacity;
+};
+
+// OffPolicyWorker.sample's `iters` iterations (worker.py:91-119: policy -> + N(0, sigma) -> env.step -> ring -> env.reset) for the
+// pendulum in ONE launch: `iters` consecutive pairs of mpg_policy_action (k_forward<4, 1, PK, 1>) and k_cp_step_store_reset with the
+// noise and env counters and the ring position advancing by one / one / n per pair.  Each of those 2 * iters launches fetches the
+// policy's weights or the agents' state again; here one 512-thread workgroup owns a 16-agent group for all iterations in the form of
+// k_worker_rollout (env_path_tracking.hip): the policy's registers are loaded once, lanes 0 .. 15 of wave 0 read one agent each (S4)
+// and keep it in registers, and per iteration the observations go from those lanes to the policy pass through LDS between workgroup
+// barriers; the action comes back in a register (cp_worker_policy).  Unlike the path-tracking env's, this env's `done` is real: an
+// agent lives in its lane's registers across many iterations, falls, is re-drawn keyed (env key, env counter + it) and goes on.  Per
+// iteration `it` an env lane does what k_cp_step_store_reset does, in its order: ring row (obs, act) at slot (next_idx + it * n + i) %
+// capacity, step_agent, (obs2, rew, done), reset_agent if done, and the next observation - into sObs instead of obs_out.  State,
+// obs_io, act_out and done_out are written after the LAST iteration only (what the chain leaves behind) and the status word is
+// reported once.  Global memory is read in the prologue only (weights, state, obs_io) and written, never read back; (noise / env)
+// c1, c2: the counters of iteration 0, carried as 64-bit sums.  The host refuses iters * n > capacity: two iterations would write one
+// ring slot from different workgroups.  Everything the chain leaves is bit-identical: the same device functions on the same operands
+// in the same order (tests/test_worker_rollout_pendulum_gpu.py).
+template <bool PK>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(const cp_worker_policy::Args pa, int n, int iters,
+                                                                              float* st, float* obs_io, float* act_out, RingPtrs ring,
+                                                                              int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                                              uint32_t c1, uint32_t c2, uint8_t* done_out) {
+    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
+    __shared__ CpRolloutEnvArgs sArg;
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<4, 1> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
+    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
+    const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
+    S4 s = {};
+    if (env_lane) s = load(st, n, i);
+    {   // the group's rows of obs_io (16 x 4 floats)
+        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.ring = ring;
+        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
+        sArg.k0 = k0; sArg.k1 = k1; sArg.nk0 = pa.k0; sArg.nk1 = pa.k1;
+        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
+        sArg.noise_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        sArg.capacity = (uint32_t)capacity;
+    }
+    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    uint32_t slot = env_lane ? (uint32_t)(((long)next_idx + i) % capacity) : 0u;
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
+        float a = cp_worker_policy::pass(pa, n, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+        if (!env_lane) continue;
+        const uint64_t nc = sArg.noise_ctr + (uint64_t)it;
+        a = cp_worker_policy::explore(a, pa.sigma, i, sArg.nk0, sArg.nk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
+        write_obs(sArg.ring.obs, slot, s);               // obs before the step
+        sArg.ring.act[slot] = a;
+        const StepOut o = step_agent(s, a);
+        write_obs(sArg.ring.obs2, slot, s);
+        sArg.ring.rew[slot] = o.reward;
+        sArg.ring.done[slot] = o.done ? 1 : 0;
+        if (o.done) {
+            const uint64_t ec = sArg.env_ctr + (uint64_t)it;
+            s = reset_agent(i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
+        }
+        if (last) {
+            sArg.act_out[i] = a;
+            uint8_t* const dn = sArg.done_out;
+            if (dn) dn[i] = o.done ? 1 : 0;
+            store(sArg.st, n, i, s);
+            write_obs(sArg.obs_io, i, s);
+        } else {
+            write_obs(sObs, threadIdx.x, s);
+        }
+        slot += (uint32_t)n;
+        if (slot >= sArg.capacity) slot -= sArg.capacity;
+    }
+    cp_worker_policy::report(pa, zmax, saw_nan);
+}
+
 }  // namespace
+
+// worker.py:91-119 for the pendulum: `iters` consecutive pairs mpg_policy_action + mpg_env_step_store_reset (noise_ctr + it, ring
+// position (next_idx + it * n) % capacity, env_ctr + it) as one launch (k_worker_rollout_pendulum: bit-identical state, observations,
+// actions, done flags, ring arrays and status word)
+extern "C" int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                                           float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity,
+                                           int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2,
+                                           uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_worker_rollout_pendulum: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_worker_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_worker_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 1, "mpg_worker_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
+                "mpg_worker_rollout_pendulum: tanh policy with an action range");
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
+                "mpg_worker_rollout_pendulum: null pointer");
+    MPG_REQUIRE(n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity,
+                "mpg_worker_rollout_pendulum: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n, capacity, next_idx);
+    MPG_REQUIRE(iters >= 1, "mpg_worker_rollout_pendulum: iters >= 1 (got %d)", iters);
+    // (what bounds one launch's run time; the reference's pendulum worker runs 512)
+    MPG_REQUIRE(iters <= 1024, "mpg_worker_rollout_pendulum: iters <= 1024 (got %d)", iters);
+    // two iterations would write one slot from different workgroups with no order between them
+    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d",
+                (long)iters * n, capacity);
+    cp_worker_policy::Args pa;
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
+    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
+    pa.out_scale = ranged ? cfg->action_range : 1.f;
+    pa.sigma = explore_sigma;
+    pa.k0 = (uint32_t)noise_seed; pa.k1 = (uint32_t)(noise_seed >> 32); pa.c1 = (uint32_t)noise_ctr; pa.c2 = (uint32_t)(noise_ctr >> 32);
+    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+    mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+    if (pa.pack)
+        hipLaunchKernelGGL(k_worker_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring,
+                           capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    else
+        hipLaunchKernelGGL(k_worker_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring,
+                           capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    mpg_prof_end(mpg_prof_of(cfg), 2, s);
+    MPG_CHECK_LAUNCH("mpg_worker_rollout_pendulum");
+    return MPG_OK;
+}
 
 namespace cart_pole {
 

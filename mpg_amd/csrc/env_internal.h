@@ -11,6 +11,10 @@ struct RingPtrs {
 // a 64-bit Philox key and a 64-bit counter as the kernels' four 32-bit arguments (k0, k1, c1, c2)
 #define MPG_KEY_CTR(key, ctr) (uint32_t)(key), (uint32_t)((key) >> 32), (uint32_t)(ctr), (uint32_t)((ctr) >> 32)
 
+// MPG_ENV_INVERTED_DOUBLE_PENDULUM names a differentiable model only (include/mpg_hip.h): every real-env entry point refuses it
+#define MPG_NO_DOUBLE_PENDULUM_ENV \
+    "the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided (only its differentiable model is: the rollout entry points)"
+
 namespace cart_pole {   // env_cart_pole.hip: analytic RK4 statement of inverted_pendulum_conti.xml
 int reset_from_obs(int n, int obs_dim, float* state, const float* init_obs, hipStream_t s);
 int reset(int n, int obs_dim, float* state, const uint8_t* done_mask, uint64_t seed, uint64_t ctr, float* obs, hipStream_t s);

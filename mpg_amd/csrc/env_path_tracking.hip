@@ -939,10 +939,6 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typena
 
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
-// MPG_ENV_INVERTED_DOUBLE_PENDULUM names a differentiable model only (include/mpg_hip.h): every real-env entry point refuses it
-#define MPG_NO_DOUBLE_PENDULUM_ENV \
-    "the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided (only its differentiable model is: the rollout entry points)"
-
 }  // namespace
 
 extern "C" int mpg_env_reset_from_obs(int env_kind, int n, int obs_dim, float* state, const float* init_obs, mpg_stream_t stream) {

@@ -88,6 +88,29 @@ inline bool worker_step_fused(const mpg_train_ctx_t* c) {
 // measurement and of tests/test_worker_rollout_gpu.py, which compares the two drivers bit for bit.
 inline bool worker_rollout_taken(const mpg_train_ctx_t* c) { return c->cfg.obs_dim == 6 && c->sample_iters > 0; }
 inline int sample_iters_of(const mpg_train_ctx_t* c) { return c->sample_iters < 0 ? -c->sample_iters : c->sample_iters; }
+// the same for the pendulum's real env (mpg_worker_rollout_pendulum instead of mpg_policy_action + mpg_env_step_store_reset per
+// iteration), under the same rule (tools/bench_worker_rollout.py --env pendulum) and with the same A/B switch
+inline bool pendulum_rollout_taken(const mpg_train_ctx_t* c) {
+    return c->cfg.env_kind == MPG_ENV_INVERTED_PENDULUM && c->cfg.obs_dim == 4 && c->cfg.act_dim == 1 && c->sample_iters > 0;
+}
+
+// what the loop of sample_and_add does behind each of the k iterations a one-launch sample has just run: the counters, and the new
+// transitions' priorities and the ring position in iteration order
+int rollout_added(mpg_train_ctx_t* c, int k, mpg_stream_t s) {
+    const int n = c->num_agent;
+    c->noise_ctr += k;
+    c->env_ctr += k;
+    for (int it = 0; it < k; ++it) {
+        // new transitions enter at the max priority (buffer.py:127-136), in iteration order: mpg_per_add reads no ring row and
+        // the worker's launch reads no tree
+        if (c->learner_version == 4 && c->prioritized)
+            TRY(mpg_per_add(c->per_sum, c->per_min, c->per_stamp, c->per_capacity, c->ring_capacity, c->ring_next, n, c->per_alpha,
+                            c->per_max_priority, reinterpret_cast<int*>(c->scratch), s));
+        c->ring_next = (c->ring_next + n) % c->ring_capacity;
+        c->ring_size = std::min(c->ring_size + n, c->ring_capacity);
+    }
+    return MPG_OK;
+}
 
 // draws_now: MPG-v2 draws its minibatch right after the add.  The last env launch then gathers it in spare workgroups (the random
 // ring reads overlap the env's sub-steps) except the rows drawn from the slots that launch is writing (path-tracking env, six-entry
@@ -106,18 +129,18 @@ int sample_and_add(mpg_train_ctx_t* c, const float* policy, bool draws_now, bool
             TRY(mpg_worker_rollout(&c->cfg, policy, n, k, c->env_state, c->w_obs, c->explore_sigma, c->worker_seed, c->noise_ctr, c->w_act,
                                    c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
                                    c->env_seed, c->env_ctr, c->w_done, s));
-            c->noise_ctr += k;
-            c->env_ctr += k;
-            for (; it < k; ++it) {
-                // new transitions enter at the max priority (buffer.py:127-136), in iteration order: mpg_per_add reads no ring row and
-                // the worker's launch reads no tree
-                if (c->learner_version == 4 && c->prioritized)
-                    TRY(mpg_per_add(c->per_sum, c->per_min, c->per_stamp, c->per_capacity, c->ring_capacity, c->ring_next, n, c->per_alpha,
-                                    c->per_max_priority, reinterpret_cast<int*>(c->scratch), s));
-                c->ring_next = (c->ring_next + n) % c->ring_capacity;
-                c->ring_size = std::min(c->ring_size + n, c->ring_capacity);
-            }
+            TRY(rollout_added(c, k, s));
+            it = k;
         }
+    }
+    // The pendulum's sample as ONE launch (mpg_worker_rollout_pendulum: bit-identical to the two launches per iteration of the loop
+    // below) under the same conditions; no iteration pre-gathers a draw on this env, so the launch takes them all.
+    if (pendulum_rollout_taken(c) && sample_iters >= 2 && sample_iters <= 1024 && (long)sample_iters * c->num_agent <= c->ring_capacity) {
+        TRY(mpg_worker_rollout_pendulum(&c->cfg, policy, c->num_agent, sample_iters, c->env_state, c->w_obs, c->explore_sigma, c->worker_seed,
+                                        c->noise_ctr, c->w_act, c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew,
+                                        c->ring_obs2, c->ring_done, c->env_seed, c->env_ctr, c->w_done, s));
+        TRY(rollout_added(c, sample_iters, s));
+        it = sample_iters;
     }
     for (; it < sample_iters; ++it) {
         MPG_REQUIRE(c->num_agent <= c->ring_capacity, "mpg_step_begin: ring smaller than one sample");

@@ -467,12 +467,15 @@ def worker_rollout(cfg, policy_params, iters, state, obs_io, explore_sigma, nois
     env.step -> ring -> env.reset) in ONE launch, bit-identical to `iters` mpg_worker_step calls with the counters advancing by one and
     the ring position by n.  state [8, n] and obs_io [n, obs_dim] are advanced in place; ring = (obs, act, rew, obs2, done) arrays of
     `capacity` >= iters * n rows, iteration `it` writes the slots (next_idx + it * n + i) % capacity; done_out [n] (optional) receives
-    the last iteration's done flags.  Returns the last iteration's actions [n, 2]."""
+    the last iteration's done flags.  Returns the last iteration's actions [n, 2].
+    A pendulum cfg (env_kind 1: obs_dim 4, actions [n, 1]) goes to mpg_worker_rollout_pendulum, the same contract against `iters`
+    pairs of mpg_policy_action + mpg_env_step_store_reset."""
     n, dev = obs_io.shape[0], obs_io.device
     act = torch.empty(n, cfg.act_dim, dtype=torch.float32, device=dev)
     r_obs, r_act, r_rew, r_obs2, r_done = ring
     assert r_done.dtype == torch.uint8 and (done_out is None or done_out.dtype == torch.uint8)
-    L.call('mpg_worker_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)), L.ptr(_f32(state)),
+    entry = 'mpg_worker_rollout_pendulum' if cfg.env_kind == 1 else 'mpg_worker_rollout'
+    L.call(entry, ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)), L.ptr(_f32(state)),
            L.ptr(_f32(obs_io)), L.c_float(explore_sigma), L.c_u64(noise_seed), L.c_u64(noise_ctr), L.ptr(act), L.c_int(int(capacity)),
            L.c_int(int(next_idx)), L.ptr(_f32(r_obs)), L.ptr(_f32(r_act)), L.ptr(_f32(r_rew)), L.ptr(_f32(r_obs2)), L.ptr(r_done),
            L.c_u64(env_seed), L.c_u64(env_ctr), L.ptr(done_out), L.stream())

@@ -1,6 +1,9 @@
 """OffPolicyWorker - device mirror of worker.py:25-123: the env-step producer that also owns the master weights and
 the optimizer state (`apply_gradients`).  `sample()` keeps the reference's loop (policy -> + N(0, sigma) ->
-env.step -> env.reset, worker.py:91-119) but every stage is one HIP launch over all `num_agent` agents."""
+env.step -> env.reset, worker.py:91-119) but every stage is one HIP launch over all `num_agent` agents.  With
+`args.one_launch_sample = True` and a deterministic policy all iterations of a sample are ONE launch, bit-identical to the
+loop: mpg_worker_rollout on PathTracking-v0, mpg_worker_rollout_pendulum on InvertedPendulumConti-v0 (where the reference's
+defaults make a sample one agent's 512 iterations)."""
 import torch
 
 from .envs import make_env
@@ -58,7 +61,12 @@ class OffPolicyWorker(object):
     def sample(self):
         """-> (obs, act, RAW reward, obs', done) stacked over batch_size/num_agent env steps (worker.py:91-119)."""
         iters = max(1, self.batch_size // self.num_agent)
-        batch = self._sample_one_launch(iters) if getattr(self.args, 'one_launch_sample', False) else self._sample_loop(iters)
+        if not getattr(self.args, 'one_launch_sample', False):
+            batch = self._sample_loop(iters)
+        elif self.env.kind == 1:
+            batch = self._sample_one_launch_pendulum(iters)
+        else:
+            batch = self._sample_one_launch(iters)
         self.num_sample += batch[0].shape[0]
         self.sample_times += 1
         # judge_is_nan (worker.py:95-107) runs inside the policy kernel: a NaN observation or action sets MPG_STATUS_NAN in the
@@ -94,12 +102,33 @@ class OffPolicyWorker(object):
         launch (mpg_worker_rollout) instead of three per iteration - the five output arrays [iters * n, .] are the launch's ring of
         capacity iters * n at position 0.  Deterministic policy on PathTracking-v0 only.  env.done_intended is NOT refreshed on this
         path (the launch does not form it; env.step does)."""
-        pw, env, n, dev = self.policy_with_value, self.env, self.num_agent, self.device
+        pw, env = self.policy_with_value, self.env
         if not getattr(pw, 'deterministic_policy', True):
             raise ValueError('one_launch_sample serves a deterministic policy only: the stochastic policy\'s loop form '
                              '(mpg_worker_sample_step per iteration) is not built')
         if env.kind != 0:
             raise ValueError('one_launch_sample serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
+        return self._one_launch(iters)
+
+    def _sample_one_launch_pendulum(self, iters):
+        """_sample_one_launch for InvertedPendulumConti-v0 (mpg_worker_rollout_pendulum instead of three launches per iteration; the
+        reference's pendulum worker: one agent, 512 iterations): the same contract - the five output arrays are the launch's ring of
+        capacity iters * n at position 0; batches, worker.obs, env state, env.done and both counters equal _sample_loop's bit for bit
+        over consecutive calls; env.done_intended is NOT refreshed.  Deterministic policy only, at most 1024 iterations."""
+        pw, env = self.policy_with_value, self.env
+        if not getattr(pw, 'deterministic_policy', True):
+            raise ValueError('one_launch_sample on the pendulum serves a deterministic policy only: a one-launch step for the '
+                             'stochastic or squashed policy is not built for this env')
+        if env.kind != 1:
+            raise ValueError('_sample_one_launch_pendulum serves InvertedPendulumConti-v0 only (the env is %s)' % type(env).__name__)
+        if iters > 1024:
+            raise ValueError('one_launch_sample on the pendulum takes at most 1024 iterations per launch (batch_size / num_agent = %d)'
+                             % iters)
+        return self._one_launch(iters)
+
+    def _one_launch(self, iters):
+        """ops.worker_rollout on a fresh ring of capacity iters * n at position 0, then the bookkeeping of `iters` loop iterations"""
+        pw, env, n, dev = self.policy_with_value, self.env, self.num_agent, self.device
         rows, od = iters * n, env.obs_dim
         f = dict(dtype=torch.float32, device=dev)
         ring = (torch.empty(rows, od, **f), torch.empty(rows, pw.act_dim, **f), torch.empty(rows, **f), torch.empty(rows, od, **f),

@@ -1,0 +1,162 @@
+"""mpg_worker_rollout_pendulum at the drop-in boundary, without a GPU: both libraries export it with the declared argument types, and
+every refusal comes back as MPG_EINVAL with a text of its own before any launch (every pointer is FAKE: a launch would fault)."""
+import ctypes
+import os
+import re
+
+import pytest
+
+from mpg_amd import _lib as L
+from mpg_amd import ops
+
+NAME = 'mpg_worker_rollout_pendulum'
+NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
+I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
+MPG_EINVAL = -1000
+ENGINES = sorted(L.ENGINES)
+
+
+@pytest.fixture(scope='module', autouse=True)
+def built():
+    from mpg_amd import build as B
+    return B.build(verbose=False)
+
+
+@pytest.mark.parametrize('engine', ENGINES)
+def test_both_libraries_export_the_entry_point(engine):
+    assert NAME in L.declared_symbols()
+    lib = ctypes.CDLL(L.ENGINES[engine])
+    assert hasattr(lib, NAME)
+    assert lib.mpg_abi_version() == 10           # a function was added: no layout or signature changed
+    assert L.declared_return_types()[NAME] == 'int'
+
+
+def test_declared_argument_types():
+    """the declaration of include/mpg_hip.h, argument by argument: mpg_worker_rollout's, in its order"""
+    src = re.sub(r'/\*.*?\*/', '', open(L.HEADER).read(), flags=re.S)
+    args = {}
+    for name in (NAME, 'mpg_worker_rollout'):
+        m = re.search(r'\bint\s+%s\s*\((.*?)\)\s*;' % name, src, flags=re.S)
+        assert m, name
+        args[name] = [re.sub(r'\s+', ' ', a).strip() for a in m.group(1).split(',')]
+    assert args[NAME] == ['const mpg_cfg_t* cfg', 'const float* policy_params', 'int n', 'int iters', 'float* state', 'float* obs_io',
+                          'float explore_sigma', 'uint64_t noise_seed', 'uint64_t noise_ctr', 'float* act_out', 'int capacity',
+                          'int next_idx', 'float* ring_obs', 'float* ring_act', 'float* ring_rew', 'float* ring_obs2',
+                          'uint8_t* ring_done', 'uint64_t env_seed', 'uint64_t env_ctr', 'uint8_t* done_out', 'mpg_stream_t stream']
+    assert args[NAME] == args['mpg_worker_rollout']
+
+
+def _cfg():
+    return ops.make_cfg('InvertedPendulumConti-v0')
+
+
+def _with(c, **kw):
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+OK = dict(policy=FAKE, n=8, iters=64, state=FAKE, obs_io=FAKE, act_out=FAKE, capacity=512, next_idx=0, ring_obs=FAKE, ring_act=FAKE,
+          ring_rew=FAKE, ring_obs2=FAKE, ring_done=FAKE, done_out=FAKE)
+REFUSALS = [
+    # (cfg, what differs from OK, the text of the refusal)
+    (lambda: ops.make_cfg('InvertedDoublePendulum-v2'), {}, 'MuJoCo'),
+    (lambda: ops.make_cfg('PathTracking-v0'), {}, 'pendulum env only'),
+    (lambda: _with(_cfg(), env_kind=3), {}, 'pendulum env only'),
+    (lambda: _with(_cfg(), obs_dim=6), {}, 'obs_dim 4 only'),
+    (lambda: _with(_cfg(), obs_dim=3), {}, 'obs_dim 4 only'),
+    (lambda: _with(_cfg(), act_dim=2), {}, 'act_dim 1 only'),
+    (lambda: ops.make_cfg('InvertedPendulumConti-v0', policy_out_activation='tanh', action_range=3.0), {}, 'tanh policy with an action range'),
+] + [(_cfg, {k: NULL}, 'null pointer') for k in ('policy', 'state', 'obs_io', 'act_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2',
+                                                  'ring_done')] + [
+    (_cfg, dict(n=0), 'bad ring'),
+    (_cfg, dict(n=8, iters=1, capacity=7), 'bad ring'),
+    (_cfg, dict(next_idx=-1), 'bad ring'),
+    (_cfg, dict(next_idx=512), 'bad ring'),
+    (_cfg, dict(iters=0), 'iters >= 1'),
+    (_cfg, dict(iters=-3), 'iters >= 1'),
+    (_cfg, dict(iters=1025, capacity=1 << 20), 'iters <= 1024'),
+    (_cfg, dict(iters=64, capacity=511), 'do not fit the ring'),
+    (_cfg, dict(n=1 << 22, iters=1024, capacity=(1 << 31) - 1), 'do not fit the ring'),     # iters * n = 2^32: no 32-bit product
+]
+
+
+def _call(lib, cfg_ref, a):
+    return getattr(lib, NAME)(cfg_ref, a['policy'], I(a['n']), I(a['iters']), a['state'], a['obs_io'], F(0.1), U64(1), U64(0), a['act_out'],
+                              I(a['capacity']), I(a['next_idx']), a['ring_obs'], a['ring_act'], a['ring_rew'], a['ring_obs2'],
+                              a['ring_done'], U64(2), U64(0), a['done_out'], NULL)
+
+
+@pytest.mark.parametrize('engine', ENGINES)
+@pytest.mark.parametrize('case', range(len(REFUSALS)),
+                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
+def test_refusals(engine, case):
+    make, diff, text = REFUSALS[case]
+    with L.engine(engine):
+        lib = L.lib()
+        cfg = make()
+        a = dict(OK)
+        a.update(diff)
+        rc = _call(lib, ctypes.byref(cfg), a)
+        msg = lib.mpg_last_error().decode()
+        assert rc == MPG_EINVAL, (rc, msg)
+        assert msg.startswith(NAME + ':') and text in msg, msg
+
+
+@pytest.mark.parametrize('engine', ENGINES)
+def test_refuses_a_null_configuration(engine):
+    with L.engine(engine):
+        lib = L.lib()
+        assert _call(lib, NULL, dict(OK)) == MPG_EINVAL
+        msg = lib.mpg_last_error().decode()
+        assert msg.startswith(NAME + ':') and 'null configuration' in msg, msg
+
+
+@pytest.mark.parametrize('engine', ENGINES)
+def test_a_null_done_out_is_no_refusal_of_its_own(engine):
+    """done_out is the one nullable pointer: with it null the NEXT refusal in line answers (nothing is launched here either)"""
+    with L.engine(engine):
+        lib = L.lib()
+        cfg = _cfg()
+        a = dict(OK, done_out=NULL, iters=0)
+        assert _call(lib, ctypes.byref(cfg), a) == MPG_EINVAL
+        assert 'iters >= 1' in lib.mpg_last_error().decode()
+
+
+def test_every_refusal_has_a_text_of_its_own():
+    """the refusals are told apart by their text: no two conditions share one"""
+    src = open(os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc', 'env_cart_pole.hip')).read()
+    body = src[src.index('extern "C" int %s(' % NAME):]
+    body = body[:body.index('hipLaunchKernelGGL')]
+    texts = re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % NAME, body, flags=re.S)
+    assert len(texts) >= 11 and len(set(texts)) == len(texts), texts
+
+
+def test_the_other_rollout_entry_point_still_refuses_the_pendulum():
+    """a new name, not a widening: mpg_worker_rollout answers a pendulum cfg as it did"""
+    lib = L.lib()
+    cfg = _cfg()
+    rc = lib.mpg_worker_rollout(ctypes.byref(cfg), FAKE, I(8), I(64), FAKE, FAKE, F(0.1), U64(1), U64(0), FAKE, I(512), I(0), FAKE, FAKE,
+                                FAKE, FAKE, FAKE, U64(2), U64(0), FAKE, NULL)
+    assert rc == MPG_EINVAL and 'path-tracking env only' in lib.mpg_last_error().decode()
+
+
+def test_python_refuses_a_stochastic_policy_and_too_many_iterations():
+    """OffPolicyWorker._sample_one_launch_pendulum raises ValueError with a text of its own before it touches the device, and
+    _sample_one_launch keeps raising for the pendulum"""
+    import types
+    from mpg_amd.worker import OffPolicyWorker
+    w = OffPolicyWorker.__new__(OffPolicyWorker)
+    w.num_agent, w.device = 1, 'cpu'
+    w.policy_with_value = types.SimpleNamespace(deterministic_policy=False)
+    w.env = types.SimpleNamespace(kind=1)
+    with pytest.raises(ValueError, match='deterministic policy only'):
+        w._sample_one_launch_pendulum(4)
+    w.policy_with_value = types.SimpleNamespace(deterministic_policy=True)
+    with pytest.raises(ValueError, match='at most 1024 iterations'):
+        w._sample_one_launch_pendulum(1025)
+    with pytest.raises(ValueError, match='PathTracking-v0 only'):
+        w._sample_one_launch(4)
+    w.env = types.SimpleNamespace(kind=0)
+    with pytest.raises(ValueError, match='InvertedPendulumConti-v0 only'):
+        w._sample_one_launch_pendulum(4)

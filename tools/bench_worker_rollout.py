@@ -13,7 +13,11 @@ back-to-back samples, a synchronise at the end of every region):
 The rule for the driver: it calls (b) for a width only if (b)'s median is at or below (a)'s at both sizes of that width.
 
     python tools/bench_worker_rollout.py [--json out.json]          prints markdown tables (EXPERIMENTS.md)
-    python tools/bench_worker_rollout.py --steps-only [--tree DIR]  (c) alone; --tree: time another checkout's build (a parent commit)"""
+    python tools/bench_worker_rollout.py --steps-only [--tree DIR]  (c) alone; --tree: time another checkout's build (a parent commit)
+    python tools/bench_worker_rollout.py --env pendulum [...]       the same for InvertedPendulumConti-v0: (a) the chain of `iters` pairs
+        mpg_policy_action + mpg_env_step_store_reset against (b) mpg_worker_rollout_pendulum at (agents, iters, explore_sigma) =
+        (1, 512, 0.1), (1, 512, 0), (64, 8, 0.1), and (c) one native NADP step at the pendulum parser's defaults (1 agent, 512
+        iterations per sample, B = 256)"""
 import argparse
 import ctypes
 import json
@@ -104,6 +108,102 @@ def sample_case(n, iters, od, sigma=0.1):
     return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb))
 
 
+PENDULUM_CASES = ((1, 512, 0.1), (1, 512, 0.), (64, 8, 0.1))       # (agents, iters, explore_sigma); 1 x 512: the reference's defaults
+
+
+def sample_case_pendulum(n, iters, sigma):
+    """--env pendulum: (a) the chain of `iters` pairs mpg_policy_action + mpg_env_step_store_reset (two launches per iteration, what
+    sample_and_add's loop enqueues on this env) against (b) mpg_worker_rollout_pendulum, as sample_case does it"""
+    import numpy as np
+    import torch
+    from mpg_amd import _lib as L
+    from mpg_amd import ops
+    from mpg_amd.envs import InvertedPendulumContiEnv
+    from tests.golden_inputs import mlp_weights_flat
+    rng = np.random.Generator(np.random.PCG64(n + 4))
+    dev = 'cuda'
+    cfg = ops.make_cfg('InvertedPendulumConti-v0')
+    pol = torch.as_tensor(mlp_weights_flat(rng, 4, 2)).to(dev)
+    wc = ops.WeightCache(pol, [(4, 2)])
+    cfg.wcache[0] = wc.pointer
+    cap = 4 * iters * n + 3 * n                   # (the ring position wraps inside a sample now and then)
+    sides, keep = [], []
+    for _ in range(2):
+        env = InvertedPendulumContiEnv(num_agent=n, seed=4)
+        t = dict(state=env._state, obs=env.reset().clone(), act=torch.empty(n, 1, device=dev), ring_obs=torch.zeros(cap, 4, device=dev),
+                 ring_act=torch.zeros(cap, 1, device=dev), ring_rew=torch.zeros(cap, device=dev), ring_obs2=torch.zeros(cap, 4, device=dev),
+                 ring_done=torch.zeros(cap, dtype=torch.uint8, device=dev), done=torch.zeros(n, dtype=torch.uint8, device=dev))
+        sd = Side(capacity=cap, next_idx=0, ctr=1)
+        for k, v in t.items():
+            setattr(sd, k, v.data_ptr())
+        sides.append((t, sd))
+        keep.append(env)
+    lib, s, c = L.lib(), L.stream(), ctypes.byref(cfg)
+    fp = lambda f: ctypes.cast(f, ctypes.c_void_p)
+    host = host_loops()
+
+    def chain(reps):
+        assert host.bench_chain_pendulum(fp(lib.mpg_policy_action), fp(lib.mpg_env_step_store_reset), c, L.ptr(pol), I(n), I(iters), F(sigma),
+                                         ctypes.byref(sides[0][1]), s, I(reps)) == 0
+
+    def launch(reps):
+        assert host.bench_launch(fp(lib.mpg_worker_rollout_pendulum), c, L.ptr(pol), I(n), I(iters), F(sigma), ctypes.byref(sides[1][1]), s,
+                                 I(reps)) == 0
+    chain(WARMUP), launch(WARMUP)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(REGIONS):                                      # alternating: both see the same machine
+        ta.append(timed(chain, batched=True))
+        tb.append(timed(launch, batched=True))
+    torch.cuda.synchronize()
+    for k in sides[0][0]:                                         # the two did the same work: bit-identical at the end
+        a, b = sides[0][0][k], sides[1][0][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
+    fell = int(sides[1][0]['ring_done'].sum().item())             # (this env's done is real: how many of the ring's rows ended an episode)
+    del keep, wc
+    return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb)), fell, cap
+
+
+def stack_pendulum(chain=False):
+    """NADP at the pendulum parser's defaults: one agent, 512 iterations per sample, B = 256"""
+    from mpg_amd.buffer import ReplayBuffer
+    from mpg_amd.config import default_args
+    from mpg_amd.learners import NADPLearner
+    from mpg_amd.optimizer import SingleProcessOffPolicyOptimizer
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    args = default_args('NADP', nan_check_interval=10 ** 9)
+    assert (args.env_id, args.num_agent, args.batch_size, args.replay_batch_size) == ('InvertedPendulumConti-v0', 1, 512, 256)
+    worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+    opt = SingleProcessOffPolicyOptimizer(worker, NADPLearner(PolicyWithQs, args), ReplayBuffer(args, 0), None, args, sampling_interval=10)
+    assert opt._fused is not None and opt._fused.c.sample_iters == 512
+    if chain:
+        opt._fused.c.sample_iters = -512          # include/mpg_hip.h: the same iterations, two launches each
+    return opt
+
+
+def step_cases_pendulum(out, ab):
+    import torch
+    from mpg_amd.optimizer import quiesce_gc
+    cases = (True, False) if ab else (False,)
+    opts = [stack_pendulum(chain) for chain in cases]
+    quiesce_gc()
+    for _ in range(40):
+        for o in opts:
+            o.step()
+    torch.cuda.synchronize()
+    t = [[] for _ in opts]
+    for _ in range(REGIONS):                                      # alternating; REPS a multiple of the sampling interval
+        for k, o in enumerate(opts):
+            t[k].append(timed(o.step, REPS))
+    print('\n| native NADP step, InvertedPendulumConti-v0, num_agent 1, batch_size 512, sampling_interval 10, B = 256 | ms per step |\n|---|---|',
+          flush=True)
+    for chain, x in zip(cases, t):
+        form = ('chain kept (sample_iters < 0)' if chain else "the driver's own choice") if ab else 'as built'
+        out['step'].append(dict(alg='NADP', form=form, step_ms=statistics.median(x), step_range=(min(x), max(x))))
+        print('| NADP, %s | %.4f (%.4f .. %.4f) |' % (form, statistics.median(x), min(x), max(x)), flush=True)
+
+
 def stack(alg, chain=False):
     from mpg_amd.buffer import ReplayBuffer
     from mpg_amd.config import default_args
@@ -147,6 +247,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--json', default=None)
     ap.add_argument('--steps-only', action='store_true', help='the native step times alone')
+    ap.add_argument('--env', default='path_tracking', choices=('path_tracking', 'pendulum'),
+                    help='pendulum: mpg_worker_rollout_pendulum against its chain, and the native NADP step at the pendulum defaults')
     ap.add_argument('--tree', default=None, help="another checkout of this project whose build is timed (with --steps-only)")
     a = ap.parse_args()
     assert not a.tree or a.steps_only, '--tree times the native steps of another checkout: pass --steps-only'
@@ -154,14 +256,26 @@ def main():
     import torch
     assert torch.cuda.is_available(), 'bench_worker_rollout.py needs a GPU: nothing here is measured without one'
     out = {'sample': [], 'step': []}
-    if not a.steps_only:
+    if a.env == 'pendulum':
+        if not a.steps_only:
+            print('| agents | iters | explore_sigma | (a) chain of mpg_policy_action + mpg_env_step_store_reset, ms | '
+                  '(b) mpg_worker_rollout_pendulum, ms | (a) / (b) | done rows in the ring |\n|---|---|---|---|---|---|---|', flush=True)
+            for n, iters, sigma in PENDULUM_CASES:
+                ma, mb, ra, rb, fell, cap = sample_case_pendulum(n, iters, sigma)
+                out['sample'].append(dict(agents=n, iters=iters, explore_sigma=sigma, chain_ms=ma, chain_range=ra, launch_ms=mb,
+                                          launch_range=rb, done_rows=fell, ring_rows=cap))
+                print('| %d | %d | %g | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f | %d of %d |'
+                      % (n, iters, sigma, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb, fell, cap), flush=True)
+        step_cases_pendulum(out, ab=not a.tree)
+    elif not a.steps_only:
         print('| agents | iters | obs_dim | (a) chain of mpg_worker_step, ms | (b) mpg_worker_rollout, ms | (a) / (b) |\n|---|---|---|---|---|---|', flush=True)
         for n, iters, od in CASES:
             ma, mb, ra, rb = sample_case(n, iters, od)
             out['sample'].append(dict(agents=n, iters=iters, obs_dim=od, chain_ms=ma, chain_range=ra, launch_ms=mb, launch_range=rb))
             print('| %d | %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f |' % (n, iters, od, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb),
                   flush=True)
-    step_cases(out, ab=not a.tree)           # (another checkout may not know the chain-kept form)
+    if a.env != 'pendulum':
+        step_cases(out, ab=not a.tree)       # (another checkout may not know the chain-kept form)
     if a.json:
         with open(a.json, 'w') as fh:
             json.dump(out, fh, indent=1)

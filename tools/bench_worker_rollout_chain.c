@@ -35,6 +35,28 @@ int bench_chain(step_fn worker_step, const mpg_cfg_t* cfg, const float* policy, 
     return 0;
 }
 
+/* the pendulum's chain (bench_worker_rollout.py --env pendulum): two launches per iteration, mpg_policy_action + mpg_env_step_store_reset,
+ * as sample_and_add's loop enqueues them; its one-launch form, mpg_worker_rollout_pendulum, has mpg_worker_rollout's signature and goes
+ * through bench_launch */
+typedef int (*action_fn)(const mpg_cfg_t*, const float*, int, const float*, float, uint64_t, uint64_t, float*, mpg_stream_t);
+typedef int (*step_store_fn)(int, int, int, float*, const float*, int, int, float*, float*, float*, float*, uint8_t*, uint64_t, uint64_t,
+                             float*, uint8_t*, mpg_stream_t);
+
+int bench_chain_pendulum(action_fn policy_action, step_store_fn step_store_reset, const mpg_cfg_t* cfg, const float* policy, int n, int iters,
+                         float sigma, worker_side_t* w, mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = policy_action(cfg, policy, n, w->obs, sigma, 11, w->ctr, w->act, s);
+            if (rc) return rc;
+            rc = step_store_reset(MPG_ENV_INVERTED_PENDULUM, n, 4, w->state, w->act, w->capacity, w->next_idx, w->ring_obs, w->ring_act,
+                                  w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->obs, w->done, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
+
 int bench_launch(rollout_fn worker_rollout, const mpg_cfg_t* cfg, const float* policy, int n, int iters, float sigma, worker_side_t* w,
                  mpg_stream_t s, int reps) {
     for (int r = 0; r < reps; ++r) {
