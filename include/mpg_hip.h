@@ -441,6 +441,29 @@ int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params
                                 float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
                                 uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
 
+/* The pendulum's worker sample for the TANH-SQUASHED Gaussian policy (SAC with an action range; worker.py:96: the action is the
+ * sample, a = action_range * tanh(mean + sigma * eps)) as ONE launch, with mpg_worker_rollout_pendulum's residency: one workgroup per
+ * 16-agent group, the policy's weights in registers, one agent per lane for all iterations.  Everything these `iters` consecutive
+ * triples leave behind, it = 0 .. iters - 1,
+ *   mpg_normal_fill(n, sample_seed, sample_ctr + it, eps, stream);
+ *   mpg_policy_sample_squashed(cfg, policy_params, n, obs_io, eps, act_out, logp, NULL, ws, ws_bytes, stream);
+ *   mpg_env_step_store_reset(MPG_ENV_INVERTED_PENDULUM, n, 4, state, act_out, capacity, (next_idx + it * n) % capacity, ring...,
+ *                            env_seed, env_ctr + it, obs_io, done_out, stream);
+ * is bit-identical: state, obs_io [n][4], act_out [n][1] and done_out [n] (nullable) of the LAST iteration, every ring array and the
+ * sticky status word (the activation-range and NaN reports of the policy pass).  Agent i draws element i of iteration it's stream
+ * inside the launch (no eps array exists); both counters are 64-bit sums.  There is no explore_sigma, as for mpg_worker_sample_step,
+ * and no log-density output: the worker discards it and the ring has no column for it.
+ * Refused before any launch with MPG_EINVAL, "mpg_worker_sample_rollout_pendulum" and a text of its own each, the outputs untouched:
+ * a null configuration, env_kind 2 (the text of the other real-env entry points), any other env that is not the pendulum (PathTracking
+ * with an action range included), what the squashed entry points refuse of a cfg (act_dim != 1, no positive finite action range, a
+ * tanh output activation, obs_dim != 4), a null pointer other than done_out, n <= 0, capacity < n, next_idx outside [0, capacity),
+ * iters < 1, iters > 1024 and iters * n > capacity.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                                       uint64_t sample_seed, uint64_t sample_ctr, float* act_out, int capacity, int next_idx,
+                                       float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
+                                       uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
 /* OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head below,
  * no explore_sigma) as ONE launch for the path-tracking env, obs_dim 6 .. 16, act_dim 2.  Bit-identical - actions, log-densities,
  * every ring row, env state, next observations, done flags and the sticky status word - to

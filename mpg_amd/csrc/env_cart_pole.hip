@@ -15,7 +15,8 @@
 // State block: rows 0..3 of the opaque [MPG_ENV_STATE_DIM][n] array (rows 4..7 unused).
 //
 // Also here, beside the device functions it steps the agents with: mpg_worker_rollout_pendulum, a worker sample's iterations on this
-// env in one launch (k_worker_rollout_pendulum).
+// env in one launch (k_worker_rollout_pendulum), and mpg_worker_sample_rollout_pendulum, the same for the tanh-squashed Gaussian policy
+// (k_worker_sample_rollout_pendulum).
 #include "env_internal.h"
 
 // The worker's policy pass rides in the one-launch worker sample (k_worker_rollout_pendulum, below).  The network engine is compiled
@@ -24,6 +25,7 @@
 // back under "off".
 #pragma clang fp contract(fast)
 #include "mlp_core.h"
+#include "gauss_head.h"
 
 // worker_policy's load / pass / explore / report (env_path_tracking.hip) for the pendulum's policy: four inputs, ONE used output of the
 // two the network has (mean | log-std) - siblings, not a generalisation: the PathTracking kernels' code stays as it is.  The used
@@ -100,6 +102,91 @@ __device__ __forceinline__ void report(const Args& a, float zmax, bool saw_nan) 
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
 }  // namespace cp_worker_policy
+
+// The same for the tanh-squashed Gaussian policy (k_worker_sample_rollout_pendulum, below): BOTH outputs of the network (mean | log-std)
+// as policy_logits launches them for mpg_policy_sample_squashed - k_forward<4, 2, PK, 1>: no action range on the logits, and the linear
+// output only (gauss::squash_refusal leaves no other) - then the row's element of the standard-normal stream and gauss::squash_row
+// itself.  A sibling of cp_worker_policy, not a generalisation: that namespace's kernels keep their code.  The two logits of row
+// `row` are formed by lanes 2 row and 2 row + 1 of wave 0 and go through sLogit [16][2] to lane `row`, the lane that holds the row's
+// agent: LDS is in order within a wave.
+// gauss_head.h is included above, under this block's contraction rule, as learner_api.hip compiles it; of what squash_row calls for the
+// ACTION - the double-precision exp of sigma_of and tanhf - the expansion does not depend on the translation unit's own mode (the
+// instructions of both were compared under the two modes: DESIGN.md section 7 f11), and the log-density's expf / log1pf are dead here.
+namespace cp_sample_policy {
+using namespace mlp;
+constexpr int IN = 4, OU = 2, XSW = xs_of<IN>(), OS = out_stride<OU>();
+static_assert(GROUP * OU <= 64, "the two logits of every row of a group are formed by one wave");
+
+struct Args {
+    const float* params;       // policy network, Keras order
+    const float* pack;         // nullable: packed forward image of W2 (weight cache)
+    int* status;               // nullable: MPG_STATUS_* word of the caller
+    float range, log_r;        // the action range and its logarithm (gauss::log_range)
+    uint32_t k0, k1, c1, c2;   // the draw's key and the counter of iteration 0
+    float scale[IN];           // obs_scale
+};
+
+__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * XSW + NWAVE * GROUP * OS; }
+
+// the policy's registers, once
+template <bool PK>
+__device__ __forceinline__ void load(const Args& a, const Lane& L, float (&w2)[128], SmallRegs<IN, OU>& r, float& b3v) {
+    const Net net = make_net(a.params, IN, OU);
+    b3v = 0.f;
+    if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
+    load_small<IN, OU>(net, L, r);
+    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
+}
+// One evaluation on the group's observations sObs [16][4] in LDS: k_forward<4, 2, PK, 1> for unit g - the same single float32 product
+// with obs_scale, the same device functions on the same operands in the same order, the same row_poison, zmax and NaN test of the
+// logits - leaving the logits in sLogit [16][2] (0 beyond `rows`), written by wave 0's own lanes.  zmax / saw_nan accumulate over
+// the passes.  Starts with the caller's LDS in order (a workgroup barrier behind the writes of sObs).
+__device__ __forceinline__ void pass(const Args& a, int rows, long g, const float* sObs, float* smem, float* sLogit, const Lane& L,
+                                     const float (&w2)[128], const SmallRegs<IN, OU>& r, float b3v, float& zmax, bool& saw_nan) {
+    float* sA = smem;
+    float* sX = sA + A_IMG;
+    float* sPart = sX + GROUP * XSW;
+    if (threadIdx.x < GROUP * XSW) {           // (columns 4 .. 7 and the rows beyond `rows` stay zero)
+        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
+        float xv = 0.f;
+        if (g * GROUP + row < rows && i < IN) xv = sObs[row * IN + i] * a.scale[i];
+        saw_nan |= xv != xv;
+        sX[threadIdx.x] = xv;
+    }
+    lds_barrier();
+    float pz = 0.f;
+    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
+    float h1[2][4], h2[2][4];
+    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    const int tid = threadIdx.x;
+    if (tid < GROUP * OU) {
+        const int row = tid / OU, o = tid % OU;
+        float y = 0.f;
+        if (g * GROUP + row < rows) {
+            y = out_preact<OS>(sPart, b3v, row, o);
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sLogit[tid] = y;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+// Row gr's action from its logits l[2]: element gr of the stream mpg_normal_fill(n, key, counter (c1, c2)) writes - Philox block gr / 4,
+// pair (gr / 2) % 2, the even or the odd element of the pair - and k_row_sums<SquashRow>'s row body on it.  The log-density is not
+// kept: the worker discards it and the ring has no column for it.
+__device__ __forceinline__ float sample(const Args& a, const float* l, int gr, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2) {
+    float z_even, z_odd;
+    gauss::normal_pair((uint32_t)gr >> 2, (gr >> 1) & 1, k0, k1, c1, c2, z_even, z_odd);
+    const float eps = (gr & 1) ? z_odd : z_even;
+    float act;
+    gauss::squash_row(1, a.range, a.log_r, l, &eps, &act);
+    return act;
+}
+__device__ __forceinline__ void report(const Args& a, float zmax, bool saw_nan) {
+    report_activation_range(a.status, zmax);
+    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
+}
+}  // namespace cp_sample_policy
 #pragma clang fp contract(off)
 
 namespace {
@@ -329,6 +416,91 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(con
     cp_worker_policy::report(pa, zmax, saw_nan);
 }
 
+// k_worker_sample_rollout_pendulum (below): CpRolloutEnvArgs for the squashed policy's launch - the draw's key and counter in the place
+// of the exploration noise's, and the head's two constants
+struct CpSampleRolloutEnvArgs {
+    RingPtrs ring;
+    float *st, *obs_io, *act_out;
+    uint8_t* done_out;
+    uint32_t k0, k1, sk0, sk1;     // env key, draw key
+    uint64_t env_ctr, sample_ctr;  // the counters of iteration 0
+    uint32_t capacity;
+};
+
+// The same `iters` iterations for the tanh-squashed Gaussian policy (SAC with an action range, worker.py:96: the action IS the sample):
+// `iters` consecutive triples of mpg_normal_fill(n, sample key, sample counter + it), mpg_policy_sample_squashed (k_forward<4, 2, PK, 1>
+// and k_row_sums<SquashRow>) and k_cp_step_store_reset in ONE launch.  A sibling of k_worker_rollout_pendulum with its residency plan:
+// one 512-thread workgroup per 16-agent group, the policy's registers loaded once, one agent (S4) per lane 0 .. 15 of wave 0 across the
+// iterations, the observations to the pass through LDS between workgroup barriers, global memory read in the prologue only, state /
+// obs_io / act_out / done_out written after the LAST iteration only, the env lanes' arguments in LDS, the status word reported once.
+// New between the pass and the env step: the row's two logits come to its env lane through sLogit, the lane draws element i of the
+// iteration's stream and forms a = range * tanh(mean + sigma * eps) (cp_sample_policy::sample), which goes to step_agent in a register.
+template <bool PK>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout_pendulum(const cp_sample_policy::Args pa, int n, int iters,
+                                                                                     float* st, float* obs_io, float* act_out, RingPtrs ring,
+                                                                                     int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                                                     uint32_t c1, uint32_t c2, uint8_t* done_out) {
+    __shared__ __attribute__((aligned(16))) float smem[cp_sample_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
+    __shared__ __attribute__((aligned(16))) float sLogit[mlp::GROUP * 2];
+    __shared__ CpSampleRolloutEnvArgs sArg;
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<4, 2> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    cp_sample_policy::load<PK>(pa, L, w2, r, b3v);
+    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
+    const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
+    S4 s = {};
+    if (env_lane) s = load(st, n, i);
+    {   // the group's rows of obs_io (16 x 4 floats)
+        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.ring = ring;
+        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
+        sArg.k0 = k0; sArg.k1 = k1; sArg.sk0 = pa.k0; sArg.sk1 = pa.k1;
+        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
+        sArg.sample_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        sArg.capacity = (uint32_t)capacity;
+    }
+    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    uint32_t slot = env_lane ? (uint32_t)(((long)next_idx + i) % capacity) : 0u;
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
+        cp_sample_policy::pass(pa, n, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
+        if (!env_lane) continue;
+        const uint64_t sc = sArg.sample_ctr + (uint64_t)it;
+        const float a = cp_sample_policy::sample(pa, sLogit + 2 * threadIdx.x, i, sArg.sk0, sArg.sk1, (uint32_t)sc, (uint32_t)(sc >> 32));
+        write_obs(sArg.ring.obs, slot, s);               // obs before the step
+        sArg.ring.act[slot] = a;
+        const StepOut o = step_agent(s, a);
+        write_obs(sArg.ring.obs2, slot, s);
+        sArg.ring.rew[slot] = o.reward;
+        sArg.ring.done[slot] = o.done ? 1 : 0;
+        if (o.done) {
+            const uint64_t ec = sArg.env_ctr + (uint64_t)it;
+            s = reset_agent(i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
+        }
+        if (last) {
+            sArg.act_out[i] = a;
+            uint8_t* const dn = sArg.done_out;
+            if (dn) dn[i] = o.done ? 1 : 0;
+            store(sArg.st, n, i, s);
+            write_obs(sArg.obs_io, i, s);
+        } else {
+            write_obs(sObs, threadIdx.x, s);
+        }
+        slot += (uint32_t)n;
+        if (slot >= sArg.capacity) slot -= sArg.capacity;
+    }
+    cp_sample_policy::report(pa, zmax, saw_nan);
+}
+
 }  // namespace
 
 // worker.py:91-119 for the pendulum: `iters` consecutive pairs mpg_policy_action + mpg_env_step_store_reset (noise_ctr + it, ring
@@ -378,6 +550,54 @@ extern "C" int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* po
                            capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_rollout_pendulum");
+    return MPG_OK;
+}
+
+// worker.py:91-119 for the pendulum under the tanh-squashed Gaussian policy: `iters` consecutive triples mpg_normal_fill(n, sample_seed,
+// sample_ctr + it) + mpg_policy_sample_squashed + mpg_env_step_store_reset (ring position (next_idx + it * n) % capacity, env_ctr + it) as
+// one launch (k_worker_sample_rollout_pendulum: bit-identical state, observations, actions, done flags, ring arrays and status word)
+extern "C" int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state,
+                                                  float* obs_io, uint64_t sample_seed, uint64_t sample_ctr, float* act_out, int capacity,
+                                                  int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2,
+                                                  uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out,
+                                                  mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_worker_sample_rollout_pendulum: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_sample_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    // (the squashed head itself is also built for PathTracking; this launch steps the pendulum)
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_worker_sample_rollout_pendulum: pendulum env only (env kind %d)",
+                cfg->env_kind);
+    // what the head asks of a cfg (the pointers and the row count are judged below, with the ring)
+    if (int rc = gauss::squash_refusal("mpg_worker_sample_rollout_pendulum", cfg, true, 1, 0.f)) return rc;
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
+                "mpg_worker_sample_rollout_pendulum: null pointer");
+    MPG_REQUIRE(n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity,
+                "mpg_worker_sample_rollout_pendulum: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n, capacity, next_idx);
+    MPG_REQUIRE(iters >= 1, "mpg_worker_sample_rollout_pendulum: iters >= 1 (got %d)", iters);
+    // (what bounds one launch's run time; the reference's pendulum worker runs 512)
+    MPG_REQUIRE(iters <= 1024, "mpg_worker_sample_rollout_pendulum: iters <= 1024 (got %d)", iters);
+    // two iterations would write one slot from different workgroups with no order between them
+    MPG_REQUIRE((long)iters * n <= capacity,
+                "mpg_worker_sample_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d", (long)iters * n, capacity);
+    cp_sample_policy::Args pa;
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    pa.range = cfg->action_range;
+    pa.log_r = gauss::log_range(cfg->action_range);
+    pa.k0 = (uint32_t)sample_seed; pa.k1 = (uint32_t)(sample_seed >> 32); pa.c1 = (uint32_t)sample_ctr; pa.c2 = (uint32_t)(sample_ctr >> 32);
+    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+    mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+    if (pa.pack)
+        hipLaunchKernelGGL(k_worker_sample_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out,
+                           ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    else
+        hipLaunchKernelGGL(k_worker_sample_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out,
+                           ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    mpg_prof_end(mpg_prof_of(cfg), 2, s);
+    MPG_CHECK_LAUNCH("mpg_worker_sample_rollout_pendulum");
     return MPG_OK;
 }
 

@@ -3,7 +3,8 @@ the optimizer state (`apply_gradients`).  `sample()` keeps the reference's loop 
 env.step -> env.reset, worker.py:91-119) but every stage is one HIP launch over all `num_agent` agents.  With
 `args.one_launch_sample = True` and a deterministic policy all iterations of a sample are ONE launch, bit-identical to the
 loop: mpg_worker_rollout on PathTracking-v0, mpg_worker_rollout_pendulum on InvertedPendulumConti-v0 (where the reference's
-defaults make a sample one agent's 512 iterations)."""
+defaults make a sample one agent's 512 iterations) - and there also with the tanh-squashed Gaussian policy (squashed_head=True):
+mpg_worker_sample_rollout_pendulum."""
 import torch
 
 from .envs import make_env
@@ -63,6 +64,8 @@ class OffPolicyWorker(object):
         iters = max(1, self.batch_size // self.num_agent)
         if not getattr(self.args, 'one_launch_sample', False):
             batch = self._sample_loop(iters)
+        elif self.env.kind == 1 and not getattr(self.policy_with_value, 'deterministic_policy', True):
+            batch = self._sample_one_launch_stochastic_pendulum(iters)
         elif self.env.kind == 1:
             batch = self._sample_one_launch_pendulum(iters)
         else:
@@ -126,8 +129,33 @@ class OffPolicyWorker(object):
                              % iters)
         return self._one_launch(iters)
 
-    def _one_launch(self, iters):
-        """ops.worker_rollout on a fresh ring of capacity iters * n at position 0, then the bookkeeping of `iters` loop iterations"""
+    def _sample_one_launch_stochastic_pendulum(self, iters):
+        """_sample_one_launch_pendulum for the tanh-squashed Gaussian policy (squashed_head=True: SAC with an action range, the one
+        stochastic head built for this env): mpg_worker_sample_rollout_pendulum instead of the loop's launches per iteration (the draw,
+        the policy pass, the head's row sums, env.step, env.reset).  The same contract: batches, worker.obs, env state, env.done and both
+        counters equal _sample_loop's bit for bit over consecutive calls; env.done_intended is NOT refreshed.  No explore_sigma (the
+        loop adds that noise with a torch op, which has no place in the launch), at most 1024 iterations."""
+        pw, env = self.policy_with_value, self.env
+        if getattr(pw, 'deterministic_policy', True):
+            raise ValueError('_sample_one_launch_stochastic_pendulum serves a stochastic policy (a deterministic one takes '
+                             '_sample_one_launch_pendulum)')
+        if not getattr(pw, 'squashed_head', False):
+            raise ValueError('one_launch_sample on the pendulum serves the tanh-squashed head only (squashed_head=True): a stochastic '
+                             'policy without an action range is not built for this env')
+        if self.explore_sigma is not None:
+            raise ValueError('one_launch_sample with a stochastic policy takes no explore_sigma (got %r): the action is the sample'
+                             % (self.explore_sigma,))
+        if env.kind != 1:
+            raise ValueError('_sample_one_launch_stochastic_pendulum serves InvertedPendulumConti-v0 only (the env is %s)'
+                             % type(env).__name__)
+        if iters > 1024:
+            raise ValueError('one_launch_sample with the squashed head takes at most 1024 iterations per launch (batch_size / num_agent '
+                             '= %d)' % iters)
+        return self._one_launch(iters, sampled=True)
+
+    def _one_launch(self, iters, sampled=False):
+        """ops.worker_rollout (sampled: ops.worker_sample_rollout, the draw keyed as the loop keys it: (seed, _noise_ctr)) on a fresh
+        ring of capacity iters * n at position 0, then the bookkeeping of `iters` loop iterations"""
         pw, env, n, dev = self.policy_with_value, self.env, self.num_agent, self.device
         rows, od = iters * n, env.obs_dim
         f = dict(dtype=torch.float32, device=dev)
@@ -135,8 +163,12 @@ class OffPolicyWorker(object):
                 torch.empty(rows, dtype=torch.uint8, device=dev))
         obs_io = self.obs.clone()               # never write into a tensor already handed to the caller
         done = torch.empty(n, dtype=torch.uint8, device=dev)
-        ops.worker_rollout(pw.cfg, pw.net('policy'), iters, env._state, obs_io, float(self.explore_sigma or 0.), self.seed, self._noise_ctr,
-                           ring, rows, 0, env.seed, env._ctr, done_out=done)
+        if sampled:
+            ops.worker_sample_rollout(pw.cfg, pw.net('policy'), iters, env._state, obs_io, self.seed, self._noise_ctr, ring, rows, 0, env.seed,
+                                      env._ctr, done_out=done)
+        else:
+            ops.worker_rollout(pw.cfg, pw.net('policy'), iters, env._state, obs_io, float(self.explore_sigma or 0.), self.seed, self._noise_ctr,
+                               ring, rows, 0, env.seed, env._ctr, done_out=done)
         self._noise_ctr += iters
         env._ctr += iters
         env.obs, env.done, env.reward = obs_io, done, ring[2][rows - n:]

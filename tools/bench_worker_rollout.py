@@ -17,7 +17,11 @@ The rule for the driver: it calls (b) for a width only if (b)'s median is at or 
     python tools/bench_worker_rollout.py --env pendulum [...]       the same for InvertedPendulumConti-v0: (a) the chain of `iters` pairs
         mpg_policy_action + mpg_env_step_store_reset against (b) mpg_worker_rollout_pendulum at (agents, iters, explore_sigma) =
         (1, 512, 0.1), (1, 512, 0), (64, 8, 0.1), and (c) one native NADP step at the pendulum parser's defaults (1 agent, 512
-        iterations per sample, B = 256)"""
+        iterations per sample, B = 256)
+    python tools/bench_worker_rollout.py --env pendulum --stochastic [--json out.json]   the tanh-squashed Gaussian policy on the pendulum:
+        (a) the chain of `iters` triples mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset (four launches per
+        iteration) against (b) mpg_worker_sample_rollout_pendulum at (agents, iters) = (1, 512) - the reference's SAC defaults - and
+        (64, 8), and (d) OffPolicyWorker.sample() of the squashed SAC stack at 1 x 512 on its loop and with one_launch_sample, alternating"""
 import argparse
 import ctypes
 import json
@@ -164,6 +168,97 @@ def sample_case_pendulum(n, iters, sigma):
     return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb)), fell, cap
 
 
+STOCHASTIC_CASES = ((1, 512), (64, 8))                              # (agents, iters); 1 x 512: built_SAC_parser's defaults
+SAMPLE_REPS = 20                                                    # worker.sample() calls per region (the loop form is 512 x 5 launches)
+
+
+def sample_case_stochastic_pendulum(n, iters):
+    """--env pendulum --stochastic: (a) the three entry points per iteration against (b) mpg_worker_sample_rollout_pendulum, as
+    sample_case_pendulum does it"""
+    import numpy as np
+    import torch
+    from mpg_amd import _lib as L
+    from mpg_amd import ops
+    from mpg_amd.envs import InvertedPendulumContiEnv
+    from tests.golden_inputs import mlp_weights_flat
+    rng = np.random.Generator(np.random.PCG64(n + 4))
+    dev = 'cuda'
+    cfg = ops.make_cfg('InvertedPendulumConti-v0')
+    pol = torch.as_tensor(mlp_weights_flat(rng, 4, 2)).to(dev)
+    wc = ops.WeightCache(pol, [(4, 2)])
+    cfg.wcache[0] = wc.pointer
+    cap = 4 * iters * n + 3 * n                   # (the ring position wraps inside a sample now and then)
+    sides, keep = [], []
+    for _ in range(2):
+        env = InvertedPendulumContiEnv(num_agent=n, seed=4)
+        t = dict(state=env._state, obs=env.reset().clone(), act=torch.empty(n, 1, device=dev), ring_obs=torch.zeros(cap, 4, device=dev),
+                 ring_act=torch.zeros(cap, 1, device=dev), ring_rew=torch.zeros(cap, device=dev), ring_obs2=torch.zeros(cap, 4, device=dev),
+                 ring_done=torch.zeros(cap, dtype=torch.uint8, device=dev), done=torch.zeros(n, dtype=torch.uint8, device=dev))
+        sd = Side(capacity=cap, next_idx=0, ctr=1)
+        for k, v in t.items():
+            setattr(sd, k, v.data_ptr())
+        sides.append((t, sd))
+        keep.append(env)
+    eps, logp = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    ws = ops._ws(dev, 0, 'mpg_policy_sample_squashed_workspace_bytes', cfg, n)
+    lib, s, c = L.lib(), L.stream(), ctypes.byref(cfg)
+    fp = lambda f: ctypes.cast(f, ctypes.c_void_p)
+    host = host_loops()
+
+    def chain(reps):
+        assert host.bench_chain_sample_pendulum(fp(lib.mpg_normal_fill), fp(lib.mpg_policy_sample_squashed), fp(lib.mpg_env_step_store_reset), c,
+                                                L.ptr(pol), I(n), I(iters), L.ptr(eps), L.ptr(logp), *ws, ctypes.byref(sides[0][1]), s,
+                                                I(reps)) == 0
+
+    def launch(reps):
+        assert host.bench_launch_sample(fp(lib.mpg_worker_sample_rollout_pendulum), c, L.ptr(pol), I(n), I(iters), ctypes.byref(sides[1][1]), s,
+                                        I(reps)) == 0
+    chain(WARMUP), launch(WARMUP)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(REGIONS):                                      # alternating: both see the same machine
+        ta.append(timed(chain, batched=True))
+        tb.append(timed(launch, batched=True))
+    torch.cuda.synchronize()
+    for k in sides[0][0]:                                         # the two did the same work: bit-identical at the end
+        a, b = sides[0][0][k], sides[1][0][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
+    fell = int(sides[1][0]['ring_done'].sum().item())
+    del keep, wc
+    return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb)), fell, cap
+
+
+def worker_sample_stochastic_pendulum(out):
+    """(d): OffPolicyWorker.sample() of the squashed SAC stack at the reference's defaults (one agent, 512 iterations) on its loop and
+    with one_launch_sample - host time included: the loop's launches are enqueued from Python, as a training run enqueues them"""
+    import torch
+    from mpg_amd.config import default_args
+    from mpg_amd.optimizer import quiesce_gc
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    workers = []
+    for one in (False, True):
+        args = default_args('SAC', env_id='InvertedPendulumConti-v0', squashed_head=True, nan_check_interval=10 ** 9,
+                            **(dict(one_launch_sample=True) if one else {}))
+        assert (args.num_agent, args.batch_size, args.action_range) == (1, 512, 3.0)
+        workers.append(OffPolicyWorker(PolicyWithQs, args.env_id, args, 0))
+    quiesce_gc()
+    for w in workers:
+        for _ in range(WARMUP):
+            w.sample()
+    torch.cuda.synchronize()
+    t = [[], []]
+    for _ in range(REGIONS):
+        for k, w in enumerate(workers):
+            t[k].append(timed(w.sample, SAMPLE_REPS))
+    for a, b in zip(workers[0].sample(), workers[1].sample()):    # the two did the same work: bit-identical at the end
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b)
+    print('\n| OffPolicyWorker.sample(), squashed SAC, InvertedPendulumConti-v0, num_agent 1, batch_size 512 | ms per sample |\n|---|---|', flush=True)
+    for form, x in zip(('the loop (five launches per iteration)', 'one_launch_sample'), t):
+        out['worker_sample'].append(dict(form=form, sample_ms=statistics.median(x), sample_range=(min(x), max(x))))
+        print('| %s | %.4f (%.4f .. %.4f) |' % (form, statistics.median(x), min(x), max(x)), flush=True)
+
+
 def stack_pendulum(chain=False):
     """NADP at the pendulum parser's defaults: one agent, 512 iterations per sample, B = 256"""
     from mpg_amd.buffer import ReplayBuffer
@@ -249,14 +344,29 @@ def main():
     ap.add_argument('--steps-only', action='store_true', help='the native step times alone')
     ap.add_argument('--env', default='path_tracking', choices=('path_tracking', 'pendulum'),
                     help='pendulum: mpg_worker_rollout_pendulum against its chain, and the native NADP step at the pendulum defaults')
+    ap.add_argument('--stochastic', action='store_true',
+                    help='with --env pendulum: mpg_worker_sample_rollout_pendulum (the tanh-squashed Gaussian policy) against its chain, '
+                         'and OffPolicyWorker.sample() both ways')
     ap.add_argument('--tree', default=None, help="another checkout of this project whose build is timed (with --steps-only)")
     a = ap.parse_args()
     assert not a.tree or a.steps_only, '--tree times the native steps of another checkout: pass --steps-only'
+    assert not a.stochastic or (a.env == 'pendulum' and not a.steps_only), '--stochastic goes with --env pendulum (no native step serves it)'
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else os.path.dirname(HERE))
     import torch
     assert torch.cuda.is_available(), 'bench_worker_rollout.py needs a GPU: nothing here is measured without one'
     out = {'sample': [], 'step': []}
-    if a.env == 'pendulum':
+    if a.stochastic:
+        out['worker_sample'] = []
+        print('| agents | iters | (a) chain of mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset, ms | '
+              '(b) mpg_worker_sample_rollout_pendulum, ms | (a) / (b) | done rows in the ring |\n|---|---|---|---|---|---|', flush=True)
+        for n, iters in STOCHASTIC_CASES:
+            ma, mb, ra, rb, fell, cap = sample_case_stochastic_pendulum(n, iters)
+            out['sample'].append(dict(agents=n, iters=iters, chain_ms=ma, chain_range=ra, launch_ms=mb, launch_range=rb, done_rows=fell,
+                                      ring_rows=cap))
+            print('| %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f | %d of %d |'
+                  % (n, iters, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb, fell, cap), flush=True)
+        worker_sample_stochastic_pendulum(out)
+    elif a.env == 'pendulum':
         if not a.steps_only:
             print('| agents | iters | explore_sigma | (a) chain of mpg_policy_action + mpg_env_step_store_reset, ms | '
                   '(b) mpg_worker_rollout_pendulum, ms | (a) / (b) | done rows in the ring |\n|---|---|---|---|---|---|---|', flush=True)

@@ -1,6 +1,6 @@
 /* Host loops of tools/bench_worker_rollout.py: one worker sample as `iters` mpg_worker_step launches (what sample_and_add of
  * train_step.cpp enqueues without the one-launch form) and as one mpg_worker_rollout launch, `reps` samples back to back, so that
- * neither is charged an interpreter or a foreign-function call per launch.  The entry points come in as pointers (the tool resolves
+ * neither is charged an interpreter or a foreign-function call per launch (and the pendulum's forms of both, further down).  The entry points come in as pointers (the tool resolves
  * them in the engine's library), so this file links against nothing.
  *
  *   cc -O2 -shared -fPIC -Iinclude tools/bench_worker_rollout_chain.c -o tools/bench_worker_rollout_chain.so
@@ -61,6 +61,45 @@ int bench_launch(rollout_fn worker_rollout, const mpg_cfg_t* cfg, const float* p
                  mpg_stream_t s, int reps) {
     for (int r = 0; r < reps; ++r) {
         int rc = worker_rollout(cfg, policy, n, iters, w->state, w->obs, sigma, 11, w->ctr, w->act, w->capacity, w->next_idx, w->ring_obs,
+                                w->ring_act, w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
+        if (rc) return rc;
+        w->ctr += (uint64_t)iters;
+        w->next_idx = (int)(((long)w->next_idx + (long)iters * n) % w->capacity);
+    }
+    return 0;
+}
+
+/* the pendulum's chain under the tanh-squashed Gaussian policy (bench_worker_rollout.py --env pendulum --stochastic): three calls per
+ * iteration, mpg_normal_fill + mpg_policy_sample_squashed (two launches) + mpg_env_step_store_reset, against its one-launch form,
+ * mpg_worker_sample_rollout_pendulum; eps / logp [n] and the workspace are the caller's */
+typedef int (*normal_fill_fn)(int, uint64_t, uint64_t, float*, mpg_stream_t);
+typedef int (*sample_squashed_fn)(const mpg_cfg_t*, const float*, int, const float*, const float*, float*, float*, float*, void*, size_t,
+                                  mpg_stream_t);
+typedef int (*sample_rollout_fn)(const mpg_cfg_t*, const float*, int, int, float*, float*, uint64_t, uint64_t, float*, int, int, float*,
+                                 float*, float*, float*, uint8_t*, uint64_t, uint64_t, uint8_t*, mpg_stream_t);
+
+int bench_chain_sample_pendulum(normal_fill_fn normal_fill, sample_squashed_fn policy_sample, step_store_fn step_store_reset,
+                                const mpg_cfg_t* cfg, const float* policy, int n, int iters, float* eps, float* logp, void* ws,
+                                size_t ws_bytes, worker_side_t* w, mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = normal_fill(n, 11, w->ctr, eps, s);
+            if (rc) return rc;
+            rc = policy_sample(cfg, policy, n, w->obs, eps, w->act, logp, 0, ws, ws_bytes, s);
+            if (rc) return rc;
+            rc = step_store_reset(MPG_ENV_INVERTED_PENDULUM, n, 4, w->state, w->act, w->capacity, w->next_idx, w->ring_obs, w->ring_act,
+                                  w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->obs, w->done, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
+
+int bench_launch_sample(sample_rollout_fn sample_rollout, const mpg_cfg_t* cfg, const float* policy, int n, int iters, worker_side_t* w,
+                        mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r) {
+        int rc = sample_rollout(cfg, policy, n, iters, w->state, w->obs, 11, w->ctr, w->act, w->capacity, w->next_idx, w->ring_obs,
                                 w->ring_act, w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
         if (rc) return rc;
         w->ctr += (uint64_t)iters;
