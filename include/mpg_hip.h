@@ -482,6 +482,32 @@ int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_params, int
                            uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out /* nullable */,
                            mpg_stream_t stream);
 
+/* OffPolicyWorker.sample's loop for a STOCHASTIC policy on the path-tracking env (obs_dim 6 .. 16, act_dim 2) as ONE launch, with
+ * mpg_worker_rollout's residency: one workgroup keeps a 16-agent group's policy weights (all four output columns) and agents in
+ * registers for all iterations; global memory is read at the start only and written, never read back.  Both heads: the plain Gaussian
+ * one (no action range) and the tanh-squashed one (cfg->action_range > 0 over a linear output: a = action_range * tanh(mean + sigma *
+ * eps)).  Everything these `iters` consecutive triples leave behind, it = 0 .. iters - 1,
+ *   mpg_normal_fill(2 n, sample_seed, sample_ctr + it, eps, stream);
+ *   mpg_policy_sample(cfg, policy_params, n, obs_io, eps, act_out, logp, NULL, ws, ws_bytes, stream);      (no action range)
+ *   mpg_policy_sample_squashed(... the same arguments ...);                                                (with one)
+ *   mpg_env_step_store_reset(MPG_ENV_PATH_TRACKING, n, obs_dim, state, act_out, capacity, (next_idx + it * n) % capacity, ring...,
+ *                            env_seed, env_ctr + it, obs_io, done_out, stream);
+ * is bit-identical: state, obs_io [n][obs_dim], act_out [n][2] and done_out [n] (nullable) of the LAST iteration, every ring array -
+ * iteration `it` writes the slots (next_idx + it * n + i) % capacity, no other slot is touched - and the sticky status word (the
+ * activation-range and NaN reports of the policy pass).  Without an action range that is also `iters` calls of mpg_worker_sample_step.
+ * Row r draws elements 2 r and 2 r + 1 of iteration it's stream inside the launch (no eps array exists); both counters are 64-bit
+ * sums.  There is no explore_sigma and no log-density output: the worker discards it and the ring has no column for it.
+ * Refused before any launch with MPG_EINVAL, "mpg_worker_sample_rollout" and a text of its own each, the outputs untouched: a null
+ * configuration, env_kind 2 (the text of the other real-env entry points), any other env that is not PathTracking, act_dim != 2,
+ * obs_dim outside 6 .. 16, with an action range what the squashed entry points refuse of it (a tanh output activation, a range that
+ * is not finite), a null pointer other than done_out, n <= 0, capacity < n, next_idx outside [0, capacity), iters < 1, iters > 1024
+ * and iters * n > capacity.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                              uint64_t sample_seed, uint64_t sample_ctr, float* act_out, int capacity, int next_idx,
+                              float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
+                              uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
 /* MPGLearner.sample / NDPGLearner.sample - learners/mpg_learner.py:109-124, learners/ndpg.py:99-114, PathTracking env, ONE launch:
  * from obs0 [rows][obs_dim] take n real-env steps, the first with the replay action act0 [rows][2], the later ones with the ONLINE
  * policy's deterministic action (no noise, no reset on done).  rewards [n][rows] RAW, last_obs [rows][obs_dim].  Bit-identical - the
@@ -797,7 +823,10 @@ typedef struct {
                                          mpg_worker_step each.  On the pendulum's real env (env_kind 1, obs_dim 4, act_dim 1) all of
                                          them are ONE mpg_worker_rollout_pendulum under the same two conditions, else
                                          mpg_policy_action + mpg_env_step_store_reset each.  sample_iters < 0 (one more accepted value of this int: no layout
-                                         changed) asks for |sample_iters| steps with the chain KEPT: the A/B form of that measurement */
+                                         changed) asks for |sample_iters| steps with the chain KEPT: the A/B form of that measurement.
+                                         Version 7 (mpg_sac_step_begin / mpg_sac_auto_step_begin): all of them are ONE
+                                         mpg_worker_sample_rollout under the same two conditions, at every obs_dim, else
+                                         one mpg_worker_sample_step each; sample_iters < 0 keeps that chain likewise */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];
     float eta;                        /* rule_based_weights, mpg_learner.py:384-399 */
@@ -869,7 +898,7 @@ int mpg_step_end(mpg_train_ctx_t* ctx, int iteration, mpg_stream_t stream);
 /* mpg_step_begin for learner_version 7 - SingleProcessOffPolicyOptimizer.step with SACLearner.compute_gradient (sac.py:169-219) on a
  * uniform replay ring, through the entry points above only and with the counters advanced as the Python classes advance them:
  *   [every sampling_interval-th iteration, sample_iters x: the stochastic worker step keyed by (worker_seed, noise_ctr++) and
- *    (env_seed, env_ctr++) -> ring];  replay_times++;  on every num_batch_reuse-th call: mpg_replay_sample_uniform,
+ *    (env_seed, env_ctr++) -> ring - as ONE mpg_worker_sample_rollout where mpg_train_ctx_t.sample_iters says so, bit-identical];  replay_times++;  on every num_batch_reuse-th call: mpg_replay_sample_uniform,
  *   mpg_normal_fill(batch * act_dim, learner_seed, 2 * (learner_counter + 1)), mpg_sac_targets with the ONLINE policy and both target
  *   critics into b_targets;  learner_counter++;  mpg_q_loss_grad for Q1 and Q2 (statistics 0, 1);
  *   mpg_normal_fill(batch * act_dim, learner_seed, 2 * learner_counter + 1);  mpg_sac_policy_grad (statistics 2 .. 4: the sums of

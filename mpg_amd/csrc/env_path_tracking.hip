@@ -257,6 +257,76 @@ __device__ __forceinline__ void report(const A& a, float zmax, bool saw_nan) {
     report_activation_range(a.status, zmax);
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
+// `sample_group` in the same two parts, for a kernel that samples one group MANY times (k_worker_sample_rollout, below), beside it and
+// beside load / pass: every shipped kernel keeps its code.  sample_load: the FOUR-output policy registers, once.  sample_pass: the
+// four logits of every row of the group on sObs [16][od] - k_forward<IN, 4, PK, 1> for unit g as policy_logits launches it: the same
+// single float32 product with obs_scale, the same device functions on the same operands in the same order, the output activation on
+// all four columns (a.out_scale and a.sigma are not read), the same row_poison, activation-range and NaN accumulation as
+// sample_group - left in sLogit [16][4] (0 beyond `rows`) by lanes 4 row .. 4 row + 3 of wave 0, the lanes that step the row's agent.
+template <bool PK, int IN>
+__device__ __forceinline__ void sample_load(const typename args_of<IN>::type& a, const Lane& L, float (&w2)[128], SmallRegs<IN, 4>& r,
+                                            float& b3v) {
+    static_assert(GROUP * 4 == 64, "the four logits of every row of a group are formed by one wave");
+    const Net net = make_net(a.params, obs_dim_of(a), 4);
+    b3v = 0.f;
+    if (threadIdx.x < GROUP * 4) b3v = net.b3[threadIdx.x % 4];
+    load_small<IN, 4>(net, L, r);
+    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
+}
+template <int IN>
+__device__ __forceinline__ void sample_pass(const typename args_of<IN>::type& a, int rows, long g, const float* sObs, float* smem,
+                                            float* sLogit, const Lane& L, const float (&w2)[128], const SmallRegs<IN, 4>& r, float b3v,
+                                            float& zmax, bool& saw_nan) {
+    constexpr int OU = 4, XSW = xs_of<IN>(), OS = out_stride<OU>();
+    const int od = obs_dim_of(a);
+    float* sA = smem;
+    float* sX = sA + A_IMG;
+    float* sPart = sX + GROUP * XSW;
+    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 and the rows beyond `rows` stay zero)
+        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
+        float xv = 0.f;
+        if (g * GROUP + row < rows && i < od) xv = sObs[row * od + i] * a.scale[i];
+        saw_nan |= xv != xv;
+        sX[threadIdx.x] = xv;
+    }
+    lds_barrier();
+    float pz = 0.f;
+    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
+    float h1[2][4], h2[2][4];
+    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    const int tid = threadIdx.x;
+    if (tid < GROUP * OU) {
+        const int row = tid / OU, o = tid % OU;
+        float y = 0.f;
+        if (g * GROUP + row < rows) {
+            float z = out_preact<OS>(sPart, b3v, row, o);
+            y = a.out_tanh ? tanhf(z) : z;
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sLogit[tid] = y;
+    }
+}
+// Row gr's action from its four logits l[4] (mean | log-std), by the first of the row's four lanes: elements 2 gr and 2 gr + 1 of the
+// stream mpg_normal_fill(2 n, key, counter (c1, c2)) writes - sample_group's draw - and k_row_sums<GaussRow>'s row body, or with SQ
+// k_row_sums<SquashRow>'s (gauss::squash_row under `range` and the host-formed log_r).  The log-density is not kept: the worker
+// discards it and the ring has no column for it.
+template <bool SQ>
+__device__ __forceinline__ void sample_act(const float* l, long gr, float range, float log_r, uint32_t k0, uint32_t k1, uint32_t c1,
+                                           uint32_t c2, float (&act)[2]) {
+    float eps[2];
+    gauss::normal_pair((uint32_t)(gr >> 1), (int)(gr & 1), k0, k1, c1, c2, eps[0], eps[1]);
+    // The row body, one component per call (ad = 1 on {mean_k, log_std_k} and eps_k): the bodies are sums over independent components,
+    // and the log-density, which joins them, is dead here.  Called on the whole row (ad = 2) the squashed instantiations had scratch
+    // (tools/kernel_resources.py); this form has none.
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float lk[2] = {l[k], l[2 + k]};
+        if constexpr (SQ) gauss::squash_row(1, range, log_r, lk, eps + k, act + k);
+        else gauss::gauss_row(1, lk, eps + k, act + k);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 }  // namespace worker_policy
 #pragma clang fp contract(off)
 
@@ -937,6 +1007,122 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typena
     worker_policy::report(pa, zmax, saw_nan);
 }
 
+// k_worker_sample_rollout (below): RolloutEnvArgs for the stochastic policy's launch - the draw's key and counter in the place of the
+// exploration noise's, and the squashed head's two constants
+struct SampleRolloutEnvArgs {
+    RingPtrs ring;
+    float *st, *obs_io, *act_out;
+    uint8_t* done_out;
+    uint32_t k0, k1, sk0, sk1;     // env key, draw key
+    uint64_t env_ctr, sample_ctr;  // the counters of iteration 0
+    uint32_t capacity;
+    float range, log_r;            // SQ: the action range and its logarithm (gauss::log_range)
+};
+
+// The same `iters` iterations for a STOCHASTIC policy (SAC; worker.py:96: the action IS the sample, no explore_sigma): `iters`
+// consecutive triples of mpg_normal_fill(2 n, sample key, sample counter + it), mpg_policy_sample (SQ: mpg_policy_sample_squashed -
+// k_forward<IN, 4, PK, 1> and k_row_sums<GaussRow / SquashRow>) and mpg_env_step_store_reset in ONE launch; without SQ that is `iters`
+// k_policy_sample_step_store_reset launches.  A sibling of k_worker_rollout with its residency plan: one 512-thread workgroup per
+// 16-agent group, the policy's registers - here all four output columns - loaded once (worker_policy::sample_load), the agents in wave
+// 0's registers, four lanes each, the observations to the pass through LDS between workgroup barriers, global memory read in the
+// prologue only, state / obs_io / act_out / done_out written after the LAST iteration only, wave 0's per-iteration arguments in LDS,
+// the status word reported once.  New between the pass and the env step: the four logits of a row are left in sLogit by the row's own
+// four lanes (worker_policy::sample_pass), the first of them draws elements 2 i, 2 i + 1 of the iteration's stream, forms the action
+// (worker_policy::sample_act) and leaves it in sAct for the four: LDS is in order within a wave.  From there on wave 0 does what
+// k_worker_rollout's env lanes do.  (pa.k0 .. pa.c2: the draw's key and the counter of iteration 0; pa.sigma, pa.out_scale: not read.)
+// IN as in k_policy_step_store_reset.
+template <bool PK, int IN, bool SQ>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const typename worker_policy::args_of<IN>::type pa, int n_launch,
+                                                                            int iters, float* st, float* obs_io, float* act_out, RingPtrs ring,
+                                                                            int capacity, int next_idx, uint32_t k0, uint32_t k1, uint32_t c1,
+                                                                            uint32_t c2, uint8_t* done_out, float range, float log_r) {
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN, 4>()];
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
+    __shared__ __attribute__((aligned(16))) float sLogit[mlp::GROUP * 4];
+    __shared__ float sAct[mlp::GROUP * 2];
+    __shared__ SampleRolloutEnvArgs sArg;
+    const int od_launch = worker_policy::obs_dim_of(pa);
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<IN, 4> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    worker_policy::sample_load<PK, IN>(pa, L, w2, r, b3v);
+    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
+    Agent ag = {};
+    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
+    {   // the group's rows of obs_io (16 x od <= 256 floats)
+        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.ring = ring;
+        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
+        sArg.k0 = k0; sArg.k1 = k1; sArg.sk0 = pa.k0; sArg.sk1 = pa.k1;
+        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
+        sArg.sample_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        sArg.capacity = (uint32_t)capacity;
+        sArg.range = range; sArg.log_r = log_r;
+    }
+    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    uint32_t slot = (uint32_t)(((long)next_idx + i_lane) % capacity);
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
+        worker_policy::sample_pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
+        if (threadIdx.x >= 64) continue;                 // wave 0 wrote sLogit itself: LDS is in order within a wave
+        // (the lane's place and the launch's sizes, opaque per iteration: k_worker_rollout says why)
+        int q = q_lane, i = i_lane, od = od_launch, n = n_launch;
+        asm volatile("" : "+v"(q), "+v"(i), "+s"(n));
+        if constexpr (IN == 16) asm volatile("" : "+s"(od));      // (a constant at IN = 6)
+        __builtin_amdgcn_wave_barrier();
+        if (i < n && q == 0) {                           // the first of the row's four lanes: the draw and the head
+            const uint64_t sc = sArg.sample_ctr + (uint64_t)it;
+            float act[2];
+            worker_policy::sample_act<SQ>(sLogit + 4 * a_loc, i, sArg.range, sArg.log_r, sArg.sk0, sArg.sk1, (uint32_t)sc,
+                                          (uint32_t)(sc >> 32), act);
+            sAct[2 * a_loc] = act[0];
+            sAct[2 * a_loc + 1] = act[1];
+            if (last) {
+                float* const ao = sArg.act_out + (size_t)i * 2;
+                ao[0] = act[0];
+                ao[1] = act[1];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (i < n) {
+            const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
+            if (q == 0) {
+                write_obs(sArg.ring.obs, (int)slot, od, ag);             // obs before the step
+                reinterpret_cast<float2*>(sArg.ring.act)[slot] = an;
+            }
+            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
+            if (q == 1) {
+                write_obs(sArg.ring.obs2, (int)slot, od, ag);
+                sArg.ring.rew[slot] = o.reward;
+                sArg.ring.done[slot] = o.done ? 1 : 0;
+                uint8_t* const dn = sArg.done_out;
+                if (last && dn) dn[i] = o.done ? 1 : 0;
+            }
+            if (o.done) {
+                const uint64_t ec = sArg.env_ctr + (uint64_t)it;
+                reset_agent(ag, i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
+            }
+            if (last) {
+                if (q == 2) store_agent(sArg.st, n, i, ag);
+                if (q == 3) write_obs(sArg.obs_io, i, od, ag);
+            } else if (q == 3) {
+                write_obs(sObs, a_loc, od, ag);
+            }
+            slot += (uint32_t)n;
+            if (slot >= sArg.capacity) slot -= sArg.capacity;
+        }
+    }
+    worker_policy::report(pa, zmax, saw_nan);
+}
+
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
 }  // namespace
@@ -1227,5 +1413,64 @@ extern "C" int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params,
     }
 #undef MPG_ROLLOUT_LAUNCH
     MPG_CHECK_LAUNCH("mpg_env_rollout");
+    return MPG_OK;
+}
+
+// worker.py:91-119 for the path-tracking env under a stochastic policy: `iters` consecutive triples mpg_normal_fill(2 n, sample_seed,
+// sample_ctr + it) + mpg_policy_sample (with cfg->action_range > 0: mpg_policy_sample_squashed) + mpg_env_step_store_reset (ring position
+// (next_idx + it * n) % capacity, env_ctr + it) as one launch (k_worker_sample_rollout: bit-identical state, observations, actions, done
+// flags, ring arrays and status word)
+extern "C" int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* state, float* obs_io,
+                                         uint64_t sample_seed, uint64_t sample_ctr, float* act_out, int capacity, int next_idx,
+                                         float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
+                                         uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_worker_sample_rollout: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_sample_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    // (the pendulum's squashed policy has a launch of its own: mpg_worker_sample_rollout_pendulum)
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_worker_sample_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(cfg->act_dim == 2, "mpg_worker_sample_rollout: act_dim 2 only (got %d)", cfg->act_dim);
+    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_worker_sample_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
+    // no action range: the Gaussian head as it stands; a range: the squashed head, and what it asks of a cfg (a linear output, a finite
+    // range; the pointers and the row count are judged below, with the ring)
+    const bool squash = cfg->action_range > 0.f;
+    if (squash)
+        if (int rc = gauss::squash_refusal("mpg_worker_sample_rollout", cfg, true, 1, 0.f)) return rc;
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
+                "mpg_worker_sample_rollout: null pointer");
+    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "mpg_worker_sample_rollout: bad ring (n %d, capacity %d < n, or next_idx %d outside it)",
+                n, capacity, next_idx);
+    MPG_REQUIRE(iters >= 1, "mpg_worker_sample_rollout: iters >= 1 (got %d)", iters);
+    // (what bounds one launch's run time; the reference's worker runs 64)
+    MPG_REQUIRE(iters <= 1024, "mpg_worker_sample_rollout: iters <= 1024 (got %d)", iters);
+    // two iterations would write one slot from different workgroups with no order between them
+    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_sample_rollout: iters * n = %ld transitions do not fit the ring's capacity %d",
+                (long)iters * n, capacity);
+    const float range = squash ? cfg->action_range : 0.f, log_r = squash ? gauss::log_range(cfg->action_range) : 0.f;
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+#define MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, SQ)                                                                                           \
+    hipLaunchKernelGGL((k_worker_sample_rollout<PK, IN, SQ>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io,     \
+                       act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out, range, log_r)
+#define MPG_SAMPLE_ROLLOUT_HEADS(PK, IN) \
+    do { if (squash) MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, true); else MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, false); } while (0)
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, 0.f, sample_seed, sample_ctr);
+        pa.out_tanh = cfg->policy_out_act == MPG_ACT_TANH;      // the logits' activation (logits_out): an action range never reaches them
+        pa.obs_dim = cfg->obs_dim;
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_SAMPLE_ROLLOUT_HEADS(true, 16); else MPG_SAMPLE_ROLLOUT_HEADS(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, 0.f, sample_seed, sample_ctr);
+        pa.out_tanh = cfg->policy_out_act == MPG_ACT_TANH;
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        if (pa.pack) MPG_SAMPLE_ROLLOUT_HEADS(true, 6); else MPG_SAMPLE_ROLLOUT_HEADS(false, 6);
+    }
+#undef MPG_SAMPLE_ROLLOUT_HEADS
+#undef MPG_SAMPLE_ROLLOUT_LAUNCH
+    mpg_prof_end(mpg_prof_of(cfg), 2, s);
+    MPG_CHECK_LAUNCH("mpg_worker_sample_rollout");
     return MPG_OK;
 }

@@ -256,10 +256,24 @@ int ndpg_gradients(mpg_train_ctx_t* c, const Layout& l, bool fresh, mpg_stream_t
 // (mpg_worker_sample_step) at every width.  Against the three calls it replaces (mpg_normal_fill, mpg_policy_sample,
 // mpg_env_step_store_reset: four launches, bit-identical) it measured faster at 8 and at 4096 agents with obs_dim 6 and 9
 // (tools/bench_sac_native.py), which is the rule for taking it.
+//
+// A sample's iterations as ONE launch (mpg_worker_sample_rollout: bit-identical to the loop of mpg_worker_sample_step calls) under
+// sample_and_add's conditions - at least two iterations, at most the 1024 that launch takes, the ring holds them all - and its rule
+// per width (tools/bench_worker_rollout.py --stochastic); sample_iters < 0 keeps the chain, as there.
+inline bool sac_rollout_taken(const mpg_train_ctx_t* c) { return c->sample_iters > 0; }
+
 int sac_sample_and_add(const char* entry, mpg_train_ctx_t* c, const float* policy, mpg_stream_t s) {
-    const int n = c->num_agent;
+    const int n = c->num_agent, sample_iters = sample_iters_of(c);
     MPG_REQUIRE(n <= c->ring_capacity, "%s: ring smaller than one sample", entry);
-    for (int it = 0; it < sample_iters_of(c); ++it) {      // (the sign: sample_and_add's chain-kept form; there is one form here)
+    int it = 0;
+    if (sac_rollout_taken(c) && sample_iters >= 2 && sample_iters <= 1024 && (long)sample_iters * n <= c->ring_capacity) {
+        TRY(mpg_worker_sample_rollout(&c->cfg, policy, n, sample_iters, c->env_state, c->w_obs, c->worker_seed, c->noise_ctr, c->w_act,
+                                      c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,
+                                      c->env_seed, c->env_ctr, c->w_done, s));
+        TRY(rollout_added(c, sample_iters, s));            // (learner_version 7: the counters and the ring position)
+        it = sample_iters;
+    }
+    for (; it < sample_iters; ++it) {
         // (the log-densities have no consumer: worker.py:96 drops them)
         TRY(mpg_worker_sample_step(&c->cfg, policy, n, c->env_state, c->w_obs, c->worker_seed, c->noise_ctr++, c->w_act, nullptr,
                                    c->ring_capacity, c->ring_next, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done,

@@ -484,15 +484,18 @@ def worker_rollout(cfg, policy_params, iters, state, obs_io, explore_sigma, nois
 
 def worker_sample_rollout(cfg, policy_params, iters, state, obs_io, sample_seed, sample_ctr, ring, capacity, next_idx, env_seed, env_ctr,
                           done_out=None):
-    """mpg_worker_sample_rollout_pendulum: `iters` iterations of OffPolicyWorker.sample's loop for the tanh-squashed Gaussian policy on
-    the pendulum (draw -> a = range * tanh(mean + sigma * eps) -> env.step -> ring -> env.reset) in ONE launch, bit-identical to `iters`
-    triples of mpg_normal_fill(n, sample_seed, sample_ctr + it), mpg_policy_sample_squashed and mpg_env_step_store_reset.  worker_rollout's
-    arguments without explore_sigma; no log-density is returned.  Returns the last iteration's actions [n, 1]."""
+    """`iters` iterations of OffPolicyWorker.sample's loop for a stochastic policy (draw -> sample -> env.step -> ring -> env.reset) in
+    ONE launch, bit-identical to `iters` triples of mpg_normal_fill(n * act_dim, sample_seed, sample_ctr + it), mpg_policy_sample[_squashed]
+    and mpg_env_step_store_reset.  worker_rollout's arguments without explore_sigma; no log-density is returned.
+    A PathTracking cfg (env_kind 0) goes to mpg_worker_sample_rollout: the Gaussian head, or with cfg.action_range > 0 the tanh-squashed
+    one (a = range * tanh(mean + sigma * eps)); returns the last iteration's actions [n, 2].  Any other cfg goes to
+    mpg_worker_sample_rollout_pendulum (the squashed head on the pendulum, actions [n, 1])."""
     n, dev = obs_io.shape[0], obs_io.device
     act = torch.empty(n, cfg.act_dim, dtype=torch.float32, device=dev)
     r_obs, r_act, r_rew, r_obs2, r_done = ring
     assert r_done.dtype == torch.uint8 and (done_out is None or done_out.dtype == torch.uint8)
-    L.call('mpg_worker_sample_rollout_pendulum', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)),
+    entry = 'mpg_worker_sample_rollout' if cfg.env_kind == 0 else 'mpg_worker_sample_rollout_pendulum'
+    L.call(entry, ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)),
            L.ptr(_f32(state)), L.ptr(_f32(obs_io)), L.c_u64(sample_seed), L.c_u64(sample_ctr), L.ptr(act), L.c_int(int(capacity)),
            L.c_int(int(next_idx)), L.ptr(_f32(r_obs)), L.ptr(_f32(r_act)), L.ptr(_f32(r_rew)), L.ptr(_f32(r_obs2)), L.ptr(r_done),
            L.c_u64(env_seed), L.c_u64(env_ctr), L.ptr(done_out), L.stream())

@@ -4,7 +4,8 @@ env.step -> env.reset, worker.py:91-119) but every stage is one HIP launch over 
 `args.one_launch_sample = True` and a deterministic policy all iterations of a sample are ONE launch, bit-identical to the
 loop: mpg_worker_rollout on PathTracking-v0, mpg_worker_rollout_pendulum on InvertedPendulumConti-v0 (where the reference's
 defaults make a sample one agent's 512 iterations) - and there also with the tanh-squashed Gaussian policy (squashed_head=True):
-mpg_worker_sample_rollout_pendulum."""
+mpg_worker_sample_rollout_pendulum.  A stochastic policy on PathTracking-v0 (SAC: the Gaussian head or the squashed one) takes
+mpg_worker_sample_rollout."""
 import torch
 
 from .envs import make_env
@@ -68,6 +69,8 @@ class OffPolicyWorker(object):
             batch = self._sample_one_launch_stochastic_pendulum(iters)
         elif self.env.kind == 1:
             batch = self._sample_one_launch_pendulum(iters)
+        elif self.env.kind == 0 and not getattr(self.policy_with_value, 'deterministic_policy', True):
+            batch = self._sample_one_launch_stochastic(iters)
         else:
             batch = self._sample_one_launch(iters)
         self.num_sample += batch[0].shape[0]
@@ -107,8 +110,8 @@ class OffPolicyWorker(object):
         path (the launch does not form it; env.step does)."""
         pw, env = self.policy_with_value, self.env
         if not getattr(pw, 'deterministic_policy', True):
-            raise ValueError('one_launch_sample serves a deterministic policy only: the stochastic policy\'s loop form '
-                             '(mpg_worker_sample_step per iteration) is not built')
+            raise ValueError('_sample_one_launch serves a deterministic policy only (a stochastic one takes '
+                             '_sample_one_launch_stochastic)')
         if env.kind != 0:
             raise ValueError('one_launch_sample serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
         return self._one_launch(iters)
@@ -151,6 +154,25 @@ class OffPolicyWorker(object):
         if iters > 1024:
             raise ValueError('one_launch_sample with the squashed head takes at most 1024 iterations per launch (batch_size / num_agent '
                              '= %d)' % iters)
+        return self._one_launch(iters, sampled=True)
+
+    def _sample_one_launch_stochastic(self, iters):
+        """_sample_one_launch for a stochastic policy on PathTracking-v0 (SAC: the Gaussian head, or with squashed_head=True the
+        tanh-squashed one): mpg_worker_sample_rollout instead of the loop's four launches per iteration (the draw, the policy pass, the
+        head's row sums, env.step / env.reset).  The same contract: batches, worker.obs, env state, env.done and both counters equal
+        _sample_loop's bit for bit over consecutive calls; env.done_intended is NOT refreshed.  No explore_sigma (the loop adds that
+        noise with a torch op, which has no place in the launch), at most 1024 iterations."""
+        pw, env = self.policy_with_value, self.env
+        if getattr(pw, 'deterministic_policy', True):
+            raise ValueError('_sample_one_launch_stochastic serves a stochastic policy (a deterministic one takes _sample_one_launch)')
+        if self.explore_sigma is not None:
+            raise ValueError('one_launch_sample with a stochastic policy takes no explore_sigma (got %r): the action is the sample'
+                             % (self.explore_sigma,))
+        if env.kind != 0:
+            raise ValueError('_sample_one_launch_stochastic serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
+        if iters > 1024:
+            raise ValueError('one_launch_sample with a stochastic policy takes at most 1024 iterations per launch (batch_size / '
+                             'num_agent = %d)' % iters)
         return self._one_launch(iters, sampled=True)
 
     def _one_launch(self, iters, sampled=False):

@@ -21,7 +21,14 @@ The rule for the driver: it calls (b) for a width only if (b)'s median is at or 
     python tools/bench_worker_rollout.py --env pendulum --stochastic [--json out.json]   the tanh-squashed Gaussian policy on the pendulum:
         (a) the chain of `iters` triples mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset (four launches per
         iteration) against (b) mpg_worker_sample_rollout_pendulum at (agents, iters) = (1, 512) - the reference's SAC defaults - and
-        (64, 8), and (d) OffPolicyWorker.sample() of the squashed SAC stack at 1 x 512 on its loop and with one_launch_sample, alternating"""
+        (64, 8), and (d) OffPolicyWorker.sample() of the squashed SAC stack at 1 x 512 on its loop and with one_launch_sample, alternating
+    python tools/bench_worker_rollout.py --stochastic [--steps-only] [--json out.json]   a stochastic policy on PathTracking-v0 (SAC):
+        (a) the chain - the plain Gaussian head: `iters` mpg_worker_sample_step launches, what sac_sample_and_add of train_step.cpp
+        enqueues without the one-launch form; the tanh-squashed head (action_range 1.5): `iters` triples mpg_normal_fill +
+        mpg_policy_sample_squashed + mpg_env_step_store_reset - against (b) mpg_worker_sample_rollout at the four cases of the
+        deterministic measurement, (d) OffPolicyWorker.sample() of both SAC stacks at 8 x 64 on the loop and with one_launch_sample, and
+        (c) one native SAC step (fixed and learned temperature) as the driver decides against the chain kept (sample_iters = -64);
+        --steps-only: (c) alone.  The driver's rule per width is the one above, on the plain head's rows."""
 import argparse
 import ctypes
 import json
@@ -259,6 +266,141 @@ def worker_sample_stochastic_pendulum(out):
         print('| %s | %.4f (%.4f .. %.4f) |' % (form, statistics.median(x), min(x), max(x)), flush=True)
 
 
+STOCHASTIC_RANGE = 1.5                                              # the squashed head's action range on PathTracking-v0
+
+
+def sample_case_stochastic(n, iters, od, squashed):
+    """--stochastic on PathTracking-v0: (a) the chain - `iters` mpg_worker_sample_step launches (plain head), or `iters` triples
+    mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset (squashed head) - against (b) mpg_worker_sample_rollout,
+    as sample_case does it"""
+    import numpy as np
+    import torch
+    from mpg_amd import _lib as L
+    from mpg_amd import ops
+    from mpg_amd.envs import PathTrackingEnv
+    from tests.golden_inputs import mlp_weights_flat
+    rng = np.random.Generator(np.random.PCG64(n + od))
+    dev = 'cuda'
+    cfg = ops.make_cfg(obs_dim=od, policy_out_activation='linear', action_range=STOCHASTIC_RANGE if squashed else None)
+    pol = torch.as_tensor(mlp_weights_flat(rng, od, 4)).to(dev)
+    wc = ops.WeightCache(pol, [(od, 4)])
+    cfg.wcache[0] = wc.pointer
+    cap = 4 * iters * n + 3 * n                   # (the ring position wraps inside a sample now and then)
+    sides, keep = [], []
+    for _ in range(2):
+        env = PathTrackingEnv(num_agent=n, num_future_data=od - 6, seed=4)
+        t = dict(state=env._state, obs=env.reset().clone(), act=torch.empty(n, 2, device=dev), ring_obs=torch.zeros(cap, od, device=dev),
+                 ring_act=torch.zeros(cap, 2, device=dev), ring_rew=torch.zeros(cap, device=dev), ring_obs2=torch.zeros(cap, od, device=dev),
+                 ring_done=torch.zeros(cap, dtype=torch.uint8, device=dev), done=torch.zeros(n, dtype=torch.uint8, device=dev))
+        sd = Side(capacity=cap, next_idx=0, ctr=1)
+        for k, v in t.items():
+            setattr(sd, k, v.data_ptr())
+        sides.append((t, sd))
+        keep.append(env)
+    eps, logp = torch.empty(2 * n, device=dev), torch.empty(n, device=dev)
+    ws = ops._ws(dev, 0, 'mpg_policy_sample_squashed_workspace_bytes', cfg, n) if squashed else None
+    lib, s, c = L.lib(), L.stream(), ctypes.byref(cfg)
+    fp = lambda f: ctypes.cast(f, ctypes.c_void_p)
+    host = host_loops()
+
+    def chain(reps):
+        if squashed:
+            assert host.bench_chain_sample(fp(lib.mpg_normal_fill), fp(lib.mpg_policy_sample_squashed), fp(lib.mpg_env_step_store_reset), c,
+                                           L.ptr(pol), I(n), I(iters), L.ptr(eps), L.ptr(logp), *ws, ctypes.byref(sides[0][1]), s, I(reps)) == 0
+        else:
+            assert host.bench_chain_sample_step(fp(lib.mpg_worker_sample_step), c, L.ptr(pol), I(n), I(iters), ctypes.byref(sides[0][1]), s,
+                                                I(reps)) == 0
+
+    def launch(reps):
+        assert host.bench_launch_sample(fp(lib.mpg_worker_sample_rollout), c, L.ptr(pol), I(n), I(iters), ctypes.byref(sides[1][1]), s,
+                                        I(reps)) == 0
+    chain(WARMUP), launch(WARMUP)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(REGIONS):                                      # alternating: both see the same machine
+        ta.append(timed(chain, batched=True))
+        tb.append(timed(launch, batched=True))
+    torch.cuda.synchronize()
+    for k in sides[0][0]:                                         # the two did the same work: bit-identical at the end
+        a, b = sides[0][0][k], sides[1][0][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
+    del keep, wc
+    return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb))
+
+
+def worker_sample_stochastic(out):
+    """(d): OffPolicyWorker.sample() of the SAC stacks on PathTracking-v0 at the reference's worker defaults (8 agents, 64 iterations) on
+    the loop and with one_launch_sample - host time included: the loop's launches are enqueued from Python, as a training run that
+    does not take the native step enqueues them"""
+    import torch
+    from mpg_amd.config import default_args
+    from mpg_amd.optimizer import quiesce_gc
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    print('\n| OffPolicyWorker.sample(), SAC, PathTracking-v0, num_agent 8, batch_size 512 | ms per sample |\n|---|---|', flush=True)
+    for head, kw in (('Gaussian head', {}), ('squashed head', dict(squashed_head=True, action_range=STOCHASTIC_RANGE))):
+        workers = []
+        for one in (False, True):
+            args = default_args('SAC', nan_check_interval=10 ** 9, **kw, **(dict(one_launch_sample=True) if one else {}))
+            assert (args.env_id, args.num_agent, args.batch_size) == ('PathTracking-v0', 8, 512)
+            workers.append(OffPolicyWorker(PolicyWithQs, args.env_id, args, 0))
+        quiesce_gc()
+        for w in workers:
+            for _ in range(WARMUP):
+                w.sample()
+        torch.cuda.synchronize()
+        t = [[], []]
+        for _ in range(REGIONS):
+            for k, w in enumerate(workers):
+                t[k].append(timed(w.sample, SAMPLE_REPS))
+        for a, b in zip(workers[0].sample(), workers[1].sample()):    # the two did the same work: bit-identical at the end
+            assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b)
+        for form, x in zip(('the loop (four launches per iteration)', 'one_launch_sample'), t):
+            out['worker_sample'].append(dict(head=head, form=form, sample_ms=statistics.median(x), sample_range=(min(x), max(x))))
+            print('| %s, %s | %.4f (%.4f .. %.4f) |' % (head, form, statistics.median(x), min(x), max(x)), flush=True)
+
+
+def stack_sac(auto, chain=False):
+    """SAC at the reference's worker defaults under the native step (fixed temperature, or the learned one)"""
+    from mpg_amd.buffer import ReplayBuffer
+    from mpg_amd.config import default_args
+    from mpg_amd.learners import SACLearner
+    from mpg_amd.optimizer import SingleProcessOffPolicyOptimizer
+    from mpg_amd.policy import PolicyWithQs
+    from mpg_amd.worker import OffPolicyWorker
+    args = default_args('SAC', nan_check_interval=10 ** 9, **(dict(alpha='auto', target_entropy=-2.) if auto else {}))
+    assert (args.num_agent, args.batch_size, args.replay_batch_size) == (8, 512, 256)
+    worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+    opt = SingleProcessOffPolicyOptimizer(worker, SACLearner(PolicyWithQs, args), ReplayBuffer(args, 0), None, args, sampling_interval=10,
+                                          native_sac=True)
+    assert opt._fused is not None and opt._fused.c.sample_iters == 64
+    if chain:
+        opt._fused.c.sample_iters = -64           # include/mpg_hip.h: the same iterations, one mpg_worker_sample_step each
+    return opt
+
+
+def step_cases_sac(out):
+    import torch
+    from mpg_amd.optimizer import quiesce_gc
+    cases = [(auto, chain) for auto in (False, True) for chain in (True, False)]
+    opts = [stack_sac(auto, chain) for auto, chain in cases]
+    quiesce_gc()
+    for _ in range(40):
+        for o in opts:
+            o.step()
+    torch.cuda.synchronize()
+    t = [[] for _ in opts]
+    for _ in range(REGIONS):                                      # alternating; REPS a multiple of the sampling interval
+        for k, o in enumerate(opts):
+            t[k].append(timed(o.step, REPS))
+    print('\n| native SAC step, num_agent 8, batch_size 512, sampling_interval 10, B = 256 | ms per step |\n|---|---|', flush=True)
+    for (auto, chain), x in zip(cases, t):
+        alg = "SAC, alpha = 'auto'" if auto else 'SAC, fixed alpha'
+        form = 'chain kept (sample_iters = -64)' if chain else "the driver's own choice"
+        out['step'].append(dict(alg=alg, form=form, step_ms=statistics.median(x), step_range=(min(x), max(x))))
+        print('| %s, %s | %.4f (%.4f .. %.4f) |' % (alg, form, statistics.median(x), min(x), max(x)), flush=True)
+
+
 def stack_pendulum(chain=False):
     """NADP at the pendulum parser's defaults: one agent, 512 iterations per sample, B = 256"""
     from mpg_amd.buffer import ReplayBuffer
@@ -345,17 +487,35 @@ def main():
     ap.add_argument('--env', default='path_tracking', choices=('path_tracking', 'pendulum'),
                     help='pendulum: mpg_worker_rollout_pendulum against its chain, and the native NADP step at the pendulum defaults')
     ap.add_argument('--stochastic', action='store_true',
-                    help='with --env pendulum: mpg_worker_sample_rollout_pendulum (the tanh-squashed Gaussian policy) against its chain, '
-                         'and OffPolicyWorker.sample() both ways')
+                    help='the stochastic (SAC) policy: mpg_worker_sample_rollout on PathTracking-v0 (both heads; with --steps-only the native '
+                         'SAC step alone), or with --env pendulum mpg_worker_sample_rollout_pendulum (the tanh-squashed Gaussian policy), '
+                         'each against its chain, and OffPolicyWorker.sample() both ways')
     ap.add_argument('--tree', default=None, help="another checkout of this project whose build is timed (with --steps-only)")
     a = ap.parse_args()
     assert not a.tree or a.steps_only, '--tree times the native steps of another checkout: pass --steps-only'
-    assert not a.stochastic or (a.env == 'pendulum' and not a.steps_only), '--stochastic goes with --env pendulum (no native step serves it)'
+    assert not (a.stochastic and a.env == 'pendulum' and a.steps_only), '--stochastic --env pendulum has no native step to time'
+    assert not (a.stochastic and a.tree), '--tree times the deterministic learners\' native steps'
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else os.path.dirname(HERE))
     import torch
     assert torch.cuda.is_available(), 'bench_worker_rollout.py needs a GPU: nothing here is measured without one'
     out = {'sample': [], 'step': []}
-    if a.stochastic:
+    if a.stochastic and a.env != 'pendulum':
+        if not a.steps_only:
+            out['worker_sample'] = []
+            print('| head | agents | iters | obs_dim | (a) chain, ms | (b) mpg_worker_sample_rollout, ms | (a) / (b) |\n|---|---|---|---|---|---|---|',
+                  flush=True)
+            for squashed in (False, True):
+                head = 'squashed: mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset' if squashed else \
+                    'Gaussian: mpg_worker_sample_step'
+                for n, iters, od in CASES:
+                    ma, mb, ra, rb = sample_case_stochastic(n, iters, od, squashed)
+                    out['sample'].append(dict(head=head, agents=n, iters=iters, obs_dim=od, chain_ms=ma, chain_range=ra, launch_ms=mb,
+                                              launch_range=rb))
+                    print('| %s | %d | %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f |'
+                          % (head, n, iters, od, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb), flush=True)
+            worker_sample_stochastic(out)
+        step_cases_sac(out)
+    elif a.stochastic:
         out['worker_sample'] = []
         print('| agents | iters | (a) chain of mpg_normal_fill + mpg_policy_sample_squashed + mpg_env_step_store_reset, ms | '
               '(b) mpg_worker_sample_rollout_pendulum, ms | (a) / (b) | done rows in the ring |\n|---|---|---|---|---|---|', flush=True)
@@ -384,7 +544,7 @@ def main():
             out['sample'].append(dict(agents=n, iters=iters, obs_dim=od, chain_ms=ma, chain_range=ra, launch_ms=mb, launch_range=rb))
             print('| %d | %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f |' % (n, iters, od, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb),
                   flush=True)
-    if a.env != 'pendulum':
+    if a.env != 'pendulum' and not a.stochastic:
         step_cases(out, ab=not a.tree)       # (another checkout may not know the chain-kept form)
     if a.json:
         with open(a.json, 'w') as fh:

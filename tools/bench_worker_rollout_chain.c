@@ -107,3 +107,41 @@ int bench_launch_sample(sample_rollout_fn sample_rollout, const mpg_cfg_t* cfg, 
     }
     return 0;
 }
+
+/* PathTracking under a stochastic policy (bench_worker_rollout.py --stochastic): the plain Gaussian head's chain is what
+ * sac_sample_and_add's loop enqueues, one mpg_worker_sample_step per iteration; the squashed head has no one-launch step, its chain is
+ * the three calls per iteration (mpg_normal_fill over 2 n elements + mpg_policy_sample_squashed + mpg_env_step_store_reset: four
+ * launches).  Both against mpg_worker_sample_rollout through bench_launch_sample. */
+typedef int (*sample_step_fn)(const mpg_cfg_t*, const float*, int, float*, float*, uint64_t, uint64_t, float*, float*, int, int, float*, float*,
+                              float*, float*, uint8_t*, uint64_t, uint64_t, uint8_t*, mpg_stream_t);
+
+int bench_chain_sample_step(sample_step_fn sample_step, const mpg_cfg_t* cfg, const float* policy, int n, int iters, worker_side_t* w,
+                            mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = sample_step(cfg, policy, n, w->state, w->obs, 11, w->ctr, w->act, 0, w->capacity, w->next_idx, w->ring_obs, w->ring_act,
+                                 w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
+
+int bench_chain_sample(normal_fill_fn normal_fill, sample_squashed_fn policy_sample, step_store_fn step_store_reset, const mpg_cfg_t* cfg,
+                       const float* policy, int n, int iters, float* eps, float* logp, void* ws, size_t ws_bytes, worker_side_t* w,
+                       mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = normal_fill(n * cfg->act_dim, 11, w->ctr, eps, s);
+            if (rc) return rc;
+            rc = policy_sample(cfg, policy, n, w->obs, eps, w->act, logp, 0, ws, ws_bytes, s);
+            if (rc) return rc;
+            rc = step_store_reset(cfg->env_kind, n, cfg->obs_dim, w->state, w->act, w->capacity, w->next_idx, w->ring_obs, w->ring_act,
+                                  w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->obs, w->done, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
