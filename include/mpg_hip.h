@@ -285,6 +285,19 @@ int mpg_nstep_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* 
                       const float* rewards, const float* last_obs, float* y, void* ws, size_t ws_bytes,
                       mpg_stream_t stream);
 
+/* The same for InvertedPendulumConti-v0, whose bootstrap value the reference clips (mpg_learner.py:163-164:
+ * all_values_tp1 = clip_by_value(all_values_tp1, -0.5, 0.)):
+ *   y = sum_t gamma^t r~_t + gamma^n min(max(Q1t(s~_n, pi_t(s~_n)), q_lo), q_hi).
+ * mpg_nstep_targets' launches with the clip in the last one, its workspace (mpg_q_targets_workspace_bytes) and its refusals under this
+ * entry point's name; refused too, with a text of its own each: a bound that is not finite, q_lo > q_hi.  A NaN value stays NaN, as
+ * TF's minimum / maximum hand it on.  mpg_nstep_targets itself keeps its kernel and its bits.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+#define MPG_PENDULUM_NSTEP_Q_LO (-0.5f) /* mpg_learner.py:163-164 */
+#define MPG_PENDULUM_NSTEP_Q_HI (0.f)
+int mpg_nstep_targets_clipped(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n,
+                              const float* rewards, const float* last_obs, float q_lo, float q_hi,
+                              float* y, void* ws, size_t ws_bytes, mpg_stream_t stream);
+
 /* MPGLearner.q_forward_and_backward  - mpg_learner.py:326-354 (also td3.py:103-118, nadp.py:173-184), ONE critic:
  *   L = 0.5 * mean_B (Q(s~,a) - y)^2 and dL/dtheta_Q.
  * inv_b_global = 1/B_global (the mean's divisor; 1/rows on one GPU).  Outputs: loss_sum[0] = this GPU's share
@@ -516,6 +529,18 @@ int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* policy_params, 
  * for any other env and for a tanh policy with an action range. */
 int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
                     float* rewards, float* last_obs, mpg_stream_t stream);
+
+/* MPGLearner.sample - learners/mpg_learner.py:85-105 - for InvertedPendulumConti-v0, ONE launch: from obs0 [rows][4] take n real-env
+ * steps, the first with the replay action act0 [rows], the later ones with the ONLINE policy's deterministic action (no noise; `done`
+ * is ignored and nothing is reset).  rewards [n][rows] RAW, last_obs [rows][4].  Bit-identical - the sticky status word included - to
+ * mpg_env_reset_from_obs followed by, for t < n, mpg_policy_action(explore_sigma 0) when t > 0 and mpg_env_step, for both weight
+ * forms (packed image and strided); no env state block, action or done array is needed.
+ * Refused before any launch with MPG_EINVAL, "mpg_env_rollout_pendulum" and a text of its own each: a null configuration, env_kind 2
+ * (the text of the other real-env entry points), any other env that is not the pendulum, obs_dim != 4, act_dim != 1, n < 1, n > 1024,
+ * rows <= 0, a null pointer, a tanh output activation with an action range.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_env_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
+                             float* rewards, float* last_obs, mpg_stream_t stream);
 
 size_t mpg_mpg_gradients_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select, int n_q);
 int mpg_mpg_gradients(const mpg_cfg_t* cfg, int n_q, const float* params, const float* target_params, int rows,
@@ -804,7 +829,8 @@ int mpg_per_sample_gather(const double* sum_tree, const double* min_tree, int ca
  * All pointers are device buffers owned by the caller; counters are advanced in place (host fields). */
 typedef struct {
     mpg_cfg_t cfg;
-    int learner_version;              /* 1: MPG-v1 (n-step real-env target), 2: MPG-v2 (clipped double-Q target),
+    int learner_version;              /* 1: MPG-v1 (n-step real-env target; on the pendulum, env_kind 1, with the bootstrap value
+                                            clipped to [MPG_PENDULUM_NSTEP_Q_LO, _HI]: mpg_nstep_targets_clipped), 2: MPG-v2 (clipped double-Q target),
                                          3: NADP (learners/nadp.py:209-241: networks [Q1 | policy]; n = the Q-target AND policy
                                             rollout horizon, n_select / select / eta / total_ite unused),
                                          4: TD3 (learners/td3.py:150-188: networks [Q1 | Q2 | policy]; n, M, select unused),
@@ -826,7 +852,10 @@ typedef struct {
                                          changed) asks for |sample_iters| steps with the chain KEPT: the A/B form of that measurement.
                                          Version 7 (mpg_sac_step_begin / mpg_sac_auto_step_begin): all of them are ONE
                                          mpg_worker_sample_rollout under the same two conditions, at every obs_dim, else
-                                         one mpg_worker_sample_step each; sample_iters < 0 keeps that chain likewise */
+                                         one mpg_worker_sample_step each; sample_iters < 0 keeps that chain likewise.
+                                         Version 1 on the pendulum: the learner's n real-env steps behind the n-step target are ONE
+                                         mpg_env_rollout_pendulum for n <= 1024; sample_iters < 0 keeps that chain
+                                         too (mpg_env_reset_from_obs, then mpg_policy_action + mpg_env_step per step) */
     int sampling_interval;            /* optimizer.py:331 (10 in the reference) */
     int batch, n, M, n_select, select[4];
     float eta;                        /* rule_based_weights, mpg_learner.py:384-399 */

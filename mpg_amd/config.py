@@ -1,5 +1,5 @@
 """Default hyper-parameters = the reference's argparse defaults (train_scripts/train_script.py:177-306 MPG,
-:57-175 AMPC, :431-549 NDPG, :551-670 TD3, :672-792 SAC; train_scripts/train_script4mujoco.py:296-411 NADP on InvertedPendulumConti-v0), under the same names,
+:57-175 AMPC, :431-549 NDPG, :551-670 TD3, :672-792 SAC; train_scripts/train_script4mujoco.py:169-293 MPG and :296-411 NADP on InvertedPendulumConti-v0), under the same names,
 so `Namespace` objects are interchangeable with the reference's `args`."""
 import argparse
 
@@ -34,6 +34,9 @@ def default_args(alg='MPG-v2', env_id=None, **overrides):
         # the reference ships no parser for this env: the single pendulum's NADP settings with this env's dimensions, unit scales and
         # a = tanh(mean) (ops.make_cfg: this project's choice)
         d.update(num_agent=1, obs_dim=11, act_dim=1, policy_out_activation='linear', action_range=1., obs_scale=[1.] * 11, rew_scale=1.)
+    if pend and alg in ('MPG-v1', 'MPG-v2'):
+        # built_MPG_parser (train_script4mujoco.py:169-293): the one default that differs from train_script.py's beside the env's own
+        d.update(rule_based_bias_total_ite=4000)
     if alg == 'AMPC':
         # built_AMPC_parser: the policy alone - no critic, no target (their settings are None); gamma = 1 reaches the Preprocessor only
         d.update(gamma=1., policy_only=True, double_Q=False, target=False, tau=None, delay_update=None)

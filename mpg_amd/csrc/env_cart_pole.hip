@@ -15,8 +15,9 @@
 // State block: rows 0..3 of the opaque [MPG_ENV_STATE_DIM][n] array (rows 4..7 unused).
 //
 // Also here, beside the device functions it steps the agents with: mpg_worker_rollout_pendulum, a worker sample's iterations on this
-// env in one launch (k_worker_rollout_pendulum), and mpg_worker_sample_rollout_pendulum, the same for the tanh-squashed Gaussian policy
-// (k_worker_sample_rollout_pendulum).
+// env in one launch (k_worker_rollout_pendulum), mpg_worker_sample_rollout_pendulum, the same for the tanh-squashed Gaussian policy
+// (k_worker_sample_rollout_pendulum), and mpg_env_rollout_pendulum, the learner's n real-env steps from a replay batch in one launch
+// (k_env_rollout_pendulum).
 #include "env_internal.h"
 
 // The worker's policy pass rides in the one-launch worker sample (k_worker_rollout_pendulum, below).  The network engine is compiled
@@ -416,6 +417,55 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(con
     cp_worker_policy::report(pa, zmax, saw_nan);
 }
 
+// MPGLearner.sample (mpg_learner.py:85-105) for the pendulum in ONE launch: from obs0 take n real-env steps, the first with the replay
+// action act0, the later ones with the ONLINE policy's deterministic action; `done` is ignored and nothing is reset.  The stand-alone
+// chain is mpg_env_reset_from_obs + n x mpg_env_step + (n - 1) x mpg_policy_action (k_forward<4, 1, PK, 1>, sigma 0) = 2 n launches,
+// every policy launch fetching the weights again and every env launch the state.  Here one 512-thread workgroup owns a 16-row group
+// for all n steps in the form of k_worker_rollout_pendulum (a sibling, not a generalisation: that kernel's code stays as it is): the
+// policy's registers are loaded once, lanes 0 .. 15 of wave 0 form their row's state from obs0 as k_cp_reset_from_obs does (S4, in
+// registers), and per step the observations go from those lanes to the policy pass through LDS between workgroup barriers; the
+// action comes back in a register.  The policy is NOT evaluated at step 0 (n - 1 passes, as in the chain, so the status word sees
+// what the chain's n - 1 policy launches report and nothing of obs0 itself).  Rewards are written every step at rewards[t * rows + row]
+// (no per-lane reward array, no bound on n from it), last_obs after the last step; global memory is read in the prologue only
+// (weights, obs0, act0) and written, never read back.  Rewards, last observations and the status word are bit-identical to the chain's:
+// the same device functions on the same operands in the same order (tests/test_env_rollout_pendulum_gpu.py).
+template <bool PK>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout_pendulum(const cp_worker_policy::Args pa, int rows, int n,
+                                                                           const float* __restrict__ obs0, const float* __restrict__ act0,
+                                                                           float* __restrict__ rewards, float* __restrict__ last_obs) {
+    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<4, 1> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
+    // the env lanes: lanes 0 .. 15 of wave 0, one whole row each
+    const int i = blockIdx.x * mlp::GROUP + (int)threadIdx.x;
+    const bool env_lane = threadIdx.x < mlp::GROUP && i < rows;
+    S4 s = {};
+    float a = 0.f;
+    if (env_lane) {                                      // k_cp_reset_from_obs: the state IS the observation
+        const float4 o = reinterpret_cast<const float4*>(obs0)[i];
+        s = S4{o.x, o.y, o.z, o.w};
+        a = act0[i];
+    }
+    for (int t = 0; t < n; ++t) {
+        if (t > 0) {
+            mlp::lds_barrier();                          // sObs of step t - 1 is complete (and the previous pass's LDS is free)
+            a = cp_worker_policy::pass(pa, rows, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+        }
+        if (!env_lane) continue;
+        if (t > 0) a = cp_worker_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
+        const StepOut o = step_agent(s, a);
+        rewards[(size_t)t * rows + i] = o.reward;
+        if (t == n - 1) write_obs(last_obs, i, s);
+        else write_obs(sObs, threadIdx.x, s);
+    }
+    cp_worker_policy::report(pa, zmax, saw_nan);
+}
+
 // k_worker_sample_rollout_pendulum (below): CpRolloutEnvArgs for the squashed policy's launch - the draw's key and counter in the place
 // of the exploration noise's, and the head's two constants
 struct CpSampleRolloutEnvArgs {
@@ -598,6 +648,43 @@ extern "C" int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const fl
                            ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_sample_rollout_pendulum");
+    return MPG_OK;
+}
+
+// mpg_learner.py:85-105 for the pendulum: mpg_env_reset_from_obs + n x (mpg_policy_action from the second step on, mpg_env_step) as one
+// launch (k_env_rollout_pendulum: bit-identical rewards, last observations and status word)
+extern "C" int mpg_env_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0,
+                                        const float* act0, float* rewards, float* last_obs, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_env_rollout_pendulum: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_env_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_env_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 1, "mpg_env_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
+    MPG_REQUIRE(n >= 1, "mpg_env_rollout_pendulum: n >= 1 steps (got %d)", n);
+    // (what bounds one launch's run time, as the worker's one-launch samples bound theirs)
+    MPG_REQUIRE(n <= 1024, "mpg_env_rollout_pendulum: n <= 1024 steps (got %d)", n);
+    MPG_REQUIRE(rows > 0, "mpg_env_rollout_pendulum: no rows (got %d)", rows);
+    MPG_REQUIRE(policy_params && obs0 && act0 && rewards && last_obs, "mpg_env_rollout_pendulum: null pointer");
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
+                "mpg_env_rollout_pendulum: tanh policy with an action range");
+    cp_worker_policy::Args pa;
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
+    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
+    pa.out_scale = ranged ? cfg->action_range : 1.f;
+    pa.sigma = 0.f;
+    pa.k0 = pa.k1 = pa.c1 = pa.c2 = 0u;
+    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
+    const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+    if (pa.pack)
+        hipLaunchKernelGGL(k_env_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs);
+    else
+        hipLaunchKernelGGL(k_env_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs);
+    MPG_CHECK_LAUNCH("mpg_env_rollout_pendulum");
     return MPG_OK;
 }
 

@@ -45,6 +45,21 @@ __global__ void k_nstep(int rows, int n, const float* __restrict__ rewards, cons
     y[i] = acc + powf(gamma, (float)n) * q[i];
 }
 
+// the same with the bootstrap value clipped to [lo, hi] first (the pendulum's target, mpg_learner.py:163-164: tf.clip_by_value =
+// minimum(maximum(q, lo), hi), which hands a NaN on - fmaxf / fminf would return the bound - so the comparisons are written out).
+// A kernel of its own: k_nstep keeps its instructions.
+__global__ void k_nstep_clipped(int rows, int n, const float* __restrict__ rewards, const float* __restrict__ q, float shift,
+                                float scale, float gamma, float lo, float hi, float* __restrict__ y) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    float acc = 0.f;
+    for (int t = 0; t < n; ++t) acc += powf(gamma, (float)t) * ((rewards[(size_t)t * rows + i] + shift) * scale);
+    float qv = q[i];
+    qv = qv < lo ? lo : qv;          // a NaN compares false both times and stays
+    qv = qv > hi ? hi : qv;
+    y[i] = acc + powf(gamma, (float)n) * qv;
+}
+
 // ---- row sums: the element-wise pass of a loss over the rows of a batch together with the one or two sums it reports ----------------
 // A row body carries its pointers and scalars, NS (the number of sums), SUM_OPTIONAL (whether a null destination means "no sum
 // wanted"), scale0() (what the finished first sum is multiplied by; the second is reported as it is) and operator()(i, s): the stores
@@ -649,23 +664,47 @@ extern "C" int mpg_td3_priority_errors(int rows, const float* y1, const float* y
     return MPG_OK;
 }
 
-extern "C" int mpg_nstep_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n,
-                                 const float* rewards, const float* last_obs, float* y, void* ws, size_t ws_bytes,
-                                 mpg_stream_t stream) {
-    MPG_REQUIRE(net_cfg_ok(cfg) && policy_t && q1t && rewards && last_obs && y && ws && rows > 0 && n > 0,
-                "mpg_nstep_targets: bad argument");
+namespace {
+// mpg_nstep_targets and mpg_nstep_targets_clipped: pi_t(s~_n), Q1t(s~_n, .), then the return - with `clip` the bootstrap value is
+// clipped to [clip[0], clip[1]] by a kernel of its own
+int nstep_targets(const char* who, const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n, const float* rewards,
+                  const float* last_obs, const float* clip, float* y, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    MPG_REQUIRE(net_cfg_ok(cfg) && policy_t && q1t && rewards && last_obs && y && ws && rows > 0 && n > 0, "%s: bad argument", who);
     Arena ar(ws, ws_bytes);
     const QTargetsWs w = q_targets_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small("mpg_nstep_targets", ws_bytes, ar.need);
+    if (!ar.fits()) return workspace_too_small(who, ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
     int rc = policy_forward(cfg, policy_t, rows, policy_x(cfg, last_obs), policy_out(cfg), w.a, nullptr, nullptr, s);
     if (rc) return rc;
     rc = critic_forward(cfg, q1t, rows, critic_x(cfg, last_obs, w.a), w.q1, nullptr, nullptr, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_nstep, dim3((rows + 255) / 256), dim3(256), 0, s, rows, n, rewards, w.q1, cfg->rew_shift,
-                       cfg->rew_scale, cfg->gamma, y);
-    MPG_CHECK_LAUNCH("k_nstep");
+    if (clip)
+        hipLaunchKernelGGL(k_nstep_clipped, dim3((rows + 255) / 256), dim3(256), 0, s, rows, n, rewards, w.q1, cfg->rew_shift,
+                           cfg->rew_scale, cfg->gamma, clip[0], clip[1], y);
+    else
+        hipLaunchKernelGGL(k_nstep, dim3((rows + 255) / 256), dim3(256), 0, s, rows, n, rewards, w.q1, cfg->rew_shift,
+                           cfg->rew_scale, cfg->gamma, y);
+    MPG_CHECK_LAUNCH(clip ? "k_nstep_clipped" : "k_nstep");
     return MPG_OK;
+}
+}  // namespace
+
+extern "C" int mpg_nstep_targets(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n,
+                                 const float* rewards, const float* last_obs, float* y, void* ws, size_t ws_bytes,
+                                 mpg_stream_t stream) {
+    return nstep_targets("mpg_nstep_targets", cfg, policy_t, q1t, rows, n, rewards, last_obs, nullptr, y, ws, ws_bytes, stream);
+}
+
+// the pendulum's n-step target (mpg_learner.py:163-164): the bootstrap value clipped to [q_lo, q_hi] before gamma^n multiplies it
+extern "C" int mpg_nstep_targets_clipped(const mpg_cfg_t* cfg, const float* policy_t, const float* q1t, int rows, int n,
+                                         const float* rewards, const float* last_obs, float q_lo, float q_hi, float* y, void* ws,
+                                         size_t ws_bytes, mpg_stream_t stream) {
+    // (written so that a NaN bound fails it too)
+    MPG_REQUIRE(q_lo >= -3.4028234664e38f && q_lo <= 3.4028234664e38f && q_hi >= -3.4028234664e38f && q_hi <= 3.4028234664e38f,
+                "mpg_nstep_targets_clipped: the clip bounds must be finite (got %g, %g)", (double)q_lo, (double)q_hi);
+    MPG_REQUIRE(q_lo <= q_hi, "mpg_nstep_targets_clipped: empty clip interval (q_lo %g > q_hi %g)", (double)q_lo, (double)q_hi);
+    const float clip[2] = {q_lo, q_hi};
+    return nstep_targets("mpg_nstep_targets_clipped", cfg, policy_t, q1t, rows, n, rewards, last_obs, clip, y, ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_q_loss_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {

@@ -94,6 +94,11 @@ inline bool pendulum_rollout_taken(const mpg_train_ctx_t* c) {
     return c->cfg.env_kind == MPG_ENV_INVERTED_PENDULUM && c->cfg.obs_dim == 4 && c->cfg.act_dim == 1 && c->sample_iters > 0;
 }
 
+// MPGLearner.sample on the pendulum (learner_version 1: the n real-env steps from the replay batch behind the n-step target) as one
+// launch (mpg_env_rollout_pendulum) instead of mpg_env_reset_from_obs + n x (mpg_policy_action, mpg_env_step), under the same rule
+// (tools/bench_env_rollout_pendulum.py) and with the same A/B switch: sample_iters < 0 keeps this chain too
+inline bool env_rollout_pendulum_taken(const mpg_train_ctx_t* c) { return c->sample_iters > 0; }
+
 // what the loop of sample_and_add does behind each of the k iterations a one-launch sample has just run: the counters, and the new
 // transitions' priorities and the ring position in iteration order
 int rollout_added(mpg_train_ctx_t* c, int k, mpg_stream_t s) {
@@ -406,11 +411,17 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
             MPG_REQUIRE(c->l_env_state && c->l_obs && c->l_act && c->l_rewards && c->l_done, "mpg_step_begin: MPG-v1 needs the learner env buffers");
             // one launch (mpg_env_rollout, bit-identical to the chain below: rewards, last observations, status word) where that entry
             // point serves the configuration; the learner's env state, action and done buffers are not written then
-            const bool one_launch = kind == MPG_ENV_PATH_TRACKING && ad == 2 && c->n < 32 &&
-                                    !(c->cfg.policy_out_act == MPG_ACT_TANH && c->cfg.action_range > 0.f);
+            const bool ranged_tanh = c->cfg.policy_out_act == MPG_ACT_TANH && c->cfg.action_range > 0.f;
+            const bool pendulum = kind == MPG_ENV_INVERTED_PENDULUM;
+            const bool one_launch = kind == MPG_ENV_PATH_TRACKING && ad == 2 && c->n < 32 && !ranged_tanh;
+            // the pendulum's one launch (mpg_env_rollout_pendulum, bit-identical to the chain too) for the horizons it serves, by the
+            // rule of the worker's one-launch samples (env_rollout_pendulum_taken, above); longer horizons keep the chain
+            const bool one_launch_pendulum = pendulum && od == 4 && ad == 1 && c->n <= 1024 && !ranged_tanh && env_rollout_pendulum_taken(c);
             if (one_launch) TRY(mpg_env_rollout(&c->cfg, policy, c->batch, c->n, c->b_obs, c->b_act, c->l_rewards, c->l_obs, s));
+            else if (one_launch_pendulum)
+                TRY(mpg_env_rollout_pendulum(&c->cfg, policy, c->batch, c->n, c->b_obs, c->b_act, c->l_rewards, c->l_obs, s));
             else TRY(mpg_env_reset_from_obs(kind, c->batch, od, c->l_env_state, c->b_obs, s));
-            for (int t = 0; t < c->n && !one_launch; ++t) {
+            for (int t = 0; t < c->n && !one_launch && !one_launch_pendulum; ++t) {
                 const float* act = c->b_act;
                 if (t > 0) {
                     TRY(mpg_policy_action(&c->cfg, policy, c->batch, c->l_obs, 0.f, 0, 0, c->l_act, s));
@@ -419,8 +430,13 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
                 TRY(mpg_env_step(kind, c->batch, od, c->l_env_state, act, c->l_obs, c->l_rewards + (size_t)t * c->batch, c->l_done,
                                  c->l_done_intended, s));
             }
-            TRY(mpg_nstep_targets(&c->cfg, policy_t, c->targets + l.off[0], c->batch, c->n, c->l_rewards, c->l_obs, c->b_targets,
-                                  c->ws0, c->ws0_bytes, s));
+            // the pendulum's bootstrap value is clipped (mpg_learner.py:163-164), whichever way the rollout was taken
+            if (pendulum)
+                TRY(mpg_nstep_targets_clipped(&c->cfg, policy_t, c->targets + l.off[0], c->batch, c->n, c->l_rewards, c->l_obs,
+                                              MPG_PENDULUM_NSTEP_Q_LO, MPG_PENDULUM_NSTEP_Q_HI, c->b_targets, c->ws0, c->ws0_bytes, s));
+            else
+                TRY(mpg_nstep_targets(&c->cfg, policy_t, c->targets + l.off[0], c->batch, c->n, c->l_rewards, c->l_obs, c->b_targets,
+                                      c->ws0, c->ws0_bytes, s));
         }
     }
     c->learner_counter++;

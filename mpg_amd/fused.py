@@ -107,7 +107,11 @@ class FusedMPGStep(object):
         if c.learner_version == 1:
             t.update(l_obs=torch.empty(B, od, **f), l_act=torch.empty(B, ad, **f), l_rewards=torch.empty(c.n, B, **f),
                      l_done=torch.ones(B, **u8), l_done_intended=torch.zeros(B, **u8))
-            c.l_env_state = L.ptr(learner.env._state)
+            if learner.env is None:         # the pendulum: one launch holds the agents in registers; the chain (sample_iters < 0,
+                self.l_env_state = torch.zeros(8, B, **f)      # n > 1024) steps this block of MPG_ENV_STATE_DIM rows
+                c.l_env_state = L.ptr(self.l_env_state)
+            else:
+                c.l_env_state = L.ptr(learner.env._state)
         elif c.learner_version == 5:        # the one-launch sampler keeps its agents in registers: rewards and last observations only
             t.update(l_obs=torch.empty(B, od, **f), l_rewards=torch.empty(c.n, B, **f))
         for k, v in t.items():

@@ -12,7 +12,9 @@ import torch
 
 from . import dist as D
 from . import ops
-from .envs import PathTrackingEnv
+from .envs import InvertedPendulumContiEnv, PathTrackingEnv
+
+PENDULUM = 'InvertedPendulumConti-v0'
 
 
 def rule_based_weights(ite, total_ite, eta, select):
@@ -148,8 +150,13 @@ class MPGLearner(_LearnerBase):
             raise ops.L.MpgError('MPG_EINVAL: mpg_mpg_gradients: too many statistics (n_select <= 3 with two critics) or an unsupported '
                                  'horizon / slice count: num_rollout_list_for_policy_update %s with %d critic(s)' % (select, n_q))
         self.env = None
+        # MPG-v1 on the pendulum (train_script4mujoco.py:169-293): the n real-env steps are one launch on the cart-pole kernel and the
+        # bootstrap value is clipped (mpg_learner.py:163-164)
+        self.pendulum = getattr(args, 'env_id', None) == PENDULUM
         if args.learner_version == 'MPG-v1':
-            self.env = PathTrackingEnv(num_agent=self.batch_size, num_future_data=args.num_future_data, device=device)
+            # (the pendulum's env is stepped only by the chain, for horizons beyond the one launch's: sample() builds it then)
+            if not self.pendulum:
+                self.env = PathTrackingEnv(num_agent=self.batch_size, num_future_data=args.num_future_data, device=device)
 
     # ---- heuristic-bias rollout (defined but never called by the reference's compute_gradient either) ----
     def model_rollout_for_q_estimation(self, start_obses, start_actions, eps=None):
@@ -173,9 +180,16 @@ class MPGLearner(_LearnerBase):
 
     def sample(self, start_obs, start_action):
         """mpg_learner.py:109-124: n real-env steps; first action from replay, then the ONLINE policy, no noise.  One launch
-        (mpg_env_rollout, bit-identical to the chain below) for the horizons it serves (n < 32); the learner's env is not stepped then."""
+        (mpg_env_rollout, bit-identical to the chain below) for the horizons it serves (n < 32); the learner's env is not stepped then.
+        On the pendulum: mpg_env_rollout_pendulum, n <= 1024."""
         pw = self.policy_with_value
-        if self.sample_num_in_learner < 32:
+        if self.pendulum:
+            if self.sample_num_in_learner <= 1024:
+                rewards, last_obs = ops.env_rollout_pendulum(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
+                return {'all_rewards': rewards, 'last_obs': last_obs}
+            if self.env is None:
+                self.env = InvertedPendulumContiEnv(num_agent=self.batch_size, device=self.device)
+        elif self.sample_num_in_learner < 32:
             rewards, last_obs = ops.env_rollout(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
             return {'all_rewards': rewards, 'last_obs': last_obs}
         obs = start_obs
@@ -191,7 +205,8 @@ class MPGLearner(_LearnerBase):
         """mpg_learner.py:146-169"""
         pw, b = self.policy_with_value, self.batch_data
         ro = self.sample(b['batch_obs'], b['batch_actions'])
-        return ops.nstep_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), ro['all_rewards'], ro['last_obs'])
+        return ops.nstep_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), ro['all_rewards'], ro['last_obs'],
+                                 clip=ops.PENDULUM_NSTEP_Q_CLIP if self.pendulum else None)
 
     def get_batch_data(self, batch_data, rb, indexes):
         self._get_batch(batch_data)

@@ -270,10 +270,18 @@ def td3_priority_errors(y1, y, td):
     return out
 
 
-def nstep_targets(cfg, policy_t, q1t, rewards, last_obs):
+PENDULUM_NSTEP_Q_CLIP = (-0.5, 0.0)      # MPG_PENDULUM_NSTEP_Q_LO / _HI (include/mpg_hip.h; mpg_learner.py:163-164)
+
+
+def nstep_targets(cfg, policy_t, q1t, rewards, last_obs, clip=None):
+    """mpg_nstep_targets; with clip=(lo, hi) mpg_nstep_targets_clipped: the bootstrap value clipped to [lo, hi] first"""
     n, rows = rewards.shape
     y = torch.empty(rows, dtype=torch.float32, device=last_obs.device)
     ws = _ws(last_obs.device, 0, 'mpg_q_targets_workspace_bytes', cfg, rows)
+    if clip is not None:
+        L.call('mpg_nstep_targets_clipped', ctypes.byref(cfg), L.ptr(_f32(policy_t)), L.ptr(_f32(q1t)), L.c_int(rows), L.c_int(n),
+               L.ptr(_f32(rewards)), L.ptr(_f32(last_obs)), L.c_float(clip[0]), L.c_float(clip[1]), L.ptr(y), *ws, L.stream())
+        return y
     L.call('mpg_nstep_targets', ctypes.byref(cfg), L.ptr(_f32(policy_t)), L.ptr(_f32(q1t)), L.c_int(rows), L.c_int(n),
            L.ptr(_f32(rewards)), L.ptr(_f32(last_obs)), L.ptr(y), *ws, L.stream())
     return y
@@ -286,6 +294,17 @@ def env_rollout(cfg, policy_params, obs0, act0, n):
     rewards = torch.empty(int(n), rows, dtype=torch.float32, device=dev)
     last_obs = torch.empty(rows, cfg.obs_dim, dtype=torch.float32, device=dev)
     L.call('mpg_env_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)),
+           L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
+    return rewards, last_obs
+
+
+def env_rollout_pendulum(cfg, policy_params, obs0, act0, n):
+    """mpg_env_rollout_pendulum: n real-env steps of the inverted pendulum from (obs0 [rows, 4], act0 [rows, 1]), later actions from the
+    policy without noise, ONE launch.  Returns (rewards [n, rows] RAW, last_obs [rows, 4])."""
+    rows, dev = obs0.shape[0], obs0.device
+    rewards = torch.empty(int(n), rows, dtype=torch.float32, device=dev)
+    last_obs = torch.empty(rows, 4, dtype=torch.float32, device=dev)
+    L.call('mpg_env_rollout_pendulum', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)),
            L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
     return rewards, last_obs
 
