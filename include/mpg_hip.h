@@ -173,7 +173,8 @@ int mpg_env_reset(int env_kind, int n, int obs_dim, float* state, const uint8_t*
  * action [n][2] in [-1,1] (scaled by [1.2pi/9, 3] and clipped inside, :457-459); outputs obs [n][obs_dim],
  * reward [n], done [n] bytes.  done follows the reference literally and is therefore always 1
  * (SURVEY.md B-0); done_intended (nullable) receives the evidently intended |alpha| > |bound| test.
- * Pendulum: inverted_pendulum_conti.py:9-19, action [n][1] clipped to +-3, 2 RK4 steps of 0.02 s, real done flag. */
+ * Pendulum: inverted_pendulum_conti.py:9-19, action [n][1] clipped to +-3, 2 RK4 steps of 0.02 s, real done flag.
+ * A NaN action is handed on (NaN state, observation and reward, done 1), infinite ones are +-3. */
 int mpg_env_step(int env_kind, int n, int obs_dim, float* state, const float* action, float* obs, float* reward,
                  uint8_t* done, uint8_t* done_intended, mpg_stream_t stream);
 

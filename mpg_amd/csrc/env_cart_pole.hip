@@ -238,7 +238,10 @@ struct StepOut {
 };
 
 __device__ __forceinline__ StepOut step_agent(S4& s, float action) {
-    const float force = GEAR * fminf(fmaxf(action, -CTRL), CTRL);
+    // fmaxf(NaN, -3) is -3: a NaN action is handed on, as np.clip / tf.clip_by_value hand it on (a NaN transition with done = 1, not a
+    // full push to the left that looks like any other step)
+    const float ctrl = fminf(fmaxf(action, -CTRL), CTRL);
+    const float force = GEAR * (action != action ? action : ctrl);
 #pragma unroll
     for (int f = 0; f < FRAME_SKIP; ++f) {
         const S4 k1 = deriv(s, force);

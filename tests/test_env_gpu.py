@@ -297,6 +297,7 @@ def test_cart_pole_env_vs_float64_restatement():
     from oracle import mpg_oracle as O
     from mpg_amd.envs import InvertedPendulumContiEnv
     rng = np.random.Generator(np.random.PCG64(11))
+    left_out = pairs = 0
     for n in (1, 64, 1000):
         env = InvertedPendulumContiEnv(num_agent=n, seed=3)
         obs0 = env.reset().cpu().numpy().astype(np.float64)
@@ -317,7 +318,12 @@ def test_cart_pole_env_vs_float64_restatement():
             # done may legitimately differ for an agent sitting within rounding of a threshold
             near = (np.abs(np.abs(ro[:, 0]) - 2.0) < 1e-4) | (np.abs(np.abs(ro[:, 1]) - 0.2) < 1e-4)
             assert (d.cpu().numpy().astype(bool) == rd)[~near].all()
+            left_out, pairs = left_out + int(near.sum()), pairs + n
         assert bool(env.done.any()) or n == 1        # random +-3 pushes for 2 s drop the pole for essentially every agent
+    # the pairs left out as near a bound are few: the float64 oracle's own closed loop from these starts under these action draws leaves
+    # out 3 of the 53250 (tests/test_cart_pole_edges.py); tests/test_cart_pole_edges_gpu.py compares done with none left out
+    print('cart-pole random walk: %d of %d pairs left out as near a done bound' % (left_out, pairs))
+    assert left_out <= 0.01 * pairs, (left_out, pairs)
     # reset(init_obs) + reset() of the done agents only
     env = InvertedPendulumContiEnv(num_agent=8, seed=1)
     init = torch.as_tensor(np.array([[0., 0., 0., 0.]] * 4 + [[2.5, 0., 0., 0.]] * 4, np.float32)).cuda()
