@@ -543,6 +543,54 @@ int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params, int rows, 
 int mpg_env_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
                              float* rewards, float* last_obs, mpg_stream_t stream);
 
+/* Evaluator.run_n_episodes_parallel's loop - evaluator.py:132-139 - on the path-tracking env (obs_dim 6 .. 16, act_dim 2) as ONE launch:
+ * from the env's own state [MPG_ENV_STATE_DIM][n] and its current observations obs_io [n][obs_dim] take `steps` steps with the policy's
+ * deterministic action (compute_mode: explore_sigma 0; for a stochastic stack the mean columns under the cfg's output rule).  `done` is
+ * not consulted, nothing is reset, and the action goes to the env unclipped and is recorded unclipped.  Everything these `steps`
+ * consecutive pairs leave behind, t = 0 .. steps - 1,
+ *   mpg_policy_action(cfg, policy_params, n, obs_io, 0, 0, 0, act_traj + t * n * 2, stream);         (obs_io recorded at obs_traj + t * n * obs_dim first)
+ *   mpg_env_step(MPG_ENV_PATH_TRACKING, n, obs_dim, state, act_traj + t * n * 2, obs_io, rew_traj + t * n, done_out, done_intended_out, stream);
+ * is bit-identical: obs_traj [steps][n][obs_dim] (the observations BEFORE each step), act_traj [steps][n][2], rew_traj [steps][n] RAW,
+ * state, obs_io and the done flags of the LAST step (both nullable), and the sticky status word - for both weight forms (packed image and
+ * strided).  One workgroup keeps a 16-agent group's policy weights and agents in registers for all steps; global memory is read at the
+ * start only and written, never read back.
+ * Refused before any launch with MPG_EINVAL, "mpg_eval_rollout" and a text of its own each, the outputs untouched: a null configuration,
+ * env_kind 2 (the text of the other real-env entry points), any other env that is not PathTracking, obs_dim outside 6 .. 16, act_dim != 2,
+ * n <= 0, steps < 1, steps > 1024 (what bounds one launch's run time; the parsers' largest fixed_steps is 500), a null pointer other than
+ * the done flags, a tanh output activation with an action range.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_eval_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
+                     float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out /* nullable */,
+                     uint8_t* done_intended_out /* nullable */, mpg_stream_t stream);
+
+/* The same for the pendulum's real env (MPG_ENV_INVERTED_PENDULUM, obs_dim 4, act_dim 1): `steps` consecutive pairs of mpg_policy_action
+ * (explore_sigma 0) and mpg_env_step as ONE launch, bit-identical in obs_traj [steps][n][4], act_traj [steps][n][1], rew_traj [steps][n],
+ * state, obs_io, done_out (nullable; the last step's) and the status word.  An agent beyond the done bound keeps stepping, as in the chain.
+ * obs_io and obs_traj are read and written four floats at a time: both must be 16-byte aligned (as mpg_env_step asks of its pendulum
+ * observations; any device allocation is).
+ * Refused before any launch with MPG_EINVAL, "mpg_eval_rollout_pendulum" and a text of its own each: a null configuration, env_kind 2,
+ * any other env that is not the pendulum, obs_dim != 4, act_dim != 1, n <= 0, steps < 1, steps > 1024, a null pointer other than
+ * done_out, a tanh output activation with an action range. */
+int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
+                              float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
+/* Evaluator.metrics_for_an_episode - evaluator.py:160-211 - for each of the n episodes of a recorded evaluation, and the mean of every
+ * metric over the episodes (:153-156), as ONE launch.  Rows in the reference's key_list order:
+ *   MPG_ENV_PATH_TRACKING (K = 8): episode_return, episode_len, delta_y_mse (obs column 3), delta_phi_mse (4), delta_v_mse (0),
+ *     stationary_rew_mean (the rewards from step 20 on; NaN = 0 / 0 with steps <= 20), steer_mse (action 0 * 1.2 * pi / 9, operator by operator), acc_mse
+ *     (action 1 * 3);
+ *   MPG_ENV_INVERTED_PENDULUM (K = 18): episode_return, episode_len, x_mean, x_var, theta_mean, theta_var, xdot_mean, xdot_var,
+ *     thetadot_mean, thetadot_var, x_mse, theta_mse, xdot_mse, thetadot_mse and the four _mse_25 over the first min(25, steps) steps.
+ * The `_mse` are ROOT mean squares, as in the reference; variances are two-pass population variances.  Every float32 entry is widened
+ * to double first and all arithmetic is double.  per_episode [K][n], mean [K] (device memory).  Sums run t ascending, then episode
+ * ascending, without atomics: two launches give the same bits.
+ * MPG_EINVAL for another env kind, n <= 0, steps < 1, an obs_dim that is not the kind's (6 .. 16; 4) and a null pointer.  The
+ * pendulum's obs_traj is read four floats at a time and must be 16-byte aligned; per_episode and mean 8-byte, as doubles are. */
+#define MPG_EVAL_METRICS_PATH_TRACKING 8
+#define MPG_EVAL_METRICS_PENDULUM 18
+int mpg_eval_metrics(int env_kind, int n, int steps, int obs_dim, const float* obs_traj, const float* act_traj, const float* rew_traj,
+                     double* per_episode /* [K][n] */, double* mean /* [K] */, mpg_stream_t stream);
+
 size_t mpg_mpg_gradients_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select, int n_q);
 int mpg_mpg_gradients(const mpg_cfg_t* cfg, int n_q, const float* params, const float* target_params, int rows,
                       float* obs, float* act, float* rew, float* obs_tp1, const float* y_in,

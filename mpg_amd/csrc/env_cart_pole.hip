@@ -16,8 +16,9 @@
 //
 // Also here, beside the device functions it steps the agents with: mpg_worker_rollout_pendulum, a worker sample's iterations on this
 // env in one launch (k_worker_rollout_pendulum), mpg_worker_sample_rollout_pendulum, the same for the tanh-squashed Gaussian policy
-// (k_worker_sample_rollout_pendulum), and mpg_env_rollout_pendulum, the learner's n real-env steps from a replay batch in one launch
-// (k_env_rollout_pendulum).
+// (k_worker_sample_rollout_pendulum), mpg_env_rollout_pendulum, the learner's n real-env steps from a replay batch in one launch
+// (k_env_rollout_pendulum), and mpg_eval_rollout_pendulum, an evaluation's steps with their trajectory in one launch
+// (k_eval_rollout_pendulum).
 #include "env_internal.h"
 
 // The worker's policy pass rides in the one-launch worker sample (k_worker_rollout_pendulum, below).  The network engine is compiled
@@ -554,7 +555,111 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout_pendu
     cp_sample_policy::report(pa, zmax, saw_nan);
 }
 
+// k_eval_rollout_pendulum (below): the env lanes' pointers, resting in LDS as CpRolloutEnvArgs does and for its reason
+struct CpEvalEnvArgs {
+    float *st, *obs_io, *obs_traj, *act_traj, *rew_traj;
+    uint8_t* done_out;
+};
+
+// Evaluator.run_n_episodes_parallel's loop (evaluator.py:132-139: compute_mode -> env.step, `done` not consulted, nothing reset) for the
+// pendulum in ONE launch: `steps` consecutive pairs of mpg_policy_action (k_forward<4, 1, PK, 1>, sigma 0) and mpg_env_step = 2 * steps
+// launches.  A sibling of k_env_rollout_pendulum with its residency plan: one 512-thread workgroup per 16-agent group, the policy's
+// registers loaded once, lanes 0 .. 15 of wave 0 hold one agent (S4) each across the steps, the observations go to the pass through LDS
+// between workgroup barriers and the action comes back in a register.  Unlike that kernel the agents come from the env's own state
+// block and the first observations from obs_io, the policy is evaluated at step 0 too (`steps` passes), and the trajectory is recorded:
+// per step t the observation BEFORE the step (out of sObs) at obs_traj[(t n + i) 4 ..], the action - unclipped, the env clips its own
+// copy - at act_traj[t n + i] and the reward at rew_traj[t n + i].  An agent beyond the done bound keeps stepping, as in the chain.
+// State, obs_io and the done flags (nullable) are written after the LAST step only; global memory is read in the prologue only (weights,
+// state, obs_io) and written, never read back; the status word is reported once.  Bit-identical to the chain: the same device functions
+// on the same operands in the same order (tests/test_eval_rollout_gpu.py).
+template <bool PK>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout_pendulum(const cp_worker_policy::Args pa, int n, int steps, float* st,
+                                                                            float* obs_io, float* obs_traj, float* act_traj,
+                                                                            float* rew_traj, uint8_t* done_out) {
+    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
+    __shared__ CpEvalEnvArgs sArg;
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<4, 1> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
+    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
+    const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
+    S4 s = {};
+    if (env_lane) s = load(st, n, i);
+    {   // the group's rows of obs_io (16 x 4 floats)
+        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.st = st; sArg.obs_io = obs_io; sArg.obs_traj = obs_traj; sArg.act_traj = act_traj; sArg.rew_traj = rew_traj;
+        sArg.done_out = done_out;
+    }
+    for (int t = 0; t < steps; ++t) {
+        mlp::lds_barrier();                              // sObs of this step is complete (and the previous pass's LDS is free)
+        float a = cp_worker_policy::pass(pa, n, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+        if (!env_lane) continue;
+        a = cp_worker_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
+        const size_t row = (size_t)t * (size_t)n + (size_t)i;
+        reinterpret_cast<float4*>(sArg.obs_traj)[row] = reinterpret_cast<const float4*>(sObs)[threadIdx.x];   // obs before the step
+        sArg.act_traj[row] = a;
+        const StepOut o = step_agent(s, a);
+        sArg.rew_traj[row] = o.reward;
+        if (t == steps - 1) {
+            uint8_t* const dn = sArg.done_out;
+            if (dn) dn[i] = o.done ? 1 : 0;
+            store(sArg.st, n, i, s);
+            write_obs(sArg.obs_io, i, s);
+        } else {
+            write_obs(sObs, threadIdx.x, s);
+        }
+    }
+    cp_worker_policy::report(pa, zmax, saw_nan);
+}
+
 }  // namespace
+
+// evaluator.py:132-139 for the pendulum: `steps` consecutive pairs mpg_policy_action (explore_sigma 0) + mpg_env_step as one launch
+// (k_eval_rollout_pendulum: bit-identical trajectories, state, observations, done flags and status word)
+extern "C" int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
+                                         float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out, mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_eval_rollout_pendulum: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_eval_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_eval_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_eval_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 1, "mpg_eval_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
+    MPG_REQUIRE(n > 0, "mpg_eval_rollout_pendulum: no agents (n %d)", n);
+    MPG_REQUIRE(steps >= 1, "mpg_eval_rollout_pendulum: steps >= 1 (got %d)", steps);
+    // (what bounds one launch's run time; the parsers' largest fixed_steps is 500)
+    MPG_REQUIRE(steps <= 1024, "mpg_eval_rollout_pendulum: steps <= 1024 (got %d)", steps);
+    MPG_REQUIRE(policy_params && state && obs_io && obs_traj && act_traj && rew_traj, "mpg_eval_rollout_pendulum: null pointer");
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
+                "mpg_eval_rollout_pendulum: tanh policy with an action range");
+    cp_worker_policy::Args pa;
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
+    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
+    pa.out_scale = ranged ? cfg->action_range : 1.f;
+    pa.sigma = 0.f;
+    pa.k0 = pa.k1 = pa.c1 = pa.c2 = 0u;
+    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+    if (pa.pack)
+        hipLaunchKernelGGL(k_eval_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj,
+                           act_traj, rew_traj, done_out);
+    else
+        hipLaunchKernelGGL(k_eval_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj,
+                           act_traj, rew_traj, done_out);
+    MPG_CHECK_LAUNCH("mpg_eval_rollout_pendulum");
+    return MPG_OK;
+}
 
 // worker.py:91-119 for the pendulum: `iters` consecutive pairs mpg_policy_action + mpg_env_step_store_reset (noise_ctr + it, ring
 // position (next_idx + it * n) % capacity, env_ctr + it) as one launch (k_worker_rollout_pendulum: bit-identical state, observations,

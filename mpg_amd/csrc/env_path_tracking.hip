@@ -1123,6 +1123,98 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const
     worker_policy::report(pa, zmax, saw_nan);
 }
 
+// k_eval_rollout (below): what wave 0 needs of the launch's arguments once per step, resting in LDS as RolloutEnvArgs does and for its
+// reason: seven pointers held in scalar registers across the whole loop, beside the env's hoisted constants, leave those no room.
+struct EvalEnvArgs {
+    float *st, *obs_io, *obs_traj, *act_traj, *rew_traj;
+    uint8_t *done_out, *done_intended_out;
+};
+
+// Evaluator.run_n_episodes_parallel's loop (evaluator.py:132-139: compute_mode -> env.step, `done` not consulted, nothing reset) in ONE
+// launch: `steps` consecutive pairs of mpg_policy_action (sigma 0) and mpg_env_step = 2 * steps launches of at most one wave per CU,
+// every policy launch fetching the weights again and every env launch the state.  A sibling of k_env_rollout with its residency plan:
+// one 512-thread workgroup owns a 16-agent group for all steps, the policy's registers are loaded once (worker_policy::load), wave 0 -
+// four lanes per agent, step_agent<4> - keeps the agents in registers, and per step the observations go from wave 0 to the policy pass
+// and the actions back through LDS between workgroup barriers.  Unlike k_env_rollout the agents come from the env's own state block
+// (load_agent, as in k_worker_rollout) and the first observations from obs_io - a drawn state does not survive the round trip through
+// its observation (reset_agent wraps phi, k_reset_from_obs does not) - the policy is evaluated at step 0 too, and the whole trajectory
+// is recorded: per step t the observation BEFORE the step (out of sObs: at t = 0 the caller's own rows, later what write_obs left
+// there) at obs_traj[(t n + i) od ..], the action as the pass formed it - unclipped, the env clips its own copy - at act_traj[(t n + i)
+// 2 ..] and the reward at rew_traj[t n + i]: the layouts torch.stack gives the evaluator's per-step tensors.  State, obs_io and the
+// done flags (k_step's two, both nullable here) are written after the LAST step only: what the chain leaves behind.  Global memory is
+// read in the prologue only (weights, state, obs_io) and written, never read back; the status word is reported once.  Everything is
+// bit-identical to the chain's: the same device functions on the same operands in the same order (tests/test_eval_rollout_gpu.py).
+// IN as in k_policy_step_store_reset.
+// NO REGISTER HEADROOM: the packed IN = 6 form takes 254 of the 256 VGPRs this launch bound allows (strided 250; IN = 16: 238 / 235),
+// without scratch.  A change to step_agent, worker_policy::pass or this loop can tip it into scratch: run
+// `tools/kernel_resources.py env_path_tracking.hip` after any such edit.
+template <bool PK, int IN>
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout(const typename worker_policy::args_of<IN>::type pa, int n_launch,
+                                                                   int steps, float* st, float* obs_io, float* obs_traj, float* act_traj,
+                                                                   float* rew_traj, uint8_t* done_out, uint8_t* done_intended_out) {
+    __shared__ __attribute__((aligned(16))) float smem[worker_policy::smem_floats<IN>()];
+    __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
+    __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
+    __shared__ float sAct[mlp::GROUP * 2];
+    __shared__ EvalEnvArgs sArg;
+    const int od_launch = worker_policy::obs_dim_of(pa);
+    const mlp::Lane L;
+    float w2[128];
+    mlp::SmallRegs<IN, 2> r;
+    float b3v, zmax = 0.f;
+    bool saw_nan = false;
+    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
+    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
+    Agent ag = {};
+    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
+    {   // the group's rows of obs_io (16 x od <= 256 floats)
+        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
+        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+        sArg.st = st; sArg.obs_io = obs_io; sArg.obs_traj = obs_traj; sArg.act_traj = act_traj; sArg.rew_traj = rew_traj;
+        sArg.done_out = done_out; sArg.done_intended_out = done_intended_out;
+    }
+    for (int t = 0; t < steps; ++t) {
+        const bool last = t == steps - 1;
+        mlp::lds_barrier();                              // sObs of this step is complete (and the previous pass's LDS is free)
+        worker_policy::pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+        if (threadIdx.x >= 64) continue;                 // wave 0 wrote sAct itself: LDS is in order within a wave
+        // (the lane's place and the launch's sizes, opaque per step: k_worker_rollout says why)
+        int q = q_lane, i = i_lane, od = od_launch, n = n_launch;
+        asm volatile("" : "+v"(q), "+v"(i), "+s"(n));
+        if constexpr (IN == 16) asm volatile("" : "+s"(od));      // (a constant at IN = 6)
+        __builtin_amdgcn_wave_barrier();
+        if (i < n) {
+            const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
+            const size_t row = (size_t)t * (size_t)n + (size_t)i;
+            {   // the observation before the step, lane q its entries q, q + 4, ..; the action by the first lane
+                float* const ot = sArg.obs_traj + row * (size_t)od;
+                for (int k = q; k < od; k += 4) ot[k] = sObs[a_loc * od + k];
+                if (q == 0) reinterpret_cast<float2*>(sArg.act_traj)[row] = an;
+            }
+            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
+            if (q == 1) {
+                sArg.rew_traj[row] = o.reward;
+                if (last) {
+                    uint8_t* const dn = sArg.done_out;
+                    uint8_t* const di = sArg.done_intended_out;
+                    if (dn) dn[i] = o.done ? 1 : 0;
+                    if (di) di[i] = o.done_intended ? 1 : 0;
+                }
+            }
+            if (last) {
+                if (q == 2) store_agent(sArg.st, n, i, ag);
+                if (q == 3) write_obs(sArg.obs_io, i, od, ag);
+            } else if (q == 3) {
+                write_obs(sObs, a_loc, od, ag);
+            }
+        }
+    }
+    worker_policy::report(pa, zmax, saw_nan);
+}
+
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
 
 }  // namespace
@@ -1472,5 +1564,43 @@ extern "C" int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* poli
 #undef MPG_SAMPLE_ROLLOUT_LAUNCH
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_sample_rollout");
+    return MPG_OK;
+}
+
+// evaluator.py:132-139 for the path-tracking env: `steps` consecutive pairs mpg_policy_action (explore_sigma 0) + mpg_env_step as one
+// launch (k_eval_rollout: bit-identical trajectories, state, observations, done flags and status word)
+extern "C" int mpg_eval_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
+                                float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out, uint8_t* done_intended_out,
+                                mpg_stream_t stream) {
+    MPG_REQUIRE(cfg, "mpg_eval_rollout: null configuration");
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_eval_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
+    // (the pendulum has a launch of its own: mpg_eval_rollout_pendulum)
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_eval_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
+    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_eval_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 2, "mpg_eval_rollout: act_dim 2 only (got %d)", cfg->act_dim);
+    MPG_REQUIRE(n > 0, "mpg_eval_rollout: no agents (n %d)", n);
+    MPG_REQUIRE(steps >= 1, "mpg_eval_rollout: steps >= 1 (got %d)", steps);
+    // (what bounds one launch's run time; the parsers' largest fixed_steps is 500)
+    MPG_REQUIRE(steps <= 1024, "mpg_eval_rollout: steps <= 1024 (got %d)", steps);
+    MPG_REQUIRE(policy_params && state && obs_io && obs_traj && act_traj && rew_traj, "mpg_eval_rollout: null pointer");
+    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_eval_rollout: tanh policy with an action range");
+    const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
+    hipStream_t s = mpg_stream(stream);
+#define MPG_EVAL_ROLLOUT_LAUNCH(PK, IN)                                                                                              \
+    hipLaunchKernelGGL((k_eval_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj, act_traj, \
+                       rew_traj, done_out, done_intended_out)
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, 0.f, 0, 0);
+        pa.obs_dim = cfg->obs_dim;
+        if (pa.pack) MPG_EVAL_ROLLOUT_LAUNCH(true, 16); else MPG_EVAL_ROLLOUT_LAUNCH(false, 16);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, 0.f, 0, 0);
+        if (pa.pack) MPG_EVAL_ROLLOUT_LAUNCH(true, 6); else MPG_EVAL_ROLLOUT_LAUNCH(false, 6);
+    }
+#undef MPG_EVAL_ROLLOUT_LAUNCH
+    MPG_CHECK_LAUNCH("mpg_eval_rollout");
     return MPG_OK;
 }

@@ -1,11 +1,18 @@
-"""Evaluator - device mirror of evaluator.py:25-236: deterministic fixed-length parallel episodes on the
-HIP env and the reference's per-episode metrics (evaluator.py:160-211), averaged over the agents.  Not on the throughput
-path; it is the learning-curve check that the fast path still learns (the reference's plots use a base score of -30,
-ploter.py:85)."""
+"""Evaluator - device mirror of evaluator.py:25-236: deterministic fixed-length episodes on the HIP env -
+parallel ones (run_n_episodes_parallel) or serial ones (run_n_episodes) - and the reference's per-episode metrics
+(evaluator.py:160-211), averaged over the episodes.  Not on the throughput path; it is the learning-curve check that the fast path
+still learns (the reference's plots use a base score of -30, ploter.py:85).
+
+`args.one_launch_eval = True` (named like args.one_launch_sample; off by default): all steps of an evaluation are ONE launch
+(ops.eval_rollout: mpg_eval_rollout on PathTracking-v0, mpg_eval_rollout_pendulum on InvertedPendulumConti-v0, bit-identical to the
+2 * fixed_steps launches of the loop), the metrics a second one (ops.eval_metrics, float64 on the device) and ONE copy brings them to
+the host; run_evaluation then follows evaluator.py:222-225 (one eval agent: num_eval_episode serial episodes)."""
 import torch
 
 from . import ops
 from .envs import make_env
+
+MAX_ONE_LAUNCH_STEPS = 1024      # what mpg_eval_rollout accepts (it bounds one launch's run time)
 
 
 class Evaluator(object):
@@ -14,12 +21,19 @@ class Evaluator(object):
         self.args = args
         self.device = torch.device(device)
         self.num_eval_agent = int(getattr(args, 'num_eval_agent', 5))
+        self.num_eval_episode = int(getattr(args, 'num_eval_episode', 5))
         self.fixed_steps = int(getattr(args, 'fixed_steps', 200))
+        self.one_launch_eval = bool(getattr(args, 'one_launch_eval', False))
+        self._check_one_launch_steps()
         self.env = make_env(env_id, num_agent=self.num_eval_agent, num_future_data=getattr(args, 'num_future_data', 0), device=device,
                             seed=int(getattr(args, 'seed', 0)) + 424242)
         self.policy_with_value = policy_cls(**vars(args), device=device)
         self.iteration = 0
         self.stats = {}
+
+    def _check_one_launch_steps(self):
+        if self.one_launch_eval and self.fixed_steps > MAX_ONE_LAUNCH_STEPS:
+            raise ValueError('one_launch_eval takes at most %d steps per launch (fixed_steps = %d)' % (MAX_ONE_LAUNCH_STEPS, self.fixed_steps))
 
     def set_weights(self, weights):
         if weights is self.policy_with_value:
@@ -32,16 +46,16 @@ class Evaluator(object):
     def set_ppc_params(self, params):
         pass
 
-    def run_n_episodes_parallel(self, n=None, init_obs=None):
-        """evaluator.py:118-156: reset, `fixed_steps` deterministic steps (done is ignored), metrics per episode.
-        init_obs (optional, [num_eval_agent, obs_dim]): start from these observations instead of a fresh reset() draw
-        (the parity test starts from the states the reference's own env drew)."""
-        pw = self.policy_with_value
+    def _reset(self, init_obs=None):
         if init_obs is not None:
-            obses = self.env.reset(init_obs=init_obs)
-        else:
-            self.env._initialised = False                  # fresh draw of every agent
-            obses = self.env.reset()
+            return self.env.reset(init_obs=init_obs)
+        self.env._initialised = False                      # fresh draw of every agent
+        return self.env.reset()
+
+    def _episodes_by_the_loop(self, obses):
+        """evaluator.py:132-152 from the observations `obses` of the env's current state: `fixed_steps` times compute_mode and env.step,
+        then the metrics of every agent's episode, as float64 device tensors [num_eval_agent]"""
+        pw = self.policy_with_value
         obs_l, act_l, rew_l = [], [], []
         for _ in range(self.fixed_steps):
             actions = ops.policy_action(pw.cfg, pw.net('policy'), obses)      # compute_mode, policy.py:173-177
@@ -64,12 +78,79 @@ class Evaluator(object):
                 per_episode[nm + '_var'] = obs[:, :, j].var(0, unbiased=False)
                 per_episode[nm + '_mse'] = rms(obs[:, :, j])
                 per_episode[nm + '_mse_25'] = rms(obs[:25, :, j])
+        return per_episode
+
+    def _episodes_in_one_launch(self, state, obs):
+        """The same episodes from (state [8, rows], obs [rows, obs_dim]) by ops.eval_rollout and ops.eval_metrics: two launches and one
+        copy to the host.  `state` is advanced in place.  Returns (per_episode, mean, last_obs, the done flags of the last step, the
+        rewards [steps, rows]): per_episode's values are float64 HOST tensors [rows], in the reference's key order."""
+        self._check_one_launch_steps()
+        pw = self.policy_with_value
+        out = ops.eval_rollout(pw.cfg, pw.net('policy'), state, obs, self.fixed_steps)
+        obs_traj, act_traj, rew_traj, last_obs = out[:4]
+        keys, rows = ops.EVAL_METRIC_KEYS[self.env.kind], obs.shape[0]
+        host = ops.eval_metrics_flat(self.env.kind, obs_traj, act_traj, rew_traj).cpu()     # ONE device-to-host copy: [K * rows | K]
+        per_episode = {k: host[j * rows:(j + 1) * rows] for j, k in enumerate(keys)}
+        mean = {k: float(host[len(keys) * rows + j]) for j, k in enumerate(keys)}
+        pw.check_status()          # NaN observations / actions, the engine's envelope: an evaluation on invalid numbers raises
+        return per_episode, mean, last_obs, out[4:], rew_traj
+
+    def _leave_env(self, last_obs, done, reward):
+        """what `fixed_steps` env.step calls leave in the env's attributes (the state block was advanced in place)"""
+        env = self.env
+        env.obs, env.reward, env.done = last_obs, reward, done[0]
+        # (the pendulum's step writes `done` into both flags)
+        env.done_intended = done[1] if len(done) > 1 else done[0].clone()
+
+    def run_n_episodes_parallel(self, n=None, init_obs=None):
+        """evaluator.py:118-156: reset, `fixed_steps` deterministic steps (done is ignored), metrics per episode.
+        init_obs (optional, [num_eval_agent, obs_dim]): start from these observations instead of a fresh reset() draw
+        (the parity test starts from the states the reference's own env drew).
+        With args.one_launch_eval the per-episode values are float64 HOST tensors (they came over in the one copy); without, float64
+        device tensors as before."""
+        pw = self.policy_with_value
+        obses = self._reset(init_obs)
+        if self.one_launch_eval:
+            per_episode, mean, last_obs, done, rew = self._episodes_in_one_launch(self.env._state, obses)
+            self._leave_env(last_obs, done, rew[-1])
+            return per_episode, mean
+        per_episode = self._episodes_by_the_loop(obses)
         mean = {k: float(v.mean().item()) for k, v in per_episode.items()}
         pw.check_status()          # NaN observations / actions, the engine's envelope: an evaluation on invalid numbers raises
         return per_episode, mean
 
+    def run_n_episodes(self, n):
+        """evaluator.py:112-122: `n` serial episodes of `fixed_steps` steps on the evaluator's env, each from a fresh reset() of every
+        agent (the env's draw counter advances per episode), and the mean of every metric over the n * num_eval_agent episodes (episode
+        e's agent a is entry e * num_eval_agent + a).
+        With args.one_launch_eval the n resets come first, their states and observations are concatenated and ONE rollout launch and one
+        metrics launch serve all rows: the rows are independent, so the trajectories equal the serial ones bit for bit.  The env is left
+        holding the last episode's state, observation and done flags either way."""
+        n = int(n)
+        assert n >= 1, n
+        pw, env, A = self.policy_with_value, self.env, self.num_eval_agent
+        if self.one_launch_eval:
+            self._check_one_launch_steps()
+            states, obs = [], []
+            for _ in range(n):
+                obs.append(self._reset())
+                states.append(env._state.clone())
+            state = torch.cat(states, 1).contiguous() if n > 1 else states[0]
+            per_episode, mean, last_obs, done, rew = self._episodes_in_one_launch(state, torch.cat(obs, 0) if n > 1 else obs[0])
+            env._state.copy_(state[:, (n - 1) * A:])
+            self._leave_env(last_obs[(n - 1) * A:].clone(), [d[(n - 1) * A:].clone() for d in done], rew[-1, (n - 1) * A:].clone())
+            return per_episode, mean
+        episodes = [self._episodes_by_the_loop(self._reset()) for _ in range(n)]
+        per_episode = {k: torch.cat([e[k] for e in episodes]) for k in episodes[0]}
+        mean = {k: float(v.mean().item()) for k, v in per_episode.items()}
+        pw.check_status()
+        return per_episode, mean
+
     def run_evaluation(self, iteration):
         self.iteration = iteration
-        _, mean = self.run_n_episodes_parallel()
+        if self.one_launch_eval and self.num_eval_agent == 1:      # evaluator.py:222-223
+            _, mean = self.run_n_episodes(self.num_eval_episode)
+        else:
+            _, mean = self.run_n_episodes_parallel()
         self.stats = dict(iteration=iteration, **mean)
         return mean

@@ -309,6 +309,60 @@ def env_rollout_pendulum(cfg, policy_params, obs0, act0, n):
     return rewards, last_obs
 
 
+EVAL_METRICS_PATH_TRACKING, EVAL_METRICS_PENDULUM = 8, 18      # MPG_EVAL_METRICS_* (include/mpg_hip.h): metrics per episode
+# the rows of eval_metrics, in the reference's key_list order (evaluator.py:161,180-181,202-205)
+EVAL_METRIC_KEYS = {
+    0: ('episode_return', 'episode_len', 'delta_y_mse', 'delta_phi_mse', 'delta_v_mse', 'stationary_rew_mean', 'steer_mse', 'acc_mse'),
+    1: ('episode_return', 'episode_len', 'x_mean', 'x_var', 'theta_mean', 'theta_var', 'xdot_mean', 'xdot_var', 'thetadot_mean',
+        'thetadot_var', 'x_mse', 'theta_mse', 'xdot_mse', 'thetadot_mse', 'x_mse_25', 'theta_mse_25', 'xdot_mse_25', 'thetadot_mse_25')}
+
+
+def eval_rollout(cfg, policy_params, state, obs, steps):
+    """mpg_eval_rollout / mpg_eval_rollout_pendulum (by cfg.env_kind): `steps` deterministic steps (policy_action without noise, then the
+    env's step; `done` is not consulted, nothing is reset) from the env's state block [8, n] and its observations obs [n, obs_dim] in ONE
+    launch, bit-identical to the 2 * steps launches it replaces.  `state` is advanced in place; `obs` is left as it is (the launch works
+    on a copy, which comes back as last_obs).  Returns (obs_traj [steps, n, obs_dim] - the observations BEFORE each step -, act_traj
+    [steps, n, act_dim], rew_traj [steps, n], last_obs [n, obs_dim], done [n] uint8 of the last step) and, on PathTracking,
+    done_intended [n] behind them."""
+    n, dev, steps = obs.shape[0], obs.device, int(steps)
+    od, ad = cfg.obs_dim, cfg.act_dim
+    assert obs.shape == (n, od) and state.shape == (8, n), (obs.shape, state.shape)
+    obs_io = _f32(obs).clone()
+    rows = max(steps, 0)
+    obs_traj = torch.empty(rows, n, od, dtype=torch.float32, device=dev)
+    act_traj = torch.empty(rows, n, ad, dtype=torch.float32, device=dev)
+    rew_traj = torch.empty(rows, n, dtype=torch.float32, device=dev)
+    done = torch.empty(n, dtype=torch.uint8, device=dev)
+    if cfg.env_kind == 1:
+        L.call('mpg_eval_rollout_pendulum', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(steps), L.ptr(_f32(state)),
+               L.ptr(obs_io), L.ptr(obs_traj), L.ptr(act_traj), L.ptr(rew_traj), L.ptr(done), L.stream())
+        return obs_traj, act_traj, rew_traj, obs_io, done
+    done_intended = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.call('mpg_eval_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(steps), L.ptr(_f32(state)), L.ptr(obs_io),
+           L.ptr(obs_traj), L.ptr(act_traj), L.ptr(rew_traj), L.ptr(done), L.ptr(done_intended), L.stream())
+    return obs_traj, act_traj, rew_traj, obs_io, done, done_intended
+
+
+def eval_metrics(env_kind, obs_traj, act_traj, rew_traj):
+    """mpg_eval_metrics: the reference's per-episode metrics (evaluator.py:160-211; rows: EVAL_METRIC_KEYS[env_kind]) of the recorded
+    trajectories [steps, n, .] and their means over the episodes, float64, in ONE launch.  Returns (per_episode [K, n], mean [K])."""
+    n = obs_traj.shape[1]
+    out = eval_metrics_flat(env_kind, obs_traj, act_traj, rew_traj)
+    K = out.numel() // (n + 1)
+    return out[:K * n].view(K, n), out[K * n:]
+
+
+def eval_metrics_flat(env_kind, obs_traj, act_traj, rew_traj):
+    """eval_metrics' two results as the ONE device array they are views of - [K * n | K] float64 - so that one copy brings both to the
+    host"""
+    steps, n, od = obs_traj.shape
+    K = {0: EVAL_METRICS_PATH_TRACKING, 1: EVAL_METRICS_PENDULUM}.get(int(env_kind), 1)
+    out = torch.empty(K * (n + 1), dtype=torch.float64, device=obs_traj.device)
+    L.call('mpg_eval_metrics', L.c_int(int(env_kind)), L.c_int(n), L.c_int(steps), L.c_int(od), L.ptr(_f32(obs_traj)),
+           L.ptr(_f32(act_traj)), L.ptr(_f32(rew_traj)), L.ptr(out[:K * n]), L.ptr(out[K * n:]), L.stream())
+    return out
+
+
 def q_loss_grad(cfg, q_params, obs, act, y, inv_b_global=None, grad_out=None, loss_out=None, want_td=False):
     rows = obs.shape[0]
     dev = obs.device
