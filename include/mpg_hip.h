@@ -591,6 +591,54 @@ int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, 
 int mpg_eval_metrics(int env_kind, int n, int steps, int obs_dim, const float* obs_traj, const float* act_traj, const float* rew_traj,
                      double* per_episode /* [K][n] */, double* mean /* [K] */, mpg_stream_t stream);
 
+/* ---- The MPC baseline, SLSQP form (mpc/main.py:75-165) ----
+ * ModelPredictiveControl.cost_function for `rows` independent problems.  x0 [rows][6] = [v_x, v_y, r, delta_y, delta_phi, x] with
+ * entry 0 the SPEED in m/s as compute_rew reads it (:133; not the env's v_x - 20), u [rows][horizon][2] NORMALISED controls.
+ *   for i < horizon:  u_i = u[i] * (MPG_MPC_STEER_SCALE, MPG_MPC_ACC_SCALE);  cost -= compute_rew(x, u_i);  x = compute_next_obses(x, u_i)
+ * (:160-163; compute_next_obses: f_xu at tau = 0.1, then v_x clipped to [1, 35] and delta_phi wrapped once into (-pi, pi], :145-154).
+ * No model noise, no 20 m/s shift: this is not the rollout sweeps' model step.
+ * mpg_mpc_cost_grad, ONE launch: cost [rows]; grad (nullable) [rows][horizon][2] = d cost / d u with respect to the NORMALISED controls
+ * (the two scales included), by the hand adjoint of the step; a step whose raw v_x leaves [1, 35] passes no adjoint through v_x (the
+ * gate of the rollout sweeps' adjoint); traj (nullable) [rows][horizon + 1][6] the states x_0 .. x_horizon.  cost is the same bits
+ * whether grad and traj are asked for or not.  float32, the hardware reciprocal / sine / cosine as in the rollout sweeps (delta_phi of
+ * x0 is expected within a few pi).  Entry 5 of the state (x) never reaches the cost.
+ *
+ * mpg_mpc_solve, ONE launch: minimises the cost over the box [-1, 1]^(2 horizon) for every row by the spectral projected gradient method
+ * (Birgin, Martinez, Raydan, SIAM J. Optim. 10, 2000) with its non-monotone line search, constants below.
+ *   setup: u = clamp(u_io, -1, 1), f and g there.
+ *   iteration k < iters:  d = clamp(u - alpha g, -1, 1) - u;  f_max = max of the last MPG_MPC_SPG_M accepted costs;
+ *     lambda = 1, 1/2, ... (at most MPG_MPC_SPG_HALVINGS halvings): the first u + lambda d with cost <= f_max + MPG_MPC_SPG_GAMMA lambda <g, d>
+ *     is accepted;  s = u_new - u, y = g_new - g, alpha = <s, s> / <s, y> if <s, y> > 0 else MPG_MPC_SPG_ALPHA_MAX_STEP, clamped to
+ *     [MPG_MPC_SPG_ALPHA_LO, MPG_MPC_SPG_ALPHA_HI];  the first alpha is MPG_MPC_SPG_ALPHA0.
+ *     (the trial point is clamped into the box once more: u + (c - u) can round one ulp past c)
+ *   A row stops when max_i |clamp(u - g, -1, 1) - u|_i <= tol (checked after the setup and after every accepted step; tol 0: never) or
+ *   when its line search accepts nothing (a NaN cost included: every comparison is false); it keeps its last accepted u.  NaN passes
+ *   through the clamps, as through np.clip, so a NaN in x0 [0 .. 4] or in the start point fails the first search: info -1.
+ * u_io [rows][horizon][2]: start point in, solution out;  cost_out [rows] the last accepted cost (bit for bit mpg_mpc_cost_grad's at the
+ * returned u);  pgnorm_out [rows] the norm above at that point;  info [rows]: the number of accepted iterations k, or -(k + 1) for a row
+ * whose search failed after k of them.  Every loop has a fixed bound (iters, the halvings, horizon).  One lane per row, its arrays in LDS
+ * (11 * horizon * 256 bytes per 64 rows); a row's result does not depend on which other rows share the launch.
+ *
+ * Both refuse before any launch with MPG_EINVAL, their own name and a text of its own each, the outputs untouched: rows <= 0, horizon < 1,
+ * horizon > MPG_MPC_MAX_HORIZON, (solve) iters < 0, iters > MPG_MPC_MAX_ITERS, a negative or NaN tol, a null pointer other than grad / traj.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+#define MPG_MPC_MAX_HORIZON 31         /* the rollout entry points' bound (n < 32) */
+#define MPG_MPC_MAX_ITERS 1000
+#define MPG_MPC_STEER_SCALE 0.4f       /* main.py:161 */
+#define MPG_MPC_ACC_SCALE 3.0f
+#define MPG_MPC_SPG_M 5                /* non-monotone memory */
+#define MPG_MPC_SPG_HALVINGS 20
+#define MPG_MPC_SPG_GAMMA 1e-4f        /* sufficient decrease */
+#define MPG_MPC_SPG_ALPHA0 0.05f
+#define MPG_MPC_SPG_ALPHA_MAX_STEP 10.0f /* the step taken when <s, y> <= 0 */
+#define MPG_MPC_SPG_ALPHA_LO 1e-6f
+#define MPG_MPC_SPG_ALPHA_HI 1e3f
+int mpg_mpc_cost_grad(int rows, int horizon, const float* x0 /* [rows][6] */, const float* u /* [rows][horizon][2] */,
+                      float* cost /* [rows] */, float* grad /* nullable, [rows][horizon][2] */,
+                      float* traj /* nullable, [rows][horizon + 1][6] */, mpg_stream_t stream);
+int mpg_mpc_solve(int rows, int horizon, int iters, float tol, const float* x0, float* u_io /* start point in, solution out */,
+                  float* cost_out /* [rows] */, float* pgnorm_out /* [rows] */, int* info /* [rows] */, mpg_stream_t stream);
+
 size_t mpg_mpg_gradients_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select, int n_q);
 int mpg_mpg_gradients(const mpg_cfg_t* cfg, int n_q, const float* params, const float* target_params, int rows,
                       float* obs, float* act, float* rew, float* obs_tp1, const float* y_in,
