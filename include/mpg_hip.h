@@ -639,6 +639,40 @@ int mpg_mpc_cost_grad(int rows, int horizon, const float* x0 /* [rows][6] */, co
 int mpg_mpc_solve(int rows, int horizon, int iters, float tol, const float* x0, float* u_io /* start point in, solution out */,
                   float* cost_out /* [rows] */, float* pgnorm_out /* [rows] */, int* info /* [rows] */, mpg_stream_t stream);
 
+/* mpg_mpc_rollout, ONE launch: the MPC side of the closed loop of mpc/main.py:168-223 for n agents of PathTracking-v0 with
+ * num_future_data = 0 (observations of 6 entries), `steps` env steps with one solve each.  Everything the following chain leaves behind,
+ * bit for bit, for t = 0 .. steps - 1:
+ *   1. obs_traj[t] = obs_io
+ *   2. x0 = obs_io + (20, 0, 0, 0, 0, 0) in float32 (entry 0 becomes (v_x - 20) + 20 from the second step on; the sum with 0 turns a -0
+ *      into +0)
+ *   3. u = a copy of u_io;  mpg_mpc_solve on (n, horizon, iters, tol, x0, u, cost_traj[t], pgnorm_traj[t], info_traj[t]);  plan_traj[t] = u
+ *   4. warm_start 1: u_io[:, i] = u[:, i + 1] for i < horizon - 1 and u_io[:, horizon - 1] = u[:, horizon - 1] - the plan one step later,
+ *      its last pair repeated (main.py:214, commented out there).  warm_start 0: u_io is only read, every solve starts from it (:184).
+ *   5. mpg_env_step on (MPG_ENV_PATH_TRACKING, n, 6, state, u[:, 0, :], obs_io, rew_traj[t], done_out, done_intended_out)
+ * state [MPG_ENV_STATE_DIM][n], obs_io [n][6] and (warm) u_io [n][horizon][2] carry everything from one step to the next, so two calls of
+ * s1 and s2 steps equal one call of s1 + s2 steps bit for bit.  They and the two done flags (nullable, uint8 [n]) are written after the
+ * LAST step only.  obs_traj [steps][n][6], plan_traj [steps][n][horizon][2] and rew_traj [steps][n] (RAW) are required; cost_traj,
+ * pgnorm_traj [steps][n] float and info_traj [steps][n] int are nullable, each on its own.
+ * One lane per agent, workgroups of one wave; the agent's state and observation stay in registers across the steps, the solver's arrays
+ * in LDS as in mpg_mpc_solve (11 * horizon * 256 bytes per 64 agents).  Global memory is read in the prologue and then written, never
+ * read back - but for u_io with warm_start 0, which no launch of this entry point writes and every solve reads.  An agent's results do
+ * not depend on which other agents share the launch.
+ * MPG_MPC_ROLLOUT_MAX_WORK bounds steps * iters, the iterations one lane can run in a launch, and with it the launch's run time on a
+ * shared device: a 200-iteration mpg_mpc_solve at horizon 25 with every CU busy was measured at 33.6 ms, 0.17 ms per iteration, so 2048
+ * iterations are about 0.35 s - twice the longest launch mpg_mpc_solve allows (MPG_MPC_MAX_ITERS).  Longer loops are run in chunks.
+ * Refuses before any launch with MPG_EINVAL, its own name and a text of its own each, the outputs untouched: n <= 0, steps < 1,
+ * steps > MPG_MPC_ROLLOUT_MAX_STEPS, horizon < 1, horizon > MPG_MPC_MAX_HORIZON, iters < 0, iters > MPG_MPC_MAX_ITERS,
+ * steps * iters > MPG_MPC_ROLLOUT_MAX_WORK, a negative or NaN tol, warm_start other than 0 or 1, a null pointer among the required ones.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+#define MPG_MPC_ROLLOUT_MAX_STEPS 1024
+#define MPG_MPC_ROLLOUT_MAX_WORK 2048  /* steps * iters of one launch */
+int mpg_mpc_rollout(int n, int steps, int horizon, int iters, float tol, int warm_start,
+                    float* state /* [MPG_ENV_STATE_DIM][n], advanced in place */, float* obs_io /* [n][6] */,
+                    float* u_io /* [n][horizon][2]: the start point of the first solve */, float* obs_traj /* [steps][n][6] */,
+                    float* plan_traj /* [steps][n][horizon][2] */, float* rew_traj /* [steps][n] */, float* cost_traj /* nullable */,
+                    float* pgnorm_traj /* nullable */, int* info_traj /* nullable */, uint8_t* done_out /* nullable */,
+                    uint8_t* done_intended_out /* nullable */, mpg_stream_t stream);
+
 size_t mpg_mpg_gradients_workspace_bytes(const mpg_cfg_t* cfg, int rows, int M, int n, int n_select, int n_q);
 int mpg_mpg_gradients(const mpg_cfg_t* cfg, int n_q, const float* params, const float* target_params, int rows,
                       float* obs, float* act, float* rew, float* obs_tp1, const float* y_in,

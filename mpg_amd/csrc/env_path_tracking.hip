@@ -330,6 +330,9 @@ __device__ __forceinline__ void sample_act(const float* l, long gr, float range,
 }  // namespace worker_policy
 #pragma clang fp contract(off)
 
+// the MPC baseline's solve, for k_mpc_rollout at the end of this file (the header is under "off" itself)
+#include "mpc_core.h"
+
 namespace {
 
 #ifdef MPG_TIMELINE   // diagnostic build only (tools/timeline.sh)
@@ -1602,5 +1605,132 @@ extern "C" int mpg_eval_rollout(const mpg_cfg_t* cfg, const float* policy_params
     }
 #undef MPG_EVAL_ROLLOUT_LAUNCH
     MPG_CHECK_LAUNCH("mpg_eval_rollout");
+    return MPG_OK;
+}
+
+// ---- mpg_mpc_rollout: the MPC side of the closed loop of mpc/main.py:168-223 in one launch --------------------------------------------
+namespace {
+
+// `steps` times: record the observation, solve from it (mpc::solve, the body of k_mpc_solve in mpc_kernels.hip), record the plan, step
+// the env with the plan's first pair (step_agent<1>, the body of k_step).  One lane per agent, workgroups of one wave: the agent's
+// state block and its observation stay in registers across the steps, the solver's four arrays in dynamic LDS as in k_mpc_solve.
+// What the chain of launches hands on through global memory is handed on here in registers and LDS, the same float32 values:
+//   the observation: write_obs's entries (v_x - 20 first), to which the next step's start state adds (20, 0, 0, 0, 0, 0) as run_mpc's
+//     obs + shift does - entry 0 is (v_x - 20) + 20, NOT v_x, and the sum with 0 turns a -0 into +0;
+//   the start point: warm, the solution moved up by one pair inside U (k_mpc_solve would clamp what it reads, which leaves entries of
+//     the box, NaN and -0 included, as they are); cold, u_io again - the one array read after the prologue, and one this kernel never
+//     writes in that mode.
+// State, obs_io, the done flags and (warm) u_io are written after the LAST step only.  Every loop has a fixed bound and leaves early
+// only on a wave-uniform condition (mpc::solve says how); lanes behind the last agent solve nothing, step nothing and store nothing.
+// The launch's pointers but u_io, the agent count, the warm-start flag and the tolerance rest in LDS, as EvalEnvArgs does for
+// k_eval_rollout and for its reason: held in scalar registers across the solver's nested loops, beside the constants of the model and
+// of the env that the compiler hoists out of the step loop, they spilled 25 of them (tools/kernel_resources.py); with only the pointers
+// moved, two.  What comes back out of LDS is a vector register: the tolerance is only ever compared with a lane's own norm.
+struct MpcRolloutArgs {
+    float *st, *obs_io, *obs_traj, *plan_traj, *rew_traj, *cost_traj, *pgnorm_traj;
+    int* info_traj;
+    uint8_t *done_out, *done_intended_out;
+    int n, warm;
+    float tol;
+};
+__global__ void __launch_bounds__(mpc::WAVE) k_mpc_rollout(const MpcRolloutArgs a, int steps, int H, int iters, float* u_io) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ MpcRolloutArgs sArg;
+    constexpr int W = mpc::WAVE;
+    const int lane = threadIdx.x, i = blockIdx.x * W + lane;
+    const bool valid = i < a.n;
+    if (lane == 0) sArg = a;                    // (one wave: LDS is in order within it)
+    float* U = lds + lane;                      // the last accepted point [2 H][W]; between two solves the next one's start point
+    float* G = U + 2 * H * W;                   // its gradient
+    float* T = G + 2 * H * W;                   // the trial point
+    float* X = T + 2 * H * W;                   // the states of the last forward pass [NX H][W]
+    Agent ag = {};
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, o4 = 0.f, o5 = 0.f;      // the observation (an idle lane's gives mpc::idle_state())
+    float* const start = u_io + (size_t)(valid ? i : 0) * 2 * H;      // this lane's row of u_io, kept as the lane's own pointer
+    if (valid) {
+        ag = load_agent(a.st, a.n, i);
+        const float* o = a.obs_io + (size_t)i * 6;
+        o0 = o[0]; o1 = o[1]; o2 = o[2]; o3 = o[3]; o4 = o[4]; o5 = o[5];
+    }
+    // (the copy loops here are kept rolled: unrolled, their precomputed trip counts were what the step loop had no scalar register for)
+#pragma unroll 1
+    for (int j = 0; j < 2 * H; ++j) U[j * W] = valid ? mpc::box(start[j]) : 0.f;
+    StepOut so = {};
+    size_t row = (size_t)i;                     // t n + i
+    __builtin_amdgcn_wave_barrier();
+    const float tol = sArg.tol;
+    for (int left = steps; left > 0; --left) {
+        if (valid) {
+            float* ot = sArg.obs_traj + row * 6;
+            ot[0] = o0; ot[1] = o1; ot[2] = o2; ot[3] = o3; ot[4] = o4; ot[5] = o5;
+        }
+        const mpc::State s0 = {o0 + 20.f, o1 + 0.f, o2 + 0.f, o3 + 0.f, o4 + 0.f, o5 + 0.f};
+        const mpc::Solved r = mpc::solve(H, iters, tol, valid, s0, U, G, T, X);
+        const float2 an = make_float2(U[0], U[W]);
+        if (valid) {
+            float* pt = sArg.plan_traj + row * 2 * H;
+#pragma unroll 1
+            for (int j = 0; j < 2 * H; ++j) pt[j] = U[j * W];
+            float* const ct = sArg.cost_traj;
+            float* const gt = sArg.pgnorm_traj;
+            int* const it = sArg.info_traj;
+            if (ct) ct[row] = r.cost;
+            if (gt) gt[row] = r.pgnorm;
+            if (it) it[row] = r.info;
+        }
+        // the next solve's start point (behind the last step: what u_io takes, or nothing)
+        if (__builtin_amdgcn_readfirstlane(sArg.warm)) {      // main.py:214: the plan one step later, its last pair repeated
+#pragma unroll 1
+            for (int j = 0; j + 2 < 2 * H; ++j) U[j * W] = U[(j + 2) * W];
+        } else {                                               // :184: the caller's, which this launch never writes
+#pragma unroll 1
+            for (int j = 0; j < 2 * H; ++j) U[j * W] = valid ? mpc::box(start[j]) : 0.f;
+        }
+        if (valid) {
+            so = step_agent<1>(ag, an);
+            sArg.rew_traj[row] = so.reward;
+            o0 = ag.vx - 20.f; o1 = ag.vy; o2 = ag.r; o3 = ag.dy; o4 = ag.dphi; o5 = ag.x;      // write_obs
+        }
+        row += (size_t)sArg.n;
+    }
+    if (valid) {
+        store_agent(sArg.st, sArg.n, i, ag);
+        write_obs(sArg.obs_io, i, 6, ag);
+        uint8_t* const dn = sArg.done_out;
+        uint8_t* const di = sArg.done_intended_out;
+        if (dn) dn[i] = so.done ? 1 : 0;
+        if (di) di[i] = so.done_intended ? 1 : 0;
+        if (sArg.warm) {
+#pragma unroll 1
+            for (int j = 0; j < 2 * H; ++j) start[j] = U[j * W];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int mpg_mpc_rollout(int n, int steps, int horizon, int iters, float tol, int warm_start, float* state, float* obs_io, float* u_io,
+                               float* obs_traj, float* plan_traj, float* rew_traj, float* cost_traj, float* pgnorm_traj, int* info_traj,
+                               uint8_t* done_out, uint8_t* done_intended_out, mpg_stream_t stream) {
+    MPG_REQUIRE(n > 0, "mpg_mpc_rollout: no agents (n %d)", n);
+    MPG_REQUIRE(steps >= 1, "mpg_mpc_rollout: steps >= 1 (got %d)", steps);
+    MPG_REQUIRE(steps <= MPG_MPC_ROLLOUT_MAX_STEPS, "mpg_mpc_rollout: steps <= %d (got %d)", MPG_MPC_ROLLOUT_MAX_STEPS, steps);
+    MPG_REQUIRE(horizon >= 1, "mpg_mpc_rollout: horizon >= 1 (got %d)", horizon);
+    MPG_REQUIRE(horizon <= MPG_MPC_MAX_HORIZON, "mpg_mpc_rollout: horizon <= %d (got %d)", MPG_MPC_MAX_HORIZON, horizon);
+    MPG_REQUIRE(iters >= 0, "mpg_mpc_rollout: iters >= 0 (got %d)", iters);
+    MPG_REQUIRE(iters <= MPG_MPC_MAX_ITERS, "mpg_mpc_rollout: iters <= %d (got %d)", MPG_MPC_MAX_ITERS, iters);
+    // (one launch's run time on a shared device: include/mpg_hip.h derives the bound; callers run longer loops in chunks)
+    MPG_REQUIRE((long)steps * iters <= MPG_MPC_ROLLOUT_MAX_WORK, "mpg_mpc_rollout: steps * iters = %ld solver iterations in one launch, at most %d",
+                (long)steps * iters, MPG_MPC_ROLLOUT_MAX_WORK);
+    MPG_REQUIRE(tol >= 0.f, "mpg_mpc_rollout: tol negative or NaN (%g)", (double)tol);
+    MPG_REQUIRE(warm_start == 0 || warm_start == 1, "mpg_mpc_rollout: warm_start is 0 or 1 (got %d)", warm_start);
+    MPG_REQUIRE(state && obs_io && u_io && obs_traj && plan_traj && rew_traj, "mpg_mpc_rollout: null pointer");
+    const size_t lds = mpc::lds_bytes(horizon, 3);
+    if (int rc = mpc::allow_lds("mpg_mpc_rollout", k_mpc_rollout, lds)) return rc;
+    const MpcRolloutArgs a = {state, obs_io, obs_traj, plan_traj, rew_traj, cost_traj, pgnorm_traj, info_traj, done_out, done_intended_out,
+                              n, warm_start, tol};
+    hipLaunchKernelGGL(k_mpc_rollout, dim3((n + mpc::WAVE - 1) / mpc::WAVE), dim3(mpc::WAVE), lds, mpg_stream(stream), a, steps, horizon, iters,
+                       u_io);
+    MPG_CHECK_LAUNCH("mpg_mpc_rollout");
     return MPG_OK;
 }

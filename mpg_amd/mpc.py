@@ -3,14 +3,15 @@ closed loop that measures a policy against it.  Names follow the reference.
 
 Where mpc/main.py runs one scipy SLSQP solve with finite-difference gradients per env step (about 2 s each), ModelPredictiveControl
 here holds B start states and solves all of them in ONE launch (mpg_mpc_solve: spectral projected gradient on the hand adjoint of the
-25-step rollout; include/mpg_hip.h states the problem, the method and its constants).  The IPOPT form (mpc/mpc_ipopt.py) needs casadi
-and is not provided."""
+25-step rollout; include/mpg_hip.h states the problem, the method and its constants), and the closed loop's MPC side runs as ONE launch
+per chunk of steps (mpg_mpc_rollout).  The IPOPT form (mpc/mpc_ipopt.py) needs casadi and is not provided."""
 import torch
 
 from . import _lib as L
 from .envs import PathTrackingEnv
 
 MAX_HORIZON, MAX_ITERS = 31, 1000        # MPG_MPC_MAX_HORIZON, MPG_MPC_MAX_ITERS
+MAX_ROLLOUT_STEPS, MAX_ROLLOUT_WORK = 1024, 2048      # MPG_MPC_ROLLOUT_MAX_STEPS, MPG_MPC_ROLLOUT_MAX_WORK (steps * iters of one launch)
 
 
 def _f32(t):
@@ -79,7 +80,38 @@ class ModelPredictiveControl(object):
         return (u[0], cost[0], pgnorm[0], info[0]) if self.single else (u, cost, pgnorm, info)
 
 
-def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device='cuda'):
+def mpc_rollout(env, u, steps, horizon, iters=200, tol=0., warm_start=False):
+    """mpg_mpc_rollout: `steps` steps of the MPC side of the closed loop - solve from the observation (+ 20 in column 0), step `env` (a
+    PathTrackingEnv with num_future_data 0) with the plan's first pair - in ONE launch, bit-identical to the chain of mpc_solve, env.step
+    and the torch ops between them.  u [n, horizon, 2]: the start point of the first solve (left as it is).  Advances env._state and
+    env.obs (env.done and env.done_intended: the last step's).  Returns (obs_traj [steps, n, 6] - the observations BEFORE each step -,
+    plan_traj [steps, n, horizon, 2], rew_traj [steps, n] raw, cost_traj, pgnorm_traj [steps, n], info_traj [steps, n] int32, u_next
+    [n, horizon, 2]: the start point of the solve after the last one - with warm_start the last plan moved up by one pair, its last pair
+    repeated (main.py:214); without, u)."""
+    assert isinstance(env, PathTrackingEnv) and env.num_future_data == 0, 'mpc_rollout: a PathTrackingEnv with num_future_data 0'
+    n, dev, steps, horizon = env.num_agent, env.obs.device, int(steps), int(horizon)
+    assert u.shape == (n, horizon, 2), (u.shape, n, horizon)
+    u_io = u.to(dev, torch.float32).contiguous().clone()
+    obs_io = env.obs.contiguous().clone()        # never write into a tensor already handed to the caller
+    rows = max(steps, 0)
+    obs_traj = torch.empty(rows, n, 6, dtype=torch.float32, device=dev)
+    plan_traj = torch.empty(rows, n, horizon, 2, dtype=torch.float32, device=dev)
+    rew_traj, cost_traj, pgnorm_traj = (torch.empty(rows, n, dtype=torch.float32, device=dev) for _ in range(3))
+    info_traj = torch.empty(rows, n, dtype=torch.int32, device=dev)
+    done, done_intended = torch.empty_like(env.done), torch.empty_like(env.done_intended)
+    L.call('mpg_mpc_rollout', L.c_int(n), L.c_int(steps), L.c_int(horizon), L.c_int(int(iters)), L.c_float(float(tol)),
+           L.c_int(1 if warm_start else 0), L.ptr(env._state), L.ptr(obs_io), L.ptr(u_io), L.ptr(obs_traj), L.ptr(plan_traj), L.ptr(rew_traj),
+           L.ptr(cost_traj), L.ptr(pgnorm_traj), L.ptr(info_traj), L.ptr(done), L.ptr(done_intended), L.stream())
+    env.obs, env.reward, env.done, env.done_intended = obs_io, rew_traj[-1], done, done_intended
+    return obs_traj, plan_traj, rew_traj, cost_traj, pgnorm_traj, info_traj, u_io
+
+
+def _shifted(plan):
+    """main.py:214, concatenate([mpc_action[2:], mpc_action[-2:]]): the plan one step later, its last pair repeated"""
+    return torch.cat([plan[:, 1:], plan[:, -1:]], 1)
+
+
+def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device='cuda', one_launch=False, warm_start=False, tol=0.):
     """The closed loop of mpc/main.py:168-223 for `num_agent` start states at once: two PathTrackingEnv (num_future_data 0) from the same
     start, one driven by the first control pair of a fresh MPC solve per step (from zeros, :184), one by `policy` (PolicyWithQs), and the
     policy's action on the MPC env's observations beside them.
@@ -89,6 +121,17 @@ def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device
     whose column 0 was the speed - today's PathTrackingEnv (and this project's) returns v_x - 20, which is why the fixture made from
     that recording subtracts 20 from it ("subtract 20 from obs[0]").  Unshifted, the baseline would drive to 40 m/s.
 
+    warm_start: every solve but the first starts from the plan of the step before, moved up by one pair (:214, commented out there),
+    not from zeros.  tol: the solver's stopping tolerance (0: every solve runs all `iters`); the warm start only saves work with one.
+    one_launch: the same record, bit for bit, from a launch per chunk of steps instead of a launch per operation: the MPC side as
+    mpc_rollout (mpg_mpc_rollout, max(1, MAX_ROLLOUT_WORK // iters) steps per launch), the policy's side as ops.eval_rollout for a
+    deterministic policy, and rl_action_mpc from one policy pass over the recorded observations.  The defaults are the loop as it was.
+    Measured on one MI355X, 90 steps at horizon 25: at equal settings one launch is at the loop's time for one
+    agent and 1 - 2.5 % SLOWER for 256 agents cold (3.20 against 3.17 s: that loop is device-bound, 35 ms of solve per step), and 9 - 11 %
+    faster for 256 agents with warm_start and tol = 1e-3 (0.140 against 0.157 s; 14.7 accepted iterations per solve against 137).  The
+    warm start changes the closed loop: 12 of those 256 agents end with a reward sum below -20 where one does from zeros (mean -9.3
+    against -4.4, median unchanged) - it is the start point, not the tolerance.
+
     Returns the reference's record keys as stacked device tensors over the steps: mpc_obs, rl_obs [steps, n, 6], mpc_action [steps, n,
     horizon, 2] (the whole plan), rl_action, rl_action_mpc [steps, n, 2], mpc_rew, rl_rew [steps, n] (the reward that led to the recorded
     observation: zeros first).  Nothing in the loop synchronises or copies to the host, so timing is the caller's: synchronise around the
@@ -97,6 +140,8 @@ def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device
     env4rl = PathTrackingEnv(num_future_data=0, num_agent=num_agent, device=device, seed=seed)
     obs = env4mpc.reset()
     obs4rl = env4rl.reset(init_obs=obs.clone())
+    if one_launch:
+        return _run_mpc_one_launch(policy, env4mpc, env4rl, int(steps), int(horizon), iters, tol, warm_start)
     shift = torch.zeros(6, dtype=torch.float32, device=obs.device)
     shift[0] = 20.
     mpc = ModelPredictiveControl(obs + shift, horizon)
@@ -104,8 +149,11 @@ def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device
     rew4rl = torch.zeros_like(rew)
     keys = ('mpc_obs', 'rl_obs', 'mpc_action', 'rl_action', 'rl_action_mpc', 'mpc_rew', 'rl_rew')
     rec = {k: [] for k in keys}
+    u_init = None
     for _ in range(steps):
-        mpc_action = mpc.solve(iters=iters)[0]
+        mpc_action = mpc.solve(u_init=u_init, iters=iters, tol=tol)[0]
+        if warm_start:
+            u_init = _shifted(mpc_action)
         rl_action_mpc = policy.compute_action(obs)[0]
         rl_action = policy.compute_action(obs4rl)[0]
         for k, v in zip(keys, (obs, obs4rl, mpc_action, rl_action, rl_action_mpc, rew, rew4rl)):
@@ -114,3 +162,55 @@ def run_mpc(policy, num_agent=1, steps=90, horizon=25, seed=0, iters=200, device
         obs4rl, rew4rl, _, _ = env4rl.step(rl_action)
         mpc.reset_init_x(obs + shift)
     return {k: torch.stack(v) for k, v in rec.items()}
+
+
+def _run_mpc_one_launch(policy, env4mpc, env4rl, steps, horizon, iters, tol, warm_start):
+    """run_mpc's record from both envs behind their resets"""
+    from . import ops
+    n, dev = env4mpc.num_agent, env4mpc.obs.device
+    # the MPC side: chunks of steps, each one launch; state, observation and start point carry over (two calls of s1 and s2 steps are
+    # one call of s1 + s2)
+    chunk = max(1, MAX_ROLLOUT_WORK // max(int(iters), 1))
+    u = torch.zeros(n, horizon, 2, dtype=torch.float32, device=dev)
+    parts = []
+    for t0 in range(0, steps, chunk):
+        out = mpc_rollout(env4mpc, u, min(chunk, steps - t0), horizon, iters, tol, warm_start)
+        u = out[6]
+        parts.append(out[:3])
+    mpc_obs, mpc_action, mpc_rew = (torch.cat([p[k] for p in parts]) for k in range(3))
+    zeros = torch.zeros(1, n, dtype=torch.float32, device=dev)
+    if policy.deterministic_policy:
+        # the policy's side: mpg_eval_rollout is policy_action and env.step per step; rl_action_mpc in ONE pass over all recorded
+        # observations - a row's action does not depend on the rows beside it (tests/test_mpc_rollout_gpu.py holds both to the loop's bits)
+        state = env4rl._state
+        rl_obs, rl_action, rl_rew, last_obs, done, done_intended = ops.eval_rollout(policy.cfg, policy.net('policy'), state, env4rl.obs, steps)
+        env4rl.obs, env4rl.reward, env4rl.done, env4rl.done_intended = last_obs, rl_rew[-1], done, done_intended
+        rl_action_mpc = policy.compute_action(mpc_obs.reshape(steps * n, 6))[0].reshape(steps, n, 2)
+    else:
+        # a sampling policy draws from its own stream, twice per step in the loop's order: the same calls in the same order
+        obs4rl, rew4rl = env4rl.obs, zeros[0]
+        rl_obs, rl_action, rl_action_mpc, rl_rew = [], [], [], []
+        for t in range(steps):
+            rl_action_mpc.append(policy.compute_action(mpc_obs[t])[0])
+            rl_action.append(policy.compute_action(obs4rl)[0])
+            rl_obs.append(obs4rl)
+            obs4rl, rew4rl, _, _ = env4rl.step(rl_action[-1])
+            rl_rew.append(rew4rl)
+        rl_obs, rl_action, rl_action_mpc, rl_rew = (torch.stack(v) for v in (rl_obs, rl_action, rl_action_mpc, rl_rew))
+    # the reward that LED to the recorded observation: zeros first, the last step's is not recorded
+    return dict(mpc_obs=mpc_obs, rl_obs=rl_obs, mpc_action=mpc_action, rl_action=rl_action, rl_action_mpc=rl_action_mpc,
+                mpc_rew=torch.cat([zeros, mpc_rew[:-1]]), rl_rew=torch.cat([zeros, rl_rew[:-1]]))
+
+
+def mpc_rl_summary(rec):
+    """What plot_mpc_rl prints of a record (mpc/mpc_ipopt.py:303-311; the two timer lines apart), per agent and for both controllers:
+    the root mean squares over the steps of delta_y, delta_v and delta_phi - under the reference's names, which say "mse" - and the
+    reward sums.  rec: run_mpc's record; its observations hold v_x - 20 in column 0 already, so nothing is subtracted again (:286 reads a
+    recording whose column 0 was the speed).  Returns a dict of [n] float64 tensors."""
+    out = {}
+    for who in ('mpc', 'rl'):
+        obs = rec[who + '_obs'].double()
+        for name, col in (('delta_y', 3), ('delta_v', 0), ('delta_phi', 4)):
+            out['%s_%s_mse' % (who, name)] = obs[:, :, col].square().mean(0).sqrt()
+        out[who + '_rew_sum'] = rec[who + '_rew'].double().sum(0)
+    return out
