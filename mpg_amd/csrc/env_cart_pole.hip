@@ -19,6 +19,8 @@
 // (k_worker_sample_rollout_pendulum), mpg_env_rollout_pendulum, the learner's n real-env steps from a replay batch in one launch
 // (k_env_rollout_pendulum), and mpg_eval_rollout_pendulum, an evaluation's steps with their trajectory in one launch
 // (k_eval_rollout_pendulum).
+#include <type_traits>
+
 #include "env_internal.h"
 
 // The worker's policy pass rides in the one-launch worker sample (k_worker_rollout_pendulum, below).  The network engine is compiled
@@ -28,16 +30,23 @@
 #pragma clang fp contract(fast)
 #include "mlp_core.h"
 #include "gauss_head.h"
+#include "policy_pass.h"
 
-// worker_policy's load / pass / explore / report (env_path_tracking.hip) for the pendulum's policy: four inputs, ONE used output of the
-// two the network has (mean | log-std) - siblings, not a generalisation: the PathTracking kernels' code stays as it is.  The used
-// output of row `row` is formed by lane `row` of wave 0, the lane that holds the row's agent (S4, one lane per agent), so the action
-// goes from the pass to the noise to the env step in a register.
-namespace cp_worker_policy {
+// The pieces of policy_pass.h for the pendulum's policy: four inputs and the network's two outputs (mean | log-std).  OU = 1, the
+// deterministic worker: ONE used output; the used output of row `row` is formed by lane `row` of wave 0, the lane that holds the row's
+// agent (S4, one lane per agent), so the action goes from the pass to the noise to the env step in a register.  OU = 2, the
+// tanh-squashed Gaussian policy: BOTH outputs as policy_logits launches them for mpg_policy_sample_squashed - k_forward<4, 2, PK, 1>: no
+// action range on the logits, and the linear output only (gauss::squash_refusal leaves no other) - then the row's element of the
+// standard-normal stream and gauss::squash_row itself.  The two logits of row `row` are formed by lanes 2 row and 2 row + 1 of wave 0
+// and go through sLogit [16][2] to lane `row`: LDS is in order within a wave.
+// gauss_head.h is included above, under this block's contraction rule, as learner_api.hip compiles it; of what squash_row calls for the
+// ACTION - the double-precision exp of sigma_of and tanhf - the expansion does not depend on the translation unit's own mode (the
+// instructions of both were compared under the two modes: DESIGN.md section 7 f11), and the log-density's expf / log1pf are dead here.
+namespace cp_policy {
 using namespace mlp;
-constexpr int IN = 4, OU = 1, XSW = xs_of<IN>(), OS = out_stride<OU>();
+constexpr int IN = 4;
 
-struct Args {
+struct Args {                  // OU = 1
     const float* params;       // policy network, Keras order
     const float* pack;         // nullable: packed forward image of W2 (weight cache)
     int* status;               // nullable: MPG_STATUS_* word of the caller
@@ -46,46 +55,50 @@ struct Args {
     uint32_t k0, k1, c1, c2;   // exploration-noise key and the counter of iteration 0
     float scale[IN];           // obs_scale
 };
+struct SampleArgs {            // OU = 2
+    const float* params;
+    const float* pack;
+    int* status;
+    float range, log_r;        // the action range and its logarithm (gauss::log_range)
+    uint32_t k0, k1, c1, c2;   // the draw's key and the counter of iteration 0
+    float scale[IN];
+};
+template <int OU> struct args_of { typedef Args type; };
+template <> struct args_of<2> { typedef SampleArgs type; };
+template <class A>
+__device__ __forceinline__ constexpr int obs_dim_of(const A&) { return IN; }
 
-__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * XSW + NWAVE * GROUP * OS; }
+template <int OU>
+__host__ __device__ constexpr int smem_floats() { return policy_pass::smem_floats<IN, OU>(); }
 
-// the policy's registers, once
-template <bool PK>
-__device__ __forceinline__ void load(const Args& a, const Lane& L, float (&w2)[128], SmallRegs<IN, OU>& r, float& b3v) {
-    const Net net = make_net(a.params, IN, 2);
-    b3v = 0.f;
-    if (threadIdx.x < GROUP * OU) b3v = net.b3[0];
-    load_small<IN, OU>(net, L, r);
-    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-}
-// One evaluation on the group's observations sObs [16][4] in LDS: k_forward<4, 1, PK, 1> (mlp_kernels.hip) for unit g as
-// mpg_policy_action launches it - the same single float32 product with obs_scale, the same device functions on the same operands in
-// the same order, the same row_poison - WITHOUT the noise and the NaN test of the action (explore, below).  Returns row
-// threadIdx.x's action on the lanes threadIdx.x < 16 (0 beyond `rows` and on every other lane).  zmax / saw_nan accumulate over the
-// passes.  Starts with the caller's LDS in order (a workgroup barrier behind the writes of sObs).
-__device__ __forceinline__ float pass(const Args& a, int rows, long g, const float* sObs, float* smem, const Lane& L, const float (&w2)[128],
-                                      const SmallRegs<IN, OU>& r, float b3v, float& zmax, bool& saw_nan) {
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
-    if (threadIdx.x < GROUP * XSW) {           // (columns 4 .. 7 and the rows beyond `rows` stay zero)
-        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
-        float xv = 0.f;
-        if (g * GROUP + row < rows && i < IN) xv = sObs[row * IN + i] * a.scale[i];
-        saw_nan |= xv != xv;
-        sX[threadIdx.x] = xv;
-    }
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+// One evaluation on the group's observations sObs [16][4] in LDS (policy_pass::stage): k_forward<4, OU, PK, 1> for unit g.
+// OU = 1: as mpg_policy_action launches it, WITHOUT the noise and the NaN test of the action (explore, below); returns row
+// threadIdx.x's action on the lanes threadIdx.x < 16 (0 beyond `rows` and on every other lane).
+// OU = 2: with the NaN test of the logits, which it leaves in sLogit [16][2] (0 beyond `rows`), written by wave 0's own lanes.
+template <int OU>
+__device__ __forceinline__ float pass(const typename args_of<OU>::type& a, int rows, long g, const float* sObs, float* smem, float* sLogit,
+                                      const Lane& L, const float (&w2)[128], const SmallRegs<IN, OU>& r, float b3v, float& zmax,
+                                      bool& saw_nan) {
+    static_assert(OU == 1 || OU == 2, "the used output, or both logits");
+    constexpr int OS = out_stride<OU>();
+    const float pz = policy_pass::stage<IN, OU>(a, rows, g, sObs, smem, L, w2, r, zmax, saw_nan);
     const int tid = threadIdx.x;
     float y = 0.f;
-    if (tid < GROUP * OU && g * GROUP + tid < rows) {
-        float z = out_preact<OS>(sPart, b3v, tid, 0);
-        y = a.out_tanh ? a.out_scale * tanhf(z) : z;
-        y += pz;
+    if constexpr (OU == 1) {
+        if (tid < GROUP * OU && g * GROUP + tid < rows) {
+            float z = out_preact<OS>(policy_pass::part_of<IN>(smem), b3v, tid, 0);
+            y = a.out_tanh ? a.out_scale * tanhf(z) : z;
+            y += pz;
+        }
+    } else if (tid < GROUP * OU) {
+        const int row = tid / OU, o = tid % OU;
+        if (g * GROUP + row < rows) {
+            y = out_preact<OS>(policy_pass::part_of<IN>(smem), b3v, row, o);
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sLogit[tid] = y;
+        __builtin_amdgcn_wave_barrier();
     }
     return y;
 }
@@ -99,84 +112,10 @@ __device__ __forceinline__ float explore(float y, float sigma, long gr, uint32_t
     saw_nan |= y != y;
     return y;
 }
-__device__ __forceinline__ void report(const Args& a, float zmax, bool saw_nan) {
-    report_activation_range(a.status, zmax);
-    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
-}
-}  // namespace cp_worker_policy
-
-// The same for the tanh-squashed Gaussian policy (k_worker_sample_rollout_pendulum, below): BOTH outputs of the network (mean | log-std)
-// as policy_logits launches them for mpg_policy_sample_squashed - k_forward<4, 2, PK, 1>: no action range on the logits, and the linear
-// output only (gauss::squash_refusal leaves no other) - then the row's element of the standard-normal stream and gauss::squash_row
-// itself.  A sibling of cp_worker_policy, not a generalisation: that namespace's kernels keep their code.  The two logits of row
-// `row` are formed by lanes 2 row and 2 row + 1 of wave 0 and go through sLogit [16][2] to lane `row`, the lane that holds the row's
-// agent: LDS is in order within a wave.
-// gauss_head.h is included above, under this block's contraction rule, as learner_api.hip compiles it; of what squash_row calls for the
-// ACTION - the double-precision exp of sigma_of and tanhf - the expansion does not depend on the translation unit's own mode (the
-// instructions of both were compared under the two modes: DESIGN.md section 7 f11), and the log-density's expf / log1pf are dead here.
-namespace cp_sample_policy {
-using namespace mlp;
-constexpr int IN = 4, OU = 2, XSW = xs_of<IN>(), OS = out_stride<OU>();
-static_assert(GROUP * OU <= 64, "the two logits of every row of a group are formed by one wave");
-
-struct Args {
-    const float* params;       // policy network, Keras order
-    const float* pack;         // nullable: packed forward image of W2 (weight cache)
-    int* status;               // nullable: MPG_STATUS_* word of the caller
-    float range, log_r;        // the action range and its logarithm (gauss::log_range)
-    uint32_t k0, k1, c1, c2;   // the draw's key and the counter of iteration 0
-    float scale[IN];           // obs_scale
-};
-
-__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * XSW + NWAVE * GROUP * OS; }
-
-// the policy's registers, once
-template <bool PK>
-__device__ __forceinline__ void load(const Args& a, const Lane& L, float (&w2)[128], SmallRegs<IN, OU>& r, float& b3v) {
-    const Net net = make_net(a.params, IN, OU);
-    b3v = 0.f;
-    if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
-    load_small<IN, OU>(net, L, r);
-    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-}
-// One evaluation on the group's observations sObs [16][4] in LDS: k_forward<4, 2, PK, 1> for unit g - the same single float32 product
-// with obs_scale, the same device functions on the same operands in the same order, the same row_poison, zmax and NaN test of the
-// logits - leaving the logits in sLogit [16][2] (0 beyond `rows`), written by wave 0's own lanes.  zmax / saw_nan accumulate over
-// the passes.  Starts with the caller's LDS in order (a workgroup barrier behind the writes of sObs).
-__device__ __forceinline__ void pass(const Args& a, int rows, long g, const float* sObs, float* smem, float* sLogit, const Lane& L,
-                                     const float (&w2)[128], const SmallRegs<IN, OU>& r, float b3v, float& zmax, bool& saw_nan) {
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
-    if (threadIdx.x < GROUP * XSW) {           // (columns 4 .. 7 and the rows beyond `rows` stay zero)
-        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
-        float xv = 0.f;
-        if (g * GROUP + row < rows && i < IN) xv = sObs[row * IN + i] * a.scale[i];
-        saw_nan |= xv != xv;
-        sX[threadIdx.x] = xv;
-    }
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
-    const int tid = threadIdx.x;
-    if (tid < GROUP * OU) {
-        const int row = tid / OU, o = tid % OU;
-        float y = 0.f;
-        if (g * GROUP + row < rows) {
-            y = out_preact<OS>(sPart, b3v, row, o);
-            y += pz;
-            saw_nan |= y != y;
-        }
-        sLogit[tid] = y;
-        __builtin_amdgcn_wave_barrier();
-    }
-}
 // Row gr's action from its logits l[2]: element gr of the stream mpg_normal_fill(n, key, counter (c1, c2)) writes - Philox block gr / 4,
 // pair (gr / 2) % 2, the even or the odd element of the pair - and k_row_sums<SquashRow>'s row body on it.  The log-density is not
 // kept: the worker discards it and the ring has no column for it.
-__device__ __forceinline__ float sample(const Args& a, const float* l, int gr, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2) {
+__device__ __forceinline__ float sample(const SampleArgs& a, const float* l, int gr, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2) {
     float z_even, z_odd;
     gauss::normal_pair((uint32_t)gr >> 2, (gr >> 1) & 1, k0, k1, c1, c2, z_even, z_odd);
     const float eps = (gr & 1) ? z_odd : z_even;
@@ -184,11 +123,7 @@ __device__ __forceinline__ float sample(const Args& a, const float* l, int gr, u
     gauss::squash_row(1, a.range, a.log_r, l, &eps, &act);
     return act;
 }
-__device__ __forceinline__ void report(const Args& a, float zmax, bool saw_nan) {
-    report_activation_range(a.status, zmax);
-    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
-}
-}  // namespace cp_sample_policy
+}  // namespace cp_policy
 #pragma clang fp contract(off)
 
 namespace {
@@ -329,39 +264,59 @@ __global__ void __launch_bounds__(64) k_cp_step_store_reset(int n, float* __rest
     write_obs(obs_out, i, s);
 }
 
-// k_worker_rollout_pendulum (below): what the env lanes need of the launch's arguments once per iteration.  They rest in LDS and are
-// read where they are used, as k_worker_rollout's do (env_path_tracking.hip): held in scalar registers for the whole loop beside the
-// policy's arguments and the Philox key schedules derived from them, eight of them were spilled (tools/kernel_resources.py).
+// ---- the resident kernels: the plan of policy_pass.h with lanes 0 .. 15 of wave 0 as the env lanes, one whole agent (S4) each ---------
+// The observations go from those lanes to the policy pass through LDS between workgroup barriers; the action comes back in a register.
+// Unlike the path-tracking env's, this env's `done` is real: in the worker rollouts an agent lives in its lane's registers across many
+// iterations, falls, is re-drawn keyed (env key, env counter + it) and goes on.
+
+// The prologue of the kernels that start from the env's own state block, behind the policy's registers: the lane's agent (env lanes
+// only), and the group's rows of obs_io (16 x 4 floats) into sObs.
+__device__ __forceinline__ void resident_prologue(S4& s, bool env_lane, int n, int g0, int i, const float* st, const float* obs_io,
+                                                  float* sObs) {
+    if (env_lane) s = load(st, n, i);
+    const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
+    if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
+}
+
+// What the env lanes need of a worker rollout's arguments once per iteration.  They rest in LDS and are read where they are used, as
+// k_worker_rollout's do (env_path_tracking.hip): held in scalar registers for the whole loop beside the policy's arguments and the
+// Philox key schedules derived from them, eight of them were spilled (tools/kernel_resources.py).
 struct CpRolloutEnvArgs {
     RingPtrs ring;
     float *st, *obs_io, *act_out;
     uint8_t* done_out;
-    uint32_t k0, k1, nk0, nk1;     // env key, noise key
-    uint64_t env_ctr, noise_ctr;   // the counters of iteration 0
+    uint32_t k0, k1, pk0, pk1;     // env key, the policy's key (exploration noise or draw)
+    uint64_t env_ctr, policy_ctr;  // the counters of iteration 0, carried as 64-bit sums
     uint32_t capacity;
+    template <class PA>
+    __device__ __forceinline__ void park(const PA& pa, float* st_, float* obs_io_, float* act_out_, const RingPtrs& ring_, int capacity_,
+                                         uint32_t k0_, uint32_t k1_, uint32_t c1, uint32_t c2, uint8_t* done_out_) {
+        ring = ring_;
+        st = st_; obs_io = obs_io_; act_out = act_out_; done_out = done_out_;
+        k0 = k0_; k1 = k1_; pk0 = pa.k0; pk1 = pa.k1;
+        env_ctr = ((uint64_t)c2 << 32) | c1;
+        policy_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        capacity = (uint32_t)capacity_;
+    }
 };
 
 // OffPolicyWorker.sample's `iters` iterations (worker.py:91-119: policy -> + N(0, sigma) -> env.step -> ring -> env.reset) for the
 // pendulum in ONE launch: `iters` consecutive pairs of mpg_policy_action (k_forward<4, 1, PK, 1>) and k_cp_step_store_reset with the
-// noise and env counters and the ring position advancing by one / one / n per pair.  Each of those 2 * iters launches fetches the
-// policy's weights or the agents' state again; here one 512-thread workgroup owns a 16-agent group for all iterations in the form of
-// k_worker_rollout (env_path_tracking.hip): the policy's registers are loaded once, lanes 0 .. 15 of wave 0 read one agent each (S4)
-// and keep it in registers, and per iteration the observations go from those lanes to the policy pass through LDS between workgroup
-// barriers; the action comes back in a register (cp_worker_policy).  Unlike the path-tracking env's, this env's `done` is real: an
-// agent lives in its lane's registers across many iterations, falls, is re-drawn keyed (env key, env counter + it) and goes on.  Per
-// iteration `it` an env lane does what k_cp_step_store_reset does, in its order: ring row (obs, act) at slot (next_idx + it * n + i) %
-// capacity, step_agent, (obs2, rew, done), reset_agent if done, and the next observation - into sObs instead of obs_out.  State,
-// obs_io, act_out and done_out are written after the LAST iteration only (what the chain leaves behind) and the status word is
-// reported once.  Global memory is read in the prologue only (weights, state, obs_io) and written, never read back; (noise / env)
-// c1, c2: the counters of iteration 0, carried as 64-bit sums.  The host refuses iters * n > capacity: two iterations would write one
-// ring slot from different workgroups.  Everything the chain leaves is bit-identical: the same device functions on the same operands
-// in the same order (tests/test_worker_rollout_pendulum_gpu.py).
+// noise and env counters and the ring position advancing by one / one / n per pair, each of which fetches the policy's weights or the
+// agents' state again.  Per iteration `it` an env lane does what k_cp_step_store_reset does, in its order: ring row (obs, act) at slot
+// (next_idx + it * n + i) % capacity, step_agent, (obs2, rew, done), reset_agent if done, and the next observation - into sObs instead
+// of obs_out.  (The two worker rollouts each carry these statements: moved into one forced-inline function, the compiler merged the
+// two stores of the next observation into one flat store and the kernels' instructions changed.)  State, obs_io, act_out and done_out
+// are written after the LAST iteration only (what the chain leaves behind).
+// (noise / env) c1, c2: the counters of iteration 0.  The host refuses iters * n > capacity: two iterations would write one ring slot
+// from different workgroups.  Everything the chain leaves is bit-identical: the same device functions on the same operands in the same
+// order (tests/test_worker_rollout_pendulum_gpu.py).
 template <bool PK>
-__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(const cp_worker_policy::Args pa, int n, int iters,
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(const cp_policy::Args pa, int n, int iters,
                                                                               float* st, float* obs_io, float* act_out, RingPtrs ring,
                                                                               int capacity, int next_idx, uint32_t k0, uint32_t k1,
                                                                               uint32_t c1, uint32_t c2, uint8_t* done_out) {
-    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float smem[cp_policy::smem_floats<1>()];
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
     __shared__ CpRolloutEnvArgs sArg;
     const mlp::Lane L;
@@ -369,33 +324,21 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(con
     mlp::SmallRegs<4, 1> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
-    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    policy_pass::load<PK, 4, 1>(pa, 2, L, w2, r, b3v);
     const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
     const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
     S4 s = {};
-    if (env_lane) s = load(st, n, i);
-    {   // the group's rows of obs_io (16 x 4 floats)
-        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
-    }
-    if (threadIdx.x == 0) {
-        sArg.ring = ring;
-        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
-        sArg.k0 = k0; sArg.k1 = k1; sArg.nk0 = pa.k0; sArg.nk1 = pa.k1;
-        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
-        sArg.noise_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
-        sArg.capacity = (uint32_t)capacity;
-    }
-    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    resident_prologue(s, env_lane, n, g0, i, st, obs_io, sObs);
+    if (threadIdx.x == 0) sArg.park(pa, st, obs_io, act_out, ring, capacity, k0, k1, c1, c2, done_out);
+    // the agent's ring slot: (next_idx + it * n + i) % capacity
     uint32_t slot = env_lane ? (uint32_t)(((long)next_idx + i) % capacity) : 0u;
     for (int it = 0; it < iters; ++it) {
         const bool last = it == iters - 1;
         mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
-        float a = cp_worker_policy::pass(pa, n, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+        float a = cp_policy::pass<1>(pa, n, blockIdx.x, sObs, smem, nullptr, L, w2, r, b3v, zmax, saw_nan);
         if (!env_lane) continue;
-        const uint64_t nc = sArg.noise_ctr + (uint64_t)it;
-        a = cp_worker_policy::explore(a, pa.sigma, i, sArg.nk0, sArg.nk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
+        const uint64_t nc = sArg.policy_ctr + (uint64_t)it;
+        a = cp_policy::explore(a, pa.sigma, i, sArg.pk0, sArg.pk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
         write_obs(sArg.ring.obs, slot, s);               // obs before the step
         sArg.ring.act[slot] = a;
         const StepOut o = step_agent(s, a);
@@ -418,34 +361,30 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout_pendulum(con
         slot += (uint32_t)n;
         if (slot >= sArg.capacity) slot -= sArg.capacity;
     }
-    cp_worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
 // MPGLearner.sample (mpg_learner.py:85-105) for the pendulum in ONE launch: from obs0 take n real-env steps, the first with the replay
 // action act0, the later ones with the ONLINE policy's deterministic action; `done` is ignored and nothing is reset.  The stand-alone
 // chain is mpg_env_reset_from_obs + n x mpg_env_step + (n - 1) x mpg_policy_action (k_forward<4, 1, PK, 1>, sigma 0) = 2 n launches,
-// every policy launch fetching the weights again and every env launch the state.  Here one 512-thread workgroup owns a 16-row group
-// for all n steps in the form of k_worker_rollout_pendulum (a sibling, not a generalisation: that kernel's code stays as it is): the
-// policy's registers are loaded once, lanes 0 .. 15 of wave 0 form their row's state from obs0 as k_cp_reset_from_obs does (S4, in
-// registers), and per step the observations go from those lanes to the policy pass through LDS between workgroup barriers; the
-// action comes back in a register.  The policy is NOT evaluated at step 0 (n - 1 passes, as in the chain, so the status word sees
-// what the chain's n - 1 policy launches report and nothing of obs0 itself).  Rewards are written every step at rewards[t * rows + row]
-// (no per-lane reward array, no bound on n from it), last_obs after the last step; global memory is read in the prologue only
-// (weights, obs0, act0) and written, never read back.  Rewards, last observations and the status word are bit-identical to the chain's:
-// the same device functions on the same operands in the same order (tests/test_env_rollout_pendulum_gpu.py).
+// every policy launch fetching the weights again and every env launch the state.  Here the env lanes form their row's state from obs0
+// as k_cp_reset_from_obs does.  The policy is NOT evaluated at step 0 (n - 1 passes, as in the chain, so the status word sees what
+// the chain's n - 1 policy launches report and nothing of obs0 itself).  Rewards are written every step at rewards[t * rows + row] (no
+// per-lane reward array, no bound on n from it), last_obs after the last step; global memory is read in the prologue only (weights,
+// obs0, act0).  Rewards, last observations and the status word are bit-identical to the chain's: the same device functions on the same
+// operands in the same order (tests/test_env_rollout_pendulum_gpu.py).
 template <bool PK>
-__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout_pendulum(const cp_worker_policy::Args pa, int rows, int n,
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout_pendulum(const cp_policy::Args pa, int rows, int n,
                                                                            const float* __restrict__ obs0, const float* __restrict__ act0,
                                                                            float* __restrict__ rewards, float* __restrict__ last_obs) {
-    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float smem[cp_policy::smem_floats<1>()];
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
     const mlp::Lane L;
     float w2[128];
     mlp::SmallRegs<4, 1> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
-    // the env lanes: lanes 0 .. 15 of wave 0, one whole row each
+    policy_pass::load<PK, 4, 1>(pa, 2, L, w2, r, b3v);
     const int i = blockIdx.x * mlp::GROUP + (int)threadIdx.x;
     const bool env_lane = threadIdx.x < mlp::GROUP && i < rows;
     S4 s = {};
@@ -458,78 +397,52 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout_pendulum(const 
     for (int t = 0; t < n; ++t) {
         if (t > 0) {
             mlp::lds_barrier();                          // sObs of step t - 1 is complete (and the previous pass's LDS is free)
-            a = cp_worker_policy::pass(pa, rows, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+            a = cp_policy::pass<1>(pa, rows, blockIdx.x, sObs, smem, nullptr, L, w2, r, b3v, zmax, saw_nan);
         }
         if (!env_lane) continue;
-        if (t > 0) a = cp_worker_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
+        if (t > 0) a = cp_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
         const StepOut o = step_agent(s, a);
         rewards[(size_t)t * rows + i] = o.reward;
         if (t == n - 1) write_obs(last_obs, i, s);
         else write_obs(sObs, threadIdx.x, s);
     }
-    cp_worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
-// k_worker_sample_rollout_pendulum (below): CpRolloutEnvArgs for the squashed policy's launch - the draw's key and counter in the place
-// of the exploration noise's, and the head's two constants
-struct CpSampleRolloutEnvArgs {
-    RingPtrs ring;
-    float *st, *obs_io, *act_out;
-    uint8_t* done_out;
-    uint32_t k0, k1, sk0, sk1;     // env key, draw key
-    uint64_t env_ctr, sample_ctr;  // the counters of iteration 0
-    uint32_t capacity;
-};
-
-// The same `iters` iterations for the tanh-squashed Gaussian policy (SAC with an action range, worker.py:96: the action IS the sample):
-// `iters` consecutive triples of mpg_normal_fill(n, sample key, sample counter + it), mpg_policy_sample_squashed (k_forward<4, 2, PK, 1>
-// and k_row_sums<SquashRow>) and k_cp_step_store_reset in ONE launch.  A sibling of k_worker_rollout_pendulum with its residency plan:
-// one 512-thread workgroup per 16-agent group, the policy's registers loaded once, one agent (S4) per lane 0 .. 15 of wave 0 across the
-// iterations, the observations to the pass through LDS between workgroup barriers, global memory read in the prologue only, state /
-// obs_io / act_out / done_out written after the LAST iteration only, the env lanes' arguments in LDS, the status word reported once.
-// New between the pass and the env step: the row's two logits come to its env lane through sLogit, the lane draws element i of the
-// iteration's stream and forms a = range * tanh(mean + sigma * eps) (cp_sample_policy::sample), which goes to step_agent in a register.
+// The worker rollout's `iters` iterations for the tanh-squashed Gaussian policy (SAC with an action range, worker.py:96: the action IS
+// the sample): `iters` consecutive triples of mpg_normal_fill(n, sample key, sample counter + it), mpg_policy_sample_squashed
+// (k_forward<4, 2, PK, 1> and k_row_sums<SquashRow>) and k_cp_step_store_reset in ONE launch.  Between the pass and the env step the
+// row's two logits come to its env lane through sLogit, the lane draws element i of the iteration's stream and forms a = range *
+// tanh(mean + sigma * eps) (cp_policy::sample), which goes to step_agent in a register.
 template <bool PK>
-__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout_pendulum(const cp_sample_policy::Args pa, int n, int iters,
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout_pendulum(const cp_policy::SampleArgs pa, int n, int iters,
                                                                                      float* st, float* obs_io, float* act_out, RingPtrs ring,
                                                                                      int capacity, int next_idx, uint32_t k0, uint32_t k1,
                                                                                      uint32_t c1, uint32_t c2, uint8_t* done_out) {
-    __shared__ __attribute__((aligned(16))) float smem[cp_sample_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float smem[cp_policy::smem_floats<2>()];
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
     __shared__ __attribute__((aligned(16))) float sLogit[mlp::GROUP * 2];
-    __shared__ CpSampleRolloutEnvArgs sArg;
+    __shared__ CpRolloutEnvArgs sArg;
     const mlp::Lane L;
     float w2[128];
     mlp::SmallRegs<4, 2> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    cp_sample_policy::load<PK>(pa, L, w2, r, b3v);
-    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    policy_pass::load<PK, 4, 2>(pa, 2, L, w2, r, b3v);
     const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
     const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
     S4 s = {};
-    if (env_lane) s = load(st, n, i);
-    {   // the group's rows of obs_io (16 x 4 floats)
-        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
-    }
-    if (threadIdx.x == 0) {
-        sArg.ring = ring;
-        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
-        sArg.k0 = k0; sArg.k1 = k1; sArg.sk0 = pa.k0; sArg.sk1 = pa.k1;
-        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
-        sArg.sample_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
-        sArg.capacity = (uint32_t)capacity;
-    }
-    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    resident_prologue(s, env_lane, n, g0, i, st, obs_io, sObs);
+    if (threadIdx.x == 0) sArg.park(pa, st, obs_io, act_out, ring, capacity, k0, k1, c1, c2, done_out);
+    // the agent's ring slot: (next_idx + it * n + i) % capacity
     uint32_t slot = env_lane ? (uint32_t)(((long)next_idx + i) % capacity) : 0u;
     for (int it = 0; it < iters; ++it) {
         const bool last = it == iters - 1;
         mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
-        cp_sample_policy::pass(pa, n, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
+        cp_policy::pass<2>(pa, n, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
         if (!env_lane) continue;
-        const uint64_t sc = sArg.sample_ctr + (uint64_t)it;
-        const float a = cp_sample_policy::sample(pa, sLogit + 2 * threadIdx.x, i, sArg.sk0, sArg.sk1, (uint32_t)sc, (uint32_t)(sc >> 32));
+        const uint64_t sc = sArg.policy_ctr + (uint64_t)it;
+        const float a = cp_policy::sample(pa, sLogit + 2 * threadIdx.x, i, sArg.pk0, sArg.pk1, (uint32_t)sc, (uint32_t)(sc >> 32));
         write_obs(sArg.ring.obs, slot, s);               // obs before the step
         sArg.ring.act[slot] = a;
         const StepOut o = step_agent(s, a);
@@ -552,7 +465,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout_pendu
         slot += (uint32_t)n;
         if (slot >= sArg.capacity) slot -= sArg.capacity;
     }
-    cp_sample_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
 // k_eval_rollout_pendulum (below): the env lanes' pointers, resting in LDS as CpRolloutEnvArgs does and for its reason
@@ -563,20 +476,17 @@ struct CpEvalEnvArgs {
 
 // Evaluator.run_n_episodes_parallel's loop (evaluator.py:132-139: compute_mode -> env.step, `done` not consulted, nothing reset) for the
 // pendulum in ONE launch: `steps` consecutive pairs of mpg_policy_action (k_forward<4, 1, PK, 1>, sigma 0) and mpg_env_step = 2 * steps
-// launches.  A sibling of k_env_rollout_pendulum with its residency plan: one 512-thread workgroup per 16-agent group, the policy's
-// registers loaded once, lanes 0 .. 15 of wave 0 hold one agent (S4) each across the steps, the observations go to the pass through LDS
-// between workgroup barriers and the action comes back in a register.  Unlike that kernel the agents come from the env's own state
-// block and the first observations from obs_io, the policy is evaluated at step 0 too (`steps` passes), and the trajectory is recorded:
-// per step t the observation BEFORE the step (out of sObs) at obs_traj[(t n + i) 4 ..], the action - unclipped, the env clips its own
-// copy - at act_traj[t n + i] and the reward at rew_traj[t n + i].  An agent beyond the done bound keeps stepping, as in the chain.
-// State, obs_io and the done flags (nullable) are written after the LAST step only; global memory is read in the prologue only (weights,
-// state, obs_io) and written, never read back; the status word is reported once.  Bit-identical to the chain: the same device functions
-// on the same operands in the same order (tests/test_eval_rollout_gpu.py).
+// launches.  Unlike k_env_rollout_pendulum the agents come from the env's own state block and the first observations from obs_io, the
+// policy is evaluated at step 0 too (`steps` passes), and the trajectory is recorded: per step t the observation BEFORE the step (out
+// of sObs) at obs_traj[(t n + i) 4 ..], the action - unclipped, the env clips its own copy - at act_traj[t n + i] and the reward at
+// rew_traj[t n + i].  An agent beyond the done bound keeps stepping, as in the chain.  State, obs_io and the done flags (nullable) are
+// written after the LAST step only.  Bit-identical to the chain: the same device functions on the same operands in the same order
+// (tests/test_eval_rollout_gpu.py).
 template <bool PK>
-__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout_pendulum(const cp_worker_policy::Args pa, int n, int steps, float* st,
+__global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout_pendulum(const cp_policy::Args pa, int n, int steps, float* st,
                                                                             float* obs_io, float* obs_traj, float* act_traj,
                                                                             float* rew_traj, uint8_t* done_out) {
-    __shared__ __attribute__((aligned(16))) float smem[cp_worker_policy::smem_floats()];
+    __shared__ __attribute__((aligned(16))) float smem[cp_policy::smem_floats<1>()];
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 4];
     __shared__ CpEvalEnvArgs sArg;
     const mlp::Lane L;
@@ -584,25 +494,20 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout_pendulum(const
     mlp::SmallRegs<4, 1> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    cp_worker_policy::load<PK>(pa, L, w2, r, b3v);
-    // the env lanes: lanes 0 .. 15 of wave 0, one whole agent each
+    policy_pass::load<PK, 4, 1>(pa, 2, L, w2, r, b3v);
     const int g0 = blockIdx.x * mlp::GROUP, i = g0 + (int)threadIdx.x;
     const bool env_lane = threadIdx.x < mlp::GROUP && i < n;
     S4 s = {};
-    if (env_lane) s = load(st, n, i);
-    {   // the group's rows of obs_io (16 x 4 floats)
-        const int live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * 4;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * 4 + threadIdx.x];
-    }
+    resident_prologue(s, env_lane, n, g0, i, st, obs_io, sObs);
     if (threadIdx.x == 0) {
         sArg.st = st; sArg.obs_io = obs_io; sArg.obs_traj = obs_traj; sArg.act_traj = act_traj; sArg.rew_traj = rew_traj;
         sArg.done_out = done_out;
     }
     for (int t = 0; t < steps; ++t) {
         mlp::lds_barrier();                              // sObs of this step is complete (and the previous pass's LDS is free)
-        float a = cp_worker_policy::pass(pa, n, blockIdx.x, sObs, smem, L, w2, r, b3v, zmax, saw_nan);
+        float a = cp_policy::pass<1>(pa, n, blockIdx.x, sObs, smem, nullptr, L, w2, r, b3v, zmax, saw_nan);
         if (!env_lane) continue;
-        a = cp_worker_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
+        a = cp_policy::explore(a, 0.f, i, 0u, 0u, 0u, 0u, saw_nan);   // sigma 0: k_forward's NaN test of the action
         const size_t row = (size_t)t * (size_t)n + (size_t)i;
         reinterpret_cast<float4*>(sArg.obs_traj)[row] = reinterpret_cast<const float4*>(sObs)[threadIdx.x];   // obs before the step
         sArg.act_traj[row] = a;
@@ -617,7 +522,30 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout_pendulum(const
             write_obs(sObs, threadIdx.x, s);
         }
     }
-    cp_worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
+}
+
+// The policy arguments of a launch for OU used outputs - OU = 1: the output activation and the exploration noise; OU = 2: the squashed
+// head's constants, `seed` / `ctr` the draw's - and the instantiation that takes them: packed when the weight cache holds W2's image.
+// launch(std::bool_constant<PK>, pa) issues the entry point's kernel.
+template <int OU, class Launch>
+void with_policy_args(const mpg_cfg_t* cfg, const float* policy_params, float explore_sigma, uint64_t seed, uint64_t ctr, Launch&& launch) {
+    typename cp_policy::args_of<OU>::type pa;
+    pa.params = policy_params;
+    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
+    pa.status = mpg_status_of(cfg);
+    if constexpr (OU == 1) {
+        const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
+        pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
+        pa.out_scale = ranged ? cfg->action_range : 1.f;
+        pa.sigma = explore_sigma;
+    } else {
+        pa.range = cfg->action_range;
+        pa.log_r = gauss::log_range(cfg->action_range);
+    }
+    pa.k0 = (uint32_t)seed; pa.k1 = (uint32_t)(seed >> 32); pa.c1 = (uint32_t)ctr; pa.c2 = (uint32_t)(ctr >> 32);
+    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
+    if (pa.pack) launch(std::true_type{}, pa); else launch(std::false_type{}, pa);
 }
 
 }  // namespace
@@ -639,24 +567,12 @@ extern "C" int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* poli
     // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
                 "mpg_eval_rollout_pendulum: tanh policy with an action range");
-    cp_worker_policy::Args pa;
-    pa.params = policy_params;
-    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
-    pa.status = mpg_status_of(cfg);
-    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
-    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    pa.out_scale = ranged ? cfg->action_range : 1.f;
-    pa.sigma = 0.f;
-    pa.k0 = pa.k1 = pa.c1 = pa.c2 = 0u;
-    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-    if (pa.pack)
-        hipLaunchKernelGGL(k_eval_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj,
-                           act_traj, rew_traj, done_out);
-    else
-        hipLaunchKernelGGL(k_eval_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj,
-                           act_traj, rew_traj, done_out);
+    with_policy_args<1>(cfg, policy_params, 0.f, 0, 0, [&](auto pk, const auto& pa) {
+        hipLaunchKernelGGL(k_eval_rollout_pendulum<decltype(pk)::value>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io,
+                           obs_traj, act_traj, rew_traj, done_out);
+    });
     MPG_CHECK_LAUNCH("mpg_eval_rollout_pendulum");
     return MPG_OK;
 }
@@ -687,25 +603,13 @@ extern "C" int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* po
     // two iterations would write one slot from different workgroups with no order between them
     MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d",
                 (long)iters * n, capacity);
-    cp_worker_policy::Args pa;
-    pa.params = policy_params;
-    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
-    pa.status = mpg_status_of(cfg);
-    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
-    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    pa.out_scale = ranged ? cfg->action_range : 1.f;
-    pa.sigma = explore_sigma;
-    pa.k0 = (uint32_t)noise_seed; pa.k1 = (uint32_t)(noise_seed >> 32); pa.c1 = (uint32_t)noise_ctr; pa.c2 = (uint32_t)(noise_ctr >> 32);
-    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-    mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-    if (pa.pack)
-        hipLaunchKernelGGL(k_worker_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring,
-                           capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
-    else
-        hipLaunchKernelGGL(k_worker_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring,
-                           capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    with_policy_args<1>(cfg, policy_params, explore_sigma, noise_seed, noise_ctr, [&](auto pk, const auto& pa) {
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        hipLaunchKernelGGL(k_worker_rollout_pendulum<decltype(pk)::value>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io,
+                           act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_rollout_pendulum");
     return MPG_OK;
@@ -737,23 +641,13 @@ extern "C" int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const fl
     // two iterations would write one slot from different workgroups with no order between them
     MPG_REQUIRE((long)iters * n <= capacity,
                 "mpg_worker_sample_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d", (long)iters * n, capacity);
-    cp_sample_policy::Args pa;
-    pa.params = policy_params;
-    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
-    pa.status = mpg_status_of(cfg);
-    pa.range = cfg->action_range;
-    pa.log_r = gauss::log_range(cfg->action_range);
-    pa.k0 = (uint32_t)sample_seed; pa.k1 = (uint32_t)(sample_seed >> 32); pa.c1 = (uint32_t)sample_ctr; pa.c2 = (uint32_t)(sample_ctr >> 32);
-    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-    mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-    if (pa.pack)
-        hipLaunchKernelGGL(k_worker_sample_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out,
-                           ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
-    else
-        hipLaunchKernelGGL(k_worker_sample_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out,
-                           ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    with_policy_args<2>(cfg, policy_params, 0.f, sample_seed, sample_ctr, [&](auto pk, const auto& pa) {
+        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
+        hipLaunchKernelGGL(k_worker_sample_rollout_pendulum<decltype(pk)::value>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state,
+                           obs_io, act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_sample_rollout_pendulum");
     return MPG_OK;
@@ -776,22 +670,12 @@ extern "C" int mpg_env_rollout_pendulum(const mpg_cfg_t* cfg, const float* polic
     // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
                 "mpg_env_rollout_pendulum: tanh policy with an action range");
-    cp_worker_policy::Args pa;
-    pa.params = policy_params;
-    pa.pack = mlp::weight_cache_lookup(cfg, mlp::make_net(policy_params, 4, 2).W2, 0);
-    pa.status = mpg_status_of(cfg);
-    const bool ranged = cfg->action_range > 0.f;       // (as mpg_policy_action forms it: policy_out, host_glue.h)
-    pa.out_tanh = (cfg->policy_out_act == MPG_ACT_TANH || ranged) ? 1 : 0;
-    pa.out_scale = ranged ? cfg->action_range : 1.f;
-    pa.sigma = 0.f;
-    pa.k0 = pa.k1 = pa.c1 = pa.c2 = 0u;
-    for (int i = 0; i < 4; ++i) pa.scale[i] = cfg->obs_scale[i];
     const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-    if (pa.pack)
-        hipLaunchKernelGGL(k_env_rollout_pendulum<true>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs);
-    else
-        hipLaunchKernelGGL(k_env_rollout_pendulum<false>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs);
+    with_policy_args<1>(cfg, policy_params, 0.f, 0, 0, [&](auto pk, const auto& pa) {
+        hipLaunchKernelGGL(k_env_rollout_pendulum<decltype(pk)::value>, dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0,
+                           rewards, last_obs);
+    });
     MPG_CHECK_LAUNCH("mpg_env_rollout_pendulum");
     return MPG_OK;
 }

@@ -10,6 +10,8 @@
 // State block (opaque to callers): v_x, v_y, r, y, phi, x, delta_y, delta_phi.
 // Observations carry 6 + K entries, K = num_future_data look-ahead delta-y terms (path_tracking_env.py:385-402).
 // env_kind MPG_ENV_INVERTED_PENDULUM is dispatched to env_cart_pole.hip.
+#include <type_traits>
+
 #include "env_internal.h"
 
 // The worker's policy pass rides in the env launch (k_policy_step_store_reset, below).  The network engine is compiled here as
@@ -18,6 +20,7 @@
 #pragma clang fp contract(fast)
 #include "mlp_core.h"
 #include "gauss_head.h"
+#include "policy_pass.h"
 
 namespace worker_policy {
 using namespace mlp;
@@ -51,23 +54,46 @@ __device__ __forceinline__ int obs_dim_of(const WideArgs& a) { return a.obs_dim;
 
 // (OU: the used outputs the pass is built for - two: the deterministic action; four: the Gaussian head's logits)
 template <int IN, int OU = 2>
-__host__ __device__ constexpr int smem_floats() { return A_IMG + GROUP * xs_of<IN>() + NWAVE * GROUP * out_stride<OU>(); }
+__host__ __device__ constexpr int smem_floats() { return policy_pass::smem_floats<IN, OU>(); }
 
-// One 16-row group of mpg_policy_action: k_forward<6, 2, PK, 1> or k_forward<16, 2, PK, 1> (mlp_kernels.hip) for unit g - the same
-// device functions on the same operands in the same order, so the actions are bit-identical to the stand-alone launch's (tests:
-// native step driver == method-by-method path, tests/test_worker_wide.py).  The group's actions go to act_out (global) and to
-// sAct [16][2] for the env lanes of wave 0.
-template <bool PK, int IN>
-__device__ __forceinline__ void group(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g, float* smem,
-                                      float* sAct, float* __restrict__ act_out) {
-    static_assert(IN == 6 || IN == 16, "the worker launch is built for six-entry observations and for the 16-wide first layer");
-    constexpr int OU = 2, XSW = xs_of<IN>();
+// One evaluation on the group's observations sObs [16][od] in LDS (policy_pass::stage), the outputs - without noise - to sOut [16][OU]
+// (0 beyond `rows`), written by wave 0's own lanes: lane tid < 16 OU forms output tid % OU of row tid / OU.  OU = 2: the action, the
+// output activation under the action range.  OU = 4: the logits as policy_logits launches them - the output activation on all four
+// columns, no action range (a.out_scale is not read) - formed by lanes 4 row .. 4 row + 3, the lanes that step the row's agent.
+template <int IN, int OU>
+__device__ __forceinline__ void pass(const typename args_of<IN>::type& a, int rows, long g, const float* sObs, float* smem, float* sOut,
+                                     const Lane& L, const float (&w2)[128], const SmallRegs<IN, OU>& r, float b3v, float& zmax,
+                                     bool& saw_nan) {
+    static_assert(IN == 6 || IN == 16, "these launches are built for six-entry observations and for the 16-wide first layer");
+    static_assert(OU == 2 || GROUP * OU == 64, "the four logits of every row of a group are formed by one wave");
+    const float pz = policy_pass::stage<IN, OU>(a, rows, g, sObs, smem, L, w2, r, zmax, saw_nan);
+    const int tid = threadIdx.x;
+    if (tid < GROUP * OU) {
+        const int row = tid / OU, o = tid % OU;
+        float y = 0.f;
+        if (g * GROUP + row < rows) {
+            float z = out_preact<out_stride<OU>()>(policy_pass::part_of<IN>(smem), b3v, row, o);
+            if constexpr (OU == 2) y = a.out_tanh ? a.out_scale * tanhf(z) : z;
+            else y = a.out_tanh ? tanhf(z) : z;
+            y += pz;
+            saw_nan |= y != y;
+        }
+        sOut[tid] = y;
+    }
+}
+
+// The same pass up to the output partials for the kernels that run it ONCE (k_policy_step_store_reset,
+// k_policy_sample_step_store_reset): the observations come from global memory, and they are requested BEFORE the weight loads are
+// issued (the worker launch's latency is what bench.py times), so policy_pass::load's statements stand here around that fetch.  Leaves
+// the lane's bias and row_poison term for the caller's outputs; returns whether the lane's input was NaN.
+template <bool PK, int IN, int OU>
+__device__ __forceinline__ bool group_forward(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g,
+                                              float* smem, float& b3v, float& pz, float& zmax) {
+    constexpr int XSW = xs_of<IN>();
     const int od = obs_dim_of(a);              // a constant at IN = 6
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
+    float* sX = smem + A_IMG;
     const Lane L;
-    const Net net = make_net(a.params, od, 2 * OU);
+    const Net net = make_net(a.params, od, 4);
     float w2[128];
     SmallRegs<IN, OU> r;
     float xv = 0.f;
@@ -76,26 +102,31 @@ __device__ __forceinline__ void group(const typename args_of<IN>::type& a, int r
         const long gr = g * GROUP + row;
         if (gr < rows && i < od) xv = obs[gr * od + i] * a.scale[i];
     }
-    float b3v = 0.f;
+    b3v = 0.f;
     if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
-    float zmax = 0.f;
-    bool saw_nan = false;
     load_small<IN, OU>(net, L, r);
     if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-    saw_nan |= xv != xv;
+    const bool saw_nan = xv != xv;
     if (threadIdx.x < GROUP * XSW) sX[threadIdx.x] = xv;
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    pz = policy_pass::forward<IN, OU>(smem, L, w2, r, zmax);
+    return saw_nan;
+}
+
+// One 16-row group of mpg_policy_action (tests: native step driver == method-by-method path, tests/test_worker_wide.py).  The group's
+// actions, with the exploration noise, go to act_out (global) and to sAct [16][2] for the env lanes of wave 0.
+template <bool PK, int IN>
+__device__ __forceinline__ void group(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g, float* smem,
+                                      float* sAct, float* __restrict__ act_out) {
+    constexpr int OU = 2;
+    float b3v, pz, zmax = 0.f;
+    bool saw_nan = group_forward<PK, IN, OU>(a, rows, obs, g, smem, b3v, pz, zmax);
     const int tid = threadIdx.x;
     if (tid < GROUP * OU) {
         const int row = (tid / OU) % GROUP, o = tid % OU;
         const long gr = g * GROUP + row;
         float y = 0.f;
         if (gr < rows) {
-            float z = out_preact(sPart, b3v, row, o);
+            float z = out_preact(policy_pass::part_of<IN>(smem), b3v, row, o);
             y = a.out_tanh ? a.out_scale * tanhf(z) : z;
             y += pz;
             if (a.sigma > 0.f) {   // OffPolicyWorker.sample: action += N(0, sigma), worker.py:97-98
@@ -112,54 +143,24 @@ __device__ __forceinline__ void group(const typename args_of<IN>::type& a, int r
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
 
-// One 16-row group of mpg_policy_sample on the worker's own draw: k_forward<6, 4, PK, 1> or k_forward<16, 4, PK, 1> for unit g as
-// policy_logits launches it (the output activation on all four columns, no action range) - the same device functions on the same
-// operands in the same order, the same row_poison, activation-range and NaN reporting - and then k_row_sums<GaussRow>'s row body
-// (gauss::gauss_row) on eps = elements 2 gr, 2 gr + 1 of the stream mpg_normal_fill writes for (a.k0 .. a.c2).  The four logits
-// of a row are formed by lanes 4 row .. 4 row + 3 of wave 0 - the lanes that step the row's agent afterwards - and go through sLogit
-// [16][4] to the first of them, which draws, samples and leaves the action in act_out, the log-density in logp_out (nullable) and the
-// action in sAct [16][2] for the env lanes: LDS is in order within a wave.  a.sigma and a.out_scale are not read.
+// One 16-row group of mpg_policy_sample on the worker's own draw: the four logits of every row, then k_row_sums<GaussRow>'s row body
+// (gauss::gauss_row) on eps = elements 2 gr, 2 gr + 1 of the stream mpg_normal_fill writes for (a.k0 .. a.c2).  The logits go through
+// sLogit [16][4] to the first of the row's four lanes, which draws, samples and leaves the action in act_out, the log-density in
+// logp_out (nullable) and the action in sAct [16][2] for the env lanes: LDS is in order within a wave.  a.sigma is not read.
 template <bool PK, int IN>
 __device__ __forceinline__ void sample_group(const typename args_of<IN>::type& a, int rows, const float* __restrict__ obs, long g,
                                              float* smem, float* sLogit, float* sAct, float* __restrict__ act_out,
                                              float* __restrict__ logp_out) {
-    static_assert(IN == 6 || IN == 16, "the worker launch is built for six-entry observations and for the 16-wide first layer");
-    constexpr int OU = 4, XSW = xs_of<IN>(), OS = out_stride<OU>();
-    static_assert(GROUP * OU == 64, "the four logits of every row of a group are formed by one wave");
-    const int od = obs_dim_of(a);              // a constant at IN = 6
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
-    const Lane L;
-    const Net net = make_net(a.params, od, OU);
-    float w2[128];
-    SmallRegs<IN, OU> r;
-    float xv = 0.f;
-    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 stay zero)
-        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
-        const long gr = g * GROUP + row;
-        if (gr < rows && i < od) xv = obs[gr * od + i] * a.scale[i];
-    }
-    float b3v = 0.f;
-    if (threadIdx.x < GROUP * OU) b3v = net.b3[threadIdx.x % OU];
-    float zmax = 0.f;
-    bool saw_nan = false;
-    load_small<IN, OU>(net, L, r);
-    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-    saw_nan |= xv != xv;
-    if (threadIdx.x < GROUP * XSW) sX[threadIdx.x] = xv;
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
+    constexpr int OU = 4;
+    float b3v, pz, zmax = 0.f;
+    bool saw_nan = group_forward<PK, IN, OU>(a, rows, obs, g, smem, b3v, pz, zmax);
     const int tid = threadIdx.x;
     if (tid < GROUP * OU) {
         const int row = tid / OU, o = tid % OU;
         const long gr = g * GROUP + row;
         float y = 0.f;
         if (gr < rows) {
-            float z = out_preact<OS>(sPart, b3v, row, o);
+            float z = out_preact<out_stride<OU>()>(policy_pass::part_of<IN>(smem), b3v, row, o);
             y = a.out_tanh ? tanhf(z) : z;
             y += pz;
             saw_nan |= y != y;
@@ -184,54 +185,6 @@ __device__ __forceinline__ void sample_group(const typename args_of<IN>::type& a
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
 
-// The same policy pass for a kernel that applies it to one group MANY times (k_env_rollout, below): `group` in two parts, beside it
-// rather than out of it (the worker launch's code stays as it is).  load: the policy's registers, once.  pass: one evaluation on the
-// group's observations sObs [16][od] that wave 0 left in LDS - the same single float32 product with obs_scale, the same device
-// functions on the same operands in the same order as `group` (so as mpg_policy_action without noise), the actions to sAct [16][2].
-// zmax / saw_nan accumulate over the passes; report() ORs them into the status word once.  pass() starts with the caller's LDS in
-// order (a workgroup barrier behind the writes of sObs) and ends with sAct written by wave 0's own lanes.
-template <bool PK, int IN>
-__device__ __forceinline__ void load(const typename args_of<IN>::type& a, const Lane& L, float (&w2)[128], SmallRegs<IN, 2>& r, float& b3v) {
-    const Net net = make_net(a.params, obs_dim_of(a), 4);
-    b3v = 0.f;
-    if (threadIdx.x < GROUP * 2) b3v = net.b3[threadIdx.x % 2];
-    load_small<IN, 2>(net, L, r);
-    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-}
-template <int IN>
-__device__ __forceinline__ void pass(const typename args_of<IN>::type& a, int rows, long g, const float* sObs, float* smem, float* sAct,
-                                     const Lane& L, const float (&w2)[128], const SmallRegs<IN, 2>& r, float b3v, float& zmax,
-                                     bool& saw_nan) {
-    constexpr int OU = 2, XSW = xs_of<IN>();
-    const int od = obs_dim_of(a);
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
-    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 and the rows beyond `rows` stay zero)
-        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
-        float xv = 0.f;
-        if (g * GROUP + row < rows && i < od) xv = sObs[row * od + i] * a.scale[i];
-        saw_nan |= xv != xv;
-        sX[threadIdx.x] = xv;
-    }
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
-    const int tid = threadIdx.x;
-    if (tid < GROUP * OU) {
-        const int row = (tid / OU) % GROUP, o = tid % OU;
-        float y = 0.f;
-        if (g * GROUP + row < rows) {
-            float z = out_preact(sPart, b3v, row, o);
-            y = a.out_tanh ? a.out_scale * tanhf(z) : z;
-            y += pz;
-            saw_nan |= y != y;
-        }
-        sAct[tid] = y;
-    }
-}
 // The exploration noise of `group` for a kernel that calls pass() (k_worker_rollout, below): lane tid < 32 of wave 0 takes its own
 // action back out of sAct, adds N(0, sigma) from the same Philox draw as `group` - row gr, output o, the 64-bit counter (c1, c2) -
 // tests the sum for NaN as `group` does (pass() tested the action before the noise: a NaN there is a NaN here) and puts it back for
@@ -251,61 +204,6 @@ __device__ __forceinline__ float explore(float sigma, int rows, long g, float* s
         sAct[tid] = y;
     }
     return y;
-}
-template <class A>
-__device__ __forceinline__ void report(const A& a, float zmax, bool saw_nan) {
-    report_activation_range(a.status, zmax);
-    if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
-}
-// `sample_group` in the same two parts, for a kernel that samples one group MANY times (k_worker_sample_rollout, below), beside it and
-// beside load / pass: every shipped kernel keeps its code.  sample_load: the FOUR-output policy registers, once.  sample_pass: the
-// four logits of every row of the group on sObs [16][od] - k_forward<IN, 4, PK, 1> for unit g as policy_logits launches it: the same
-// single float32 product with obs_scale, the same device functions on the same operands in the same order, the output activation on
-// all four columns (a.out_scale and a.sigma are not read), the same row_poison, activation-range and NaN accumulation as
-// sample_group - left in sLogit [16][4] (0 beyond `rows`) by lanes 4 row .. 4 row + 3 of wave 0, the lanes that step the row's agent.
-template <bool PK, int IN>
-__device__ __forceinline__ void sample_load(const typename args_of<IN>::type& a, const Lane& L, float (&w2)[128], SmallRegs<IN, 4>& r,
-                                            float& b3v) {
-    static_assert(GROUP * 4 == 64, "the four logits of every row of a group are formed by one wave");
-    const Net net = make_net(a.params, obs_dim_of(a), 4);
-    b3v = 0.f;
-    if (threadIdx.x < GROUP * 4) b3v = net.b3[threadIdx.x % 4];
-    load_small<IN, 4>(net, L, r);
-    if constexpr (PK) load_w2_packed(a.pack, L, w2); else load_w2_fwd(net.W2, L, w2);
-}
-template <int IN>
-__device__ __forceinline__ void sample_pass(const typename args_of<IN>::type& a, int rows, long g, const float* sObs, float* smem,
-                                            float* sLogit, const Lane& L, const float (&w2)[128], const SmallRegs<IN, 4>& r, float b3v,
-                                            float& zmax, bool& saw_nan) {
-    constexpr int OU = 4, XSW = xs_of<IN>(), OS = out_stride<OU>();
-    const int od = obs_dim_of(a);
-    float* sA = smem;
-    float* sX = sA + A_IMG;
-    float* sPart = sX + GROUP * XSW;
-    if (threadIdx.x < GROUP * XSW) {           // (columns od .. XSW - 1 and the rows beyond `rows` stay zero)
-        const int row = threadIdx.x / XSW, i = threadIdx.x % XSW;
-        float xv = 0.f;
-        if (g * GROUP + row < rows && i < od) xv = sObs[row * od + i] * a.scale[i];
-        saw_nan |= xv != xv;
-        sX[threadIdx.x] = xv;
-    }
-    lds_barrier();
-    float pz = 0.f;
-    if (threadIdx.x < GROUP * OU) pz = row_poison(sX + (threadIdx.x / OU) * XSW, XSW);
-    float h1[2][4], h2[2][4];
-    forward_group<IN, OU>(sX, sA, sPart, L, w2, r, h1, h2, nullptr, 0, nullptr, &zmax);
-    const int tid = threadIdx.x;
-    if (tid < GROUP * OU) {
-        const int row = tid / OU, o = tid % OU;
-        float y = 0.f;
-        if (g * GROUP + row < rows) {
-            float z = out_preact<OS>(sPart, b3v, row, o);
-            y = a.out_tanh ? tanhf(z) : z;
-            y += pz;
-            saw_nan |= y != y;
-        }
-        sLogit[tid] = y;
-    }
 }
 // Row gr's action from its four logits l[4] (mean | log-std), by the first of the row's four lanes: elements 2 gr and 2 gr + 1 of the
 // stream mpg_normal_fill(2 n, key, counter (c1, c2)) writes - sample_group's draw - and k_row_sums<GaussRow>'s row body, or with SQ
@@ -782,6 +680,20 @@ __global__ void __launch_bounds__(64) k_step_store_reset_1(int n, float* __restr
     env_lane<1>(ag, an, n, i, 0, nullptr, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_out, done_out, od);
 }
 
+// The env tail of the two launches below: the group's policy pass has left the actions in sAct [16][2]; wave 0, four lanes per agent,
+// steps the group's 16 agents with env_lane<4> (it wrote sAct itself: LDS is in order within a wave).  The other waves are done.
+__device__ __forceinline__ void group_env_lanes(int n, int od, float* __restrict__ st, float* __restrict__ obs_io, const float* sAct,
+                                                float* s_quad, const RingPtrs& ring, int capacity, int next_idx, uint32_t k0, uint32_t k1,
+                                                uint32_t c1, uint32_t c2, uint8_t* __restrict__ done_out) {
+    if (threadIdx.x >= 64) return;
+    __builtin_amdgcn_wave_barrier();
+    const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
+    if (i >= n) return;
+    const Agent ag = load_agent(st, n, i);
+    const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
+    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_io, done_out, od);
+}
+
 // OffPolicyWorker.sample's whole inner body (worker.py:95-112) in ONE launch: the policy pass of a 16-agent group by a 512-thread
 // workgroup, then env_lane<4> for those 16 agents on wave 0.  The stand-alone pair is two launches of one wave per CU each (7 + 14 us
 // at 4096 agents); fused, the env lanes start the moment their group's actions exist.  Blocks beyond the policy groups gather the
@@ -803,21 +715,14 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
     __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
     __shared__ float sAct[mlp::GROUP * 2];
     worker_policy::group<PK, IN>(pa, n, obs_io, blockIdx.x, smem, sAct, act_out);
-    if (threadIdx.x >= 64) return;                     // the env lanes: wave 0, four lanes per agent (it wrote sAct itself: LDS is in
-    __builtin_amdgcn_wave_barrier();                   // order within a wave)
-    const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
-    if (i >= n) return;
-    const Agent ag = load_agent(st, n, i);
-    const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
-    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_io, done_out,
-                worker_policy::obs_dim_of(pa));
+    group_env_lanes(n, worker_policy::obs_dim_of(pa), st, obs_io, sAct, s_quad, ring, capacity, next_idx, k0, k1, c1, c2, done_out);
 }
 
 // OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head, no
 // explore_sigma) in ONE launch: mpg_normal_fill + mpg_policy_sample (k_forward<IN, 4>, k_row_sums<GaussRow>) + mpg_env_step_store_reset
-// are four launches of at most one wave per CU each; here a 512-thread workgroup runs the four-logit policy pass of a 16-agent group,
-// wave 0 draws and samples (worker_policy::sample_group) and then steps those agents with env_lane<4>, exactly as in
-// k_policy_step_store_reset.  No spare workgroups: there is no pre-gathered draw.  IN as in k_policy_step_store_reset.
+// are four launches of at most one wave per CU each; here wave 0 draws and samples behind the four-logit pass
+// (worker_policy::sample_group) and then steps the agents as in k_policy_step_store_reset.  No spare workgroups: there is no
+// pre-gathered draw.  IN as in k_policy_step_store_reset.
 template <bool PK, int IN>
 __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_sample_step_store_reset(const typename worker_policy::args_of<IN>::type pa,
                                                                                      int n, float* __restrict__ st,
@@ -831,26 +736,18 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_sample_step_store_re
     __shared__ float sLogit[mlp::GROUP * 4];
     __shared__ float sAct[mlp::GROUP * 2];
     worker_policy::sample_group<PK, IN>(pa, n, obs_io, blockIdx.x, smem, sLogit, sAct, act_out, logp_out);
-    if (threadIdx.x >= 64) return;                     // the env lanes: wave 0, four lanes per agent (it wrote sAct itself: LDS is in
-    __builtin_amdgcn_wave_barrier();                   // order within a wave)
-    const int i = blockIdx.x * mlp::GROUP + (threadIdx.x >> 2), q = threadIdx.x & 3;
-    if (i >= n) return;
-    const Agent ag = load_agent(st, n, i);
-    const float2 an = make_float2(sAct[2 * (threadIdx.x >> 2)], sAct[2 * (threadIdx.x >> 2) + 1]);
-    env_lane<4>(ag, an, n, i, q, s_quad + (threadIdx.x >> 2) * 100, st, ring, capacity, next_idx, k0, k1, c1, c2, obs_io, done_out,
-                worker_policy::obs_dim_of(pa));
+    group_env_lanes(n, worker_policy::obs_dim_of(pa), st, obs_io, sAct, s_quad, ring, capacity, next_idx, k0, k1, c1, c2, done_out);
 }
 
 // MPGLearner.sample / NDPGLearner.sample (mpg_learner.py:109-124, ndpg.py:99-114) in ONE launch: from obs0 take n real-env steps, the
 // first with the replay action act0, the later ones with the policy's deterministic action.  The stand-alone chain is
 // mpg_env_reset_from_obs + n x mpg_env_step + (n - 1) x mpg_policy_action = 2 n launches of one wave per CU each, every policy launch
-// fetching the weights again.  Here one 512-thread workgroup owns 16 rows for all n steps: the policy's registers are loaded once
-// (worker_policy::load), wave 0 - four lanes per row, step_agent<4> - builds the agents from obs0 as k_reset_from_obs does and keeps
-// them in registers, and per step the observations go from wave 0 to the policy pass and the actions back THROUGH LDS between
-// workgroup barriers.  Global memory is read in the prologue only (obs0, act0, weights) and written for rewards / last_obs only, never
-// read back.  No done flag has a consumer (k_step does not reset, neither sample() nor mpg_nstep_targets reads them).  Rewards, last
-// observations and the status word are bit-identical to the chain's: the same device functions on the same operands in the same
-// order (tests/test_ndpg_gpu.py).  IN as in k_policy_step_store_reset.
+// fetching the weights again.  Here the resident plan (policy_pass.h) on 16 rows for all n steps: wave 0 - four lanes per row,
+// step_agent<4> - builds the agents from obs0 as k_reset_from_obs does; the policy is not evaluated at step 0.  Global memory is read
+// in the prologue only (obs0, act0, weights) and written for rewards / last_obs only.  No done flag has a consumer (k_step does not
+// reset, neither sample() nor mpg_nstep_targets reads them).  Rewards, last observations and the status word are bit-identical to the
+// chain's: the same device functions on the same operands in the same order (tests/test_ndpg_gpu.py).  IN as in
+// k_policy_step_store_reset.
 template <bool PK, int IN>
 __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename worker_policy::args_of<IN>::type pa, int rows, int n,
                                                                   const float* __restrict__ obs0, const float* __restrict__ act0,
@@ -865,7 +762,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename 
     mlp::SmallRegs<IN, 2> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
+    policy_pass::load<PK, IN, 2>(pa, 4, L, w2, r, b3v);
     // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
     const int a_loc = threadIdx.x >> 2, q = threadIdx.x & 3, i = blockIdx.x * mlp::GROUP + a_loc;
     const bool env_lane_on = threadIdx.x < 64 && i < rows;
@@ -884,7 +781,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename 
     for (int t = 0; t < n; ++t) {
         if (t > 0) {
             mlp::lds_barrier();                          // sObs of step t - 1 is complete (and the previous pass's LDS is free)
-            worker_policy::pass<IN>(pa, rows, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+            worker_policy::pass<IN, 2>(pa, rows, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
             if (threadIdx.x < 64) {                      // wave 0 wrote sAct itself: LDS is in order within a wave
                 __builtin_amdgcn_wave_barrier();
                 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
@@ -899,31 +796,88 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout(const typename 
             }
         }
     }
-    worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
-// k_worker_rollout (below): what wave 0 needs of the launch's arguments once per iteration.  They rest in LDS and are read where they
-// are used: held in scalar registers for the whole loop, beside the env's hoisted constants, they and the Philox key schedules
-// derived from them were spilled.
+// ---- the resident kernels on the env's own state block: k_worker_rollout, k_worker_sample_rollout, k_eval_rollout ---------------------
+// The resident plan of policy_pass.h with wave 0 as the env lanes, four lanes per agent, each holding the whole agent (step_agent<4>).
+// State, obs_io, act_out and the done flags are written after the LAST iteration only: what the chain of launches leaves behind.
+
+// Their prologue behind the policy's registers: the lane's agent (env lanes only), and the group's rows of obs_io (16 x od <= 256
+// floats) into sObs.
+__device__ __forceinline__ void resident_prologue(Agent& ag, int n, int od, int i_lane, const float* st, const float* obs_io, float* sObs) {
+    if (threadIdx.x < 64 && i_lane < n) ag = load_agent(st, n, i_lane);
+    const int g0 = blockIdx.x * mlp::GROUP, live = (n - g0 < mlp::GROUP ? n - g0 : mlp::GROUP) * od;
+    if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od + threadIdx.x];
+}
+
+// What wave 0 needs of a worker rollout's arguments once per iteration.  They rest in LDS and are read where they are used: held in
+// scalar registers for the whole loop, beside the env's hoisted constants, they and the Philox key schedules derived from them were
+// spilled.  Head: what the policy's head adds - nothing, or the squashed Gaussian head's two constants.
+struct NoHead {};
+struct SquashHead {
+    float range, log_r;            // SQ: the action range and its logarithm (gauss::log_range)
+};
+template <class Head>
 struct RolloutEnvArgs {
     RingPtrs ring;
     float *st, *obs_io, *act_out;
     uint8_t* done_out;
-    uint32_t k0, k1, nk0, nk1;     // env key, noise key
-    uint64_t env_ctr, noise_ctr;   // the counters of iteration 0
+    uint32_t k0, k1, pk0, pk1;     // env key, the policy's key (exploration noise or draw)
+    uint64_t env_ctr, policy_ctr;  // the counters of iteration 0, carried as 64-bit sums
     uint32_t capacity;
+    Head head;
+    template <class PA>
+    __device__ __forceinline__ void park(const PA& pa, float* st_, float* obs_io_, float* act_out_, const RingPtrs& ring_, int capacity_,
+                                         uint32_t k0_, uint32_t k1_, uint32_t c1, uint32_t c2, uint8_t* done_out_) {
+        ring = ring_;
+        st = st_; obs_io = obs_io_; act_out = act_out_; done_out = done_out_;
+        k0 = k0_; k1 = k1_; pk0 = pa.k0; pk1 = pa.k1;
+        env_ctr = ((uint64_t)c2 << 32) | c1;
+        policy_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
+        capacity = (uint32_t)capacity_;
+    }
 };
+
+// One iteration `it` of an env lane with its action in sAct: what env_lane<4> does, in its order - ring row (obs, act) at `slot`,
+// step_agent<4>, (obs2, rew, done), reset_agent keyed (env key, env counter + it) if done, and the next observation: into sObs, or
+// behind the last iteration state, obs_io and done_out - then the slot advanced by n (n <= capacity < 2^31: no overflow).
+template <class A>
+__device__ __forceinline__ void rollout_env_iteration(A& sArg, Agent& ag, uint32_t& slot, int it, bool last, int q, int i, int od, int n,
+                                                      int a_loc, const float* sAct, float* sObs, float* s_quad) {
+    if (i < n) {
+        const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
+        if (q == 0) {
+            write_obs(sArg.ring.obs, (int)slot, od, ag);             // obs before the step
+            reinterpret_cast<float2*>(sArg.ring.act)[slot] = an;
+        }
+        const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
+        if (q == 1) {
+            write_obs(sArg.ring.obs2, (int)slot, od, ag);
+            sArg.ring.rew[slot] = o.reward;
+            sArg.ring.done[slot] = o.done ? 1 : 0;
+            uint8_t* const dn = sArg.done_out;
+            if (last && dn) dn[i] = o.done ? 1 : 0;
+        }
+        if (o.done) {
+            const uint64_t ec = sArg.env_ctr + (uint64_t)it;
+            reset_agent(ag, i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
+        }
+        if (last) {
+            if (q == 2) store_agent(sArg.st, n, i, ag);
+            if (q == 3) write_obs(sArg.obs_io, i, od, ag);
+        } else if (q == 3) {
+            write_obs(sObs, a_loc, od, ag);
+        }
+        slot += (uint32_t)n;
+        if (slot >= sArg.capacity) slot -= sArg.capacity;
+    }
+}
 
 // OffPolicyWorker.sample's `iters` iterations (worker.py:91-119: policy -> + N(0, sigma) -> env.step -> ring -> env.reset) in ONE
 // launch: `iters` consecutive k_policy_step_store_reset launches with the noise and env counters and the ring position advancing by
-// one / one / n per launch.  Each of those fetches the policy's weights and the agents' state again; here one 512-thread workgroup owns
-// a 16-agent group for all iterations in the form of k_env_rollout: the policy's registers are loaded once (worker_policy::load),
-// wave 0 - four lanes per agent - reads the agents once and keeps them in registers, and per iteration the observations go from wave 0
-// to the policy pass and the actions back through LDS between workgroup barriers.  Per iteration `it` wave 0 does what env_lane<4>
-// does, in its order: ring row (obs, act) at slot (next_idx + it * n + i) % capacity, step_agent<4>, (obs2, rew, done), reset_agent
-// keyed (env key, env counter + it) if done, and the next observation - into sObs instead of obs_io.  State, obs_io, act_out and
-// done_out are written after the LAST iteration only (what the chain leaves behind).  Global memory is read in the prologue only
-// (weights, state, obs_io) and written, never read back; (noise / env) c1, c2: the counters of iteration 0, carried as 64-bit sums.
+// one / one / n per launch, each of which fetches the policy's weights and the agents' state again.  Between the pass and the env
+// step lanes 0 .. 31 of wave 0 add the exploration noise (worker_policy::explore).  (noise / env) c1, c2: the counters of iteration 0.
 // The host refuses iters * n > capacity: two iterations would write one ring slot from different workgroups.  Everything the chain
 // leaves is bit-identical: the same device functions on the same operands in the same order (tests/test_worker_rollout_gpu.py).
 // IN as in k_policy_step_store_reset.
@@ -936,36 +890,24 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typena
     __shared__ __attribute__((aligned(16))) float s_quad[16 * 100];
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
     __shared__ float sAct[mlp::GROUP * 2];
-    __shared__ RolloutEnvArgs sArg;
+    __shared__ RolloutEnvArgs<NoHead> sArg;
     const int od_launch = worker_policy::obs_dim_of(pa);
     const mlp::Lane L;
     float w2[128];
     mlp::SmallRegs<IN, 2> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
-    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    policy_pass::load<PK, IN, 2>(pa, 4, L, w2, r, b3v);
     const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
     Agent ag = {};
-    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
-    {   // the group's rows of obs_io (16 x od <= 256 floats)
-        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
-    }
-    if (threadIdx.x == 0) {
-        sArg.ring = ring;
-        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
-        sArg.k0 = k0; sArg.k1 = k1; sArg.nk0 = pa.k0; sArg.nk1 = pa.k1;
-        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
-        sArg.noise_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
-        sArg.capacity = (uint32_t)capacity;
-    }
-    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    resident_prologue(ag, n_launch, od_launch, i_lane, st, obs_io, sObs);
+    if (threadIdx.x == 0) sArg.park(pa, st, obs_io, act_out, ring, capacity, k0, k1, c1, c2, done_out);
+    // the agent's ring slot: (next_idx + it * n + i) % capacity
     uint32_t slot = (uint32_t)(((long)next_idx + i_lane) % capacity);
     for (int it = 0; it < iters; ++it) {
         const bool last = it == iters - 1;
         mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
-        worker_policy::pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+        worker_policy::pass<IN, 2>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
         if (threadIdx.x >= 64) continue;                 // wave 0 wrote sAct itself: LDS is in order within a wave
         // The lane's place and the launch's sizes, opaque per iteration: what is derived from them - the predicates q == 0 .. 3 and
         // i < n, row strides, the group's offset - is then formed where it is used and not held in scalar registers across the whole
@@ -974,66 +916,24 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typena
         asm volatile("" : "+v"(q), "+v"(i), "+s"(g), "+s"(n));
         if constexpr (IN == 16) asm volatile("" : "+s"(od));      // (a constant at IN = 6)
         if (threadIdx.x < mlp::GROUP * 2) {
-            const uint64_t nc = sArg.noise_ctr + (uint64_t)it;
-            const float y = worker_policy::explore(pa.sigma, n, g, sAct, sArg.nk0, sArg.nk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
+            const uint64_t nc = sArg.policy_ctr + (uint64_t)it;
+            const float y = worker_policy::explore(pa.sigma, n, g, sAct, sArg.pk0, sArg.pk1, (uint32_t)nc, (uint32_t)(nc >> 32), saw_nan);
             if (last && g * mlp::GROUP + (int)threadIdx.x / 2 < n) sArg.act_out[(size_t)g * mlp::GROUP * 2 + threadIdx.x] = y;
         }
         __builtin_amdgcn_wave_barrier();
-        if (i < n) {
-            const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
-            if (q == 0) {
-                write_obs(sArg.ring.obs, (int)slot, od, ag);             // obs before the step
-                reinterpret_cast<float2*>(sArg.ring.act)[slot] = an;
-            }
-            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
-            if (q == 1) {
-                write_obs(sArg.ring.obs2, (int)slot, od, ag);
-                sArg.ring.rew[slot] = o.reward;
-                sArg.ring.done[slot] = o.done ? 1 : 0;
-                uint8_t* const dn = sArg.done_out;
-                if (last && dn) dn[i] = o.done ? 1 : 0;
-            }
-            if (o.done) {
-                const uint64_t ec = sArg.env_ctr + (uint64_t)it;
-                reset_agent(ag, i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
-            }
-            if (last) {
-                if (q == 2) store_agent(sArg.st, n, i, ag);
-                if (q == 3) write_obs(sArg.obs_io, i, od, ag);
-            } else if (q == 3) {
-                write_obs(sObs, a_loc, od, ag);
-            }
-            slot += (uint32_t)n;
-            if (slot >= sArg.capacity) slot -= sArg.capacity;
-        }
+        rollout_env_iteration(sArg, ag, slot, it, last, q, i, od, n, a_loc, sAct, sObs, s_quad);
     }
-    worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
-
-// k_worker_sample_rollout (below): RolloutEnvArgs for the stochastic policy's launch - the draw's key and counter in the place of the
-// exploration noise's, and the squashed head's two constants
-struct SampleRolloutEnvArgs {
-    RingPtrs ring;
-    float *st, *obs_io, *act_out;
-    uint8_t* done_out;
-    uint32_t k0, k1, sk0, sk1;     // env key, draw key
-    uint64_t env_ctr, sample_ctr;  // the counters of iteration 0
-    uint32_t capacity;
-    float range, log_r;            // SQ: the action range and its logarithm (gauss::log_range)
-};
 
 // The same `iters` iterations for a STOCHASTIC policy (SAC; worker.py:96: the action IS the sample, no explore_sigma): `iters`
 // consecutive triples of mpg_normal_fill(2 n, sample key, sample counter + it), mpg_policy_sample (SQ: mpg_policy_sample_squashed -
 // k_forward<IN, 4, PK, 1> and k_row_sums<GaussRow / SquashRow>) and mpg_env_step_store_reset in ONE launch; without SQ that is `iters`
-// k_policy_sample_step_store_reset launches.  A sibling of k_worker_rollout with its residency plan: one 512-thread workgroup per
-// 16-agent group, the policy's registers - here all four output columns - loaded once (worker_policy::sample_load), the agents in wave
-// 0's registers, four lanes each, the observations to the pass through LDS between workgroup barriers, global memory read in the
-// prologue only, state / obs_io / act_out / done_out written after the LAST iteration only, wave 0's per-iteration arguments in LDS,
-// the status word reported once.  New between the pass and the env step: the four logits of a row are left in sLogit by the row's own
-// four lanes (worker_policy::sample_pass), the first of them draws elements 2 i, 2 i + 1 of the iteration's stream, forms the action
-// (worker_policy::sample_act) and leaves it in sAct for the four: LDS is in order within a wave.  From there on wave 0 does what
-// k_worker_rollout's env lanes do.  (pa.k0 .. pa.c2: the draw's key and the counter of iteration 0; pa.sigma, pa.out_scale: not read.)
-// IN as in k_policy_step_store_reset.
+// k_policy_sample_step_store_reset launches.  The policy's registers hold all four output columns.  Between the pass and the env step
+// the four logits of a row lie in sLogit, left by the row's own four lanes; the first of them draws elements 2 i, 2 i + 1 of the
+// iteration's stream, forms the action (worker_policy::sample_act) and leaves it in sAct for the four: LDS is in order within a wave.
+// (pa.k0 .. pa.c2: the draw's key and the counter of iteration 0; pa.sigma, pa.out_scale: not read.)  IN as in
+// k_policy_step_store_reset.
 template <bool PK, int IN, bool SQ>
 __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const typename worker_policy::args_of<IN>::type pa, int n_launch,
                                                                             int iters, float* st, float* obs_io, float* act_out, RingPtrs ring,
@@ -1044,37 +944,27 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const
     __shared__ __attribute__((aligned(16))) float sObs[mlp::GROUP * 16];
     __shared__ __attribute__((aligned(16))) float sLogit[mlp::GROUP * 4];
     __shared__ float sAct[mlp::GROUP * 2];
-    __shared__ SampleRolloutEnvArgs sArg;
+    __shared__ RolloutEnvArgs<SquashHead> sArg;
     const int od_launch = worker_policy::obs_dim_of(pa);
     const mlp::Lane L;
     float w2[128];
     mlp::SmallRegs<IN, 4> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    worker_policy::sample_load<PK, IN>(pa, L, w2, r, b3v);
-    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    policy_pass::load<PK, IN, 4>(pa, 4, L, w2, r, b3v);
     const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
     Agent ag = {};
-    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
-    {   // the group's rows of obs_io (16 x od <= 256 floats)
-        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
-    }
+    resident_prologue(ag, n_launch, od_launch, i_lane, st, obs_io, sObs);
     if (threadIdx.x == 0) {
-        sArg.ring = ring;
-        sArg.st = st; sArg.obs_io = obs_io; sArg.act_out = act_out; sArg.done_out = done_out;
-        sArg.k0 = k0; sArg.k1 = k1; sArg.sk0 = pa.k0; sArg.sk1 = pa.k1;
-        sArg.env_ctr = ((uint64_t)c2 << 32) | c1;
-        sArg.sample_ctr = ((uint64_t)pa.c2 << 32) | pa.c1;
-        sArg.capacity = (uint32_t)capacity;
-        sArg.range = range; sArg.log_r = log_r;
+        sArg.park(pa, st, obs_io, act_out, ring, capacity, k0, k1, c1, c2, done_out);
+        sArg.head.range = range; sArg.head.log_r = log_r;
     }
-    // the agent's ring slot: (next_idx + it * n + i) % capacity, advanced by n per iteration (n <= capacity < 2^31: no overflow)
+    // the agent's ring slot: (next_idx + it * n + i) % capacity
     uint32_t slot = (uint32_t)(((long)next_idx + i_lane) % capacity);
     for (int it = 0; it < iters; ++it) {
         const bool last = it == iters - 1;
         mlp::lds_barrier();                              // sObs of this iteration is complete (and the previous pass's LDS is free)
-        worker_policy::sample_pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
+        worker_policy::pass<IN, 4>(pa, n_launch, blockIdx.x, sObs, smem, sLogit, L, w2, r, b3v, zmax, saw_nan);
         if (threadIdx.x >= 64) continue;                 // wave 0 wrote sLogit itself: LDS is in order within a wave
         // (the lane's place and the launch's sizes, opaque per iteration: k_worker_rollout says why)
         int q = q_lane, i = i_lane, od = od_launch, n = n_launch;
@@ -1082,9 +972,9 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const
         if constexpr (IN == 16) asm volatile("" : "+s"(od));      // (a constant at IN = 6)
         __builtin_amdgcn_wave_barrier();
         if (i < n && q == 0) {                           // the first of the row's four lanes: the draw and the head
-            const uint64_t sc = sArg.sample_ctr + (uint64_t)it;
+            const uint64_t sc = sArg.policy_ctr + (uint64_t)it;
             float act[2];
-            worker_policy::sample_act<SQ>(sLogit + 4 * a_loc, i, sArg.range, sArg.log_r, sArg.sk0, sArg.sk1, (uint32_t)sc,
+            worker_policy::sample_act<SQ>(sLogit + 4 * a_loc, i, sArg.head.range, sArg.head.log_r, sArg.pk0, sArg.pk1, (uint32_t)sc,
                                           (uint32_t)(sc >> 32), act);
             sAct[2 * a_loc] = act[0];
             sAct[2 * a_loc + 1] = act[1];
@@ -1095,35 +985,9 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_sample_rollout(const
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (i < n) {
-            const float2 an = make_float2(sAct[2 * a_loc], sAct[2 * a_loc + 1]);
-            if (q == 0) {
-                write_obs(sArg.ring.obs, (int)slot, od, ag);             // obs before the step
-                reinterpret_cast<float2*>(sArg.ring.act)[slot] = an;
-            }
-            const StepOut o = step_agent<4>(ag, an, q, s_quad + a_loc * 100);
-            if (q == 1) {
-                write_obs(sArg.ring.obs2, (int)slot, od, ag);
-                sArg.ring.rew[slot] = o.reward;
-                sArg.ring.done[slot] = o.done ? 1 : 0;
-                uint8_t* const dn = sArg.done_out;
-                if (last && dn) dn[i] = o.done ? 1 : 0;
-            }
-            if (o.done) {
-                const uint64_t ec = sArg.env_ctr + (uint64_t)it;
-                reset_agent(ag, i, sArg.k0, sArg.k1, (uint32_t)ec, (uint32_t)(ec >> 32));
-            }
-            if (last) {
-                if (q == 2) store_agent(sArg.st, n, i, ag);
-                if (q == 3) write_obs(sArg.obs_io, i, od, ag);
-            } else if (q == 3) {
-                write_obs(sObs, a_loc, od, ag);
-            }
-            slot += (uint32_t)n;
-            if (slot >= sArg.capacity) slot -= sArg.capacity;
-        }
+        rollout_env_iteration(sArg, ag, slot, it, last, q, i, od, n, a_loc, sAct, sObs, s_quad);
     }
-    worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
 // k_eval_rollout (below): what wave 0 needs of the launch's arguments once per step, resting in LDS as RolloutEnvArgs does and for its
@@ -1135,21 +999,16 @@ struct EvalEnvArgs {
 
 // Evaluator.run_n_episodes_parallel's loop (evaluator.py:132-139: compute_mode -> env.step, `done` not consulted, nothing reset) in ONE
 // launch: `steps` consecutive pairs of mpg_policy_action (sigma 0) and mpg_env_step = 2 * steps launches of at most one wave per CU,
-// every policy launch fetching the weights again and every env launch the state.  A sibling of k_env_rollout with its residency plan:
-// one 512-thread workgroup owns a 16-agent group for all steps, the policy's registers are loaded once (worker_policy::load), wave 0 -
-// four lanes per agent, step_agent<4> - keeps the agents in registers, and per step the observations go from wave 0 to the policy pass
-// and the actions back through LDS between workgroup barriers.  Unlike k_env_rollout the agents come from the env's own state block
-// (load_agent, as in k_worker_rollout) and the first observations from obs_io - a drawn state does not survive the round trip through
-// its observation (reset_agent wraps phi, k_reset_from_obs does not) - the policy is evaluated at step 0 too, and the whole trajectory
-// is recorded: per step t the observation BEFORE the step (out of sObs: at t = 0 the caller's own rows, later what write_obs left
-// there) at obs_traj[(t n + i) od ..], the action as the pass formed it - unclipped, the env clips its own copy - at act_traj[(t n + i)
-// 2 ..] and the reward at rew_traj[t n + i]: the layouts torch.stack gives the evaluator's per-step tensors.  State, obs_io and the
-// done flags (k_step's two, both nullable here) are written after the LAST step only: what the chain leaves behind.  Global memory is
-// read in the prologue only (weights, state, obs_io) and written, never read back; the status word is reported once.  Everything is
-// bit-identical to the chain's: the same device functions on the same operands in the same order (tests/test_eval_rollout_gpu.py).
-// IN as in k_policy_step_store_reset.
+// every policy launch fetching the weights again and every env launch the state.  Unlike k_env_rollout the agents come from the env's
+// own state block and the first observations from obs_io - a drawn state does not survive the round trip through its observation
+// (reset_agent wraps phi, k_reset_from_obs does not) - the policy is evaluated at step 0 too, and the whole trajectory is recorded:
+// per step t the observation BEFORE the step (out of sObs: at t = 0 the caller's own rows, later what write_obs left there) at
+// obs_traj[(t n + i) od ..], the action as the pass formed it - unclipped, the env clips its own copy - at act_traj[(t n + i) 2 ..] and
+// the reward at rew_traj[t n + i]: the layouts torch.stack gives the evaluator's per-step tensors.  The done flags are k_step's two,
+// both nullable here.  Everything is bit-identical to the chain's: the same device functions on the same operands in the same order
+// (tests/test_eval_rollout_gpu.py).  IN as in k_policy_step_store_reset.
 // NO REGISTER HEADROOM: the packed IN = 6 form takes 254 of the 256 VGPRs this launch bound allows (strided 250; IN = 16: 238 / 235),
-// without scratch.  A change to step_agent, worker_policy::pass or this loop can tip it into scratch: run
+// without scratch.  A change to step_agent, worker_policy::pass, policy_pass::stage or this loop can tip it into scratch: run
 // `tools/kernel_resources.py env_path_tracking.hip` after any such edit.
 template <bool PK, int IN>
 __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout(const typename worker_policy::args_of<IN>::type pa, int n_launch,
@@ -1166,15 +1025,10 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout(const typename
     mlp::SmallRegs<IN, 2> r;
     float b3v, zmax = 0.f;
     bool saw_nan = false;
-    worker_policy::load<PK, IN>(pa, L, w2, r, b3v);
-    // the env lanes: wave 0, four lanes per agent, each holding the whole agent (step_agent<4>)
+    policy_pass::load<PK, IN, 2>(pa, 4, L, w2, r, b3v);
     const int a_loc = threadIdx.x >> 2, q_lane = threadIdx.x & 3, i_lane = blockIdx.x * mlp::GROUP + a_loc;
     Agent ag = {};
-    if (threadIdx.x < 64 && i_lane < n_launch) ag = load_agent(st, n_launch, i_lane);
-    {   // the group's rows of obs_io (16 x od <= 256 floats)
-        const int g0 = blockIdx.x * mlp::GROUP, live = (n_launch - g0 < mlp::GROUP ? n_launch - g0 : mlp::GROUP) * od_launch;
-        if ((int)threadIdx.x < live) sObs[threadIdx.x] = obs_io[(size_t)g0 * od_launch + threadIdx.x];
-    }
+    resident_prologue(ag, n_launch, od_launch, i_lane, st, obs_io, sObs);
     if (threadIdx.x == 0) {
         sArg.st = st; sArg.obs_io = obs_io; sArg.obs_traj = obs_traj; sArg.act_traj = act_traj; sArg.rew_traj = rew_traj;
         sArg.done_out = done_out; sArg.done_intended_out = done_intended_out;
@@ -1182,7 +1036,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout(const typename
     for (int t = 0; t < steps; ++t) {
         const bool last = t == steps - 1;
         mlp::lds_barrier();                              // sObs of this step is complete (and the previous pass's LDS is free)
-        worker_policy::pass<IN>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
+        worker_policy::pass<IN, 2>(pa, n_launch, blockIdx.x, sObs, smem, sAct, L, w2, r, b3v, zmax, saw_nan);
         if (threadIdx.x >= 64) continue;                 // wave 0 wrote sAct itself: LDS is in order within a wave
         // (the lane's place and the launch's sizes, opaque per step: k_worker_rollout says why)
         int q = q_lane, i = i_lane, od = od_launch, n = n_launch;
@@ -1215,7 +1069,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_eval_rollout(const typename
             }
         }
     }
-    worker_policy::report(pa, zmax, saw_nan);
+    policy_pass::report(pa, zmax, saw_nan);
 }
 
 inline bool pt_obs_dim_ok(int od) { return od >= 6 && od <= 6 + MPG_ENV_MAX_FUTURE; }
@@ -1348,6 +1202,25 @@ void fill_policy_args(A& pa, int n_scale, const mpg_cfg_t* cfg, const float* pol
     pa.k0 = (uint32_t)noise_seed; pa.k1 = (uint32_t)(noise_seed >> 32); pa.c1 = (uint32_t)noise_ctr; pa.c2 = (uint32_t)(noise_ctr >> 32);
     for (int i = 0; i < n_scale; ++i) pa.scale[i] = i < cfg->obs_dim ? cfg->obs_scale[i] : 1.f;
 }
+
+// The policy arguments of a launch and the instantiation that takes them: Args for six-entry observations, WideArgs beyond; packed when
+// the weight cache holds W2's image.  launch(std::bool_constant<PK>, std::integral_constant<int, IN>, pa) issues the entry point's kernel.
+template <class Launch>
+void with_policy_args(const mpg_cfg_t* cfg, const float* policy_params, float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr,
+                      Launch&& launch) {
+    if (cfg->obs_dim > 6) {
+        worker_policy::WideArgs pa;
+        fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        pa.obs_dim = cfg->obs_dim;
+        if (pa.pack) launch(std::true_type{}, std::integral_constant<int, 16>{}, pa);
+        else launch(std::false_type{}, std::integral_constant<int, 16>{}, pa);
+    } else {
+        worker_policy::Args pa;
+        fill_policy_args(pa, 8, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
+        if (pa.pack) launch(std::true_type{}, std::integral_constant<int, 6>{}, pa);
+        else launch(std::false_type{}, std::integral_constant<int, 6>{}, pa);
+    }
+}
 }  // namespace
 
 extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params, int n, float* state, float* obs_io, float explore_sigma,
@@ -1371,22 +1244,12 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
     pd.env_blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     const int blocks = pd.env_blocks + (pd.rows + mlp::NTHREAD - 1) / mlp::NTHREAD;
     hipStream_t s = mpg_stream(stream);
-#define MPG_WORKER_LAUNCH(PK, IN)                                                                                                        \
-    hipLaunchKernelGGL((k_policy_step_store_reset<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, ring, \
-                       capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out, pd)
-    if (wide) {             // (pd.rows == 0: the grid is the policy groups)
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
-        pa.obs_dim = cfg->obs_dim;
+    // (wide: pd.rows == 0, the grid is the policy groups)
+    with_policy_args(cfg, policy_params, explore_sigma, noise_seed, noise_ctr, [&](auto pk, auto in, const auto& pa) {
         mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_LAUNCH(true, 16); else MPG_WORKER_LAUNCH(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
-        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_LAUNCH(true, 6); else MPG_WORKER_LAUNCH(false, 6);
-    }
-#undef MPG_WORKER_LAUNCH
+        hipLaunchKernelGGL((k_policy_step_store_reset<decltype(pk)::value, decltype(in)::value>), dim3(blocks), dim3(mlp::NTHREAD), 0, s,
+                           pa, n, state, obs_io, act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out, pd);
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_step");
     return MPG_OK;
@@ -1419,22 +1282,11 @@ extern "C" int mpg_worker_rollout(const mpg_cfg_t* cfg, const float* policy_para
                 (long)iters * n, capacity);
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-#define MPG_WORKER_ROLLOUT_LAUNCH(PK, IN)                                                                                                \
-    hipLaunchKernelGGL((k_worker_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring, \
-                       capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out)
-    if (cfg->obs_dim > 6) {
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
-        pa.obs_dim = cfg->obs_dim;
+    with_policy_args(cfg, policy_params, explore_sigma, noise_seed, noise_ctr, [&](auto pk, auto in, const auto& pa) {
         mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_ROLLOUT_LAUNCH(true, 16); else MPG_WORKER_ROLLOUT_LAUNCH(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, explore_sigma, noise_seed, noise_ctr);
-        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_ROLLOUT_LAUNCH(true, 6); else MPG_WORKER_ROLLOUT_LAUNCH(false, 6);
-    }
-#undef MPG_WORKER_ROLLOUT_LAUNCH
+        hipLaunchKernelGGL((k_worker_rollout<decltype(pk)::value, decltype(in)::value>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n,
+                           iters, state, obs_io, act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out);
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_rollout");
     return MPG_OK;
@@ -1457,22 +1309,12 @@ extern "C" int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_
                 capacity, n, next_idx);
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-#define MPG_WORKER_LAUNCH(PK, IN)                                                                                                         \
-    hipLaunchKernelGGL((k_policy_sample_step_store_reset<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, state, obs_io, act_out, \
-                       logp_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out)
-    if (cfg->obs_dim > 6) {
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, 0.f, sample_seed, sample_ctr);
-        pa.obs_dim = cfg->obs_dim;
+    with_policy_args(cfg, policy_params, 0.f, sample_seed, sample_ctr, [&](auto pk, auto in, const auto& pa) {
         mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_LAUNCH(true, 16); else MPG_WORKER_LAUNCH(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, 0.f, sample_seed, sample_ctr);
-        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_WORKER_LAUNCH(true, 6); else MPG_WORKER_LAUNCH(false, 6);
-    }
-#undef MPG_WORKER_LAUNCH
+        hipLaunchKernelGGL((k_policy_sample_step_store_reset<decltype(pk)::value, decltype(in)::value>), dim3(blocks), dim3(mlp::NTHREAD),
+                           0, s, pa, n, state, obs_io, act_out, logp_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr),
+                           done_out);
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_sample_step");
     return MPG_OK;
@@ -1494,19 +1336,10 @@ extern "C" int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params,
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_env_rollout: tanh policy with an action range");
     const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-#define MPG_ROLLOUT_LAUNCH(PK, IN) \
-    hipLaunchKernelGGL((k_env_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n, obs0, act0, rewards, last_obs)
-    if (cfg->obs_dim > 6) {
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, 0.f, 0, 0);
-        pa.obs_dim = cfg->obs_dim;
-        if (pa.pack) MPG_ROLLOUT_LAUNCH(true, 16); else MPG_ROLLOUT_LAUNCH(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, 0.f, 0, 0);
-        if (pa.pack) MPG_ROLLOUT_LAUNCH(true, 6); else MPG_ROLLOUT_LAUNCH(false, 6);
-    }
-#undef MPG_ROLLOUT_LAUNCH
+    with_policy_args(cfg, policy_params, 0.f, 0, 0, [&](auto pk, auto in, const auto& pa) {
+        hipLaunchKernelGGL((k_env_rollout<decltype(pk)::value, decltype(in)::value>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, rows, n,
+                           obs0, act0, rewards, last_obs);
+    });
     MPG_CHECK_LAUNCH("mpg_env_rollout");
     return MPG_OK;
 }
@@ -1544,27 +1377,16 @@ extern "C" int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* poli
     const float range = squash ? cfg->action_range : 0.f, log_r = squash ? gauss::log_range(cfg->action_range) : 0.f;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-#define MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, SQ)                                                                                           \
-    hipLaunchKernelGGL((k_worker_sample_rollout<PK, IN, SQ>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io,     \
-                       act_out, ring, capacity, next_idx, MPG_KEY_CTR(env_seed, env_ctr), done_out, range, log_r)
-#define MPG_SAMPLE_ROLLOUT_HEADS(PK, IN) \
-    do { if (squash) MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, true); else MPG_SAMPLE_ROLLOUT_LAUNCH(PK, IN, false); } while (0)
-    if (cfg->obs_dim > 6) {
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, 0.f, sample_seed, sample_ctr);
+    with_policy_args(cfg, policy_params, 0.f, sample_seed, sample_ctr, [&](auto pk, auto in, auto pa) {
         pa.out_tanh = cfg->policy_out_act == MPG_ACT_TANH;      // the logits' activation (logits_out): an action range never reaches them
-        pa.obs_dim = cfg->obs_dim;
         mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_SAMPLE_ROLLOUT_HEADS(true, 16); else MPG_SAMPLE_ROLLOUT_HEADS(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, 0.f, sample_seed, sample_ctr);
-        pa.out_tanh = cfg->policy_out_act == MPG_ACT_TANH;
-        mpg_prof_begin(mpg_prof_of(cfg), 2, s);
-        if (pa.pack) MPG_SAMPLE_ROLLOUT_HEADS(true, 6); else MPG_SAMPLE_ROLLOUT_HEADS(false, 6);
-    }
-#undef MPG_SAMPLE_ROLLOUT_HEADS
-#undef MPG_SAMPLE_ROLLOUT_LAUNCH
+        auto launch = [&](auto sq) {
+            hipLaunchKernelGGL((k_worker_sample_rollout<decltype(pk)::value, decltype(in)::value, decltype(sq)::value>), dim3(blocks),
+                               dim3(mlp::NTHREAD), 0, s, pa, n, iters, state, obs_io, act_out, ring, capacity, next_idx,
+                               MPG_KEY_CTR(env_seed, env_ctr), done_out, range, log_r);
+        };
+        if (squash) launch(std::true_type{}); else launch(std::false_type{});
+    });
     mpg_prof_end(mpg_prof_of(cfg), 2, s);
     MPG_CHECK_LAUNCH("mpg_worker_sample_rollout");
     return MPG_OK;
@@ -1590,20 +1412,10 @@ extern "C" int mpg_eval_rollout(const mpg_cfg_t* cfg, const float* policy_params
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_eval_rollout: tanh policy with an action range");
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
-#define MPG_EVAL_ROLLOUT_LAUNCH(PK, IN)                                                                                              \
-    hipLaunchKernelGGL((k_eval_rollout<PK, IN>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps, state, obs_io, obs_traj, act_traj, \
-                       rew_traj, done_out, done_intended_out)
-    if (cfg->obs_dim > 6) {
-        worker_policy::WideArgs pa;
-        fill_policy_args(pa, 16, cfg, policy_params, 0.f, 0, 0);
-        pa.obs_dim = cfg->obs_dim;
-        if (pa.pack) MPG_EVAL_ROLLOUT_LAUNCH(true, 16); else MPG_EVAL_ROLLOUT_LAUNCH(false, 16);
-    } else {
-        worker_policy::Args pa;
-        fill_policy_args(pa, 8, cfg, policy_params, 0.f, 0, 0);
-        if (pa.pack) MPG_EVAL_ROLLOUT_LAUNCH(true, 6); else MPG_EVAL_ROLLOUT_LAUNCH(false, 6);
-    }
-#undef MPG_EVAL_ROLLOUT_LAUNCH
+    with_policy_args(cfg, policy_params, 0.f, 0, 0, [&](auto pk, auto in, const auto& pa) {
+        hipLaunchKernelGGL((k_eval_rollout<decltype(pk)::value, decltype(in)::value>), dim3(blocks), dim3(mlp::NTHREAD), 0, s, pa, n, steps,
+                           state, obs_io, obs_traj, act_traj, rew_traj, done_out, done_intended_out);
+    });
     MPG_CHECK_LAUNCH("mpg_eval_rollout");
     return MPG_OK;
 }
