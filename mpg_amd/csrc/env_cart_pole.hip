@@ -113,7 +113,7 @@ __device__ __forceinline__ float explore(float y, float sigma, long gr, uint32_t
     return y;
 }
 // Row gr's action from its logits l[2]: element gr of the stream mpg_normal_fill(n, key, counter (c1, c2)) writes - Philox block gr / 4,
-// pair (gr / 2) % 2, the even or the odd element of the pair - and k_row_sums<SquashRow>'s row body on it.  The log-density is not
+// pair (gr / 2) % 2, the even or the odd element of the pair - and k_row_sums<HeadRow<SquashedHead>>'s row body on it.  The log-density is not
 // kept: the worker discards it and the ring has no column for it.
 __device__ __forceinline__ float sample(const SampleArgs& a, const float* l, int gr, uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2) {
     float z_even, z_odd;
@@ -411,7 +411,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_env_rollout_pendulum(const 
 
 // The worker rollout's `iters` iterations for the tanh-squashed Gaussian policy (SAC with an action range, worker.py:96: the action IS
 // the sample): `iters` consecutive triples of mpg_normal_fill(n, sample key, sample counter + it), mpg_policy_sample_squashed
-// (k_forward<4, 2, PK, 1> and k_row_sums<SquashRow>) and k_cp_step_store_reset in ONE launch.  Between the pass and the env step the
+// (k_forward<4, 2, PK, 1> and k_row_sums<HeadRow<SquashedHead>>) and k_cp_step_store_reset in ONE launch.  Between the pass and the env step the
 // row's two logits come to its env lane through sLogit, the lane draws element i of the iteration's stream and forms a = range *
 // tanh(mean + sigma * eps) (cp_policy::sample), which goes to step_agent in a register.
 template <bool PK>

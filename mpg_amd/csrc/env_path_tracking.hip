@@ -143,7 +143,7 @@ __device__ __forceinline__ void group(const typename args_of<IN>::type& a, int r
     if (a.status && saw_nan) atomicOr(a.status, MPG_STATUS_NAN);
 }
 
-// One 16-row group of mpg_policy_sample on the worker's own draw: the four logits of every row, then k_row_sums<GaussRow>'s row body
+// One 16-row group of mpg_policy_sample on the worker's own draw: the four logits of every row, then k_row_sums<HeadRow<PlainHead>>'s row body
 // (gauss::gauss_row) on eps = elements 2 gr, 2 gr + 1 of the stream mpg_normal_fill writes for (a.k0 .. a.c2).  The logits go through
 // sLogit [16][4] to the first of the row's four lanes, which draws, samples and leaves the action in act_out, the log-density in
 // logp_out (nullable) and the action in sAct [16][2] for the env lanes: LDS is in order within a wave.  a.sigma is not read.
@@ -206,8 +206,8 @@ __device__ __forceinline__ float explore(float sigma, int rows, long g, float* s
     return y;
 }
 // Row gr's action from its four logits l[4] (mean | log-std), by the first of the row's four lanes: elements 2 gr and 2 gr + 1 of the
-// stream mpg_normal_fill(2 n, key, counter (c1, c2)) writes - sample_group's draw - and k_row_sums<GaussRow>'s row body, or with SQ
-// k_row_sums<SquashRow>'s (gauss::squash_row under `range` and the host-formed log_r).  The log-density is not kept: the worker
+// stream mpg_normal_fill(2 n, key, counter (c1, c2)) writes - sample_group's draw - and k_row_sums<HeadRow<PlainHead>>'s row body, or with SQ
+// k_row_sums<HeadRow<SquashedHead>>'s (gauss::squash_row under `range` and the host-formed log_r).  The log-density is not kept: the worker
 // discards it and the ring has no column for it.
 template <bool SQ>
 __device__ __forceinline__ void sample_act(const float* l, long gr, float range, float log_r, uint32_t k0, uint32_t k1, uint32_t c1,
@@ -719,7 +719,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_policy_step_store_reset(con
 }
 
 // OffPolicyWorker.sample's inner body for a STOCHASTIC policy (worker.py:95-112 with the action sampled from the Gaussian head, no
-// explore_sigma) in ONE launch: mpg_normal_fill + mpg_policy_sample (k_forward<IN, 4>, k_row_sums<GaussRow>) + mpg_env_step_store_reset
+// explore_sigma) in ONE launch: mpg_normal_fill + mpg_policy_sample (k_forward<IN, 4>, k_row_sums<HeadRow<PlainHead>>) + mpg_env_step_store_reset
 // are four launches of at most one wave per CU each; here wave 0 draws and samples behind the four-logit pass
 // (worker_policy::sample_group) and then steps the agents as in k_policy_step_store_reset.  No spare workgroups: there is no
 // pre-gathered draw.  IN as in k_policy_step_store_reset.
@@ -928,7 +928,7 @@ __global__ void __launch_bounds__(mlp::NTHREAD, 2) k_worker_rollout(const typena
 
 // The same `iters` iterations for a STOCHASTIC policy (SAC; worker.py:96: the action IS the sample, no explore_sigma): `iters`
 // consecutive triples of mpg_normal_fill(2 n, sample key, sample counter + it), mpg_policy_sample (SQ: mpg_policy_sample_squashed -
-// k_forward<IN, 4, PK, 1> and k_row_sums<GaussRow / SquashRow>) and mpg_env_step_store_reset in ONE launch; without SQ that is `iters`
+// k_forward<IN, 4, PK, 1> and k_row_sums<HeadRow<PlainHead / SquashedHead>>) and mpg_env_step_store_reset in ONE launch; without SQ that is `iters`
 // k_policy_sample_step_store_reset launches.  The policy's registers hold all four output columns.  Between the pass and the env step
 // the four logits of a row lie in sLogit, left by the row's own four lanes; the first of them draws elements 2 i, 2 i + 1 of the
 // iteration's stream, forms the action (worker_policy::sample_act) and leaves it in sAct for the four: LDS is in order within a wave.

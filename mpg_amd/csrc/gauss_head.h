@@ -1,6 +1,6 @@
 // Gaussian policy head (policy.py:179-204: MultivariateNormalDiag(mean, exp(clip(log_std, -5, 1))); with action_range None no bijector,
 // with one the tanh-squashed sibling further down) on the 2 act_dim logits of the policy pass, and the element function of the library's standard-normal stream.  Shared by the two
-// translation units that evaluate the head - learner_api.hip (k_row_sums<GaussRow>, k_sac_dlogits) and env_path_tracking.hip (the
+// translation units that evaluate the head - learner_api.hip (k_row_sums<HeadRow<Head>>, k_sac_dlogits<Head, Temp>) and env_path_tracking.hip (the
 // stochastic worker launch) - which must agree bit for bit: include it where contraction is allowed (env_path_tracking.hip: inside
 // its `#pragma clang fp contract(fast)` block), so that both compile these expressions under the same rule.
 #pragma once
@@ -89,9 +89,44 @@ __device__ __forceinline__ float squash_logp(int ad, float log_r, const float* _
     return (lp - ldj) - (float)ad * log_r;
 }
 
+// ---- the head as a type: what a kernel that serves both heads is instantiated with.  row / logp are the functions above; dsample is
+// dL/du of loss = mean(alpha * logp - qmin) at the pre-bijector sample u = mean + sigma * eps of one column, given
+// ga = d(-inv_b qmin)/da.  Plain: a = u, so ga, and u is not looked at (READS_U: the caller need not form it).  Squashed: a = R tanh(u)
+// and logp = ... - log(1 - tanh(u)^2) - log R, so ga R (1 - t^2) + 2 alpha inv_b t (t = tanh u).
+struct PlainHead {
+    static constexpr bool READS_U = false;
+    __device__ __forceinline__ float row(int ad, const float* __restrict__ l, const float* __restrict__ e, float* __restrict__ a) const {
+        return gauss_row(ad, l, e, a);
+    }
+    __device__ __forceinline__ float logp(int ad, const float* __restrict__ l, const float* __restrict__ e) const { return gauss_logp(ad, l, e); }
+    __device__ __forceinline__ float dsample(float ga, float, float, float) const { return ga; }
+};
+struct SquashedHead {
+    static constexpr bool READS_U = true;
+    float range, log_r;
+    __device__ __forceinline__ float row(int ad, const float* __restrict__ l, const float* __restrict__ e, float* __restrict__ a) const {
+        return squash_row(ad, range, log_r, l, e, a);
+    }
+    __device__ __forceinline__ float logp(int ad, const float* __restrict__ l, const float* __restrict__ e) const {
+        return squash_logp(ad, log_r, l, e);
+    }
+    __device__ __forceinline__ float dsample(float ga, float u, float alpha, float inv_b) const {
+        return ga * range * sech2(u) + 2.f * alpha * inv_b * tanhf(u);
+    }
+};
+
 // alpha = exp(log_alpha) of the learned temperature, under sigma_of's rule and for its reason: the correctly rounded float32
 // exponential, which anyone can re-form on the host bit for bit
 __device__ __forceinline__ float alpha_of(const float* __restrict__ log_alpha) { return (float)exp((double)*log_alpha); }
+// ---- the temperature as a type: the caller's number, or the learned one read on the device
+struct FixedTemp {
+    float alpha;
+    __device__ __forceinline__ float operator()() const { return alpha; }
+};
+struct DeviceTemp {
+    const float* __restrict__ log_alpha;
+    __device__ __forceinline__ float operator()() const { return alpha_of(log_alpha); }
+};
 
 // Elements 4 q + 2 pair and 4 q + 2 pair + 1 of the stream mpg_normal_fill writes for (key, counter): Philox block q, Box-Muller on
 // the words (v[0], v[1]) (pair 0) or (v[2], v[3]) (pair 1) - the cosine for the even element, the sine for the odd one.  k_normal_fill

@@ -47,7 +47,8 @@ __global__ void k_nstep(int rows, int n, const float* __restrict__ rewards, cons
 
 // the same with the bootstrap value clipped to [lo, hi] first (the pendulum's target, mpg_learner.py:163-164: tf.clip_by_value =
 // minimum(maximum(q, lo), hi), which hands a NaN on - fmaxf / fminf would return the bound - so the comparisons are written out).
-// A kernel of its own: k_nstep keeps its instructions.
+// A kernel of its own: as one template over the clip, whichever of the two reads q[i] at the other's place in the statement order
+// loses its instructions (EXPERIMENTS.md, "One policy head and one temperature type").
 __global__ void k_nstep_clipped(int rows, int n, const float* __restrict__ rewards, const float* __restrict__ q, float shift,
                                 float scale, float gamma, float lo, float hi, float* __restrict__ y) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -66,7 +67,7 @@ __global__ void k_nstep_clipped(int rows, int n, const float* __restrict__ rewar
 // of row i and its terms added into s[NS].
 constexpr int ERR_PARTS = 64;
 constexpr int ERR_MB_MIN_ROWS = 8192;          // below: the one-block form (one launch instead of two)
-// a row body may also carry scale1(), what its finished SECOND sum is multiplied by (GaussRow2); without one it is reported as it is
+// a row body may also carry scale1(), what its finished SECOND sum is multiplied by (HeadRow2); without one it is reported as it is
 template <class Row, class = void>
 struct Scale1 {
     static constexpr bool ANY = false;
@@ -232,30 +233,34 @@ __global__ void k_sum_action_grad(int rows, int od, int ad, const float* __restr
     ga[i] = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
 }
 
-// ---- Gaussian policy head (gauss_head.h: the clip bounds, sigma_of, gauss_row) on the four logits of the policy pass, one thread per
-// row ---------------------------------------------------------------------------------------------------------------------------
+// ---- the policy head (gauss_head.h: PlainHead - the diagonal Gaussian on the logits of the policy pass - or SquashedHead, the same
+// under the bijectors of an action range), one thread per row -----------------------------------------------------------------------
 // logits [rows][2 ad], eps [rows][ad] -> act [rows][ad], logp [rows]; the sum of logp over the rows, where one is wanted
-struct GaussRow {
+template <class Head>
+struct HeadRow {
     int ad;
+    Head head;
     const float *__restrict__ logits, *__restrict__ eps;
     float *__restrict__ act, *__restrict__ logp;
     static constexpr int NS = 1;
     static constexpr bool SUM_OPTIONAL = true;
     __host__ __device__ float scale0() const { return 1.f; }
     __device__ __forceinline__ void operator()(int i, float* s) const {
-        const float lp = gauss_row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
+        const float lp = head.row(ad, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
         logp[i] = lp;
         s[0] += lp;
     }
 };
 
-// GaussRow for the policy draw and, in the same pass over the same logits, the temperature's share of the batch (sac.py:138-148): the
-// head's log-density under a SECOND draw eps_alpha (the reference's third compute_action: the same policy on the same observations,
-// only the noise differs - so no third network pass), with target_entropy added per row.  The second sum is finished as
-// -inv_b * sum_rows(logp_alpha + target_entropy): this rank's share of d alpha_loss / d log_alpha.  The clipped log-std of a NaN logit
-// is a bound (fmaxf / fminf return the other operand), so logp_alpha is finite whatever the policy produced.
-struct GaussRow2 {
+// HeadRow for the policy draw and, in the same pass over the same logits, the temperature's share of the batch (sac.py:138-148): the
+// head's log-density under a SECOND draw eps_alpha (the reference's third compute_action: the same policy on the same observations
+// through the same bijectors, only the noise differs - so no third network pass), with target_entropy added per row.  The second sum is
+// finished as -inv_b * sum_rows(logp_alpha + target_entropy): this rank's share of d alpha_loss / d log_alpha.  The clipped log-std of a
+// NaN logit is a bound (fmaxf / fminf return the other operand), so the plain logp_alpha is finite whatever the policy produced.
+template <class Head>
+struct HeadRow2 {
     int ad;
+    Head head;
     const float *__restrict__ logits, *__restrict__ eps, *__restrict__ eps_alpha;
     float target_entropy, inv_b;
     float *__restrict__ act, *__restrict__ logp;
@@ -265,118 +270,50 @@ struct GaussRow2 {
     __host__ __device__ float scale1() const { return -inv_b; }
     __device__ __forceinline__ void operator()(int i, float* s) const {
         const float* l = logits + (size_t)i * 2 * ad;
-        const float lp = gauss_row(ad, l, eps + (size_t)i * ad, act + (size_t)i * ad);
+        const float lp = head.row(ad, l, eps + (size_t)i * ad, act + (size_t)i * ad);
         logp[i] = lp;
         s[0] += lp;
-        s[1] += gauss_logp(ad, l, eps_alpha + (size_t)i * ad) + target_entropy;
+        s[1] += head.logp(ad, l, eps_alpha + (size_t)i * ad) + target_entropy;
     }
 };
 
-// soft target (sac.py:78-79): y = (rew + shift) * scale + gamma * (min(q1, q2) - alpha * logp)
+// soft target (sac.py:78-79): y = (rew + shift) * scale + gamma * (min(q1, q2) - alpha * logp), alpha = temp() (gauss_head.h)
+template <class Temp>
 __global__ void k_sac_combine(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
-                              const float* __restrict__ logp, float alpha, float shift, float scale, float gamma, float* __restrict__ y) {
+                              const float* __restrict__ logp, const Temp temp, float shift, float scale, float gamma, float* __restrict__ y) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const float alpha = temp();
     y[i] = (rew[i] + shift) * scale + gamma * (fminf(q1[i], q2[i]) - alpha * logp[i]);
 }
 
-// the same with the learned temperature read on the device (alpha_of, gauss_head.h): a sibling, so that k_sac_combine keeps its code
-__global__ void k_sac_combine_auto(int n, const float* __restrict__ rew, const float* __restrict__ q1, const float* __restrict__ q2,
-                                   const float* __restrict__ logp, const float* __restrict__ log_alpha, float shift, float scale, float gamma,
-                                   float* __restrict__ y) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float alpha = alpha_of(log_alpha);
-    y[i] = (rew[i] + shift) * scale + gamma * (fminf(q1[i], q2[i]) - alpha * logp[i]);
-}
-
-// dL/dlogits [rows][2 ad] of loss = mean(alpha * logp - qmin) (sac.py:128) with a = mean + sigma * eps, logp = sum(-0.5 eps^2 - log_std - c):
+// dL/dlogits [rows][2 ad] of loss = mean(alpha * logp - qmin) (sac.py:128) with u = mean + sigma * eps, a = u or R tanh(u):
 // ga_k = dx1[row][od + k] + dx2[row][od + k] is d(-inv_b qmin)/da_k (the critics' input gradients under Td3DyRow's dy);
-// mean column k: ga_k; log-std column k: ga_k sigma_k eps_k - alpha inv_b, and ZERO where the clip is active - strictly outside
-// [-5, 1]: clip_by_value passes the gradient at the bounds themselves (the stand-in's clamp, and TF's own rule)
+// mean column k: du_k = head.dsample (PlainHead: ga_k); log-std column k: du_k sigma_k eps_k - alpha inv_b, and ZERO where the clip is
+// active - strictly outside [-5, 1]: clip_by_value passes the gradient at the bounds themselves (the stand-in's clamp, and TF's own
+// rule).  The policy's gradient does not flow into a learned temperature (sac.py:127-128).
+// The head and the temperature travel as one argument, in which an empty head takes no room (as a kernel argument of its own it would
+// take a slot, and move the ones behind it).
+template <class Head, class Temp>
+struct HeadTemp {
+    Temp temp;
+    [[no_unique_address]] Head head;
+};
+template <class Head, class Temp>
 __global__ void k_sac_dlogits(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
-                              const float* __restrict__ eps, const float* __restrict__ logits, float alpha, float inv_b,
+                              const float* __restrict__ eps, const float* __restrict__ logits, const HeadTemp<Head, Temp> ht, float inv_b,
                               float* __restrict__ dlogits) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * ad) return;
+    const float alpha = ht.temp();
     const int row = i / ad, k = i % ad;
     const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
     const float raw = logits[(long)row * 2 * ad + ad + k];
     const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
     const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-    dlogits[(long)row * 2 * ad + k] = ga;
-    dlogits[(long)row * 2 * ad + ad + k] = inside ? ga * sigma * eps[i] - alpha * inv_b : 0.f;
-}
-
-// k_sac_dlogits with the learned temperature read on the device (the policy's gradient does not flow into log_alpha, sac.py:127-128)
-__global__ void k_sac_dlogits_auto(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
-                                   const float* __restrict__ eps, const float* __restrict__ logits, const float* __restrict__ log_alpha,
-                                   float inv_b, float* __restrict__ dlogits) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * ad) return;
-    const float alpha = alpha_of(log_alpha);
-    const int row = i / ad, k = i % ad;
-    const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
-    const float raw = logits[(long)row * 2 * ad + ad + k];
-    const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
-    const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-    dlogits[(long)row * 2 * ad + k] = ga;
-    dlogits[(long)row * 2 * ad + ad + k] = inside ? ga * sigma * eps[i] - alpha * inv_b : 0.f;
-}
-
-// ---- the tanh-squashed head (gauss_head.h squash_row): GaussRow / GaussRow2 / k_sac_dlogits under an action range.  Siblings, so that
-// every kernel above keeps its code; the bijectors' correction rides in the same launches ------------------------------------------------
-struct SquashRow {
-    int ad;
-    float range, log_r;
-    const float *__restrict__ logits, *__restrict__ eps;
-    float *__restrict__ act, *__restrict__ logp;
-    static constexpr int NS = 1;
-    static constexpr bool SUM_OPTIONAL = true;
-    __host__ __device__ float scale0() const { return 1.f; }
-    __device__ __forceinline__ void operator()(int i, float* s) const {
-        const float lp = squash_row(ad, range, log_r, logits + (size_t)i * 2 * ad, eps + (size_t)i * ad, act + (size_t)i * ad);
-        logp[i] = lp;
-        s[0] += lp;
-    }
-};
-// (the temperature's sum takes the SQUASHED log-density under the further draw: the third compute_action goes through the same bijectors)
-struct SquashRow2 {
-    int ad;
-    float range, log_r;
-    const float *__restrict__ logits, *__restrict__ eps, *__restrict__ eps_alpha;
-    float target_entropy, inv_b;
-    float *__restrict__ act, *__restrict__ logp;
-    static constexpr int NS = 2;
-    static constexpr bool SUM_OPTIONAL = false;
-    __host__ __device__ float scale0() const { return 1.f; }
-    __host__ __device__ float scale1() const { return -inv_b; }
-    __device__ __forceinline__ void operator()(int i, float* s) const {
-        const float* l = logits + (size_t)i * 2 * ad;
-        const float lp = squash_row(ad, range, log_r, l, eps + (size_t)i * ad, act + (size_t)i * ad);
-        logp[i] = lp;
-        s[0] += lp;
-        s[1] += squash_logp(ad, log_r, l, eps_alpha + (size_t)i * ad) + target_entropy;
-    }
-};
-
-// k_sac_dlogits under the bijectors: a = R tanh(u), logp = ... - log(1 - tanh(u)^2) - log R with u = mean + sigma * eps, so
-// dL/du_k = ga_k R (1 - t_k^2) + 2 alpha inv_b t_k (t = tanh u); mean column: dL/du; log-std column: dL/du sigma eps - alpha inv_b, zero
-// where the clip is active.  AUTO: the learned temperature read on the device (alpha_of) - `alpha` is then not looked at.
-template <bool AUTO>
-__global__ void k_sac_dlogits_squashed(int rows, int od, int ad, const float* __restrict__ dx1, const float* __restrict__ dx2,
-                                       const float* __restrict__ eps, const float* __restrict__ logits, float alpha,
-                                       const float* __restrict__ log_alpha, float range, float inv_b, float* __restrict__ dlogits) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * ad) return;
-    if constexpr (AUTO) alpha = alpha_of(log_alpha);
-    const int row = i / ad, k = i % ad;
-    const float ga = dx1[(long)row * (od + ad) + od + k] + dx2[(long)row * (od + ad) + od + k];
-    const float raw = logits[(long)row * 2 * ad + ad + k];
-    const bool inside = raw >= LOG_STD_MIN && raw <= LOG_STD_MAX;
-    const float sigma = sigma_of(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-    const float u = mul_then_add(sigma, eps[i], logits[(long)row * 2 * ad + k]);
-    const float du = ga * range * sech2(u) + 2.f * alpha * inv_b * tanhf(u);
+    float u = 0.f;          // (left to the optimiser, an unread u still changes the plain kernels' schedule and registers)
+    if constexpr (Head::READS_U) u = mul_then_add(sigma, eps[i], logits[(long)row * 2 * ad + k]);
+    const float du = ht.head.dsample(ga, u, alpha, inv_b);
     dlogits[(long)row * 2 * ad + k] = du;
     dlogits[(long)row * 2 * ad + ad + k] = inside ? du * sigma * eps[i] - alpha * inv_b : 0.f;
 }
@@ -459,54 +396,80 @@ int policy_logits(const mpg_cfg_t* c, const float* params, int rows, const float
     return launch_forward(c, params, c->obs_dim, 2 * c->act_dim, 2 * c->act_dim, rows, policy_x(c, obs), logits_out(c), logits, 2 * c->act_dim,
                           h1, h2, s);
 }
-// the head on `logits`: act, logp and (nullable) the sum of logp; `squash`: under the bijectors of cfg->action_range
-int gauss_head(const mpg_cfg_t* c, int rows, const float* logits, const float* eps, float* act, float* logp, float* logp_sum, float* parts,
-               hipStream_t s, bool squash = false) {
-    if (squash)
-        return launch_row_sums("k_row_sums<SquashRow>", SquashRow{c->act_dim, c->action_range, log_range(c->action_range), logits, eps, act, logp},
-                               rows, parts, logp_sum, nullptr, nullptr, s);
-    return launch_row_sums("k_row_sums<GaussRow>", GaussRow{c->act_dim, logits, eps, act, logp}, rows, parts, logp_sum, nullptr, nullptr, s);
-}
-
-// The policy gradient through the critic(s), td3.py:120-134 / ndpg.py:174-186 / sac.py:119-136: policy forward (eps: all four logits and
-// the head's sample in place of the mean), the critics' forwards, dL/dq and the statistic sums, the critics' backwards down to dx, the
-// policy's output gradient, the policy's backward and weight gradient.  q2 null: one critic (DPG), whose dx is dQ/da as it stands; eps
-// (with alpha, logp_sum) non-null: the Gaussian head, two critics only (SAC).  `at` non-null: the learned temperature - alpha is
-// exp(*at->log_alpha) read on the device, and the head's pass also sums the temperature's gradient into at->alpha_grad (GaussRow2).
+// The stochastic head of a call: the draws, which head, and the temperature - the caller's number, or (learned) exp(*log_alpha) read on
+// the device.  The policy gradient under a learned temperature also sums the temperature's own gradient in the head's pass (AutoTemp).
 struct AutoTemp {
-    const float *log_alpha, *eps_alpha;
+    const float* eps_alpha;
     float target_entropy;
     float* alpha_grad;
 };
+struct HeadSpec {
+    const float* eps;
+    bool squash, learned;
+    float alpha;                  // !learned (0 otherwise: the refusals' alpha test passes)
+    const float* log_alpha;       // learned
+    AutoTemp at;                  // learned, policy gradient only
+};
+HeadSpec fixed_temp(const float* eps, bool squash, float alpha) { return {eps, squash, false, alpha, nullptr, {}}; }
+HeadSpec learned_temp(const float* eps, bool squash, const float* log_alpha, AutoTemp at = {}) { return {eps, squash, true, 0.f, log_alpha, at}; }
+
+// f(the head of the call) / f(its temperature), as the types the kernels are instantiated with (gauss_head.h)
+template <class F>
+int with_head(const mpg_cfg_t* c, const HeadSpec& h, F f) {
+    return h.squash ? f(SquashedHead{c->action_range, log_range(c->action_range)}) : f(PlainHead{});
+}
+template <class F>
+int with_temp(const HeadSpec& h, F f) {
+    return h.learned ? f(DeviceTemp{h.log_alpha}) : f(FixedTemp{h.alpha});
+}
+// the refusal of an entry point's family: the plain Gaussian head's, or the squashed one's
+int head_refusal(bool squash, const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
+    return squash ? squash_refusal(entry, cfg, pointers, rows, alpha) : gauss_refusal(entry, cfg, pointers, rows, alpha);
+}
+template <class Describe, class... A>
+size_t head_workspace_bytes(bool squash, const char* entry, const mpg_cfg_t* cfg, int rows, Describe describe, A... more) {
+    return head_refusal(squash, entry, cfg, true, rows, 0.f) ? 0 : measured(describe, cfg, rows, more...);
+}
+
+// the head on `logits`: act, logp and (nullable) the sum of logp
+int head_rows(const mpg_cfg_t* c, const HeadSpec& h, int rows, const float* logits, float* act, float* logp, hipStream_t s) {
+    return with_head(c, h, [&](auto head) {
+        return launch_row_sums("k_row_sums<HeadRow>", HeadRow<decltype(head)>{c->act_dim, head, logits, h.eps, act, logp}, rows, nullptr, nullptr,
+                               nullptr, nullptr, s);
+    });
+}
+
+// The policy gradient through the critic(s), td3.py:120-134 / ndpg.py:174-186 / sac.py:119-136: policy forward (a head: all 2 act_dim
+// logits and the head's sample in place of the mean), the critics' forwards, dL/dq and the statistic sums, the critics' backwards down
+// to dx, the policy's output gradient, the policy's backward and weight gradient.  q2 null: one critic (DPG), whose dx is dQ/da as it
+// stands; Head other than NoHead (with h, temp, logp_sum): the stochastic head, two critics only (SAC).  h.at.eps_alpha non-null: the
+// head's pass also sums the learned temperature's gradient into h.at.alpha_grad (HeadRow2).
+struct NoHead {};          // the deterministic policy of TD3 and DPG
+template <class Head, class Temp>
 int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
-                const float* eps, float alpha, float inv_b, float* q_sum, float* q_sqsum, float* logp_sum, float* grad, void* ws,
-                size_t ws_bytes, mpg_stream_t stream, const AutoTemp* at = nullptr, bool squash = false) {
+                const HeadSpec& h, Head head, Temp temp, float inv_b, float* q_sum, float* q_sqsum, float* logp_sum, float* grad, void* ws,
+                size_t ws_bytes, mpg_stream_t stream) {
+    constexpr bool sampled = !std::is_same<Head, NoHead>::value;
     const int n_q = q2 ? 2 : 1;
     Arena ar(ws, ws_bytes);
-    const PolicyGradWs w = policy_grad_ws(ar, cfg, rows, n_q, eps != nullptr);
+    const PolicyGradWs w = policy_grad_ws(ar, cfg, rows, n_q, sampled);
     if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
     hipStream_t s = mpg_stream(stream);
-    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, ou = eps ? 2 * ad : ad;
+    const int od = cfg->obs_dim, ad = cfg->act_dim, qin = od + ad, ou = sampled ? 2 * ad : ad;
     // (the backward of the logits pass undoes the logits' output rule - the plain activation on every column: with an action range
     // policy_out is the DETERMINISTIC output rule, range * tanh on the mean, which the squashed head applies itself)
-    const OutSpec po = squash ? logits_out(cfg) : policy_out(cfg);
+    const OutSpec po = std::is_same<Head, SquashedHead>::value ? logits_out(cfg) : policy_out(cfg);
     const XSpec xp = policy_x(cfg, obs);
     const float* const q[2] = {q1, q2};
     int rc;
-    if (eps) {
+    if constexpr (sampled) {
         rc = policy_logits(cfg, policy, rows, obs, w.logits, w.hp1, w.hp2, s);
         if (rc) return rc;
-        if (at && squash)
-            rc = launch_row_sums("k_row_sums<SquashRow2>",
-                                 SquashRow2{cfg->act_dim, cfg->action_range, log_range(cfg->action_range), w.logits, eps, at->eps_alpha,
-                                            at->target_entropy, inv_b, w.a, w.logp},
-                                 rows, w.lparts, logp_sum, at->alpha_grad, nullptr, s);
-        else if (at)
-            rc = launch_row_sums("k_row_sums<GaussRow2>",
-                                 GaussRow2{cfg->act_dim, w.logits, eps, at->eps_alpha, at->target_entropy, inv_b, w.a, w.logp}, rows, w.lparts,
-                                 logp_sum, at->alpha_grad, nullptr, s);
-        else
-            rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, logp_sum, w.lparts, s, squash);
+        rc = h.at.eps_alpha ? launch_row_sums("k_row_sums<HeadRow2>",
+                                              HeadRow2<Head>{ad, head, w.logits, h.eps, h.at.eps_alpha, h.at.target_entropy, inv_b, w.a, w.logp},
+                                              rows, w.lparts, logp_sum, h.at.alpha_grad, nullptr, s)
+                            : launch_row_sums("k_row_sums<HeadRow>", HeadRow<Head>{ad, head, w.logits, h.eps, w.a, w.logp}, rows, w.lparts,
+                                              logp_sum, nullptr, nullptr, s);
     } else {
         rc = policy_forward(cfg, policy, rows, xp, po, w.a, w.hp1, w.hp2, s);
     }
@@ -532,29 +495,80 @@ int policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, co
     const float* g = w.dx[0] + od;
     int ldg = qin;
     if (n_q == 2) {
-        if (squash && at)
-            hipLaunchKernelGGL(k_sac_dlogits_squashed<true>, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps,
-                               w.logits, 0.f, at->log_alpha, cfg->action_range, inv_b, w.g);
-        else if (squash)
-            hipLaunchKernelGGL(k_sac_dlogits_squashed<false>, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps,
-                               w.logits, alpha, (const float*)nullptr, cfg->action_range, inv_b, w.g);
-        else if (at)
-            hipLaunchKernelGGL(k_sac_dlogits_auto, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits,
-                               at->log_alpha, inv_b, w.g);
-        else if (eps)
-            hipLaunchKernelGGL(k_sac_dlogits, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], eps, w.logits, alpha,
-                               inv_b, w.g);
+        if constexpr (sampled)
+            hipLaunchKernelGGL((k_sac_dlogits<Head, Temp>), dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], h.eps,
+                               w.logits, HeadTemp<Head, Temp>{temp, head}, inv_b, w.g);
         else
             hipLaunchKernelGGL(k_sum_action_grad, dim3((rows * ad + 255) / 256), dim3(256), 0, s, rows, od, ad, w.dx[0], w.dx[1], w.g);
-        MPG_CHECK_LAUNCH(eps ? "k_sac_dlogits" : "k_sum_action_grad");
+        MPG_CHECK_LAUNCH(sampled ? "k_sac_dlogits" : "k_sum_action_grad");
         g = w.g;
         ldg = ou;
     }
-    rc = launch_backward(cfg, policy, od, 2 * ad, ou, rows, g, ldg, eps ? w.logits : w.a, ou, po.out_tanh, po.out_scale, w.hp1, w.hp2,
+    rc = launch_backward(cfg, policy, od, 2 * ad, ou, rows, g, ldg, sampled ? w.logits : w.a, ou, po.out_tanh, po.out_scale, w.hp1, w.hp2,
                          thin ? nullptr : w.dz1, w.dz2, w.dz3, nullptr, 0, s, thin ? &xp : nullptr, thin ? w.dz1 : nullptr);
     if (rc) return rc;
     return launch_wgrad(cfg, od, 2 * ad, ou, rows, xp, w.hp1, w.hp2, w.dz1, w.dz2, w.dz3, inv_b, grad, w.slabs, s, thin, thin ? w.dz1 : nullptr,
                         thin ? backward_thin_parts(rows) : 0, fin.part ? &fin : nullptr);
+}
+
+// mpg_policy_sample / mpg_policy_sample_squashed
+int policy_sample(const char* entry, bool squash, const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps,
+                  float* act_out, float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = head_refusal(squash, entry, cfg, policy && obs && eps && act_out && logp_out && ws, rows, 0.f);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const PolicySampleWs w = policy_sample_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    float* logits = logits_out ? logits_out : w.logits;
+    rc = policy_logits(cfg, policy, rows, obs, logits, nullptr, nullptr, s);
+    if (rc) return rc;
+    return head_rows(cfg, fixed_temp(eps, squash, 0.f), rows, logits, act_out, logp_out, s);
+}
+// mpg_sac_targets and its _auto / _squashed forms
+int sac_targets(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                const float* obs_tp1, const HeadSpec& h, float* y, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    int rc = head_refusal(h.squash, entry, cfg, policy && q1t && q2t && rew && obs_tp1 && h.eps && (h.log_alpha || !h.learned) && y && ws, rows,
+                          h.alpha);
+    if (rc) return rc;
+    Arena ar(ws, ws_bytes);
+    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
+    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
+    hipStream_t s = mpg_stream(stream);
+    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);          // sac.py:71
+    if (rc) return rc;
+    rc = head_rows(cfg, h, rows, w.logits, w.a, w.logp, s);
+    if (rc) return rc;
+    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
+    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);                     // :73
+    if (rc) return rc;
+    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);                     // :74
+    if (rc) return rc;
+    return with_temp(h, [&](auto temp) -> int {
+        hipLaunchKernelGGL(k_sac_combine<decltype(temp)>, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, temp,
+                           cfg->rew_shift, cfg->rew_scale, cfg->gamma, y);                  // :78-79
+        MPG_CHECK_LAUNCH("k_sac_combine");
+        return MPG_OK;
+    });
+}
+// mpg_sac_policy_grad and its _auto / _squashed forms: mpg_td3_policy_grad with the sampled action in place of the mean - the policy
+// pass keeps all its logits, the head samples, the critics' input gradients come back as in TD3 (the same dy rows: the gradient flows
+// through the smaller critic), k_sac_dlogits turns them into the output gradient, and the policy's backward / weight gradient run on
+// 2 act_dim outputs (the pendulum's two take the THIN backward like TD3's two actions; PathTracking's four the plain one)
+int sac_policy_grad(const char* entry, const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                    const HeadSpec& h, float inv_b, float* qmin_sum, float* qmin_sqsum, float* logp_sum, float* grad, void* ws, size_t ws_bytes,
+                    mpg_stream_t stream) {
+    const bool temp_ok = !h.learned || (h.log_alpha && h.at.eps_alpha && h.at.alpha_grad);
+    int rc = head_refusal(h.squash, entry, cfg, policy && q1 && q2 && obs && h.eps && temp_ok && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
+                          rows, h.alpha);
+    if (rc) return rc;
+    MPG_REQUIRE(!h.learned || std::isfinite(h.at.target_entropy), "%s: target_entropy must be finite (got %g)", entry,
+                (double)h.at.target_entropy);
+    return with_head(cfg, h, [&](auto head) {
+        return with_temp(h, [&](auto temp) {
+            return policy_grad(entry, cfg, policy, q1, q2, rows, obs, h, head, temp, inv_b, qmin_sum, qmin_sqsum, logp_sum, grad, ws, ws_bytes, stream);
+        });
+    });
 }
 
 }  // namespace
@@ -750,8 +764,8 @@ extern "C" int mpg_td3_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
                                    float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
     MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && q2 && obs && qmin_sum && qmin_sqsum && grad && ws && rows > 0,
                 "mpg_td3_policy_grad: bad argument");
-    return policy_grad("mpg_td3_policy_grad", cfg, policy_params, q1, q2, rows, obs, nullptr, 0.f, inv_b_global, qmin_sum, qmin_sqsum, nullptr,
-                       grad, ws, ws_bytes, stream);
+    return policy_grad("mpg_td3_policy_grad", cfg, policy_params, q1, q2, rows, obs, HeadSpec{}, NoHead{}, FixedTemp{}, inv_b_global, qmin_sum,
+                       qmin_sqsum, nullptr, grad, ws, ws_bytes, stream);
 }
 
 extern "C" size_t mpg_dpg_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
@@ -767,178 +781,90 @@ extern "C" int mpg_dpg_policy_grad(const mpg_cfg_t* cfg, const float* policy_par
                                    mpg_stream_t stream) {
     MPG_REQUIRE(net_cfg_ok(cfg) && policy_params && q1 && obs && q_sum && q_sqsum && grad && ws && rows > 0,
                 "mpg_dpg_policy_grad: bad argument");
-    return policy_grad("mpg_dpg_policy_grad", cfg, policy_params, q1, nullptr, rows, obs, nullptr, 0.f, inv_b_global, q_sum, q_sqsum, nullptr, grad,
-                       ws, ws_bytes, stream);
+    return policy_grad("mpg_dpg_policy_grad", cfg, policy_params, q1, nullptr, rows, obs, HeadSpec{}, NoHead{}, FixedTemp{}, inv_b_global, q_sum, q_sqsum,
+                       nullptr, grad, ws, ws_bytes, stream);
 }
 
+// ---- SAC: the Gaussian head (PathTracking without an action range) and, as mpg_*_squashed, the tanh-squashed one under
+// cfg->action_range (PathTracking or the inverted pendulum); _auto: the learned temperature, alpha = exp(*log_alpha) read on the device.
+// One body per call (policy_sample, sac_targets, sac_policy_grad above), the same launches and workspaces for every form ----
 extern "C" size_t mpg_policy_sample_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (gauss_refusal("mpg_policy_sample_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(policy_sample_ws, cfg, rows);
+    return head_workspace_bytes(false, "mpg_policy_sample_workspace_bytes", cfg, rows, policy_sample_ws);
 }
-
-namespace {
-// the refusal of an entry point's family: the plain Gaussian head's, or the squashed one's
-int head_refusal(bool squash, const char* entry, const mpg_cfg_t* cfg, bool pointers, int rows, float alpha) {
-    return squash ? squash_refusal(entry, cfg, pointers, rows, alpha) : gauss_refusal(entry, cfg, pointers, rows, alpha);
+extern "C" size_t mpg_policy_sample_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    return head_workspace_bytes(true, "mpg_policy_sample_squashed_workspace_bytes", cfg, rows, policy_sample_ws);
 }
-// mpg_policy_sample / mpg_policy_sample_squashed
-int policy_sample(const char* entry, bool squash, const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps,
-                  float* act_out, float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = head_refusal(squash, entry, cfg, policy && obs && eps && act_out && logp_out && ws, rows, 0.f);
-    if (rc) return rc;
-    Arena ar(ws, ws_bytes);
-    const PolicySampleWs w = policy_sample_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    float* logits = logits_out ? logits_out : w.logits;
-    rc = policy_logits(cfg, policy, rows, obs, logits, nullptr, nullptr, s);
-    if (rc) return rc;
-    return gauss_head(cfg, rows, logits, eps, act_out, logp_out, nullptr, nullptr, s, squash);
+extern "C" size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    return head_workspace_bytes(false, "mpg_sac_targets_workspace_bytes", cfg, rows, sac_targets_ws);
 }
-// mpg_sac_targets and its _auto / _squashed forms (log_alpha non-null: the learned temperature, read on the device)
-int sac_targets(const char* entry, bool squash, const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
-                const float* rew, const float* obs_tp1, const float* eps, bool auto_alpha, float alpha, const float* log_alpha, float* y,
-                void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = head_refusal(squash, entry, cfg, policy && q1t && q2t && rew && obs_tp1 && eps && (log_alpha || !auto_alpha) && y && ws, rows,
-                          auto_alpha ? 0.f : alpha);
-    if (rc) return rc;
-    Arena ar(ws, ws_bytes);
-    const SacTargetsWs w = sac_targets_ws(ar, cfg, rows);
-    if (!ar.fits()) return workspace_too_small(entry, ws_bytes, ar.need);
-    hipStream_t s = mpg_stream(stream);
-    rc = policy_logits(cfg, policy, rows, obs_tp1, w.logits, nullptr, nullptr, s);          // sac.py:71
-    if (rc) return rc;
-    rc = gauss_head(cfg, rows, w.logits, eps, w.a, w.logp, nullptr, nullptr, s, squash);
-    if (rc) return rc;
-    const XSpec xq = critic_x(cfg, obs_tp1, w.a);
-    rc = critic_forward(cfg, q1t, rows, xq, w.q1, nullptr, nullptr, s);                     // :73
-    if (rc) return rc;
-    rc = critic_forward(cfg, q2t, rows, xq, w.q2, nullptr, nullptr, s);                     // :74
-    if (rc) return rc;
-    if (auto_alpha)
-        hipLaunchKernelGGL(k_sac_combine_auto, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, log_alpha, cfg->rew_shift,
-                           cfg->rew_scale, cfg->gamma, y);
-    else
-        hipLaunchKernelGGL(k_sac_combine, dim3((rows + 255) / 256), dim3(256), 0, s, rows, rew, w.q1, w.q2, w.logp, alpha, cfg->rew_shift,
-                           cfg->rew_scale, cfg->gamma, y);                                  // :78-79
-    MPG_CHECK_LAUNCH(auto_alpha ? "k_sac_combine_auto" : "k_sac_combine");
-    return MPG_OK;
+extern "C" size_t mpg_sac_targets_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    return head_workspace_bytes(true, "mpg_sac_targets_squashed_workspace_bytes", cfg, rows, sac_targets_ws);
 }
-}  // namespace
+extern "C" size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    return head_workspace_bytes(false, "mpg_sac_policy_grad_workspace_bytes", cfg, rows, policy_grad_ws, 2, true);
+}
+extern "C" size_t mpg_sac_policy_grad_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
+    return head_workspace_bytes(true, "mpg_sac_policy_grad_squashed_workspace_bytes", cfg, rows, policy_grad_ws, 2, true);
+}
 
 extern "C" int mpg_policy_sample(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps, float* act_out,
                                  float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
     return policy_sample("mpg_policy_sample", false, cfg, policy, rows, obs, eps, act_out, logp_out, logits_out, ws, ws_bytes, stream);
 }
-
-extern "C" size_t mpg_sac_targets_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (gauss_refusal("mpg_sac_targets_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(sac_targets_ws, cfg, rows);
-}
-
-extern "C" int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
-                               const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes,
-                               mpg_stream_t stream) {
-    return sac_targets("mpg_sac_targets", false, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, false, alpha, nullptr, y, ws, ws_bytes, stream);
-}
-
-extern "C" size_t mpg_sac_policy_grad_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (gauss_refusal("mpg_sac_policy_grad_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(policy_grad_ws, cfg, rows, 2, true);
-}
-
-// mpg_td3_policy_grad with the sampled action in place of the mean: the policy pass keeps all four logits, the head samples, the
-// critics' input gradients come back as in TD3 (the same dy rows: the gradient flows through the smaller critic), k_sac_dlogits
-// turns them into the four-column output gradient, and the policy's backward / weight gradient run in their four-output form
-extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
-                                   const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
-                                   float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = gauss_refusal("mpg_sac_policy_grad", cfg, policy && q1 && q2 && obs && eps && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
-                           rows, alpha);
-    if (rc) return rc;
-    return policy_grad("mpg_sac_policy_grad", cfg, policy, q1, q2, rows, obs, eps, alpha, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
-                       ws_bytes, stream);
-}
-
-// ---- the learned temperature (alpha = 'auto'): the two entry points above with alpha = exp(*log_alpha) read on the device ----
-extern "C" int mpg_sac_targets_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
-                                    const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
-                                    mpg_stream_t stream) {
-    return sac_targets("mpg_sac_targets_auto", false, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, true, 0.f, log_alpha, y, ws, ws_bytes,
-                       stream);
-}
-
-extern "C" int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
-                                        const float* eps, const float* log_alpha, const float* eps_alpha, float target_entropy,
-                                        float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum, float* alpha_grad, float* grad,
-                                        void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = gauss_refusal("mpg_sac_policy_grad_auto", cfg,
-                           policy && q1 && q2 && obs && eps && log_alpha && eps_alpha && qmin_sum && qmin_sqsum && logp_sum && alpha_grad && grad && ws,
-                           rows, 0.f);
-    if (rc) return rc;
-    MPG_REQUIRE(std::isfinite(target_entropy), "mpg_sac_policy_grad_auto: target_entropy must be finite (got %g)", (double)target_entropy);
-    const AutoTemp at{log_alpha, eps_alpha, target_entropy, alpha_grad};
-    return policy_grad("mpg_sac_policy_grad_auto", cfg, policy, q1, q2, rows, obs, eps, 0.f, inv_b_global, qmin_sum, qmin_sqsum, logp_sum, grad, ws,
-                       ws_bytes, stream, &at);
-}
-
-// ---- the tanh-squashed head (gauss_head.h squash_row): the five entry points above under cfg->action_range, on PathTracking or the
-// inverted pendulum.  The same launches as their plain siblings, the same workspaces described for the cfg's act_dim ----
-extern "C" size_t mpg_policy_sample_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (squash_refusal("mpg_policy_sample_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(policy_sample_ws, cfg, rows);
-}
-
 extern "C" int mpg_policy_sample_squashed(const mpg_cfg_t* cfg, const float* policy, int rows, const float* obs, const float* eps,
                                           float* act_out, float* logp_out, float* logits_out, void* ws, size_t ws_bytes, mpg_stream_t stream) {
     return policy_sample("mpg_policy_sample_squashed", true, cfg, policy, rows, obs, eps, act_out, logp_out, logits_out, ws, ws_bytes, stream);
 }
 
-extern "C" size_t mpg_sac_targets_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (squash_refusal("mpg_sac_targets_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(sac_targets_ws, cfg, rows);
+extern "C" int mpg_sac_targets(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                               const float* obs_tp1, const float* eps, float alpha, float* y, void* ws, size_t ws_bytes,
+                               mpg_stream_t stream) {
+    return sac_targets("mpg_sac_targets", cfg, policy, q1t, q2t, rows, rew, obs_tp1, fixed_temp(eps, false, alpha), y, ws, ws_bytes, stream);
 }
-
+extern "C" int mpg_sac_targets_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows, const float* rew,
+                                    const float* obs_tp1, const float* eps, const float* log_alpha, float* y, void* ws, size_t ws_bytes,
+                                    mpg_stream_t stream) {
+    return sac_targets("mpg_sac_targets_auto", cfg, policy, q1t, q2t, rows, rew, obs_tp1, learned_temp(eps, false, log_alpha), y, ws, ws_bytes,
+                       stream);
+}
 extern "C" int mpg_sac_targets_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
                                         const float* rew, const float* obs_tp1, const float* eps, float alpha, float* y, void* ws,
                                         size_t ws_bytes, mpg_stream_t stream) {
-    return sac_targets("mpg_sac_targets_squashed", true, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, false, alpha, nullptr, y, ws, ws_bytes,
+    return sac_targets("mpg_sac_targets_squashed", cfg, policy, q1t, q2t, rows, rew, obs_tp1, fixed_temp(eps, true, alpha), y, ws, ws_bytes,
                        stream);
 }
-
 extern "C" int mpg_sac_targets_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1t, const float* q2t, int rows,
                                              const float* rew, const float* obs_tp1, const float* eps, const float* log_alpha, float* y,
                                              void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    return sac_targets("mpg_sac_targets_squashed_auto", true, cfg, policy, q1t, q2t, rows, rew, obs_tp1, eps, true, 0.f, log_alpha, y, ws,
+    return sac_targets("mpg_sac_targets_squashed_auto", cfg, policy, q1t, q2t, rows, rew, obs_tp1, learned_temp(eps, true, log_alpha), y, ws,
                        ws_bytes, stream);
 }
 
-extern "C" size_t mpg_sac_policy_grad_squashed_workspace_bytes(const mpg_cfg_t* cfg, int rows) {
-    if (squash_refusal("mpg_sac_policy_grad_squashed_workspace_bytes", cfg, true, rows, 0.f)) return 0;
-    return measured(policy_grad_ws, cfg, rows, 2, true);
+extern "C" int mpg_sac_policy_grad(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                                   const float* eps, float alpha, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
+                                   float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    return sac_policy_grad("mpg_sac_policy_grad", cfg, policy, q1, q2, rows, obs, fixed_temp(eps, false, alpha), inv_b_global, qmin_sum,
+                           qmin_sqsum, logp_sum, grad, ws, ws_bytes, stream);
 }
-
-// (the pendulum's two logits take the THIN backward like TD3's two actions; PathTracking's four the plain one, as mpg_sac_policy_grad)
+extern "C" int mpg_sac_policy_grad_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows, const float* obs,
+                                        const float* eps, const float* log_alpha, const float* eps_alpha, float target_entropy,
+                                        float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum, float* alpha_grad, float* grad,
+                                        void* ws, size_t ws_bytes, mpg_stream_t stream) {
+    return sac_policy_grad("mpg_sac_policy_grad_auto", cfg, policy, q1, q2, rows, obs,
+                           learned_temp(eps, false, log_alpha, {eps_alpha, target_entropy, alpha_grad}), inv_b_global, qmin_sum, qmin_sqsum,
+                           logp_sum, grad, ws, ws_bytes, stream);
+}
 extern "C" int mpg_sac_policy_grad_squashed(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows,
                                             const float* obs, const float* eps, float alpha, float inv_b_global, float* qmin_sum,
                                             float* qmin_sqsum, float* logp_sum, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = squash_refusal("mpg_sac_policy_grad_squashed", cfg, policy && q1 && q2 && obs && eps && qmin_sum && qmin_sqsum && logp_sum && grad && ws,
-                            rows, alpha);
-    if (rc) return rc;
-    return policy_grad("mpg_sac_policy_grad_squashed", cfg, policy, q1, q2, rows, obs, eps, alpha, inv_b_global, qmin_sum, qmin_sqsum, logp_sum,
-                       grad, ws, ws_bytes, stream, nullptr, true);
+    return sac_policy_grad("mpg_sac_policy_grad_squashed", cfg, policy, q1, q2, rows, obs, fixed_temp(eps, true, alpha), inv_b_global, qmin_sum,
+                           qmin_sqsum, logp_sum, grad, ws, ws_bytes, stream);
 }
-
 extern "C" int mpg_sac_policy_grad_squashed_auto(const mpg_cfg_t* cfg, const float* policy, const float* q1, const float* q2, int rows,
                                                  const float* obs, const float* eps, const float* log_alpha, const float* eps_alpha,
                                                  float target_entropy, float inv_b_global, float* qmin_sum, float* qmin_sqsum, float* logp_sum,
                                                  float* alpha_grad, float* grad, void* ws, size_t ws_bytes, mpg_stream_t stream) {
-    int rc = squash_refusal("mpg_sac_policy_grad_squashed_auto", cfg,
-                            policy && q1 && q2 && obs && eps && log_alpha && eps_alpha && qmin_sum && qmin_sqsum && logp_sum && alpha_grad && grad && ws,
-                            rows, 0.f);
-    if (rc) return rc;
-    MPG_REQUIRE(std::isfinite(target_entropy), "mpg_sac_policy_grad_squashed_auto: target_entropy must be finite (got %g)", (double)target_entropy);
-    const AutoTemp at{log_alpha, eps_alpha, target_entropy, alpha_grad};
-    return policy_grad("mpg_sac_policy_grad_squashed_auto", cfg, policy, q1, q2, rows, obs, eps, 0.f, inv_b_global, qmin_sum, qmin_sqsum, logp_sum,
-                       grad, ws, ws_bytes, stream, &at, true);
+    return sac_policy_grad("mpg_sac_policy_grad_squashed_auto", cfg, policy, q1, q2, rows, obs,
+                           learned_temp(eps, true, log_alpha, {eps_alpha, target_entropy, alpha_grad}), inv_b_global, qmin_sum, qmin_sqsum,
+                           logp_sum, grad, ws, ws_bytes, stream);
 }

@@ -505,8 +505,9 @@ class SACLearner(_LearnerBase):
     def alpha(self):
         return self.policy_with_value.alpha
 
-    def _sac_targets(self, *a):
-        return (ops.sac_targets_squashed if self.squashed else ops.sac_targets)(*a)
+    def _op(self, call, learned):
+        """ops.<call>[_squashed][_auto] for this learner's head, looked up at call time"""
+        return getattr(ops, call + ('_squashed' if self.squashed else '') + ('_auto' if learned else ''))
 
     def _draw(self, rows, ctr, stream=0):
         ad = self.cfg.act_dim
@@ -517,11 +518,8 @@ class SACLearner(_LearnerBase):
         pw, b = self.policy_with_value, self.batch_data
         if eps_target is None:
             eps_target = self._draw(b['batch_obs'].shape[0], 2 * (self.counter + 1))
-        if self.auto_alpha:
-            return ops.sac_targets_auto(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'],
-                                        b['batch_obs_tp1'], eps_target, pw.log_alpha, _squashed=self.squashed)
-        return self._sac_targets(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'], b['batch_obs_tp1'],
-                               eps_target, self.alpha)
+        return self._op('sac_targets', self.auto_alpha)(self.cfg, pw.net('policy'), pw.net('Q1', True), pw.net('Q2', True), b['batch_rewards'],
+                                                         b['batch_obs_tp1'], eps_target, pw.log_alpha if self.auto_alpha else self.alpha)
 
     def compute_td_error(self, eps=None, ctr=None):
         """sac.py:82-91 (signed): r~ + gamma Q1_target(s', a') - Q1(s, a), a' its own draw from the TARGET policy - the soft target's
@@ -530,8 +528,8 @@ class SACLearner(_LearnerBase):
         pw, b = self.policy_with_value, self.batch_data
         if eps is None:
             eps = self._draw(b['batch_obs'].shape[0], 2 * self.counter if ctr is None else ctr, stream=1)
-        y1 = self._sac_targets(self.cfg, pw.net('policy', True), pw.net('Q1', True), pw.net('Q1', True), b['batch_rewards'],
-                             b['batch_obs_tp1'], eps, 0.0)
+        y1 = self._op('sac_targets', False)(self.cfg, pw.net('policy', True), pw.net('Q1', True), pw.net('Q1', True), b['batch_rewards'],
+                                            b['batch_obs_tp1'], eps, 0.0)
         return y1 - pw.compute_Q1(b['batch_obs'], b['batch_actions'])
 
     def get_batch_data(self, batch_data, rb, indexes, eps_target=None):
@@ -550,17 +548,16 @@ class SACLearner(_LearnerBase):
                             grad_out=self.grad(nm), loss_out=stats[i:i + 1])
         if eps_policy is None:
             eps_policy = self._draw(rows, 2 * self.counter + 1)
+        grad_fn = self._op('sac_policy_grad', self.auto_alpha)
         if not self.auto_alpha:
-            grad_fn = ops.sac_policy_grad_squashed if self.squashed else ops.sac_policy_grad
             grad_fn(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, self.alpha, inv_b_global=inv_b,
                     grad_out=self.grad('policy'), stats_out=stats[2:5])                                    # :119-136
             return self._finish(iteration)
         if eps_alpha is None:                                                                          # :139: the third draw
             eps_alpha = self._draw(rows, self.counter, stream=2)
         g_alpha = self.flat[self.n_net_grad:self.n_grad]
-        ops.sac_policy_grad_auto(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, pw.log_alpha,
-                                 eps_alpha, pw.target_entropy, inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5],
-                                 alpha_grad_out=g_alpha, _squashed=self.squashed)                      # :119-148
+        grad_fn(self.cfg, pw.net('policy'), pw.net('Q1'), pw.net('Q2'), b['batch_obs'], eps_policy, pw.log_alpha, eps_alpha, pw.target_entropy,
+                inv_b_global=inv_b, grad_out=self.grad('policy'), stats_out=stats[2:5], alpha_grad_out=g_alpha)   # :119-148
         fresh = self._views is None
         views = self._finish(iteration)
         if fresh:

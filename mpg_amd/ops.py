@@ -482,16 +482,18 @@ def rollout_q_estimation(cfg, policy_params, q1t, obs0, act0, eps, select, M=1, 
     return y
 
 
-def _policy_grad(name, cfg, policy_params, critics, obs, extra, n_stats, inv_b_global, grad_out, stats_out):
-    """the mpg_*_policy_grad call: (cfg, policy, critics..., rows, obs, extra..., inv_b, one pointer per statistic, grad, workspace)"""
+def _policy_grad(name, cfg, policy_params, critics, obs, extra, n_stats, inv_b_global, grad_out, stats_out, more_out=()):
+    """the mpg_*_policy_grad call: (cfg, policy, critics..., rows, obs, extra..., inv_b, one pointer per statistic, more_out..., grad,
+    workspace); more_out: further one-float outputs (None: allocated here), returned behind (stats, grad)"""
     rows, dev = obs.shape[0], obs.device
+    more_out = tuple(t if t is not None else torch.empty(1, dtype=torch.float32, device=dev) for t in more_out)
     grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
     stats = stats_out if stats_out is not None else torch.empty(n_stats, dtype=torch.float32, device=dev)
-    ws = _ws(dev, 1, name + '_workspace_bytes', cfg, rows)
+    ws = _ws(dev, 1, name.replace('_auto', '') + '_workspace_bytes', cfg, rows)      # (an _auto form: its fixed-alpha sibling's query)
     L.call(name, ctypes.byref(cfg), L.ptr(_f32(policy_params)), *[L.ptr(_f32(q)) for q in critics], L.c_int(rows), L.ptr(_f32(obs)), *extra,
            L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), *[L.ptr(stats[i:i + 1]) for i in range(n_stats)],
-           L.ptr(grad), *ws, L.stream())
-    return stats, grad
+           *[L.ptr(t) for t in more_out], L.ptr(grad), *ws, L.stream())
+    return (stats, grad) + more_out
 
 
 def td3_policy_grad(cfg, policy_params, q1, q2, obs, inv_b_global=None, grad_out=None, stats_out=None):
@@ -503,17 +505,28 @@ def dpg_policy_grad(cfg, policy_params, q1, obs, inv_b_global=None, grad_out=Non
     return _policy_grad('mpg_dpg_policy_grad', cfg, policy_params, (q1,), obs, (), 2, inv_b_global, grad_out, stats_out)
 
 
-def policy_sample(cfg, policy_params, obs, eps, want_logits=False, _entry='mpg_policy_sample'):
-    """mpg_policy_sample: (act, logp[, logits]) of the Gaussian policy on the caller's standard-normal draws eps [rows, act_dim]
-    (PolicyWithQs.compute_action, stochastic branch, policy.py:200-204)"""
+# ---- SAC's stochastic head, one body per call: on the plain Gaussian head or - the mpg_*_squashed entry points, include/mpg_hip.h "SAC with
+# an action range": R = cfg.action_range > 0, PathTracking (act_dim 2) or the inverted pendulum (act_dim 1) - the tanh-squashed one
+def _policy_sample(entry, cfg, policy_params, obs, eps, want_logits):
     rows, dev = obs.shape[0], obs.device
     act = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
     logp = torch.empty(rows, dtype=torch.float32, device=dev)
     logits = torch.empty(rows, 2 * cfg.act_dim, dtype=torch.float32, device=dev) if want_logits else None
-    ws = _ws(dev, 0, _entry + '_workspace_bytes', cfg, rows)
-    L.call(_entry, ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.ptr(_f32(obs)), L.ptr(_f32(eps)),
+    ws = _ws(dev, 0, entry + '_workspace_bytes', cfg, rows)
+    L.call(entry, ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.ptr(_f32(obs)), L.ptr(_f32(eps)),
            L.ptr(act), L.ptr(logp), L.ptr(logits), *ws, L.stream())
     return (act, logp, logits) if want_logits else (act, logp)
+
+
+def policy_sample(cfg, policy_params, obs, eps, want_logits=False):
+    """mpg_policy_sample: (act, logp[, logits]) of the Gaussian policy on the caller's standard-normal draws eps [rows, act_dim]
+    (PolicyWithQs.compute_action, stochastic branch, policy.py:200-204)"""
+    return _policy_sample('mpg_policy_sample', cfg, policy_params, obs, eps, want_logits)
+
+
+def policy_sample_squashed(cfg, policy_params, obs, eps, want_logits=False):
+    """mpg_policy_sample_squashed: act = R tanh(mean + sigma eps), logp with the bijectors' correction[, the plain logits]"""
+    return _policy_sample('mpg_policy_sample_squashed', cfg, policy_params, obs, eps, want_logits)
 
 
 def worker_sample_step(cfg, policy_params, state, obs_io, sample_seed, sample_ctr, ring, capacity, next_idx, env_seed, env_ctr,
@@ -575,23 +588,61 @@ def worker_sample_rollout(cfg, policy_params, iters, state, obs_io, sample_seed,
     return act
 
 
-def sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha, _entry='mpg_sac_targets'):
-    """mpg_sac_targets: y = (rew + shift) * scale + gamma * (min(Q1t, Q2t)(s', a') - alpha * logp'), (a', logp') sampled from
-    `policy` - the ONLINE one in the reference, sac.py:71 - with eps"""
-    rows = obs_tp1.shape[0]
+def _sac_targets(entry, cfg, policy, q1t, q2t, rew, obs_tp1, eps, temp):
+    rows = obs_tp1.shape[0]          # (temp: the entry point's temperature argument - alpha as a c_float, or the pointer to log_alpha)
     y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
-    ws = _ws(obs_tp1.device, 0, _entry + '_workspace_bytes', cfg, rows)
-    L.call(_entry, ctypes.byref(cfg), L.ptr(_f32(policy)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows), L.ptr(_f32(rew)),
-           L.ptr(_f32(obs_tp1)), L.ptr(_f32(eps)), L.c_float(alpha), L.ptr(y), *ws, L.stream())
+    ws = _ws(obs_tp1.device, 0, entry.replace('_auto', '') + '_workspace_bytes', cfg, rows)
+    L.call(entry, ctypes.byref(cfg), L.ptr(_f32(policy)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows), L.ptr(_f32(rew)),
+           L.ptr(_f32(obs_tp1)), L.ptr(_f32(eps)), temp, L.ptr(y), *ws, L.stream())
     return y
 
 
-def sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None,
-                    _entry='mpg_sac_policy_grad'):
+def sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
+    """mpg_sac_targets: y = (rew + shift) * scale + gamma * (min(Q1t, Q2t)(s', a') - alpha * logp'), (a', logp') sampled from
+    `policy` - the ONLINE one in the reference, sac.py:71 - with eps"""
+    return _sac_targets('mpg_sac_targets', cfg, policy, q1t, q2t, rew, obs_tp1, eps, L.c_float(alpha))
+
+
+def sac_targets_squashed(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
+    return _sac_targets('mpg_sac_targets_squashed', cfg, policy, q1t, q2t, rew, obs_tp1, eps, L.c_float(alpha))
+
+
+def sac_targets_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha):
+    """mpg_sac_targets_auto: mpg_sac_targets with alpha = exp(log_alpha[0]) read on the device (log_alpha: device tensor)"""
+    return _sac_targets('mpg_sac_targets_auto', cfg, policy, q1t, q2t, rew, obs_tp1, eps, L.ptr(_f32(log_alpha)))
+
+
+def sac_targets_squashed_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha):
+    return _sac_targets('mpg_sac_targets_squashed_auto', cfg, policy, q1t, q2t, rew, obs_tp1, eps, L.ptr(_f32(log_alpha)))
+
+
+def sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None):
     """mpg_sac_policy_grad: mean(alpha * logp - min Q) and its policy gradient over all four output columns.
     Returns (stats = [qmin_sum, qmin_sqsum, logp_sum], grad)."""
-    return _policy_grad(_entry, cfg, policy_params, (q1, q2), obs, (L.ptr(_f32(eps)), L.c_float(alpha)), 3, inv_b_global,
+    return _policy_grad('mpg_sac_policy_grad', cfg, policy_params, (q1, q2), obs, (L.ptr(_f32(eps)), L.c_float(alpha)), 3, inv_b_global,
                         grad_out, stats_out)
+
+
+def sac_policy_grad_squashed(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None):
+    return _policy_grad('mpg_sac_policy_grad_squashed', cfg, policy_params, (q1, q2), obs, (L.ptr(_f32(eps)), L.c_float(alpha)), 3,
+                        inv_b_global, grad_out, stats_out)
+
+
+def sac_policy_grad_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global=None, grad_out=None,
+                         stats_out=None, alpha_grad_out=None):
+    """mpg_sac_policy_grad_auto: mpg_sac_policy_grad with the device temperature, and this process's share of the temperature's
+    gradient -inv_b * sum(logp(eps_alpha) + target_entropy) from the same pass.  Returns (stats = [qmin_sum, qmin_sqsum, logp_sum],
+    grad, alpha_grad [1])."""
+    return _policy_grad('mpg_sac_policy_grad_auto', cfg, policy_params, (q1, q2), obs,
+                        (L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(_f32(eps_alpha)), L.c_float(target_entropy)), 3, inv_b_global, grad_out,
+                        stats_out, (alpha_grad_out,))
+
+
+def sac_policy_grad_squashed_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global=None,
+                                  grad_out=None, stats_out=None, alpha_grad_out=None):
+    return _policy_grad('mpg_sac_policy_grad_squashed_auto', cfg, policy_params, (q1, q2), obs,
+                        (L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(_f32(eps_alpha)), L.c_float(target_entropy)), 3, inv_b_global, grad_out,
+                        stats_out, (alpha_grad_out,))
 
 
 class SacAlphaStruct(ctypes.Structure):
@@ -603,59 +654,6 @@ class SacAlphaStruct(ctypes.Structure):
 
 ALPHA_STATE_FLOATS = 8
 ALPHA_LOG, ALPHA_M, ALPHA_V, ALPHA_SNAPSHOT, ALPHA_LOSS, ALPHA_NORM, ALPHA_NONFINITE = range(7)      # slots of the state block
-
-
-def sac_targets_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha, _squashed=False):
-    """mpg_sac_targets_auto: mpg_sac_targets with alpha = exp(log_alpha[0]) read on the device (log_alpha: device tensor)"""
-    rows = obs_tp1.shape[0]
-    y = torch.empty(rows, dtype=torch.float32, device=obs_tp1.device)
-    ws = _ws(obs_tp1.device, 0, 'mpg_sac_targets_squashed_workspace_bytes' if _squashed else 'mpg_sac_targets_workspace_bytes', cfg, rows)
-    L.call('mpg_sac_targets_squashed_auto' if _squashed else 'mpg_sac_targets_auto', ctypes.byref(cfg), L.ptr(_f32(policy)), L.ptr(_f32(q1t)), L.ptr(_f32(q2t)), L.c_int(rows),
-           L.ptr(_f32(rew)), L.ptr(_f32(obs_tp1)), L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(y), *ws, L.stream())
-    return y
-
-
-def sac_policy_grad_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global=None, grad_out=None,
-                         stats_out=None, alpha_grad_out=None, _squashed=False):
-    """mpg_sac_policy_grad_auto: mpg_sac_policy_grad with the device temperature, and this process's share of the temperature's
-    gradient -inv_b * sum(logp(eps_alpha) + target_entropy) from the same pass.  Returns (stats = [qmin_sum, qmin_sqsum, logp_sum],
-    grad, alpha_grad [1])."""
-    rows, dev = obs.shape[0], obs.device
-    grad = grad_out if grad_out is not None else torch.empty(policy_size(cfg), dtype=torch.float32, device=dev)
-    stats = stats_out if stats_out is not None else torch.empty(3, dtype=torch.float32, device=dev)
-    ag = alpha_grad_out if alpha_grad_out is not None else torch.empty(1, dtype=torch.float32, device=dev)
-    ws = _ws(dev, 1, 'mpg_sac_policy_grad_squashed_workspace_bytes' if _squashed else 'mpg_sac_policy_grad_workspace_bytes', cfg, rows)
-    L.call('mpg_sac_policy_grad_squashed_auto' if _squashed else 'mpg_sac_policy_grad_auto', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.ptr(_f32(q1)), L.ptr(_f32(q2)), L.c_int(rows),
-           L.ptr(_f32(obs)), L.ptr(_f32(eps)), L.ptr(_f32(log_alpha)), L.ptr(_f32(eps_alpha)), L.c_float(target_entropy),
-           L.c_float(inv_b_global if inv_b_global is not None else 1.0 / rows), *[L.ptr(stats[i:i + 1]) for i in range(3)], L.ptr(ag),
-           L.ptr(grad), *ws, L.stream())
-    return stats, grad, ag
-
-
-# ---- the tanh-squashed head (include/mpg_hip.h, "SAC with an action range"): the five wrappers above on the mpg_*_squashed entry points,
-# R = cfg.action_range > 0; PathTracking (act_dim 2) or the inverted pendulum (act_dim 1) ----
-def policy_sample_squashed(cfg, policy_params, obs, eps, want_logits=False):
-    """mpg_policy_sample_squashed: act = R tanh(mean + sigma eps), logp with the bijectors' correction[, the plain logits]"""
-    return policy_sample(cfg, policy_params, obs, eps, want_logits, _entry='mpg_policy_sample_squashed')
-
-
-def sac_targets_squashed(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha):
-    return sac_targets(cfg, policy, q1t, q2t, rew, obs_tp1, eps, alpha, _entry='mpg_sac_targets_squashed')
-
-
-def sac_policy_grad_squashed(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global=None, grad_out=None, stats_out=None):
-    return sac_policy_grad(cfg, policy_params, q1, q2, obs, eps, alpha, inv_b_global, grad_out, stats_out,
-                           _entry='mpg_sac_policy_grad_squashed')
-
-
-def sac_targets_squashed_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha):
-    return sac_targets_auto(cfg, policy, q1t, q2t, rew, obs_tp1, eps, log_alpha, _squashed=True)
-
-
-def sac_policy_grad_squashed_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global=None,
-                                  grad_out=None, stats_out=None, alpha_grad_out=None):
-    return sac_policy_grad_auto(cfg, policy_params, q1, q2, obs, eps, log_alpha, eps_alpha, target_entropy, inv_b_global, grad_out,
-                                stats_out, alpha_grad_out, _squashed=True)
 
 
 def sac_alpha_update(desc, g, clip=1.0, do_clip=False, do_adam=False, skip_flag=None):

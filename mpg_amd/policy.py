@@ -321,7 +321,7 @@ class PolicyWithQs(object):
                         skip_flag=self.nonfinite, wc_w=self.wc_params, wc_target=self.wc_targets)
         if self.auto_alpha and delayed:
             # (optimizer.py:357-361: a non-finite gradient anywhere zeroes the whole list - the networks' flags reach the temperature;
-            # its own gradient is finite whatever the policy produced, csrc/learner_api.hip GaussRow2)
+            # its own gradient is finite whatever the policy produced, csrc/learner_api.hip HeadRow2)
             ops.sac_alpha_update(self.alpha_desc, grads[n_nets:n_nets + 1], do_adam=True, skip_flag=self.nonfinite)
 
     # ---- checkpoint (flat blob) ----

@@ -1,6 +1,6 @@
 """SAC's learned temperature (alpha = 'auto') on the GPU, both engines.
  1. the device-temperature entry points equal the host-alpha ones bit for bit, given alpha = float32(exp(float64(log_alpha)));
- 2. the second sum of the head's pass (k_row_sums<GaussRow2>): the same tree as logp_sum on the same draw, and the float64 sum of
+ 2. the second sum of the head's pass (k_row_sums<HeadRow2>): the same tree as logp_sum on the same draw, and the float64 sum of
     mpg_policy_sample's log-densities on an independent one, in the one-block and the many-block form;
  3. mpg_sac_alpha_update: clip, snapshot, Adam against mpg_adam_polyak on a one-element segment, skip flags;
  4. SACLearner / PolicyWithQs with alpha = 'auto': repeated launches, the training loop (reproducible, resumes bit-identically, the
