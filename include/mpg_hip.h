@@ -972,7 +972,16 @@ typedef struct {
                                             replay; n, M, select, smooth_* unused).  Served by mpg_sac_step_begin, which carries the
                                             temperature as an argument (this struct gains no field: the ABI version stays 10);
                                             mpg_step_begin refuses it and names that function.  6 is not assigned: it stays refused
-                                            everywhere (mpg_step_workspace_bytes, mpg_step_begin, mpg_sac_step_begin) */
+                                            everywhere (mpg_step_workspace_bytes, mpg_step_begin, mpg_sac_step_begin),
+                                         8: AMPC (learners/ampc.py:105-122: networks [policy] alone, uniform replay, a fresh batch on
+                                            every call: num_batch_reuse must be 1; n = the rollout horizon, 0 < n < 32, M copies per row,
+                                            batch * M % 16 == 0.  The two statistics - the sums of the M-mean reward sum and of its
+                                            square - are grad[n_grad] and grad[n_grad + 1].  n_select / select / eta / total_ite, ws0 /
+                                            ws0_bytes, b_targets, tau and delay_update are not read: a policy-only stack has no delay
+                                            and no target (policy.py:125-127).  `targets` stays a required pointer - mpg_step_end's
+                                            launch and the weight-cache pair take it - and is never written.  Served by
+                                            mpg_step_workspace_bytes, mpg_step_begin and mpg_step_end: no new symbol, no new field, the
+                                            ABI version stays 10.  mpg_sac_step_begin / mpg_sac_auto_step_* refuse it */
     int num_agent, sample_iters;      /* worker: sample_iters env steps of num_agent agents per sampling call.  mpg_step_begin issues
                                          all of them but the one that pre-gathers MPG-v2's draw as ONE launch (mpg_worker_rollout,
                                          bit-identical) where there are at least two, the ring holds them (iters * num_agent <=
@@ -1049,6 +1058,22 @@ typedef struct {
                                          (where the partial gradient is written: e.g. the caller's own staging slot of the
                                          exchange) and mpg_step_end (the reduced buffer): it is read at call time. */
 } mpg_train_ctx_t;
+
+/* learner_version 8 - SingleProcessOffPolicyOptimizer.step with AMPCLearner.compute_gradient (ampc.py:105-122), the calls in order:
+ *   mpg_step_begin:  [every sampling_interval-th iteration: the worker's sample as for version 3 - the one-launch samples
+ *                    (mpg_worker_rollout / mpg_worker_rollout_pendulum) where sample_iters says so, the chain with sample_iters < 0,
+ *                    explore_sigma passed on; noise_ctr, env_ctr, ring_next, ring_size advance per iteration];  replay_times++;
+ *                    mpg_replay_sample_uniform;  learner_counter++;  mpg_ampc_pg(cfg, policy, batch, M, n, b_obs, eps = NULL,
+ *                    learner_seed, 2 * learner_counter + 1, 1 / (batch * world_size), grad + n_grad, grad + n_grad + 1, grad, ws1).
+ *   mpg_step_end:    mpg_sq_partials as for every non-MPG version (clip_partials_ready stands after an exchange), then
+ *                    mpg_clip_adam_polyak over the one segment with the policy's learning rate, do_adam = 1 on EVERY iteration and
+ *                    do_polyak = 0 always; opt_steps[0] advances on every call.  delay_update and tau are not looked at.
+ *   mpg_step_workspace_bytes: *ws0 = 0, *ws1 = mpg_ampc_pg_workspace_bytes(cfg, batch, M, n).
+ * Refused by mpg_step_begin with MPG_EINVAL, its name and a text of its own each, before anything is enqueued or any counter moves
+ * (what mpg_ampc_pg would refuse is found through its workspace query up front, not after the sample has run): n outside 0 < n < 32,
+ * batch * M % 16 != 0, M <= 0, an unsupported cfg (the workspace query refuses these four under its own name), num_batch_reuse != 1,
+ * prioritized != 0, env_kind 2 (the text of every version), a null pointer among params, targets, grad, ws1, env_state, w_obs, w_act,
+ * w_done, ring_*, idx, b_obs, b_act, b_rew, b_obs2, b_done (named in the text); ws1_bytes below the need: MPG_EWORKSPACE with both sizes. */
 
 /* workspace requirements of a context (ws0: targets / critic; ws1: rollout) */
 int mpg_step_workspace_bytes(const mpg_train_ctx_t* ctx, size_t* ws0_bytes, size_t* ws1_bytes);

@@ -21,6 +21,7 @@ Layout layout(const mpg_train_ctx_t* c) {
     l.q_size = net_size(c->cfg.obs_dim + c->cfg.act_dim, 1);
     l.p_size = net_size(c->cfg.obs_dim, 2 * c->cfg.act_dim);
     l.n_nets = (c->learner_version == 2 || c->learner_version == 4 || c->learner_version == 7) ? 3 : 2;        // MPG-v2 / TD3 / SAC: double Q
+    if (c->learner_version == 8) l.n_nets = 1;                                                                 // AMPC: the policy alone
     int o = 0;
     for (int k = 0; k < l.n_nets; ++k) {
         l.sizes[k] = k == l.n_nets - 1 ? l.p_size : l.q_size;
@@ -59,9 +60,14 @@ void rule_based_weights(int ite, int total_ite, float eta, const int* select, in
 inline bool exchanged(const mpg_train_ctx_t* c) { return c->world_size > 1 || c->grads_exchanged != 0; }
 
 inline bool is_mpg(const mpg_train_ctx_t* c) { return c->learner_version == 1 || c->learner_version == 2; }
+inline bool is_ampc(const mpg_train_ctx_t* c) { return c->learner_version == 8; }
 
 bool ctx_ok(const mpg_train_ctx_t* c) {
-    if (!c || c->learner_version < 1 || (c->learner_version > 5 && c->learner_version != 7)) return false;
+    if (!c || c->learner_version < 1 || c->learner_version == 6 || c->learner_version > 8) return false;
+    // AMPC: no critic and no target, so no ws0; mpg_step_begin has said what is wrong in words of its own (ampc_refusal) before it asks here
+    if (is_ampc(c))
+        return c->num_agent > 0 && c->batch > 0 && c->world_size > 0 && c->sampling_interval > 0 && c->num_batch_reuse == 1 &&
+               c->ring_capacity > 0 && c->params && c->targets && c->grad && c->ws1 && c->n > 0 && c->M > 0 && !c->prioritized;
     const bool common = c->num_agent > 0 && c->batch > 0 && c->world_size > 0 && c->sampling_interval > 0 && c->num_batch_reuse > 0 &&
                         c->ring_capacity > 0 && c->params && c->targets && c->grad && c->ws0 && c->ws1;
     if (!common) return false;
@@ -73,6 +79,53 @@ bool ctx_ok(const mpg_train_ctx_t* c) {
     // TD3: the scratch block, and the trees when the replay is prioritized
     return c->scratch && c->num_batch_reuse == 1 &&
            (!c->prioritized || (c->per_sum && c->per_min && c->per_stamp && c->per_capacity >= c->ring_capacity && c->per_max_priority && c->b_weights));
+}
+
+// the driver's first act is the worker's sample on the REAL env, which this model does not have
+int real_env_refusal(const mpg_train_ctx_t* c) {
+    MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
+                "mpg_step_begin: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
+                "samples it) does not serve this model; use the rollout entry points (NADPLearner) on caller-supplied batches");
+    return MPG_OK;
+}
+
+// ---- AMPC (learner_version 8): what mpg_ampc_pg would refuse of (cfg, batch, M, n), said under the caller's name BEFORE the sample runs ----
+int ampc_shape_refusal(const char* entry, const mpg_train_ctx_t* c) {
+    MPG_REQUIRE(c->batch > 0, "%s: learner_version 8 (AMPC): no rows (batch %d)", entry, c->batch);
+    MPG_REQUIRE(c->M > 0, "%s: learner_version 8 (AMPC): M must be positive (got %d)", entry, c->M);
+    MPG_REQUIRE(c->n > 0 && c->n < 32, "%s: learner_version 8 (AMPC): horizon out of range: 0 < n < 32 (got %d)", entry, c->n);
+    const long R = (long)c->batch * c->M;
+    MPG_REQUIRE(R % 16 == 0, "%s: learner_version 8 (AMPC): every step is differentiated through the policy: needs batch*M %% 16 == 0 (got %ld)",
+                entry, R);
+    MPG_REQUIRE(mpg_ampc_pg_workspace_bytes(&c->cfg, c->batch, c->M, c->n) != 0,
+                "%s: learner_version 8 (AMPC): unsupported cfg (obs/act dims, env_kind) for mpg_ampc_pg", entry);
+    return MPG_OK;
+}
+
+// everything mpg_step_begin refuses of an AMPC context, each with its own text, before anything is enqueued or any counter moves
+int ampc_refusal(const char* entry, const mpg_train_ctx_t* c) {
+    MPG_REQUIRE(c->num_agent > 0 && c->batch > 0 && c->world_size > 0 && c->sampling_interval > 0 && c->ring_capacity > 0,
+                "%s: incomplete context (learner_version 8: num_agent %d, batch %d, world_size %d, sampling_interval %d, ring_capacity %d "
+                "must all be positive)", entry, c->num_agent, c->batch, c->world_size, c->sampling_interval, c->ring_capacity);
+    TRY(real_env_refusal(c));
+    MPG_REQUIRE(c->num_batch_reuse == 1, "%s: learner_version 8 (AMPC) draws a fresh batch on every call: num_batch_reuse must be 1 (got %d)",
+                entry, c->num_batch_reuse);
+    MPG_REQUIRE(!c->prioritized, "%s: learner_version 8 (AMPC): a prioritized replay buffer is not served (prioritized = %d)", entry,
+                c->prioritized);
+    TRY(ampc_shape_refusal(entry, c));
+    MPG_REQUIRE(c->num_agent <= c->ring_capacity, "%s: ring smaller than one sample", entry);
+    const struct { const char* name; const void* p; } need[] = {
+        {"params", c->params}, {"targets", c->targets}, {"grad", c->grad}, {"ws1", c->ws1},
+        {"env_state", c->env_state}, {"w_obs", c->w_obs}, {"w_act", c->w_act}, {"w_done", c->w_done},
+        {"ring_obs", c->ring_obs}, {"ring_act", c->ring_act}, {"ring_rew", c->ring_rew}, {"ring_obs2", c->ring_obs2}, {"ring_done", c->ring_done},
+        {"idx", c->idx}, {"b_obs", c->b_obs}, {"b_act", c->b_act}, {"b_rew", c->b_rew}, {"b_obs2", c->b_obs2}, {"b_done", c->b_done}};
+    for (const auto& q : need) MPG_REQUIRE(q.p, "%s: learner_version 8 (AMPC): null pointer: %s", entry, q.name);
+    const size_t ws1 = mpg_ampc_pg_workspace_bytes(&c->cfg, c->batch, c->M, c->n);
+    if (c->ws1_bytes < ws1) {
+        mpg_set_error("%s: learner_version 8 (AMPC): ws1 too small for mpg_ampc_pg (%zu < %zu)", entry, c->ws1_bytes, ws1);
+        return MPG_EWORKSPACE;
+    }
+    return MPG_OK;
 }
 
 // ---- worker.sample + replay_buffer.add_batch (optimizer.py:332-337, worker.py:91-119) ----
@@ -326,12 +379,27 @@ int sac_gradients(mpg_train_ctx_t* c, const Layout& l, float alpha, const mpg_sa
                                c->ws1, c->ws1_bytes, s);
 }
 
+// ---- AMPCLearner.compute_gradient, learners/ampc.py:105-122 (networks [policy]): the statistics are the two return sums; the noise
+//      counter is the one AMPCLearner uses after _begin has counted the call ----
+int ampc_gradients(mpg_train_ctx_t* c, const Layout& l, mpg_stream_t s) {
+    const float inv_b = 1.f / ((float)c->batch * (float)c->world_size);
+    float* stats = c->grad + l.n_grad;
+    return mpg_ampc_pg(&c->cfg, c->params, c->batch, c->M, c->n, c->b_obs, nullptr, c->learner_seed, 2 * c->learner_counter + 1, inv_b, stats,
+                       stats + 1, c->grad, c->ws1, c->ws1_bytes, s);
+}
+
 }  // namespace
 
 extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, size_t* ws1) {
     MPG_REQUIRE(c && ws0 && ws1, "mpg_step_workspace_bytes: null pointer");
-    MPG_REQUIRE((c->learner_version >= 1 && c->learner_version <= 5) || c->learner_version == 7,
+    MPG_REQUIRE((c->learner_version >= 1 && c->learner_version <= 5) || c->learner_version == 7 || c->learner_version == 8,
                 "mpg_step_workspace_bytes: unknown learner_version %d", c->learner_version);
+    if (is_ampc(c)) {                    // AMPC: no target and no critic; the rollout gradient
+        TRY(ampc_shape_refusal("mpg_step_workspace_bytes", c));
+        *ws0 = 0;
+        *ws1 = mpg_ampc_pg_workspace_bytes(&c->cfg, c->batch, c->M, c->n);
+        return MPG_OK;
+    }
     if (c->learner_version == 7) {       // SAC: soft targets / critic loss; the Gaussian-head policy gradient
         *ws0 = std::max(mpg_sac_targets_workspace_bytes(&c->cfg, c->batch), mpg_q_loss_grad_workspace_bytes(&c->cfg, c->batch));
         *ws1 = mpg_sac_policy_grad_workspace_bytes(&c->cfg, c->batch);
@@ -355,16 +423,14 @@ extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, s
 extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
     MPG_REQUIRE(!c || c->learner_version != 7,
                 "mpg_step_begin: learner_version 7 (SAC) takes its temperature as an argument: call mpg_sac_step_begin");
+    if (c && is_ampc(c)) TRY(ampc_refusal("mpg_step_begin", c));      // each refusal in its own words; ctx_ok then holds
     MPG_REQUIRE(ctx_ok(c), "mpg_step_begin: incomplete context");
-    // the driver's first act is the worker's sample on the REAL env, which this model does not have: refused before anything is enqueued
-    MPG_REQUIRE(c->cfg.env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM,
-                "mpg_step_begin: the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided, so the native step driver (which "
-                "samples it) does not serve this model; use the rollout entry points (NADPLearner) on caller-supplied batches");
+    TRY(real_env_refusal(c));                                       // refused before anything is enqueued
     const Layout l = layout(c);
     const int od = c->cfg.obs_dim, ad = c->cfg.act_dim, kind = c->cfg.env_kind;
     const float* policy = c->params + l.off[l.n_nets - 1];
     const float* policy_t = c->targets + l.off[l.n_nets - 1];
-    if (!is_mpg(c)) {        // ---- NADP / TD3 / NDPG: sample, add, replay, gradients (optimizer.py:330-353) ----
+    if (!is_mpg(c)) {        // ---- NADP / TD3 / NDPG / AMPC: sample, add, replay, gradients (optimizer.py:330-353) ----
         if (iteration % c->sampling_interval == 0) TRY(sample_and_add(c, policy, false, nullptr, nullptr, s));
         MPG_REQUIRE(c->ring_size > 0, "mpg_step_begin: empty replay ring");
         c->replay_times++;
@@ -383,6 +449,7 @@ extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s)
                                           c->b_done, s));
         }
         c->learner_counter++;
+        if (is_ampc(c)) return ampc_gradients(c, l, s);
         return c->learner_version == 3 ? nadp_gradients(c, l, s) : td3_gradients(c, l, s);
     }
     // ---- worker.sample + replay_buffer.add_batch; MPG-v2 draws its minibatch right after the add ----
@@ -512,7 +579,8 @@ extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
     // sums with mpg_sum_slots_sq has left them already (clip_partials_ready)
     if ((exchanged(c) && !c->clip_partials_ready) || (!exchanged(c) && !is_mpg(c))) TRY(mpg_sq_partials(c->grad, l.sizes, l.n_nets, c->clip_scratch, s));
     // PolicyWithQs.apply_gradients, policy.py:123-156
-    const bool delayed = iteration % c->delay_update == 0;
+    // (AMPC: a policy-only stack has no delay and no target, policy.py:125-127 - delay_update and tau are not looked at)
+    const bool delayed = is_ampc(c) || iteration % c->delay_update == 0;
     float lr_t[3];
     int do_adam[3], do_polyak[3];
     for (int k = 0; k < l.n_nets; ++k) {
@@ -521,7 +589,7 @@ extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
         const long long t = c->opt_steps[k] + 1;
         lr_t[k] = adam_step_size(is_policy ? c->policy_lr : c->value_lr, c->opt_steps[k]);
         do_adam[k] = upd ? 1 : 0;
-        do_polyak[k] = delayed ? 1 : 0;
+        do_polyak[k] = delayed && !is_ampc(c) ? 1 : 0;
         if (upd) c->opt_steps[k] = t;
     }
     mpg_prof_begin(c->cfg.prof, 9, mpg_stream(s));

@@ -50,11 +50,13 @@ class FusedMPGStep(object):
     PolicyWithQs: MPGLearner + ReplayBuffer (learner_version 1 / 2), NADPLearner + ReplayBuffer (3), TD3Learner + ReplayBuffer
     or PrioritizedReplayBuffer (4; the priority update of optimizer.py:351-353 included), NDPGLearner + ReplayBuffer (5),
     SACLearner + ReplayBuffer without explore_sigma (7: mpg_sac_step_begin, which takes the learner's fixed alpha, or with
-    alpha = 'auto' the pair mpg_sac_auto_step_begin / mpg_sac_auto_step_end on the policy's device-resident temperature)."""
+    alpha = 'auto' the pair mpg_sac_auto_step_begin / mpg_sac_auto_step_end on the policy's device-resident temperature),
+    AMPCLearner + ReplayBuffer (8: the policy alone - no critic, no target, no ws0; SingleProcessOffPolicyOptimizer takes it with
+    native_ampc=True)."""
 
     def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
         from .buffer import PrioritizedReplayBuffer
-        from .learners import MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
+        from .learners import AMPCLearner, MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
         per = isinstance(rb, PrioritizedReplayBuffer)
         assert per == (learner.args.buffer_type != 'normal')
         assert learner.policy_with_value is worker.policy_with_value
@@ -79,6 +81,9 @@ class FusedMPGStep(object):
         elif type(learner) is SACLearner:
             assert not per and worker.explore_sigma is None
             c.learner_version, c.n, c.M, c.n_select = 7, 1, 1, 1
+        elif type(learner) is AMPCLearner:
+            assert not per
+            c.learner_version, c.n, c.M, c.n_select = 8, learner.n, learner.M, 1
         else:
             assert type(learner) is TD3Learner and learner.num_batch_reuse == 1
             c.learner_version, c.n, c.M, c.n_select = 4, 1, 1, 1
@@ -94,7 +99,9 @@ class FusedMPGStep(object):
         c.grads_exchanged = 1 if (c.world_size > 1 or self.always_exchange) else 0
         c.explore_sigma = float(worker.explore_sigma or 0.)
         for i in range(3):
-            c.value_lr[i], c.policy_lr[i] = pw.schedules['Q1'][i], pw.schedules['policy'][i]
+            c.policy_lr[i] = pw.schedules['policy'][i]
+            if 'Q1' in pw.schedules:            # (a policy-only stack has no critic schedule: value_lr stays zero)
+                c.value_lr[i] = pw.schedules['Q1'][i]
         c.worker_seed, c.env_seed, c.replay_seed, c.learner_seed = worker.seed, worker.env.seed, rb.seed, learner.seed
         n, B, od, ad = worker.num_agent, learner.batch_size, pw.obs_dim, pw.act_dim
         f = dict(dtype=torch.float32, device=dev)

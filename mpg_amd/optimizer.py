@@ -18,13 +18,15 @@ def quiesce_gc():
 
 class SingleProcessOffPolicyOptimizer(object):
     def __init__(self, worker, learner, replay_buffer, evaluator, args, sampling_interval=10, fused=True,
-                 always_exchange=False, native_sac=False):
-        if native_sac:
-            # SAC's native step (mpg_sac_step_begin, or the mpg_sac_auto_step_* pair with alpha = 'auto') is taken on request only; a request it cannot serve is an error - raised before
+                 always_exchange=False, native_sac=False, native_ampc=False):
+        if native_sac or native_ampc:
+            # SAC's native step (mpg_sac_step_begin, or the mpg_sac_auto_step_* pair with alpha = 'auto') and AMPC's (learner_version 8 of
+            # mpg_step_begin / mpg_step_end) are taken on request only; a request the driver cannot serve is an error - raised before
             # anything is sampled - never a silent fall-back to the method path
-            reason = self._native_sac_refusal(worker, learner, replay_buffer, args)
+            keyword = 'native_ampc' if native_ampc else 'native_sac'
+            reason = self._native_refusal(keyword, worker, learner, replay_buffer, args, both=bool(native_sac and native_ampc))
             if reason:
-                raise ValueError('native_sac=True: ' + reason)
+                raise ValueError('%s=True: %s' % (keyword, reason))
         self.args = args
         self.worker, self.learner, self.replay_buffer, self.evaluator = worker, learner, replay_buffer, evaluator
         self.num_sampled_steps = 0
@@ -40,7 +42,7 @@ class SingleProcessOffPolicyOptimizer(object):
         # native step driver (mpg_step_begin/_end) when the stock MPG components are plugged in; otherwise the
         # method-by-method path below, which computes the same thing
         self._fused = None
-        if native_sac:
+        if native_sac or native_ampc:
             from .fused import FusedMPGStep
             self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
         elif fused:
@@ -57,14 +59,27 @@ class SingleProcessOffPolicyOptimizer(object):
                 self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
 
     @staticmethod
-    def _native_sac_refusal(worker, learner, replay_buffer, args):
-        """why mpg_sac_step_begin does not serve this stack, or None"""
+    def _native_refusal(keyword, worker, learner, replay_buffer, args, both=False):
+        """why the native step asked for by `keyword` ('native_sac': mpg_sac_step_begin; 'native_ampc': learner_version 8 of
+        mpg_step_begin) does not serve this stack, or None"""
         from .buffer import PrioritizedReplayBuffer
-        from .learners import SACLearner
-        if type(learner) is not SACLearner:
-            return 'the learner is %s, not SACLearner (every other learner takes the native step by default)' % type(learner).__name__
+        from .learners import AMPCLearner, SACLearner
+        if both:
+            return 'native_sac and native_ampc are both set: a stack has one learner, ask for its keyword alone'
+        cls, what = {'native_sac': (SACLearner, 'SAC'), 'native_ampc': (AMPCLearner, 'AMPC')}[keyword]
+        if type(learner) is not cls:
+            return 'the learner is %s, not %s (every learner but SACLearner and AMPCLearner takes the native step by default)' \
+                % (type(learner).__name__, cls.__name__)
         if isinstance(replay_buffer, PrioritizedReplayBuffer) or getattr(args, 'buffer_type', 'normal') != 'normal':
-            return 'a prioritized replay buffer is not served by the native SAC step (uniform ReplayBuffer only)'
+            return 'a prioritized replay buffer is not served by the native %s step (uniform ReplayBuffer only)' % what
+        if keyword == 'native_ampc':
+            # what mpg_step_begin refuses of a learner_version 8 context (include/mpg_hip.h), said where the stack is built
+            if not 1 <= learner.n <= 31:
+                return 'the rollout horizon n = %d is outside 1 .. 31 (mpg_ampc_pg: 0 < n < 32)' % learner.n
+            if (learner.batch_size * learner.M) % 16 != 0:
+                return 'replay_batch_size * M = %d is not a multiple of 16 (mpg_ampc_pg differentiates every step through the policy ' \
+                       'in 16-row groups)' % (learner.batch_size * learner.M)
+            return None
         if getattr(learner, 'squashed', False) or getattr(getattr(worker, 'policy_with_value', None), 'squashed_head', False):
             return 'the tanh-squashed head (squashed_head=True) is not served by the native SAC step: build the optimizer without native_sac'
         if worker.explore_sigma is not None:
@@ -91,9 +106,9 @@ class SingleProcessOffPolicyOptimizer(object):
 
     def step(self):
         if self._fused is not None:
+            self._fused.step(self.iteration)                   # (a refused step raises here: nothing below has been counted)
             if self.iteration % self.sampling_interval == 0:
                 self.num_sampled_steps += self.worker.num_agent * abs(self._fused.c.sample_iters)      # (< 0: the chain kept, include/mpg_hip.h)
-            self._fused.step(self.iteration)
             self.learner._lazy_stats = self.learner._native_lazy_stats(self.iteration)
             self.iteration += 1
             self._check_status()
