@@ -45,6 +45,35 @@ class TrainCtx(ctypes.Structure):
         ('critics_ready_event', _P), ('grad_opts', GradOpts), ('clip_partials_ready', ctypes.c_int)]
 
 
+ON_REQUEST = (7, 8)       # SAC and AMPC are served, but taken only where the optimizer is asked to (native_sac / native_ampc)
+
+
+def native_stack(worker, learner, rb):
+    """(learner_version, n, M, n_select) of the mpg_train_ctx_t that serves this (worker, learner, replay buffer), or None where the
+    driver does not serve it"""
+    from .buffer import PrioritizedReplayBuffer
+    from .learners import AMPCLearner, MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
+    per, kind = isinstance(rb, PrioritizedReplayBuffer), type(learner)
+    if per != (getattr(getattr(learner, 'args', None), 'buffer_type', 'normal') != 'normal'):
+        return None
+    if kind is TD3Learner:              # the one learner whose replay may be prioritized
+        return (4, 1, 1, 1) if learner.num_batch_reuse == 1 else None
+    if per:
+        return None
+    if kind is MPGLearner and not learner.deriv_interval_policy:
+        sel = list(learner.num_rollout_list_for_policy_update)
+        return (1 if learner.args.learner_version == 'MPG-v1' else 2, max(sel), learner.M, len(sel))
+    if kind is NADPLearner and learner.n_q == learner.n_pi and learner.num_batch_reuse == 1:
+        return (3, learner.n_pi, 1, 2)
+    if kind is NDPGLearner:
+        return (5, learner.sample_num_in_learner, 1, 1)
+    if kind is SACLearner and worker.explore_sigma is None:
+        return (7, 1, 1, 1)
+    if kind is AMPCLearner:
+        return (8, learner.n, learner.M, 1)
+    return None
+
+
 class FusedMPGStep(object):
     """step(iteration) == SingleProcessOffPolicyOptimizer.step for (OffPolicyWorker, replay buffer, learner) sharing one
     PolicyWithQs: MPGLearner + ReplayBuffer (learner_version 1 / 2), NADPLearner + ReplayBuffer (3), TD3Learner + ReplayBuffer
@@ -55,38 +84,19 @@ class FusedMPGStep(object):
     native_ampc=True)."""
 
     def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
-        from .buffer import PrioritizedReplayBuffer
-        from .learners import AMPCLearner, MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
-        per = isinstance(rb, PrioritizedReplayBuffer)
-        assert per == (learner.args.buffer_type != 'normal')
+        stack = native_stack(worker, learner, rb)
+        assert stack is not None, 'the native step driver does not serve this stack'
         assert learner.policy_with_value is worker.policy_with_value
         self.worker, self.learner, self.rb = worker, learner, rb
         pw, a, dev = worker.policy_with_value, learner.args, worker.device
         self.pw = pw
         c = self.c = TrainCtx()
         c.cfg = pw.cfg
-        if type(learner) is MPGLearner:
-            assert not per
-            c.learner_version = 1 if a.learner_version == 'MPG-v1' else 2
-            sel = list(learner.num_rollout_list_for_policy_update)
-            c.n, c.M, c.n_select = max(sel), learner.M, len(sel)
-            for i, k in enumerate(sel):
+        c.learner_version, c.n, c.M, c.n_select = stack
+        if c.learner_version in (1, 2):
+            for i, k in enumerate(learner.num_rollout_list_for_policy_update):
                 c.select[i] = k
-        elif type(learner) is NADPLearner:
-            assert not per and learner.n_q == learner.n_pi and learner.num_batch_reuse == 1
-            c.learner_version, c.n, c.M, c.n_select = 3, learner.n_pi, 1, 2
-        elif type(learner) is NDPGLearner:
-            assert not per
-            c.learner_version, c.n, c.M, c.n_select = 5, learner.sample_num_in_learner, 1, 1
-        elif type(learner) is SACLearner:
-            assert not per and worker.explore_sigma is None
-            c.learner_version, c.n, c.M, c.n_select = 7, 1, 1, 1
-        elif type(learner) is AMPCLearner:
-            assert not per
-            c.learner_version, c.n, c.M, c.n_select = 8, learner.n, learner.M, 1
-        else:
-            assert type(learner) is TD3Learner and learner.num_batch_reuse == 1
-            c.learner_version, c.n, c.M, c.n_select = 4, 1, 1, 1
+        if c.learner_version == 4:
             c.smooth_sigma, c.smooth_clip = float(a.policy_smoothing_sigma), float(a.policy_smoothing_clip)
         c.num_agent, c.sample_iters = worker.num_agent, max(1, worker.batch_size // worker.num_agent)
         c.sampling_interval = sampling_interval
@@ -137,6 +147,7 @@ class FusedMPGStep(object):
         if c.learner_version == 4:
             self.scratch = torch.empty(max(B * (ad + 3), 2 * n) + 64, **f)
             c.scratch = L.ptr(self.scratch)
+            per = a.buffer_type != 'normal'          # (native_stack: the buffer's class says the same)
             c.prioritized = 1 if per else 0
             if per:
                 t['b_weights'] = torch.empty(B, **f)
@@ -165,6 +176,20 @@ class FusedMPGStep(object):
         c.ws0, c.ws1, c.ws0_bytes, c.ws1_bytes = L.ptr(self.ws0), L.ptr(self.ws1), self.ws0.numel(), self.ws1.numel()
         self._lib = L.lib()
         self._ref = ctypes.byref(c)
+        # the entry points of this version, chosen once (the library is looked up at call time: self._lib may be wrapped)
+        self._end = lambda it, s: L.check(self._lib.mpg_step_end(self._ref, ctypes.c_int(it), s), 'mpg_step_end')
+        if c.learner_version == 7 and self.auto_alpha:
+            # the learned temperature: read on the device, never here (its step counter lives in the policy's own struct: nothing to
+            # pull or push)
+            self._begin = lambda it, s: L.check(
+                self._lib.mpg_sac_auto_step_begin(self._ref, ctypes.byref(pw.alpha_desc), ctypes.c_int(it), s), 'mpg_sac_auto_step_begin')
+            self._end = lambda it, s: L.check(
+                self._lib.mpg_sac_auto_step_end(self._ref, ctypes.byref(pw.alpha_desc), ctypes.c_int(it), s), 'mpg_sac_auto_step_end')
+        elif c.learner_version == 7:        # the fixed temperature travels as an argument (mpg_train_ctx_t has no field for it)
+            self._begin = lambda it, s: L.check(
+                self._lib.mpg_sac_step_begin(self._ref, ctypes.c_float(learner.alpha), ctypes.c_int(it), s), 'mpg_sac_step_begin')
+        else:
+            self._begin = lambda it, s: L.check(self._lib.mpg_step_begin(self._ref, ctypes.c_int(it), s), 'mpg_step_begin')
         # the python objects now look at the driver's buffers
         learner.batch_data = {'batch_obs': t['b_obs'], 'batch_actions': t['b_act'], 'batch_rewards': t['b_rew'],
                               'batch_obs_tp1': t['b_obs2'], 'batch_dones': t['b_done'], 'batch_targets': t['b_targets']}
@@ -219,14 +244,7 @@ class FusedMPGStep(object):
         try:
             if slot is not None:
                 c.grad = slot.data_ptr()
-            if c.learner_version == 7 and self.auto_alpha:       # the learned temperature: read on the device, never here
-                L.check(self._lib.mpg_sac_auto_step_begin(self._ref, ctypes.byref(self.pw.alpha_desc), ctypes.c_int(iteration), s),
-                        'mpg_sac_auto_step_begin')
-            elif c.learner_version == 7:     # the temperature travels as an argument (mpg_train_ctx_t has no field for it)
-                L.check(self._lib.mpg_sac_step_begin(self._ref, ctypes.c_float(self.learner.alpha), ctypes.c_int(iteration), s),
-                        'mpg_sac_step_begin')
-            else:
-                L.check(self._lib.mpg_step_begin(self._ref, ctypes.c_int(iteration), s), 'mpg_step_begin')
+            self._begin(iteration, s)
             if c.grads_exchanged:
                 # the ONE exchange step, timed under the caller's kernel timer (slot 8, HIP events on the launch stream: bench.py's
                 # `exchange_ms`) - a null or stopped timer makes both calls no-ops
@@ -254,10 +272,5 @@ class FusedMPGStep(object):
             c.grad = flat.data_ptr()
             if slot is not None and not c.clip_partials_ready:
                 D.release_slot(flat.numel())
-        if c.learner_version == 7 and self.auto_alpha:
-            # (the temperature's step counter lives in the policy's own struct: nothing to pull or push)
-            L.check(self._lib.mpg_sac_auto_step_end(self._ref, ctypes.byref(self.pw.alpha_desc), ctypes.c_int(iteration), s),
-                    'mpg_sac_auto_step_end')
-        else:
-            L.check(self._lib.mpg_step_end(self._ref, ctypes.c_int(iteration), s), 'mpg_step_end')
+        self._end(iteration, s)
         self.push()

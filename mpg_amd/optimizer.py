@@ -42,20 +42,10 @@ class SingleProcessOffPolicyOptimizer(object):
         # native step driver (mpg_step_begin/_end) when the stock MPG components are plugged in; otherwise the
         # method-by-method path below, which computes the same thing
         self._fused = None
-        if native_sac or native_ampc:
-            from .fused import FusedMPGStep
-            self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
-        elif fused:
-            from .buffer import PrioritizedReplayBuffer
-            from .learners import MPGLearner, NADPLearner, NDPGLearner, TD3Learner
-            per = isinstance(replay_buffer, PrioritizedReplayBuffer)
-            normal = getattr(args, 'buffer_type', 'normal') == 'normal'
-            ok = (type(learner) is MPGLearner and not per and normal and not learner.deriv_interval_policy) or \
-                 (type(learner) is NADPLearner and not per and normal and learner.num_batch_reuse == 1 and learner.n_q == learner.n_pi) or \
-                 (type(learner) is TD3Learner and per == (not normal) and learner.num_batch_reuse == 1) or \
-                 (type(learner) is NDPGLearner and not per and normal)
-            if ok:
-                from .fused import FusedMPGStep
+        if native_sac or native_ampc or fused:
+            from .fused import ON_REQUEST, FusedMPGStep, native_stack
+            stack = native_stack(worker, learner, replay_buffer)
+            if native_sac or native_ampc or (stack is not None and stack[0] not in ON_REQUEST):
                 self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
 
     @staticmethod

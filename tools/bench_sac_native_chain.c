@@ -22,7 +22,7 @@ typedef struct {
     int capacity;
 } bench_bufs_t;
 
-/* what sac_sample_and_add (train_step.cpp) enqueues where it takes the chain: 4 launches per step */
+/* what sample (train_step.cpp) enqueues where it takes the chain: 4 launches per step */
 int bench_chain(fill_fn fill, sample_fn sample, store_fn store, const mpg_cfg_t* cfg, const float* policy, int n, const bench_bufs_t* b,
                 uint64_t ctr0, mpg_stream_t s, int reps) {
     int next = 0;

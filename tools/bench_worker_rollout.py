@@ -2,7 +2,7 @@
 """Times of one worker sample on the GPU, one process, medians of REGIONS timed regions after a warm-up (device events around REPS
 back-to-back samples, a synchronise at the end of every region):
 
-  (a) the sample as the chain of `iters` mpg_worker_step launches - what sample_and_add of train_step.cpp enqueues without the
+  (a) the sample as the chain of `iters` mpg_worker_step launches - what sample of train_step.cpp enqueues without the
       one-launch form - enqueued by a C loop (tools/bench_worker_rollout_chain.c, compiled on first use), REPS samples per call into it;
   (b) mpg_worker_rollout, the same sample as ONE launch (bit-identical: tests/test_worker_rollout_gpu.py; asserted here at the end);
       cases (agents, iters, obs_dim) = (8, 64, 6), (256, 16, 6), (8, 64, 9), (256, 16, 9), explore_sigma 0.1, the packed weight
@@ -23,7 +23,7 @@ The rule for the driver: it calls (b) for a width only if (b)'s median is at or 
         iteration) against (b) mpg_worker_sample_rollout_pendulum at (agents, iters) = (1, 512) - the reference's SAC defaults - and
         (64, 8), and (d) OffPolicyWorker.sample() of the squashed SAC stack at 1 x 512 on its loop and with one_launch_sample, alternating
     python tools/bench_worker_rollout.py --stochastic [--steps-only] [--json out.json]   a stochastic policy on PathTracking-v0 (SAC):
-        (a) the chain - the plain Gaussian head: `iters` mpg_worker_sample_step launches, what sac_sample_and_add of train_step.cpp
+        (a) the chain - the plain Gaussian head: `iters` mpg_worker_sample_step launches, what sample of train_step.cpp
         enqueues without the one-launch form; the tanh-squashed head (action_range 1.5): `iters` triples mpg_normal_fill +
         mpg_policy_sample_squashed + mpg_env_step_store_reset - against (b) mpg_worker_sample_rollout at the four cases of the
         deterministic measurement, (d) OffPolicyWorker.sample() of both SAC stacks at 8 x 64 on the loop and with one_launch_sample, and
@@ -124,7 +124,7 @@ PENDULUM_CASES = ((1, 512, 0.1), (1, 512, 0.), (64, 8, 0.1))       # (agents, it
 
 def sample_case_pendulum(n, iters, sigma):
     """--env pendulum: (a) the chain of `iters` pairs mpg_policy_action + mpg_env_step_store_reset (two launches per iteration, what
-    sample_and_add's loop enqueues on this env) against (b) mpg_worker_rollout_pendulum, as sample_case does it"""
+    sample's loop enqueues on this env) against (b) mpg_worker_rollout_pendulum, as sample_case does it"""
     import numpy as np
     import torch
     from mpg_amd import _lib as L

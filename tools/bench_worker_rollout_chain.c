@@ -1,4 +1,4 @@
-/* Host loops of tools/bench_worker_rollout.py: one worker sample as `iters` mpg_worker_step launches (what sample_and_add of
+/* Host loops of tools/bench_worker_rollout.py: one worker sample as `iters` mpg_worker_step launches (what sample of
  * train_step.cpp enqueues without the one-launch form) and as one mpg_worker_rollout launch, `reps` samples back to back, so that
  * neither is charged an interpreter or a foreign-function call per launch (and the pendulum's forms of both, further down).  The entry points come in as pointers (the tool resolves
  * them in the engine's library), so this file links against nothing.
@@ -36,7 +36,7 @@ int bench_chain(step_fn worker_step, const mpg_cfg_t* cfg, const float* policy, 
 }
 
 /* the pendulum's chain (bench_worker_rollout.py --env pendulum): two launches per iteration, mpg_policy_action + mpg_env_step_store_reset,
- * as sample_and_add's loop enqueues them; its one-launch form, mpg_worker_rollout_pendulum, has mpg_worker_rollout's signature and goes
+ * as sample's loop enqueues them; its one-launch form, mpg_worker_rollout_pendulum, has mpg_worker_rollout's signature and goes
  * through bench_launch */
 typedef int (*action_fn)(const mpg_cfg_t*, const float*, int, const float*, float, uint64_t, uint64_t, float*, mpg_stream_t);
 typedef int (*step_store_fn)(int, int, int, float*, const float*, int, int, float*, float*, float*, float*, uint8_t*, uint64_t, uint64_t,
@@ -109,7 +109,7 @@ int bench_launch_sample(sample_rollout_fn sample_rollout, const mpg_cfg_t* cfg, 
 }
 
 /* PathTracking under a stochastic policy (bench_worker_rollout.py --stochastic): the plain Gaussian head's chain is what
- * sac_sample_and_add's loop enqueues, one mpg_worker_sample_step per iteration; the squashed head has no one-launch step, its chain is
+ * sample's loop enqueues, one mpg_worker_sample_step per iteration; the squashed head has no one-launch step, its chain is
  * the three calls per iteration (mpg_normal_fill over 2 n elements + mpg_policy_sample_squashed + mpg_env_step_store_reset: four
  * launches).  Both against mpg_worker_sample_rollout through bench_launch_sample. */
 typedef int (*sample_step_fn)(const mpg_cfg_t*, const float*, int, float*, float*, uint64_t, uint64_t, float*, float*, int, int, float*, float*,
