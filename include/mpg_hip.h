@@ -512,8 +512,8 @@ int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_params, int
  * Row r draws elements 2 r and 2 r + 1 of iteration it's stream inside the launch (no eps array exists); both counters are 64-bit
  * sums.  There is no explore_sigma and no log-density output: the worker discards it and the ring has no column for it.
  * Refused before any launch with MPG_EINVAL, "mpg_worker_sample_rollout" and a text of its own each, the outputs untouched: a null
- * configuration, env_kind 2 (the text of the other real-env entry points), any other env that is not PathTracking, act_dim != 2,
- * obs_dim outside 6 .. 16, with an action range what the squashed entry points refuse of it (a tanh output activation, a range that
+ * configuration, env_kind 2 (the text of the other real-env entry points), any other env that is not PathTracking, obs_dim outside
+ * 6 .. 16, act_dim != 2 (in the order of the other seven one-launch rollouts), with an action range what the squashed entry points refuse of it (a tanh output activation, a range that
  * is not finite), a null pointer other than done_out, n <= 0, capacity < n, next_idx outside [0, capacity), iters < 1, iters > 1024
  * and iters * n > capacity.
  * (added without a signature change elsewhere: the ABI version stays 10) */

@@ -554,19 +554,11 @@ void with_policy_args(const mpg_cfg_t* cfg, const float* policy_params, float ex
 // (k_eval_rollout_pendulum: bit-identical trajectories, state, observations, done flags and status word)
 extern "C" int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
                                          float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_eval_rollout_pendulum: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_eval_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_eval_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_eval_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 1, "mpg_eval_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
-    MPG_REQUIRE(n > 0, "mpg_eval_rollout_pendulum: no agents (n %d)", n);
-    MPG_REQUIRE(steps >= 1, "mpg_eval_rollout_pendulum: steps >= 1 (got %d)", steps);
-    // (what bounds one launch's run time; the parsers' largest fixed_steps is 500)
-    MPG_REQUIRE(steps <= 1024, "mpg_eval_rollout_pendulum: steps <= 1024 (got %d)", steps);
-    MPG_REQUIRE(policy_params && state && obs_io && obs_traj && act_traj && rew_traj, "mpg_eval_rollout_pendulum: null pointer");
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
-                "mpg_eval_rollout_pendulum: tanh policy with an action range");
+    if (int rc = env_cfg_refusal("mpg_eval_rollout_pendulum", PENDULUM_ENV, cfg)) return rc;
+    if (int rc = eval_rollout_refusal("mpg_eval_rollout_pendulum", n, steps,
+                                      policy_params && state && obs_io && obs_traj && act_traj && rew_traj))
+        return rc;
+    if (int rc = tanh_range_refusal("mpg_eval_rollout_pendulum", cfg)) return rc;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args<1>(cfg, policy_params, 0.f, 0, 0, [&](auto pk, const auto& pa) {
@@ -584,25 +576,12 @@ extern "C" int mpg_worker_rollout_pendulum(const mpg_cfg_t* cfg, const float* po
                                            float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity,
                                            int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2,
                                            uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_worker_rollout_pendulum: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_worker_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_worker_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 1, "mpg_worker_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
-                "mpg_worker_rollout_pendulum: tanh policy with an action range");
     const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
-    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
-                "mpg_worker_rollout_pendulum: null pointer");
-    MPG_REQUIRE(n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity,
-                "mpg_worker_rollout_pendulum: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n, capacity, next_idx);
-    MPG_REQUIRE(iters >= 1, "mpg_worker_rollout_pendulum: iters >= 1 (got %d)", iters);
-    // (what bounds one launch's run time; the reference's pendulum worker runs 512)
-    MPG_REQUIRE(iters <= 1024, "mpg_worker_rollout_pendulum: iters <= 1024 (got %d)", iters);
-    // two iterations would write one slot from different workgroups with no order between them
-    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d",
-                (long)iters * n, capacity);
+    if (int rc = env_cfg_refusal("mpg_worker_rollout_pendulum", PENDULUM_ENV, cfg)) return rc;
+    if (int rc = tanh_range_refusal("mpg_worker_rollout_pendulum", cfg)) return rc;
+    if (int rc = ring_rollout_refusal("mpg_worker_rollout_pendulum", policy_params && state && obs_io && act_out, n, iters, capacity,
+                                      next_idx, ring))
+        return rc;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args<1>(cfg, policy_params, explore_sigma, noise_seed, noise_ctr, [&](auto pk, const auto& pa) {
@@ -623,24 +602,14 @@ extern "C" int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const fl
                                                   int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2,
                                                   uint8_t* ring_done, uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out,
                                                   mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_worker_sample_rollout_pendulum: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_sample_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    // (the squashed head itself is also built for PathTracking; this launch steps the pendulum)
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_worker_sample_rollout_pendulum: pendulum env only (env kind %d)",
-                cfg->env_kind);
-    // what the head asks of a cfg (the pointers and the row count are judged below, with the ring)
-    if (int rc = gauss::squash_refusal("mpg_worker_sample_rollout_pendulum", cfg, true, 1, 0.f)) return rc;
     const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
-    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
-                "mpg_worker_sample_rollout_pendulum: null pointer");
-    MPG_REQUIRE(n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity,
-                "mpg_worker_sample_rollout_pendulum: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n, capacity, next_idx);
-    MPG_REQUIRE(iters >= 1, "mpg_worker_sample_rollout_pendulum: iters >= 1 (got %d)", iters);
-    // (what bounds one launch's run time; the reference's pendulum worker runs 512)
-    MPG_REQUIRE(iters <= 1024, "mpg_worker_sample_rollout_pendulum: iters <= 1024 (got %d)", iters);
-    // two iterations would write one slot from different workgroups with no order between them
-    MPG_REQUIRE((long)iters * n <= capacity,
-                "mpg_worker_sample_rollout_pendulum: iters * n = %ld transitions do not fit the ring's capacity %d", (long)iters * n, capacity);
+    // (the squashed head itself is also built for PathTracking; this launch steps the pendulum)
+    if (int rc = env_kind_refusal("mpg_worker_sample_rollout_pendulum", PENDULUM_ENV, cfg)) return rc;
+    // what the head asks of a cfg, the widths included (the pointers and the row count are judged below, with the ring)
+    if (int rc = gauss::squash_refusal("mpg_worker_sample_rollout_pendulum", cfg, true, 1, 0.f)) return rc;
+    if (int rc = ring_rollout_refusal("mpg_worker_sample_rollout_pendulum", policy_params && state && obs_io && act_out, n, iters, capacity,
+                                      next_idx, ring))
+        return rc;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args<2>(cfg, policy_params, 0.f, sample_seed, sample_ctr, [&](auto pk, const auto& pa) {
@@ -657,19 +626,13 @@ extern "C" int mpg_worker_sample_rollout_pendulum(const mpg_cfg_t* cfg, const fl
 // launch (k_env_rollout_pendulum: bit-identical rewards, last observations and status word)
 extern "C" int mpg_env_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0,
                                         const float* act0, float* rewards, float* last_obs, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_env_rollout_pendulum: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_rollout_pendulum: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_PENDULUM, "mpg_env_rollout_pendulum: pendulum env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(cfg->obs_dim == 4, "mpg_env_rollout_pendulum: obs_dim 4 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 1, "mpg_env_rollout_pendulum: act_dim 1 only (got %d)", cfg->act_dim);
+    if (int rc = env_cfg_refusal("mpg_env_rollout_pendulum", PENDULUM_ENV, cfg)) return rc;
     MPG_REQUIRE(n >= 1, "mpg_env_rollout_pendulum: n >= 1 steps (got %d)", n);
     // (what bounds one launch's run time, as the worker's one-launch samples bound theirs)
     MPG_REQUIRE(n <= 1024, "mpg_env_rollout_pendulum: n <= 1024 steps (got %d)", n);
     MPG_REQUIRE(rows > 0, "mpg_env_rollout_pendulum: no rows (got %d)", rows);
     MPG_REQUIRE(policy_params && obs0 && act0 && rewards && last_obs, "mpg_env_rollout_pendulum: null pointer");
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f),
-                "mpg_env_rollout_pendulum: tanh policy with an action range");
+    if (int rc = tanh_range_refusal("mpg_env_rollout_pendulum", cfg)) return rc;
     const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args<1>(cfg, policy_params, 0.f, 0, 0, [&](auto pk, const auto& pa) {

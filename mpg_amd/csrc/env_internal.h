@@ -15,6 +15,68 @@ struct RingPtrs {
 #define MPG_NO_DOUBLE_PENDULUM_ENV \
     "the real InvertedDoublePendulum-v2 env is MuJoCo and is not provided (only its differentiable model is: the rollout entry points)"
 
+// ---- The refusals the one-launch rollouts of both environments share, stated once the way gauss::gauss_refusal is (gauss_head.h):
+// `entry` names the caller in every text, MPG_OK lets the call proceed.  What an entry point alone asks stays in its body.
+
+// what a launch built for one real env asks of a cfg, and the words its refusals say it in
+struct EnvDesc {
+    int kind, obs_lo, obs_hi, act_dim;
+    const char *name, *obs_dims;
+};
+constexpr EnvDesc PATH_TRACKING_ENV{MPG_ENV_PATH_TRACKING, 6, 6 + MPG_ENV_MAX_FUTURE, 2, "path-tracking", "6 .. 16"};
+constexpr EnvDesc PENDULUM_ENV{MPG_ENV_INVERTED_PENDULUM, 4, 4, 1, "pendulum", "4"};
+
+// a cfg of env `e`: not null, not the double pendulum, no other env kind (each env has a launch of its own: mpg_*_rollout[_pendulum])
+inline int env_kind_refusal(const char* entry, const EnvDesc& e, const mpg_cfg_t* cfg) {
+    MPG_REQUIRE(cfg, "%s: null configuration", entry);
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "%s: " MPG_NO_DOUBLE_PENDULUM_ENV, entry);
+    MPG_REQUIRE(cfg->env_kind == e.kind, "%s: %s env only (env kind %d)", entry, e.name, cfg->env_kind);
+    return MPG_OK;
+}
+
+// ... and of its widths (mpg_worker_sample_rollout_pendulum leaves them to gauss::squash_refusal, whose texts its callers know)
+inline int env_cfg_refusal(const char* entry, const EnvDesc& e, const mpg_cfg_t* cfg) {
+    if (int rc = env_kind_refusal(entry, e, cfg)) return rc;
+    MPG_REQUIRE(cfg->obs_dim >= e.obs_lo && cfg->obs_dim <= e.obs_hi, "%s: obs_dim %s only (got %d)", entry, e.obs_dims, cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == e.act_dim, "%s: act_dim %d only (got %d)", entry, e.act_dim, cfg->act_dim);
+    return MPG_OK;
+}
+
+// (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
+inline int tanh_range_refusal(const char* entry, const mpg_cfg_t* cfg) {
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "%s: tanh policy with an action range", entry);
+    return MPG_OK;
+}
+
+// what the step -> ring entry points ask of the agent count and the ring
+inline bool ring_ok(int n, int capacity, int next_idx, const RingPtrs& ring) {
+    return n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done;
+}
+
+// the four worker rollouts: `pointers` - the entry point's own non-null ones -, the ring, and `iters` iterations of n transitions in it
+inline int ring_rollout_refusal(const char* entry, bool pointers, int n, int iters, int capacity, int next_idx, const RingPtrs& ring) {
+    MPG_REQUIRE(pointers && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done, "%s: null pointer", entry);
+    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "%s: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", entry, n, capacity,
+                next_idx);
+    MPG_REQUIRE(iters >= 1, "%s: iters >= 1 (got %d)", entry, iters);
+    // (what bounds one launch's run time; the reference's worker runs 64, its pendulum worker 512)
+    MPG_REQUIRE(iters <= 1024, "%s: iters <= 1024 (got %d)", entry, iters);
+    // two iterations would write one slot from different workgroups with no order between them
+    MPG_REQUIRE((long)iters * n <= capacity, "%s: iters * n = %ld transitions do not fit the ring's capacity %d", entry, (long)iters * n,
+                capacity);
+    return MPG_OK;
+}
+
+// the two evaluation rollouts: n agents, `steps` steps, `pointers` - all of them but the nullable done flags
+inline int eval_rollout_refusal(const char* entry, int n, int steps, bool pointers) {
+    MPG_REQUIRE(n > 0, "%s: no agents (n %d)", entry, n);
+    MPG_REQUIRE(steps >= 1, "%s: steps >= 1 (got %d)", entry, steps);
+    // (what bounds one launch's run time; the parsers' largest fixed_steps is 500)
+    MPG_REQUIRE(steps <= 1024, "%s: steps <= 1024 (got %d)", entry, steps);
+    MPG_REQUIRE(pointers, "%s: null pointer", entry);
+    return MPG_OK;
+}
+
 namespace cart_pole {   // env_cart_pole.hip: analytic RK4 statement of inverted_pendulum_conti.xml
 int reset_from_obs(int n, int obs_dim, float* state, const float* init_obs, hipStream_t s);
 int reset(int n, int obs_dim, float* state, const uint8_t* done_mask, uint64_t seed, uint64_t ctr, float* obs, hipStream_t s);

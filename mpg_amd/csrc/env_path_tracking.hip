@@ -1112,11 +1112,6 @@ extern "C" int mpg_env_step(int env_kind, int n, int obs_dim, float* state, cons
 }
 
 namespace {
-// what the three step -> ring entry points ask of the agent count and the ring
-inline bool ring_ok(int n, int capacity, int next_idx, const RingPtrs& ring) {
-    return n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done;
-}
-
 // the caller's draw request as the kernels take it (pd.env_blocks is the launch's own); `who`: the entry point, for the refusal
 int make_predraw(const char* who, const mpg_replay_draw_t* draw, int rows, float* b_obs, float* b_act, float* b_rew, float* b_obs2,
                  int capacity, PreDraw& pd) {
@@ -1233,8 +1228,7 @@ extern "C" int mpg_worker_step(const mpg_cfg_t* cfg, const float* policy_params,
                 "mpg_worker_step: path-tracking env with obs_dim 6 .. 16 only");
     const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
     MPG_REQUIRE(policy_params && ring_ok(n, capacity, next_idx, ring) && state && obs_io && act_out, "mpg_worker_step: bad argument");
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_step: tanh policy with an action range");
+    if (int rc = tanh_range_refusal("mpg_worker_step", cfg)) return rc;
     const bool wide = cfg->obs_dim > 6;
     // the rows are gathered six wide (predraw_row) for the fused gradient launch, which exists for six-entry observations only
     MPG_REQUIRE(!(draw && wide), "mpg_worker_step: the pre-gathered draw serves obs_dim 6 only (got obs_dim %d: pass draw = NULL)", cfg->obs_dim);
@@ -1262,24 +1256,11 @@ extern "C" int mpg_worker_rollout(const mpg_cfg_t* cfg, const float* policy_para
                                   float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx,
                                   float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
                                   uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_worker_rollout: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_worker_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_worker_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 2, "mpg_worker_rollout: act_dim 2 only (got %d)", cfg->act_dim);
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_worker_rollout: tanh policy with an action range");
     const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
-    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
-                "mpg_worker_rollout: null pointer");
-    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "mpg_worker_rollout: bad ring (n %d, capacity %d < n, or next_idx %d outside it)", n,
-                capacity, next_idx);
-    MPG_REQUIRE(iters >= 1, "mpg_worker_rollout: iters >= 1 (got %d)", iters);
-    // (what bounds one launch's run time; the reference's worker runs 64)
-    MPG_REQUIRE(iters <= 1024, "mpg_worker_rollout: iters <= 1024 (got %d)", iters);
-    // two iterations would write one slot from different workgroups with no order between them
-    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_rollout: iters * n = %ld transitions do not fit the ring's capacity %d",
-                (long)iters * n, capacity);
+    if (int rc = env_cfg_refusal("mpg_worker_rollout", PATH_TRACKING_ENV, cfg)) return rc;
+    if (int rc = tanh_range_refusal("mpg_worker_rollout", cfg)) return rc;
+    if (int rc = ring_rollout_refusal("mpg_worker_rollout", policy_params && state && obs_io && act_out, n, iters, capacity, next_idx, ring))
+        return rc;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args(cfg, policy_params, explore_sigma, noise_seed, noise_ctr, [&](auto pk, auto in, const auto& pa) {
@@ -1324,16 +1305,11 @@ extern "C" int mpg_worker_sample_step(const mpg_cfg_t* cfg, const float* policy_
 // step on, mpg_env_step) as one launch (k_env_rollout: bit-identical rewards, last observations and status word).
 extern "C" int mpg_env_rollout(const mpg_cfg_t* cfg, const float* policy_params, int rows, int n, const float* obs0, const float* act0,
                                float* rewards, float* last_obs, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_env_rollout: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_env_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_env_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_env_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 2, "mpg_env_rollout: act_dim 2 only (got %d)", cfg->act_dim);
+    if (int rc = env_cfg_refusal("mpg_env_rollout", PATH_TRACKING_ENV, cfg)) return rc;
     MPG_REQUIRE(n >= 1 && n < 32, "mpg_env_rollout: 1 <= n < 32 steps (got %d)", n);
     MPG_REQUIRE(rows > 0, "mpg_env_rollout: no rows");
     MPG_REQUIRE(policy_params && obs0 && act0 && rewards && last_obs, "mpg_env_rollout: null pointer");
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_env_rollout: tanh policy with an action range");
+    if (int rc = tanh_range_refusal("mpg_env_rollout", cfg)) return rc;
     const int blocks = (rows + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args(cfg, policy_params, 0.f, 0, 0, [&](auto pk, auto in, const auto& pa) {
@@ -1352,28 +1328,16 @@ extern "C" int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* poli
                                          uint64_t sample_seed, uint64_t sample_ctr, float* act_out, int capacity, int next_idx,
                                          float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
                                          uint64_t env_seed, uint64_t env_ctr, uint8_t* done_out, mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_worker_sample_rollout: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_worker_sample_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    // (the pendulum's squashed policy has a launch of its own: mpg_worker_sample_rollout_pendulum)
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_worker_sample_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(cfg->act_dim == 2, "mpg_worker_sample_rollout: act_dim 2 only (got %d)", cfg->act_dim);
-    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_worker_sample_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
+    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
+    if (int rc = env_cfg_refusal("mpg_worker_sample_rollout", PATH_TRACKING_ENV, cfg)) return rc;
     // no action range: the Gaussian head as it stands; a range: the squashed head, and what it asks of a cfg (a linear output, a finite
     // range; the pointers and the row count are judged below, with the ring)
     const bool squash = cfg->action_range > 0.f;
     if (squash)
         if (int rc = gauss::squash_refusal("mpg_worker_sample_rollout", cfg, true, 1, 0.f)) return rc;
-    const RingPtrs ring{ring_obs, ring_act, ring_rew, ring_obs2, ring_done};
-    MPG_REQUIRE(policy_params && state && obs_io && act_out && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done,
-                "mpg_worker_sample_rollout: null pointer");
-    MPG_REQUIRE(ring_ok(n, capacity, next_idx, ring), "mpg_worker_sample_rollout: bad ring (n %d, capacity %d < n, or next_idx %d outside it)",
-                n, capacity, next_idx);
-    MPG_REQUIRE(iters >= 1, "mpg_worker_sample_rollout: iters >= 1 (got %d)", iters);
-    // (what bounds one launch's run time; the reference's worker runs 64)
-    MPG_REQUIRE(iters <= 1024, "mpg_worker_sample_rollout: iters <= 1024 (got %d)", iters);
-    // two iterations would write one slot from different workgroups with no order between them
-    MPG_REQUIRE((long)iters * n <= capacity, "mpg_worker_sample_rollout: iters * n = %ld transitions do not fit the ring's capacity %d",
-                (long)iters * n, capacity);
+    if (int rc = ring_rollout_refusal("mpg_worker_sample_rollout", policy_params && state && obs_io && act_out, n, iters, capacity, next_idx,
+                                      ring))
+        return rc;
     const float range = squash ? cfg->action_range : 0.f, log_r = squash ? gauss::log_range(cfg->action_range) : 0.f;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
@@ -1397,19 +1361,10 @@ extern "C" int mpg_worker_sample_rollout(const mpg_cfg_t* cfg, const float* poli
 extern "C" int mpg_eval_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, float* state, float* obs_io,
                                 float* obs_traj, float* act_traj, float* rew_traj, uint8_t* done_out, uint8_t* done_intended_out,
                                 mpg_stream_t stream) {
-    MPG_REQUIRE(cfg, "mpg_eval_rollout: null configuration");
-    MPG_REQUIRE(cfg->env_kind != MPG_ENV_INVERTED_DOUBLE_PENDULUM, "mpg_eval_rollout: " MPG_NO_DOUBLE_PENDULUM_ENV);
-    // (the pendulum has a launch of its own: mpg_eval_rollout_pendulum)
-    MPG_REQUIRE(cfg->env_kind == MPG_ENV_PATH_TRACKING, "mpg_eval_rollout: path-tracking env only (env kind %d)", cfg->env_kind);
-    MPG_REQUIRE(pt_obs_dim_ok(cfg->obs_dim), "mpg_eval_rollout: obs_dim 6 .. 16 only (got %d)", cfg->obs_dim);
-    MPG_REQUIRE(cfg->act_dim == 2, "mpg_eval_rollout: act_dim 2 only (got %d)", cfg->act_dim);
-    MPG_REQUIRE(n > 0, "mpg_eval_rollout: no agents (n %d)", n);
-    MPG_REQUIRE(steps >= 1, "mpg_eval_rollout: steps >= 1 (got %d)", steps);
-    // (what bounds one launch's run time; the parsers' largest fixed_steps is 500)
-    MPG_REQUIRE(steps <= 1024, "mpg_eval_rollout: steps <= 1024 (got %d)", steps);
-    MPG_REQUIRE(policy_params && state && obs_io && obs_traj && act_traj && rew_traj, "mpg_eval_rollout: null pointer");
-    // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
-    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "mpg_eval_rollout: tanh policy with an action range");
+    if (int rc = env_cfg_refusal("mpg_eval_rollout", PATH_TRACKING_ENV, cfg)) return rc;
+    if (int rc = eval_rollout_refusal("mpg_eval_rollout", n, steps, policy_params && state && obs_io && obs_traj && act_traj && rew_traj))
+        return rc;
+    if (int rc = tanh_range_refusal("mpg_eval_rollout", cfg)) return rc;
     const int blocks = (n + mlp::GROUP - 1) / mlp::GROUP;
     hipStream_t s = mpg_stream(stream);
     with_policy_args(cfg, policy_params, 0.f, 0, 0, [&](auto pk, auto in, const auto& pa) {

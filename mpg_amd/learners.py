@@ -183,15 +183,11 @@ class MPGLearner(_LearnerBase):
         (mpg_env_rollout, bit-identical to the chain below) for the horizons it serves (n < 32); the learner's env is not stepped then.
         On the pendulum: mpg_env_rollout_pendulum, n <= 1024."""
         pw = self.policy_with_value
-        if self.pendulum:
-            if self.sample_num_in_learner <= 1024:
-                rewards, last_obs = ops.env_rollout_pendulum(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
-                return {'all_rewards': rewards, 'last_obs': last_obs}
-            if self.env is None:
-                self.env = InvertedPendulumContiEnv(num_agent=self.batch_size, device=self.device)
-        elif self.sample_num_in_learner < 32:
+        if self.sample_num_in_learner <= 1024 if self.pendulum else self.sample_num_in_learner < 32:
             rewards, last_obs = ops.env_rollout(self.cfg, pw.net('policy'), start_obs, start_action, self.sample_num_in_learner)
             return {'all_rewards': rewards, 'last_obs': last_obs}
+        if self.pendulum and self.env is None:
+            self.env = InvertedPendulumContiEnv(num_agent=self.batch_size, device=self.device)
         obs = start_obs
         self.env.reset(init_obs=obs)
         rewards = []

@@ -287,26 +287,20 @@ def nstep_targets(cfg, policy_t, q1t, rewards, last_obs, clip=None):
     return y
 
 
-def env_rollout(cfg, policy_params, obs0, act0, n):
-    """mpg_env_rollout: n real-env steps from (obs0, act0), later actions from the policy without noise, ONE launch.
-    Returns (rewards [n, rows] RAW, last_obs [rows, obs_dim])."""
+def env_rollout(cfg, policy_params, obs0, act0, n, entry=None):
+    """mpg_env_rollout / mpg_env_rollout_pendulum (by cfg.env_kind): n real-env steps from (obs0 [rows, obs_dim], act0 [rows, act_dim]),
+    later actions from the policy without noise, ONE launch.  Returns (rewards [n, rows] RAW, last_obs [rows, obs_dim])."""
     rows, dev = obs0.shape[0], obs0.device
     rewards = torch.empty(int(n), rows, dtype=torch.float32, device=dev)
     last_obs = torch.empty(rows, cfg.obs_dim, dtype=torch.float32, device=dev)
-    L.call('mpg_env_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)),
-           L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
+    L.call(entry or ('mpg_env_rollout_pendulum' if cfg.env_kind == 1 else 'mpg_env_rollout'), ctypes.byref(cfg), L.ptr(_f32(policy_params)),
+           L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)), L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
     return rewards, last_obs
 
 
 def env_rollout_pendulum(cfg, policy_params, obs0, act0, n):
-    """mpg_env_rollout_pendulum: n real-env steps of the inverted pendulum from (obs0 [rows, 4], act0 [rows, 1]), later actions from the
-    policy without noise, ONE launch.  Returns (rewards [n, rows] RAW, last_obs [rows, 4])."""
-    rows, dev = obs0.shape[0], obs0.device
-    rewards = torch.empty(int(n), rows, dtype=torch.float32, device=dev)
-    last_obs = torch.empty(rows, 4, dtype=torch.float32, device=dev)
-    L.call('mpg_env_rollout_pendulum', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(rows), L.c_int(int(n)), L.ptr(_f32(obs0)),
-           L.ptr(_f32(act0)), L.ptr(rewards), L.ptr(last_obs), L.stream())
-    return rewards, last_obs
+    """env_rollout through the pendulum's entry point whatever cfg says: another env's cfg is refused under that name, not served"""
+    return env_rollout(cfg, policy_params, obs0, act0, n, entry='mpg_env_rollout_pendulum')
 
 
 EVAL_METRICS_PATH_TRACKING, EVAL_METRICS_PENDULUM = 8, 18      # MPG_EVAL_METRICS_* (include/mpg_hip.h): metrics per episode

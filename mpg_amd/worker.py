@@ -11,6 +11,25 @@ import torch
 from .envs import make_env
 from . import ops
 
+# args.one_launch_sample, stated once: (env.kind, stochastic policy) -> the method sample() takes, what it says to the other policy kind
+# and to another env (% the env's class), and how it names itself where it bounds the iterations (None: only the library's own bound).
+# _one_launch_checked raises them; ops.worker_rollout / ops.worker_sample_rollout choose the entry point by cfg.env_kind.
+ONE_LAUNCH = {
+    (0, False): ('_sample_one_launch',
+                 '_sample_one_launch serves a deterministic policy only (a stochastic one takes _sample_one_launch_stochastic)',
+                 'one_launch_sample serves PathTracking-v0 only (the env is %s)', None),
+    (1, False): ('_sample_one_launch_pendulum',
+                 'one_launch_sample on the pendulum serves a deterministic policy only: a one-launch step for the stochastic or squashed '
+                 'policy is not built for this env',
+                 '_sample_one_launch_pendulum serves InvertedPendulumConti-v0 only (the env is %s)', 'on the pendulum'),
+    (1, True): ('_sample_one_launch_stochastic_pendulum',
+                '_sample_one_launch_stochastic_pendulum serves a stochastic policy (a deterministic one takes _sample_one_launch_pendulum)',
+                '_sample_one_launch_stochastic_pendulum serves InvertedPendulumConti-v0 only (the env is %s)', 'with the squashed head'),
+    (0, True): ('_sample_one_launch_stochastic',
+                '_sample_one_launch_stochastic serves a stochastic policy (a deterministic one takes _sample_one_launch)',
+                '_sample_one_launch_stochastic serves PathTracking-v0 only (the env is %s)', 'with a stochastic policy'),
+}
+
 
 class OffPolicyWorker(object):
     def __init__(self, policy_cls, env_id, args, worker_id, device='cuda'):
@@ -65,14 +84,9 @@ class OffPolicyWorker(object):
         iters = max(1, self.batch_size // self.num_agent)
         if not getattr(self.args, 'one_launch_sample', False):
             batch = self._sample_loop(iters)
-        elif self.env.kind == 1 and not getattr(self.policy_with_value, 'deterministic_policy', True):
-            batch = self._sample_one_launch_stochastic_pendulum(iters)
-        elif self.env.kind == 1:
-            batch = self._sample_one_launch_pendulum(iters)
-        elif self.env.kind == 0 and not getattr(self.policy_with_value, 'deterministic_policy', True):
-            batch = self._sample_one_launch_stochastic(iters)
-        else:
-            batch = self._sample_one_launch(iters)
+        else:       # (an env kind without a row of its own: _sample_one_launch, which refuses it)
+            stochastic = not getattr(self.policy_with_value, 'deterministic_policy', True)
+            batch = getattr(self, ONE_LAUNCH.get((self.env.kind, stochastic), ONE_LAUNCH[0, False])[0])(iters)
         self.num_sample += batch[0].shape[0]
         self.sample_times += 1
         # judge_is_nan (worker.py:95-107) runs inside the policy kernel: a NaN observation or action sets MPG_STATUS_NAN in the
@@ -107,73 +121,44 @@ class OffPolicyWorker(object):
         """args.one_launch_sample = True: the same batch, observations, env state and counters as _sample_loop, bit for bit, from ONE
         launch (mpg_worker_rollout) instead of three per iteration - the five output arrays [iters * n, .] are the launch's ring of
         capacity iters * n at position 0.  Deterministic policy on PathTracking-v0 only.  env.done_intended is NOT refreshed on this
-        path (the launch does not form it; env.step does)."""
-        pw, env = self.policy_with_value, self.env
-        if not getattr(pw, 'deterministic_policy', True):
-            raise ValueError('_sample_one_launch serves a deterministic policy only (a stochastic one takes '
-                             '_sample_one_launch_stochastic)')
-        if env.kind != 0:
-            raise ValueError('one_launch_sample serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
-        return self._one_launch(iters)
+        path (the launch does not form it; env.step does).  The three methods below keep this contract over consecutive calls."""
+        return self._one_launch_checked(0, False, iters)
 
     def _sample_one_launch_pendulum(self, iters):
-        """_sample_one_launch for InvertedPendulumConti-v0 (mpg_worker_rollout_pendulum instead of three launches per iteration; the
-        reference's pendulum worker: one agent, 512 iterations): the same contract - the five output arrays are the launch's ring of
-        capacity iters * n at position 0; batches, worker.obs, env state, env.done and both counters equal _sample_loop's bit for bit
-        over consecutive calls; env.done_intended is NOT refreshed.  Deterministic policy only, at most 1024 iterations."""
-        pw, env = self.policy_with_value, self.env
-        if not getattr(pw, 'deterministic_policy', True):
-            raise ValueError('one_launch_sample on the pendulum serves a deterministic policy only: a one-launch step for the '
-                             'stochastic or squashed policy is not built for this env')
-        if env.kind != 1:
-            raise ValueError('_sample_one_launch_pendulum serves InvertedPendulumConti-v0 only (the env is %s)' % type(env).__name__)
-        if iters > 1024:
-            raise ValueError('one_launch_sample on the pendulum takes at most 1024 iterations per launch (batch_size / num_agent = %d)'
-                             % iters)
-        return self._one_launch(iters)
+        """_sample_one_launch for InvertedPendulumConti-v0: mpg_worker_rollout_pendulum (the reference's pendulum worker: one agent, 512
+        iterations).  Deterministic policy only, at most 1024 iterations."""
+        return self._one_launch_checked(1, False, iters)
 
     def _sample_one_launch_stochastic_pendulum(self, iters):
         """_sample_one_launch_pendulum for the tanh-squashed Gaussian policy (squashed_head=True: SAC with an action range, the one
         stochastic head built for this env): mpg_worker_sample_rollout_pendulum instead of the loop's launches per iteration (the draw,
-        the policy pass, the head's row sums, env.step, env.reset).  The same contract: batches, worker.obs, env state, env.done and both
-        counters equal _sample_loop's bit for bit over consecutive calls; env.done_intended is NOT refreshed.  No explore_sigma (the
-        loop adds that noise with a torch op, which has no place in the launch), at most 1024 iterations."""
-        pw, env = self.policy_with_value, self.env
-        if getattr(pw, 'deterministic_policy', True):
-            raise ValueError('_sample_one_launch_stochastic_pendulum serves a stochastic policy (a deterministic one takes '
-                             '_sample_one_launch_pendulum)')
-        if not getattr(pw, 'squashed_head', False):
-            raise ValueError('one_launch_sample on the pendulum serves the tanh-squashed head only (squashed_head=True): a stochastic '
-                             'policy without an action range is not built for this env')
-        if self.explore_sigma is not None:
-            raise ValueError('one_launch_sample with a stochastic policy takes no explore_sigma (got %r): the action is the sample'
-                             % (self.explore_sigma,))
-        if env.kind != 1:
-            raise ValueError('_sample_one_launch_stochastic_pendulum serves InvertedPendulumConti-v0 only (the env is %s)'
-                             % type(env).__name__)
-        if iters > 1024:
-            raise ValueError('one_launch_sample with the squashed head takes at most 1024 iterations per launch (batch_size / num_agent '
-                             '= %d)' % iters)
-        return self._one_launch(iters, sampled=True)
+        the policy pass, the head's row sums, env.step, env.reset).  No explore_sigma (the loop adds that noise with a torch op, which
+        has no place in the launch), at most 1024 iterations."""
+        return self._one_launch_checked(1, True, iters)
 
     def _sample_one_launch_stochastic(self, iters):
         """_sample_one_launch for a stochastic policy on PathTracking-v0 (SAC: the Gaussian head, or with squashed_head=True the
-        tanh-squashed one): mpg_worker_sample_rollout instead of the loop's four launches per iteration (the draw, the policy pass, the
-        head's row sums, env.step / env.reset).  The same contract: batches, worker.obs, env state, env.done and both counters equal
-        _sample_loop's bit for bit over consecutive calls; env.done_intended is NOT refreshed.  No explore_sigma (the loop adds that
-        noise with a torch op, which has no place in the launch), at most 1024 iterations."""
+        tanh-squashed one): mpg_worker_sample_rollout.  No explore_sigma, at most 1024 iterations."""
+        return self._one_launch_checked(0, True, iters)
+
+    def _one_launch_checked(self, kind, stochastic, iters):
+        """the one-launch contract of ONE_LAUNCH[kind, stochastic]: its refusals - the policy kind, the head, explore_sigma, the env, the
+        iteration count, in that order, each a ValueError before anything touches the device - and then the launch"""
+        _, wrong_policy, wrong_env, too_many = ONE_LAUNCH[kind, stochastic]
         pw, env = self.policy_with_value, self.env
-        if getattr(pw, 'deterministic_policy', True):
-            raise ValueError('_sample_one_launch_stochastic serves a stochastic policy (a deterministic one takes _sample_one_launch)')
-        if self.explore_sigma is not None:
+        if stochastic == bool(getattr(pw, 'deterministic_policy', True)):
+            raise ValueError(wrong_policy)
+        if stochastic and kind == 1 and not getattr(pw, 'squashed_head', False):
+            raise ValueError('one_launch_sample on the pendulum serves the tanh-squashed head only (squashed_head=True): a stochastic '
+                             'policy without an action range is not built for this env')
+        if stochastic and self.explore_sigma is not None:
             raise ValueError('one_launch_sample with a stochastic policy takes no explore_sigma (got %r): the action is the sample'
                              % (self.explore_sigma,))
-        if env.kind != 0:
-            raise ValueError('_sample_one_launch_stochastic serves PathTracking-v0 only (the env is %s)' % type(env).__name__)
-        if iters > 1024:
-            raise ValueError('one_launch_sample with a stochastic policy takes at most 1024 iterations per launch (batch_size / '
-                             'num_agent = %d)' % iters)
-        return self._one_launch(iters, sampled=True)
+        if env.kind != kind:
+            raise ValueError(wrong_env % type(env).__name__)
+        if too_many and iters > 1024:
+            raise ValueError('one_launch_sample %s takes at most 1024 iterations per launch (batch_size / num_agent = %d)' % (too_many, iters))
+        return self._one_launch(iters, sampled=stochastic)
 
     def _one_launch(self, iters, sampled=False):
         """ops.worker_rollout (sampled: ops.worker_sample_rollout, the draw keyed as the loop keys it: (seed, _noise_ctr)) on a fresh

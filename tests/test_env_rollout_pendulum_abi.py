@@ -9,19 +9,11 @@ import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import abi_harness as H
+from tests.abi_harness import CSRC, ENGINES, F, FAKE, I, NULL, MPG_EINVAL, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 ROLLOUT, CLIPPED = 'mpg_env_rollout_pendulum', 'mpg_nstep_targets_clipped'
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I, F, SZ = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-CSRC = os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
+SZ = ctypes.c_size_t
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -70,12 +62,6 @@ def _cfg():
     return ops.make_cfg('InvertedPendulumConti-v0')
 
 
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
 # ---- mpg_env_rollout_pendulum ---------------------------------------------------------------------------------------------------
 OK = dict(policy=FAKE, rows=40, n=25, obs0=FAKE, act0=FAKE, rewards=FAKE, last_obs=FAKE)
 REFUSALS = [
@@ -100,38 +86,16 @@ def _rollout(lib, cfg_ref, a):
     return getattr(lib, ROLLOUT)(cfg_ref, a['policy'], I(a['rows']), I(a['n']), a['obs0'], a['act0'], a['rewards'], a['last_obs'], NULL)
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
-def test_rollout_refusals(engine, case):
-    make, diff, text = REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        rc = _rollout(lib, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(ROLLOUT + ':') and text in msg, msg
+test_rollout_refusals = H.refusal_test(ROLLOUT, REFUSALS, OK, _rollout)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 def test_rollout_refuses_a_null_configuration(engine):
-    with L.engine(engine):
-        lib = L.lib()
-        assert _rollout(lib, NULL, dict(OK)) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith(ROLLOUT + ':') and 'null configuration' in msg, msg
+    H.null_configuration_refused(engine, ROLLOUT, _rollout, OK)
 
 
 def test_every_rollout_refusal_has_a_text_of_its_own():
-    """the refusals are told apart by their text: no two conditions share one"""
-    src = open(os.path.join(CSRC, 'env_cart_pole.hip')).read()
-    body = src[src.index('extern "C" int %s(' % ROLLOUT):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    texts = re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % ROLLOUT, body, flags=re.S)
-    assert len(texts) >= 10 and len(set(texts)) == len(texts), texts
+    H.refusal_texts_are_unique(ROLLOUT, 'env_cart_pole.hip', 10)
 
 
 def test_the_path_tracking_entry_points_answer_the_pendulum_as_they_did():
@@ -167,20 +131,7 @@ def _clipped(lib, cfg_ref, a):
                                  F(a['hi']), a['y'], a['ws'], SZ(a['ws_bytes']), NULL)
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(T_REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(T_REFUSALS)])
-def test_clipped_target_refusals(engine, case):
-    make, diff, text = T_REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(TOK)
-        a.update(diff)
-        rc = _clipped(lib, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(CLIPPED + ':') and text in msg, msg
+test_clipped_target_refusals = H.refusal_test(CLIPPED, T_REFUSALS, TOK, _clipped)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -213,7 +164,9 @@ def test_the_wrappers_call_path_raises_mpg_error():
     cfg = _cfg()
     with pytest.raises(L.MpgError, match=CLIPPED + ': empty clip interval'):
         L.call(CLIPPED, ctypes.byref(cfg), FAKE, FAKE, I(64), I(25), FAKE, FAKE, F(0.5), F(0.0), FAKE, FAKE, SZ(1 << 30), NULL)
-    assert "L.call('%s'" % ROLLOUT in inspect.getsource(ops.env_rollout_pendulum)
+    # (the pendulum's wrapper is ops.env_rollout held to this entry point, whatever the cfg's env kind)
+    assert "entry='%s'" % ROLLOUT in inspect.getsource(ops.env_rollout_pendulum)
+    assert 'L.call(entry or ' in inspect.getsource(ops.env_rollout)
     assert "L.call('%s'" % CLIPPED in inspect.getsource(ops.nstep_targets)
     # the default leaves today's call untouched
     assert inspect.signature(ops.nstep_targets).parameters['clip'].default is None

@@ -9,19 +9,10 @@ import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import abi_harness as H
+from tests.abi_harness import CSRC, ENGINES, FAKE, I, NULL, MPG_EINVAL, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 PT, PEND, METRICS = 'mpg_eval_rollout', 'mpg_eval_rollout_pendulum', 'mpg_eval_metrics'
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I = ctypes.c_int
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-CSRC = os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -80,12 +71,6 @@ def _pend():
     return ops.make_cfg('InvertedPendulumConti-v0')
 
 
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
 POINTERS = ('policy', 'state', 'obs_io', 'obs_traj', 'act_traj', 'rew_traj')
 OK = dict(policy=FAKE, n=5, steps=200, state=FAKE, obs_io=FAKE, obs_traj=FAKE, act_traj=FAKE, rew_traj=FAKE, done=FAKE, done_i=FAKE)
 STEPS = [(dict(steps=0), 'steps >= 1'), (dict(steps=-1), 'steps >= 1'), (dict(steps=1025), 'steps <= 1024')]
@@ -133,53 +118,23 @@ def _call(lib, name, cfg_ref, a):
                               a['rew_traj'], *tail)
 
 
-def _ids(table):
-    return ['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(table)]
+def _calls(name):
+    return lambda lib, cfg_ref, a: _call(lib, name, cfg_ref, a)
 
 
-def _refused(engine, name, case):
-    make, diff, text = case
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        rc = _call(lib, name, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(name + ':') and text in msg, msg
-
-
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(PT_REFUSALS)), ids=_ids(PT_REFUSALS))
-def test_path_tracking_refusals(engine, case):
-    _refused(engine, PT, PT_REFUSALS[case])
-
-
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(PEND_REFUSALS)), ids=_ids(PEND_REFUSALS))
-def test_pendulum_refusals(engine, case):
-    _refused(engine, PEND, PEND_REFUSALS[case])
+test_path_tracking_refusals = H.refusal_test(PT, PT_REFUSALS, OK, _calls(PT))
+test_pendulum_refusals = H.refusal_test(PEND, PEND_REFUSALS, OK, _calls(PEND))
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 @pytest.mark.parametrize('name', [PT, PEND])
 def test_a_null_configuration_is_refused(engine, name):
-    with L.engine(engine):
-        lib = L.lib()
-        assert _call(lib, name, NULL, dict(OK)) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith(name + ':') and 'null configuration' in msg, msg
+    H.null_configuration_refused(engine, name, _calls(name), OK)
 
 
 @pytest.mark.parametrize('name, src', [(PT, 'env_path_tracking.hip'), (PEND, 'env_cart_pole.hip'), (METRICS, 'eval_kernels.hip')])
 def test_every_refusal_has_a_text_of_its_own(name, src):
-    """the refusals are told apart by their text: no two conditions share one"""
-    src = open(os.path.join(CSRC, src)).read()
-    body = src[src.index('extern "C" int %s(' % name):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    texts = re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % name, body, flags=re.S)
-    assert len(texts) >= (6 if name == METRICS else 10) and len(set(texts)) == len(texts), texts
+    H.refusal_texts_are_unique(name, src, 6 if name == METRICS else 10)
 
 
 # ---- mpg_eval_metrics -----------------------------------------------------------------------------------------------------------

@@ -1,24 +1,14 @@
 """mpg_worker_rollout at the drop-in boundary, without a GPU: both libraries export it with the declared argument types, and every
 refusal comes back as MPG_EINVAL with a text of its own before any launch (every pointer is FAKE: a launch would fault)."""
 import ctypes
-import os
 import re
 
 import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
-
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
+from tests import abi_harness as H
+from tests.abi_harness import ENGINES, F, FAKE, I, NULL, U64, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -44,12 +34,6 @@ def test_declared_argument_types():
 
 def _cfg(obs_dim=6):
     return ops.make_cfg('PathTracking-v0', obs_dim=obs_dim)
-
-
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
 
 
 OK = dict(policy=FAKE, n=8, iters=64, state=FAKE, obs_io=FAKE, act_out=FAKE, capacity=512, next_idx=0, ring_obs=FAKE, ring_act=FAKE,
@@ -82,38 +66,16 @@ def _call(lib, cfg_ref, a):
                                   a['ring_done'], U64(2), U64(0), a['done_out'], NULL)
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
-def test_refusals(engine, case):
-    make, diff, text = REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        rc = _call(lib, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith('mpg_worker_rollout:') and text in msg, msg
+test_refusals = H.refusal_test('mpg_worker_rollout', REFUSALS, OK, _call)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 def test_refuses_a_null_configuration(engine):
-    with L.engine(engine):
-        lib = L.lib()
-        assert _call(lib, NULL, dict(OK)) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith('mpg_worker_rollout:') and 'null configuration' in msg, msg
+    H.null_configuration_refused(engine, 'mpg_worker_rollout', _call, OK)
 
 
 def test_every_refusal_has_a_text_of_its_own():
-    """the refusals are told apart by their text: no two conditions share one"""
-    src = open(os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc', 'env_path_tracking.hip')).read()
-    body = src[src.index('extern "C" int mpg_worker_rollout('):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    texts = re.findall(r'MPG_REQUIRE\(.*?"(mpg_worker_rollout: [^"]*)"', body, flags=re.S)
-    assert len(texts) >= 11 and len(set(texts)) == len(texts), texts
+    H.refusal_texts_are_unique('mpg_worker_rollout', 'env_path_tracking.hip', 11)
 
 
 def test_python_refuses_a_stochastic_policy_and_another_env():

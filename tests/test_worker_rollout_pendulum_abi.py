@@ -1,25 +1,16 @@
 """mpg_worker_rollout_pendulum at the drop-in boundary, without a GPU: both libraries export it with the declared argument types, and
 every refusal comes back as MPG_EINVAL with a text of its own before any launch (every pointer is FAKE: a launch would fault)."""
 import ctypes
-import os
 import re
 
 import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import abi_harness as H
+from tests.abi_harness import ENGINES, F, FAKE, I, NULL, U64, MPG_EINVAL, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 NAME = 'mpg_worker_rollout_pendulum'
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -48,12 +39,6 @@ def test_declared_argument_types():
 
 def _cfg():
     return ops.make_cfg('InvertedPendulumConti-v0')
-
-
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
 
 
 OK = dict(policy=FAKE, n=8, iters=64, state=FAKE, obs_io=FAKE, act_out=FAKE, capacity=512, next_idx=0, ring_obs=FAKE, ring_act=FAKE,
@@ -87,29 +72,12 @@ def _call(lib, cfg_ref, a):
                               a['ring_done'], U64(2), U64(0), a['done_out'], NULL)
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
-def test_refusals(engine, case):
-    make, diff, text = REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        rc = _call(lib, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(NAME + ':') and text in msg, msg
+test_refusals = H.refusal_test(NAME, REFUSALS, OK, _call)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 def test_refuses_a_null_configuration(engine):
-    with L.engine(engine):
-        lib = L.lib()
-        assert _call(lib, NULL, dict(OK)) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith(NAME + ':') and 'null configuration' in msg, msg
+    H.null_configuration_refused(engine, NAME, _call, OK)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -124,12 +92,7 @@ def test_a_null_done_out_is_no_refusal_of_its_own(engine):
 
 
 def test_every_refusal_has_a_text_of_its_own():
-    """the refusals are told apart by their text: no two conditions share one"""
-    src = open(os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc', 'env_cart_pole.hip')).read()
-    body = src[src.index('extern "C" int %s(' % NAME):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    texts = re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % NAME, body, flags=re.S)
-    assert len(texts) >= 11 and len(set(texts)) == len(texts), texts
+    H.refusal_texts_are_unique(NAME, 'env_cart_pole.hip', 11)
 
 
 def test_the_other_rollout_entry_point_still_refuses_the_pendulum():

@@ -3,28 +3,18 @@ refusal comes back as MPG_EINVAL with a text of its own before any launch.  Ever
 byte: a launch would fault on it, and a refusal leaves every byte as it was.  The Python side: OffPolicyWorker's refusals and the
 dispatch of sample()."""
 import ctypes
-import os
 import re
 
 import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import abi_harness as H
+from tests.abi_harness import ENGINES, F, FAKE, I, NULL, U64, MPG_EINVAL, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 NAME = 'mpg_worker_sample_rollout'
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-CSRC = os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc')
 POISON, NBYTES = 0xA5, 256
 OUTPUTS = ('state', 'obs_io', 'act_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'done_out')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -60,12 +50,6 @@ def _cfg(obs_dim=6, **kw):
 
 def _squashed(**kw):
     return _cfg(policy_out_activation='linear', action_range=1.5, **kw)
-
-
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
 
 
 OK = dict(policy=FAKE, n=8, iters=64, capacity=512, next_idx=0)
@@ -113,33 +97,20 @@ def _untouched(bufs):
     return all(bytes(b) == bytes([POISON]) * NBYTES for b in bufs.values())
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
-def test_refusals(engine, case):
-    make, diff, text = REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        bufs = _buffers()
-        rc = _call(lib, ctypes.byref(cfg), a, bufs)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(NAME + ':') and text in msg, msg
-        assert _untouched(bufs)
+def _call_on_poison(lib, cfg_ref, a):
+    """_call on fresh poison buffers, which the refusal has left as they were"""
+    bufs = _buffers()
+    rc = _call(lib, cfg_ref, a, bufs)
+    assert _untouched(bufs)
+    return rc
+
+
+test_refusals = H.refusal_test(NAME, REFUSALS, OK, _call_on_poison)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 def test_refuses_a_null_configuration(engine):
-    with L.engine(engine):
-        lib = L.lib()
-        bufs = _buffers()
-        assert _call(lib, NULL, dict(OK), bufs) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith(NAME + ':') and 'null configuration' in msg, msg
-        assert _untouched(bufs)
+    H.null_configuration_refused(engine, NAME, _call_on_poison, OK)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -158,21 +129,8 @@ def test_a_range_that_is_no_range_is_the_plain_head(engine):
 
 
 def test_every_refusal_has_a_text_of_its_own():
-    """the refusals are told apart by their text: no two conditions share one - neither among the entry point's own, nor among those of
-    gauss::squash_refusal it calls under an action range, nor between the two lists"""
-    src = open(os.path.join(CSRC, 'env_path_tracking.hip')).read()
-    body = src[src.index('extern "C" int %s(' % NAME):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    assert 'gauss::squash_refusal("%s"' % NAME in body
-    own = [t[len(NAME) + 2:] for t in re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % NAME, body, flags=re.S)]
-    head = open(os.path.join(CSRC, 'gauss_head.h')).read()
-    head = head[head.index('inline int squash_refusal('):]
-    head = head[:head.index('return MPG_OK')]
-    shared = [t[4:] for t in re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"', head, flags=re.S)]
-    assert len(own) >= 10 and len(shared) >= 7, (own, shared)
-    # (the head's own null-pointer and row-count refusals cannot answer here: the entry point passes it no pointer and one row)
-    texts = own + [t for t in shared if t not in ('null pointer', 'rows must be positive (got %d)')]
-    assert len(set(texts)) == len(texts), texts
+    """(the entry point's own texts and those of gauss::squash_refusal, which it calls under an action range)"""
+    H.refusal_texts_are_unique(NAME, 'env_path_tracking.hip', 10, head_at_least=7)
 
 
 def test_the_other_entry_points_answer_as_before():

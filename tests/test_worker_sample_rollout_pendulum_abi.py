@@ -1,27 +1,17 @@
 """mpg_worker_sample_rollout_pendulum at the drop-in boundary, without a GPU: both libraries export it with the declared argument types,
 and every refusal comes back as MPG_EINVAL with a text of its own before any launch (every pointer is FAKE: a launch would fault)."""
 import ctypes
-import os
 import re
 
 import pytest
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import abi_harness as H
+from tests.abi_harness import ENGINES, F, FAKE, I, NULL, U64, MPG_EINVAL, _with, built  # noqa: F401 (built: the module's autouse fixture)
 
 NAME = 'mpg_worker_sample_rollout_pendulum'
 PEND = 'InvertedPendulumConti-v0'
-NULL, FAKE = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
-I, F, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-MPG_EINVAL = -1000
-ENGINES = sorted(L.ENGINES)
-CSRC = os.path.join(os.path.dirname(L.HEADER), '..', 'mpg_amd', 'csrc')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def built():
-    from mpg_amd import build as B
-    return B.build(verbose=False)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -54,12 +44,6 @@ def _cfg():
     """the pendulum under an action range over a linear output: what the squashed head is built for (make_cfg's default range: 3)"""
     c = ops.make_cfg(PEND)
     assert c.env_kind == 1 and c.action_range == 3.0
-    return c
-
-
-def _with(c, **kw):
-    for k, v in kw.items():
-        setattr(c, k, v)
     return c
 
 
@@ -100,29 +84,12 @@ def _call(lib, cfg_ref, a):
                               a['ring_done'], U64(2), U64(0), a['done_out'], NULL)
 
 
-@pytest.mark.parametrize('engine', ENGINES)
-@pytest.mark.parametrize('case', range(len(REFUSALS)),
-                         ids=['%02d-%s' % (i, re.sub(r'[^a-z0-9]+', '_', c[2].lower())) for i, c in enumerate(REFUSALS)])
-def test_refusals(engine, case):
-    make, diff, text = REFUSALS[case]
-    with L.engine(engine):
-        lib = L.lib()
-        cfg = make()
-        a = dict(OK)
-        a.update(diff)
-        rc = _call(lib, ctypes.byref(cfg), a)
-        msg = lib.mpg_last_error().decode()
-        assert rc == MPG_EINVAL, (rc, msg)
-        assert msg.startswith(NAME + ':') and text in msg, msg
+test_refusals = H.refusal_test(NAME, REFUSALS, OK, _call)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
 def test_refuses_a_null_configuration(engine):
-    with L.engine(engine):
-        lib = L.lib()
-        assert _call(lib, NULL, dict(OK)) == MPG_EINVAL
-        msg = lib.mpg_last_error().decode()
-        assert msg.startswith(NAME + ':') and 'null configuration' in msg, msg
+    H.null_configuration_refused(engine, NAME, _call, OK)
 
 
 @pytest.mark.parametrize('engine', ENGINES)
@@ -137,21 +104,8 @@ def test_a_null_done_out_is_no_refusal_of_its_own(engine):
 
 
 def test_every_refusal_has_a_text_of_its_own():
-    """the refusals are told apart by their text: no two conditions share one - neither among the entry point's own, nor among those of
-    gauss::squash_refusal it calls, nor between the two lists (the entry point's begin with its name, the head's with '%s: ')"""
-    src = open(os.path.join(CSRC, 'env_cart_pole.hip')).read()
-    body = src[src.index('extern "C" int %s(' % NAME):]
-    body = body[:body.index('hipLaunchKernelGGL')]
-    assert 'gauss::squash_refusal("%s"' % NAME in body
-    own = [t[len(NAME) + 2:] for t in re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"' % NAME, body, flags=re.S)]
-    head = open(os.path.join(CSRC, 'gauss_head.h')).read()
-    head = head[head.index('inline int squash_refusal('):]
-    head = head[:head.index('return MPG_OK')]
-    shared = [t[4:] for t in re.findall(r'MPG_REQUIRE\(.*?"(%s: [^"]*)"', head, flags=re.S)]
-    assert len(own) >= 8 and len(shared) >= 7, (own, shared)
-    # (the head's own null-pointer and row-count refusals cannot answer here: the entry point passes it no pointer and one row)
-    texts = own + [t for t in shared if t not in ('null pointer', 'rows must be positive (got %d)')]
-    assert len(set(texts)) == len(texts), texts
+    """(the entry point's own texts and those of gauss::squash_refusal, which it calls)"""
+    H.refusal_texts_are_unique(NAME, 'env_cart_pole.hip', 8, head_at_least=7)
 
 
 def test_the_other_entry_points_answer_as_before():
