@@ -1106,6 +1106,59 @@ int mpg_sac_step_begin(mpg_train_ctx_t* ctx, float alpha, int iteration, mpg_str
 int mpg_sac_auto_step_begin(mpg_train_ctx_t* ctx, const mpg_sac_alpha_t* a, int iteration, mpg_stream_t stream);
 int mpg_sac_auto_step_end(mpg_train_ctx_t* ctx, mpg_sac_alpha_t* a, int iteration, mpg_stream_t stream);
 
+/* The lagged worker sample - the reference's default optimizer, OffPolicyAsync, whose workers sample with weights up to
+ * max_weight_sync_delay iterations old and whose rows arrive when they arrive, in a DETERMINISTIC form.  With lag = L
+ * (1 <= L <= sampling_interval) the sample that starts at iteration k (k % sampling_interval == 0) reads the policy as it stands at
+ * the start of iteration k; its rows enter the ring (and the priority trees) at the start of iteration k + L, before that iteration's
+ * draw; the draws of iterations k .. k + L - 1 do not see them.  noise_ctr and env_ctr advance at k; ring_next, ring_size and the
+ * trees at k + L.  The sample's launches then need nothing the step writes, and run on a second stream beside it.
+ *
+ * The object is the caller's, like mpg_prof_t: the library keeps nothing.  Every pointer is a device buffer of the caller; the stream
+ * and the two events are created by the caller ONCE (nothing is created inside a step) and outlive the last call.
+ *   pending, due: host-side state, zero before the first call; the library counts the iterations staged and the iteration they are
+ *   due at.  lag <= sampling_interval keeps it to one pending sample. */
+typedef struct {
+    int lag;                 /* 1 .. ctx->sampling_interval */
+    mpg_stream_t side;       /* hipStream_t of the sample's launches.  NULL, or the step's own stream: no event is touched and the same
+                                calls run in the same order on the one stream - the reference form (bit-identical) */
+    void *forked, *done;     /* hipEvent_t, required with a side stream: `forked` is recorded on the step's stream where the sample may
+                                start, `done` on the side stream behind the sample's last launch */
+    float* policy;           /* the worker's copy of the policy network: net_size(obs_dim, 2 * act_dim) floats.  It lies outside every
+                                mpg_wcache_t, so the sample's launches take the strided weight loads (bit-identical; packed images of
+                                the copy measured no faster: DESIGN.md 7 f18) */
+    float *s_obs, *s_act, *s_rew, *s_obs2;   /* staging rows of ONE sample, laid out as the ring: |sample_iters| * num_agent rows */
+    uint8_t* s_done;
+    int pending;             /* iterations staged and not yet added (0: none) */
+    int due;                 /* the iteration at whose start they are added */
+} mpg_lagged_sample_t;
+
+/* mpg_step_begin / mpg_sac_step_begin / mpg_sac_auto_step_begin with a lagged sample; mpg_step_end / mpg_sac_auto_step_end follow as
+ * they are.  No field of mpg_train_ctx_t and no existing signature changed: the ABI version stays 10.  The calls, in order:
+ *   1. a sample is due (pending and iteration >= due): the step's stream waits for `done`; mpg_replay_add(ring_capacity, ring_next,
+ *      pending * num_agent rows) from the staging rows, wrap included; on a prioritized context one mpg_per_add per iteration, in
+ *      iteration order; ring_next and ring_size advance.  All on the step's stream, before the draw.
+ *   2. iteration % sampling_interval == 0: the policy's floats are copied into `policy` ON THE STEP'S STREAM (this iteration's
+ *      mpg_step_end writes them; a copy on the side stream would race it); `forked` is recorded there - behind the last optimizer launch
+ *      and behind the add of 1., which is what makes the staging rows free again - and the side stream waits for it;
+ *      the sample's launches run on the side stream exactly as mpg_step_begin would issue them (the one-launch sample or the chain:
+ *      sample_iters as documented above) with the staging rows as their ring - capacity = the rows of one sample, position 0, then
+ *      it * num_agent along a chain - reading `policy`, the env state, w_* and the status word (OR-ed atomically by both streams) and
+ *      nothing the step writes before the join; `done` is recorded.  MPG-v2's pre-gathered draw is not taken: it exists because the draw
+ *      follows the add.  noise_ctr, env_ctr advance; pending = |sample_iters|, due = iteration + lag.
+ *   3. replay_times++ and the version's gradients, unchanged.
+ * w_obs, w_done and the env state belong to the side stream from the fork to the next join (or drain).
+ * Refused with MPG_EINVAL under the entry point's name, before anything is enqueued or counted: a null object; everything the plain
+ * begin of the version refuses; lag outside 1 .. sampling_interval; missing staging rows; a missing policy copy; cfg.prof together
+ * with a side stream (its events belong to one stream); a side stream without both events; world_size > 1; sample_iters == 0; a ring
+ * smaller than one sample; an empty ring with nothing due; a sample still pending at a sampling iteration.
+ * mpg_lagged_sample_drain: a pending sample is joined and added now (step 1 alone), whatever its due iteration - the end of a run,
+ * or ahead of anything that reads the ring, the worker's observation or the env state on the host side. */
+int mpg_step_begin_lagged(mpg_train_ctx_t* ctx, mpg_lagged_sample_t* lagged, int iteration, mpg_stream_t stream);
+int mpg_sac_step_begin_lagged(mpg_train_ctx_t* ctx, float alpha, mpg_lagged_sample_t* lagged, int iteration, mpg_stream_t stream);
+int mpg_sac_auto_step_begin_lagged(mpg_train_ctx_t* ctx, const mpg_sac_alpha_t* a, mpg_lagged_sample_t* lagged, int iteration,
+                                   mpg_stream_t stream);
+int mpg_lagged_sample_drain(mpg_train_ctx_t* ctx, mpg_lagged_sample_t* lagged, mpg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

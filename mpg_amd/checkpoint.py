@@ -66,7 +66,11 @@ def state_of(optimizer):
 
 
 def save_checkpoint(path, optimizer):
-    """Write the whole training state of a SingleProcessOffPolicyOptimizer to `path` (.npz)."""
+    """Write the whole training state of a SingleProcessOffPolicyOptimizer to `path` (.npz).  With sample_lag a sample may be pending
+    (taken, its rows not in the buffer yet): the format has no place for it, so that is refused - call optimizer.drain() first."""
+    if getattr(optimizer, 'sample_pending', False):
+        raise ValueError('save_checkpoint: a lagged sample is pending (sample_lag=%r): its rows are in neither the replay buffer nor the '
+                         'file format - call optimizer.drain() first' % (optimizer.sample_lag,))
     meta, arrays = state_of(optimizer)
     torch.cuda.synchronize()
     with open(path, 'wb') as f:
@@ -84,6 +88,8 @@ def load_checkpoint(path, optimizer):
         raise ValueError('checkpoint format %r, this build reads %d' % (meta['format_version'], FORMAT_VERSION))
     w, ln, rb = optimizer.worker, optimizer.learner, optimizer.replay_buffer
     pw = w.policy_with_value
+    if hasattr(optimizer, 'discard_pending'):
+        optimizer.discard_pending()            # (sample_lag: a pending sample of the state that is being replaced)
     if meta['names'] != list(pw.names) or meta['learner_cls'] != type(ln).__name__ or meta['buffer_cls'] != type(rb).__name__:
         raise ValueError('checkpoint was written by a different configuration: %s / %s / %s' %
                          (meta['learner_cls'], meta['buffer_cls'], meta['names']))

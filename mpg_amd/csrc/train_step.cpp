@@ -1,7 +1,8 @@
 // Native step driver: SingleProcessOffPolicyOptimizer.step (optimizer.py:330-362), built purely from the public entry points of this
 // library so that Python is not on the launch path.  One table describes the learner versions (VERSIONS), one function is the worker's
 // sample (sample), one skeleton stands behind the three begin entry points (begin); what a version enqueues is its *_gradients
-// function, read top to bottom.
+// function, read top to bottom.  The lagged worker sample (mpg_lagged_sample_t: the *_lagged entry points at the end) is the same sample and
+// the same gradients with the add moved `lag` iterations on, so that the sample can run on a second stream beside the steps between.
 #include <algorithm>
 #include <cmath>
 
@@ -17,6 +18,15 @@ inline int net_size(int in_dim, int out_dim) { return in_dim * H + H + H * H + H
     do {                     \
         int rc_ = (call);    \
         if (rc_) return rc_; \
+    } while (0)
+
+#define HIP_TRY(entry, call)                                                   \
+    do {                                                                       \
+        hipError_t e_ = (call);                                                \
+        if (e_ != hipSuccess) {                                                \
+            mpg_set_error("%s: %s: %s", entry, #call, hipGetErrorString(e_));  \
+            return -(int)e_;                                                   \
+        }                                                                      \
     } while (0)
 
 struct Layout {
@@ -516,6 +526,107 @@ int begin(const char* entry, mpg_train_ctx_t* c, int iteration, float alpha, con
     return t.gradients(c, l, st, s);
 }
 
+// what mpg_step_begin refuses, under the caller's name (mpg_step_begin_lagged refuses the same)
+int step_begin_refusal(const char* entry, const mpg_train_ctx_t* c) {
+    MPG_REQUIRE(!c || c->learner_version != SAC,
+                "%s: learner_version 7 (SAC) takes its temperature as an argument: call mpg_sac_step_begin", entry);
+    if (c && c->learner_version == AMPC) TRY(ampc_refusal(entry, c));      // each refusal in its own words; ctx_ok then holds
+    MPG_REQUIRE(ctx_ok(c), "%s: incomplete context", entry);
+    return real_env_refusal(entry, c);                              // refused before anything is enqueued
+}
+int sac_fixed_refusal(const char* entry, const mpg_train_ctx_t* c, float alpha) {
+    TRY(sac_begin_refusal(entry, c));
+    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "%s: alpha must be finite and not negative (got %g)", entry, (double)alpha);
+    return real_env_refusal(entry, c);
+}
+int sac_auto_refusal(const char* entry, const mpg_train_ctx_t* c, const mpg_sac_alpha_t* a) {
+    TRY(sac_begin_refusal(entry, c));
+    MPG_REQUIRE(a, "%s: null temperature struct", entry);
+    MPG_REQUIRE(a->state, "%s: null temperature state", entry);
+    MPG_REQUIRE(std::isfinite(a->target_entropy), "%s: target_entropy must be finite (got %g)", entry, (double)a->target_entropy);
+    return real_env_refusal(entry, c);
+}
+
+// ================================================ the lagged sample ================================================
+// sample_lag = L (include/mpg_hip.h, mpg_lagged_sample_t): the sample that starts at iteration k reads the policy as it stands at the
+// start of k and its rows enter the ring at the start of k + L.  In between they sit in the object's staging rows, written by the
+// sample's launches on the side stream; the worker's counters move at k, the ring's at k + L.
+
+inline bool two_streams(const mpg_lagged_sample_t* g, mpg_stream_t s) { return g->side && g->side != s; }
+
+// what the lagged form refuses beyond its version's begin, before anything is enqueued or counted (the context has passed that begin's
+// refusals: it is complete)
+int lagged_refusal(const char* entry, const mpg_train_ctx_t* c, const mpg_lagged_sample_t* g, mpg_stream_t s) {
+    MPG_REQUIRE(g->lag >= 1 && g->lag <= c->sampling_interval, "%s: lag out of range: 1 <= lag <= sampling_interval = %d (got %d)", entry,
+                c->sampling_interval, g->lag);
+    MPG_REQUIRE(g->s_obs && g->s_act && g->s_rew && g->s_obs2 && g->s_done,
+                "%s: missing staging rows (s_obs, s_act, s_rew, s_obs2, s_done: |sample_iters| * num_agent rows each)", entry);
+    MPG_REQUIRE(g->policy, "%s: missing policy copy (the worker's own net_size(policy) floats)", entry);
+    MPG_REQUIRE(!(c->cfg.prof && two_streams(g, s)), "%s: a kernel timer (cfg.prof) records on one stream: not served with a side stream",
+                entry);
+    MPG_REQUIRE(!two_streams(g, s) || (g->forked && g->done), "%s: a side stream needs both events (forked, done)", entry);
+    MPG_REQUIRE(c->world_size == 1, "%s: world_size > 1 is not served with a lagged sample (got %d)", entry, c->world_size);
+    MPG_REQUIRE(sample_iters_of(c) > 0, "%s: a lagged sample of no iteration (sample_iters = 0)", entry);
+    MPG_REQUIRE((long)sample_iters_of(c) * c->num_agent <= c->ring_capacity, "%s: ring smaller than one sample", entry);
+    MPG_REQUIRE(g->pending >= 0 && g->pending <= sample_iters_of(c), "%s: pending count out of range (got %d)", entry, g->pending);
+    return MPG_OK;
+}
+
+// the staged rows enter the ring (and the trees, iteration by iteration) on the MAIN stream, behind the sample's last launch
+int join(const char* entry, mpg_train_ctx_t* c, const Traits& t, mpg_lagged_sample_t* g, mpg_stream_t s) {
+    if (two_streams(g, s)) HIP_TRY(entry, hipStreamWaitEvent(mpg_stream(s), static_cast<hipEvent_t>(g->done), 0));
+    TRY(mpg_replay_add(c->ring_capacity, c->ring_next, g->pending * c->num_agent, c->cfg.obs_dim, c->cfg.act_dim, g->s_obs, g->s_act,
+                       g->s_rew, g->s_obs2, g->s_done, c->ring_obs, c->ring_act, c->ring_rew, c->ring_obs2, c->ring_done, s));
+    for (int k = 0; k < g->pending; ++k) TRY(iteration_added(c, t, s));
+    g->pending = 0;
+    return MPG_OK;
+}
+
+// The policy's floats go into the worker's copy on the MAIN stream, ahead of the fork event: the step's own optimizer launch
+// (mpg_step_end of this iteration) writes them, and nothing orders it behind a copy made on the side stream.  The sample's launches then
+// run on the side stream with the staging rows as their ring (capacity = the rows of one sample, position 0: what
+// OffPolicyWorker._one_launch hands them), reading the copy alone (it matches no packed image: the strided loads, bit-identical).
+// MPG-v2's pre-gathered draw is not taken: the draw does not follow this add.
+int fork(const char* entry, mpg_train_ctx_t* c, const Traits& t, const Layout& l, mpg_lagged_sample_t* g, int iteration, mpg_stream_t s) {
+    const bool two = two_streams(g, s);
+    const mpg_stream_t side = two ? g->side : s;
+    HIP_TRY(entry, hipMemcpyAsync(g->policy, c->params + l.off[l.n_nets - 1], sizeof(float) * (size_t)l.p_size, hipMemcpyDeviceToDevice,
+                                  mpg_stream(s)));
+    if (two) {
+        HIP_TRY(entry, hipEventRecord(static_cast<hipEvent_t>(g->forked), mpg_stream(s)));
+        HIP_TRY(entry, hipStreamWaitEvent(mpg_stream(side), static_cast<hipEvent_t>(g->forked), 0));
+    }
+    mpg_train_ctx_t w = *c;
+    w.ring_obs = g->s_obs; w.ring_act = g->s_act; w.ring_rew = g->s_rew; w.ring_obs2 = g->s_obs2; w.ring_done = g->s_done;
+    w.ring_capacity = sample_iters_of(c) * c->num_agent;
+    w.ring_next = w.ring_size = 0;
+    w.prioritized = 0;                      // the trees are the join's
+    TRY(sample(entry, &w, t, g->policy, nullptr, side));
+    c->noise_ctr = w.noise_ctr;
+    c->env_ctr = w.env_ctr;
+    if (two) HIP_TRY(entry, hipEventRecord(static_cast<hipEvent_t>(g->done), mpg_stream(side)));
+    g->pending = sample_iters_of(c);
+    g->due = iteration + g->lag;
+    return MPG_OK;
+}
+
+// begin with the add moved on: join what is due, fork on the interval, the version's gradients.  The caller has made its refusals.
+int begin_lagged(const char* entry, mpg_train_ctx_t* c, mpg_lagged_sample_t* g, int iteration, float alpha, const mpg_sac_alpha_t* at,
+                 mpg_stream_t s) {
+    TRY(lagged_refusal(entry, c, g, s));
+    const Traits& t = *traits(c->learner_version);
+    const Layout l = layout(c, t);
+    const bool due = g->pending > 0 && iteration >= g->due, forks = iteration % c->sampling_interval == 0;
+    MPG_REQUIRE(!(forks && g->pending > 0 && !due), "%s: the sample due at iteration %d is still pending at a sampling iteration (%d)",
+                entry, g->due, iteration);
+    MPG_REQUIRE(c->ring_size > 0 || due, "%s: empty replay ring", entry);
+    const Step st = {iteration, c->learner_counter % c->num_batch_reuse == 0, -1, alpha, at};
+    if (due) TRY(join(entry, c, t, g, s));
+    if (forks) TRY(fork(entry, c, t, l, g, iteration, s));
+    c->replay_times++;
+    return t.gradients(c, l, st, s);
+}
+
 // the end's own requirements, under the caller's name
 bool end_ok(const mpg_train_ctx_t* c) { return ctx_ok(c) && c->norms && c->nonfinite && c->adam_m && c->adam_v && c->clip_scratch; }
 
@@ -532,29 +643,46 @@ extern "C" int mpg_step_workspace_bytes(const mpg_train_ctx_t* c, size_t* ws0, s
 }
 
 extern "C" int mpg_step_begin(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {
-    MPG_REQUIRE(!c || c->learner_version != SAC,
-                "mpg_step_begin: learner_version 7 (SAC) takes its temperature as an argument: call mpg_sac_step_begin");
-    if (c && c->learner_version == AMPC) TRY(ampc_refusal("mpg_step_begin", c));      // each refusal in its own words; ctx_ok then holds
-    MPG_REQUIRE(ctx_ok(c), "mpg_step_begin: incomplete context");
-    TRY(real_env_refusal("mpg_step_begin", c));                     // refused before anything is enqueued
+    TRY(step_begin_refusal("mpg_step_begin", c));
     return begin("mpg_step_begin", c, iteration, 0.f, nullptr, s);
 }
 
 extern "C" int mpg_sac_step_begin(mpg_train_ctx_t* c, float alpha, int iteration, mpg_stream_t s) {
-    TRY(sac_begin_refusal("mpg_sac_step_begin", c));
-    MPG_REQUIRE(alpha >= 0.f && alpha <= 3.4028234664e38f, "mpg_sac_step_begin: alpha must be finite and not negative (got %g)",
-                (double)alpha);
-    TRY(real_env_refusal("mpg_sac_step_begin", c));
+    TRY(sac_fixed_refusal("mpg_sac_step_begin", c, alpha));
     return begin("mpg_sac_step_begin", c, iteration, alpha, nullptr, s);
 }
 
 extern "C" int mpg_sac_auto_step_begin(mpg_train_ctx_t* c, const mpg_sac_alpha_t* a, int iteration, mpg_stream_t s) {
-    TRY(sac_begin_refusal("mpg_sac_auto_step_begin", c));
-    MPG_REQUIRE(a, "mpg_sac_auto_step_begin: null temperature struct");
-    MPG_REQUIRE(a->state, "mpg_sac_auto_step_begin: null temperature state");
-    MPG_REQUIRE(std::isfinite(a->target_entropy), "mpg_sac_auto_step_begin: target_entropy must be finite (got %g)", (double)a->target_entropy);
-    TRY(real_env_refusal("mpg_sac_auto_step_begin", c));
+    TRY(sac_auto_refusal("mpg_sac_auto_step_begin", c, a));
     return begin("mpg_sac_auto_step_begin", c, iteration, 0.f, a, s);
+}
+
+// ---- the same three with a lagged sample (include/mpg_hip.h, mpg_lagged_sample_t) ----
+extern "C" int mpg_step_begin_lagged(mpg_train_ctx_t* c, mpg_lagged_sample_t* g, int iteration, mpg_stream_t s) {
+    MPG_REQUIRE(g, "mpg_step_begin_lagged: null lagged-sample object");
+    TRY(step_begin_refusal("mpg_step_begin_lagged", c));
+    return begin_lagged("mpg_step_begin_lagged", c, g, iteration, 0.f, nullptr, s);
+}
+
+extern "C" int mpg_sac_step_begin_lagged(mpg_train_ctx_t* c, float alpha, mpg_lagged_sample_t* g, int iteration, mpg_stream_t s) {
+    MPG_REQUIRE(g, "mpg_sac_step_begin_lagged: null lagged-sample object");
+    TRY(sac_fixed_refusal("mpg_sac_step_begin_lagged", c, alpha));
+    return begin_lagged("mpg_sac_step_begin_lagged", c, g, iteration, alpha, nullptr, s);
+}
+
+extern "C" int mpg_sac_auto_step_begin_lagged(mpg_train_ctx_t* c, const mpg_sac_alpha_t* a, mpg_lagged_sample_t* g, int iteration,
+                                              mpg_stream_t s) {
+    MPG_REQUIRE(g, "mpg_sac_auto_step_begin_lagged: null lagged-sample object");
+    TRY(sac_auto_refusal("mpg_sac_auto_step_begin_lagged", c, a));
+    return begin_lagged("mpg_sac_auto_step_begin_lagged", c, g, iteration, 0.f, a, s);
+}
+
+// a pending sample is joined and added now, whatever its due iteration: the end of a run
+extern "C" int mpg_lagged_sample_drain(mpg_train_ctx_t* c, mpg_lagged_sample_t* g, mpg_stream_t s) {
+    MPG_REQUIRE(g, "mpg_lagged_sample_drain: null lagged-sample object");
+    MPG_REQUIRE(ctx_ok(c), "mpg_lagged_sample_drain: incomplete context");
+    TRY(lagged_refusal("mpg_lagged_sample_drain", c, g, s));
+    return g->pending > 0 ? join("mpg_lagged_sample_drain", c, *traits(c->learner_version), g, s) : MPG_OK;
 }
 
 extern "C" int mpg_step_end(mpg_train_ctx_t* c, int iteration, mpg_stream_t s) {

@@ -45,7 +45,13 @@ class TrainCtx(ctypes.Structure):
         ('critics_ready_event', _P), ('grad_opts', GradOpts), ('clip_partials_ready', ctypes.c_int)]
 
 
-ON_REQUEST = (7, 8)       # SAC and AMPC are served, but taken only where the optimizer is asked to (native_sac / native_ampc)
+class LaggedSample(ctypes.Structure):
+    """mpg_lagged_sample_t"""
+    _fields_ = [('lag', ctypes.c_int), ('side', _P), ('forked', _P), ('done', _P), ('policy', _P),
+                ('s_obs', _P), ('s_act', _P), ('s_rew', _P), ('s_obs2', _P), ('s_done', _P), ('pending', ctypes.c_int), ('due', ctypes.c_int)]
+
+
+ON_REQUEST = (7, 8)      # SAC and AMPC are served, but taken only where the optimizer is asked to (native_sac / native_ampc)
 
 
 def native_stack(worker, learner, rb):
@@ -81,9 +87,15 @@ class FusedMPGStep(object):
     SACLearner + ReplayBuffer without explore_sigma (7: mpg_sac_step_begin, which takes the learner's fixed alpha, or with
     alpha = 'auto' the pair mpg_sac_auto_step_begin / mpg_sac_auto_step_end on the policy's device-resident temperature),
     AMPCLearner + ReplayBuffer (8: the policy alone - no critic, no target, no ws0; SingleProcessOffPolicyOptimizer takes it with
-    native_ampc=True)."""
+    native_ampc=True).
 
-    def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False):
+    sample_lag = L (1 .. sampling_interval; include/mpg_hip.h, mpg_lagged_sample_t): the sample that starts at iteration k reads the
+    policy as it stands then and its rows enter the ring at the start of iteration k + L; it runs on a second stream beside the steps
+    between (side_stream=False: the same calls in the same order on the one stream - the reference form, bit-identical).  This object
+    owns the side stream, the two events, the worker's copy and the staging rows.  From a fork to the next join the worker's observation, done mask and env state belong to
+    the side stream: the worker's Python-side `obs` and counters, and the ring, are valid after drain() or at the next join."""
+
+    def __init__(self, worker, learner, rb, sampling_interval, always_exchange=False, sample_lag=None, side_stream=True):
         stack = native_stack(worker, learner, rb)
         assert stack is not None, 'the native step driver does not serve this stack'
         assert learner.policy_with_value is worker.policy_with_value
@@ -190,11 +202,67 @@ class FusedMPGStep(object):
                 self._lib.mpg_sac_step_begin(self._ref, ctypes.c_float(learner.alpha), ctypes.c_int(it), s), 'mpg_sac_step_begin')
         else:
             self._begin = lambda it, s: L.check(self._lib.mpg_step_begin(self._ref, ctypes.c_int(it), s), 'mpg_step_begin')
+        self.lagged = None
+        if sample_lag is not None:
+            self._bind_lagged(int(sample_lag), side_stream)
         # the python objects now look at the driver's buffers
         learner.batch_data = {'batch_obs': t['b_obs'], 'batch_actions': t['b_act'], 'batch_rewards': t['b_rew'],
                               'batch_obs_tp1': t['b_obs2'], 'batch_dones': t['b_done'], 'batch_targets': t['b_targets']}
         learner._views = None
         self.pull()
+
+    def _bind_lagged(self, lag, side_stream):
+        """the caller-owned half of mpg_lagged_sample_t and the *_lagged entry points in the place of the plain begins"""
+        c, pw, dev = self.c, self.pw, self.worker.device
+        if not 1 <= lag <= c.sampling_interval:
+            raise ValueError('sample_lag must be within 1 .. sampling_interval = %d (got %d)' % (c.sampling_interval, lag))
+        if c.world_size > 1:
+            raise ValueError('sample_lag is not served with world_size > 1 (got %d)' % c.world_size)
+        g = self.lagged = LaggedSample()
+        g.lag = lag
+        rows, od, ad = abs(c.sample_iters) * c.num_agent, pw.obs_dim, pw.act_dim
+        f = dict(dtype=torch.float32, device=dev)
+        self.lag_t = lt = dict(policy=torch.empty(pw.sizes[-1], **f), s_obs=torch.empty(rows, od, **f), s_act=torch.empty(rows, ad, **f),
+                               s_rew=torch.empty(rows, **f), s_obs2=torch.empty(rows, od, **f),
+                               s_done=torch.empty(rows, dtype=torch.uint8, device=dev))
+        for k, v in lt.items():
+            setattr(g, k, L.ptr(v))
+        if side_stream:
+            self.side = torch.cuda.Stream(device=dev)
+            self.lag_events = e1, e2 = torch.cuda.Event(), torch.cuda.Event()
+            e1.record()                       # (the handle exists once the event has been recorded)
+            e2.record()
+            g.side, g.forked, g.done = self.side.cuda_stream, e1.cuda_event, e2.cuda_event
+        gref = ctypes.byref(g)
+        learner, I = self.learner, ctypes.c_int
+        if c.learner_version == 7 and self.auto_alpha:
+            self._begin = lambda it, s: L.check(
+                self._lib.mpg_sac_auto_step_begin_lagged(self._ref, ctypes.byref(pw.alpha_desc), gref, I(it), s), 'mpg_sac_auto_step_begin_lagged')
+        elif c.learner_version == 7:
+            self._begin = lambda it, s: L.check(
+                self._lib.mpg_sac_step_begin_lagged(self._ref, ctypes.c_float(learner.alpha), gref, I(it), s), 'mpg_sac_step_begin_lagged')
+        else:
+            self._begin = lambda it, s: L.check(self._lib.mpg_step_begin_lagged(self._ref, gref, I(it), s), 'mpg_step_begin_lagged')
+
+    @property
+    def pending(self):
+        """a lagged sample has been started and its rows are not in the ring yet"""
+        return self.lagged is not None and self.lagged.pending > 0
+
+    def drain(self):
+        """mpg_lagged_sample_drain: a pending sample is joined and added now (the end of a run, ahead of a checkpoint or of any stock
+        method that reads the ring or the worker)"""
+        if self.lagged is None:
+            return
+        self.sync_in()
+        L.check(self._lib.mpg_lagged_sample_drain(self._ref, ctypes.byref(self.lagged), L.stream()), 'mpg_lagged_sample_drain')
+        self.push()
+
+    def discard_pending(self):
+        """ahead of a checkpoint restore: a sample of the state about to be replaced finishes, and its rows are dropped"""
+        if self.pending:
+            torch.cuda.synchronize()
+            self.lagged.pending = 0
 
     def pull(self):
         """python objects -> context counters"""

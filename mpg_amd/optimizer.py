@@ -18,7 +18,23 @@ def quiesce_gc():
 
 class SingleProcessOffPolicyOptimizer(object):
     def __init__(self, worker, learner, replay_buffer, evaluator, args, sampling_interval=10, fused=True,
-                 always_exchange=False, native_sac=False, native_ampc=False):
+                 always_exchange=False, native_sac=False, native_ampc=False, sample_lag=None):
+        """sample_lag = L (1 <= L <= sampling_interval; None: off, the serial order of the reference's single-process optimizer): the
+        deterministic form of the reference's default optimizer, OffPolicyAsync, whose workers sample with weights up to
+        max_weight_sync_delay iterations old.  The sample that starts at iteration k (k % sampling_interval == 0) reads the policy as it
+        stands at the start of iteration k; its rows enter the replay buffer at the start of iteration k + L, before that iteration's
+        draw; num_sampled_steps counts at k.  On the native driver the sample then runs on a second stream beside the steps
+        (mpg_amd/fused.py); there the worker's Python-side `obs` and counters, and the buffer, are valid after drain() or at the next
+        join.  drain() adds a held batch now: the end of a run, or ahead of save_checkpoint, which refuses a pending sample."""
+        if sample_lag is not None:
+            from . import dist as D
+            if isinstance(sample_lag, bool) or int(sample_lag) != sample_lag or not 1 <= sample_lag <= sampling_interval:
+                raise ValueError('sample_lag must be an integer within 1 .. sampling_interval = %d (got %r)' % (sampling_interval, sample_lag))
+            if D.world_size() > 1:
+                raise ValueError('sample_lag is not served with world_size > 1 (got %d): every rank would hold a pending sample of its own'
+                                 % D.world_size())
+        self.sample_lag = None if sample_lag is None else int(sample_lag)
+        self._held = None                  # the method path's pending sample: (batch, the iteration it is due at)
         if native_sac or native_ampc:
             # SAC's native step (mpg_sac_step_begin, or the mpg_sac_auto_step_* pair with alpha = 'auto') and AMPC's (learner_version 8 of
             # mpg_step_begin / mpg_step_end) are taken on request only; a request the driver cannot serve is an error - raised before
@@ -46,7 +62,8 @@ class SingleProcessOffPolicyOptimizer(object):
             from .fused import ON_REQUEST, FusedMPGStep, native_stack
             stack = native_stack(worker, learner, replay_buffer)
             if native_sac or native_ampc or (stack is not None and stack[0] not in ON_REQUEST):
-                self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange)
+                self._fused = FusedMPGStep(worker, learner, replay_buffer, sampling_interval, always_exchange=always_exchange,
+                                           sample_lag=self.sample_lag)
 
     @staticmethod
     def _native_refusal(keyword, worker, learner, replay_buffer, args, both=False):
@@ -103,10 +120,15 @@ class SingleProcessOffPolicyOptimizer(object):
             self.iteration += 1
             self._check_status()
             return
+        if self._held is not None and self.iteration >= self._held[1]:     # sample_lag: the rows of iteration k enter at k + L
+            self.drain()
         if self.iteration % self.sampling_interval == 0:                   # optimizer.py:332-337
             sample_batch, count = self.worker.sample_with_count()
             self.num_sampled_steps += count
-            self.replay_buffer.add_batch(sample_batch)
+            if self.sample_lag is None:
+                self.replay_buffer.add_batch(sample_batch)
+            else:
+                self._held = (sample_batch, self.iteration + self.sample_lag)
         samples = self.replay_buffer.replay()                              # :340-341
         self.learner.set_weights(self.worker.policy_with_value)            # :345 (shared object: no copy)
         grads = self.learner.compute_gradient(samples[:5], self.replay_buffer, samples[-1], self.iteration)   # :349
@@ -118,6 +140,26 @@ class SingleProcessOffPolicyOptimizer(object):
         self.get_stats()
         self.iteration += 1
         self._check_status()
+
+    @property
+    def sample_pending(self):
+        """sample_lag: a sample has been taken whose rows are not in the replay buffer yet"""
+        return self._held is not None or (self._fused is not None and self._fused.pending)
+
+    def drain(self):
+        """sample_lag: add a held batch now, whatever its due iteration (the native driver: mpg_lagged_sample_drain, which joins the
+        side stream first).  For the end of a run and ahead of save_checkpoint; without a pending sample it does nothing."""
+        if self._fused is not None:
+            self._fused.drain()
+        if self._held is not None:
+            self.replay_buffer.add_batch(self._held[0])
+            self._held = None
+
+    def discard_pending(self):
+        """sample_lag, ahead of load_checkpoint: a pending sample belongs to the state about to be replaced - it is dropped, not added"""
+        self._held = None
+        if self._fused is not None:
+            self._fused.discard_pending()
 
     def _check_status(self):
         """judge_is_nan / the engine's numerical envelope (include/mpg_hip.h): every kernel of the step ORs its findings into the
