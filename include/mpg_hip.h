@@ -919,7 +919,8 @@ int mpg_per_init(double* sum_tree, double* min_tree, int* stamp, int capacity, m
  * priority > 0; learners hand signed td errors, SURVEY.md B-3, hence |.| + eps), then every internal node is
  * recomputed as left + right / min(left, right).  Duplicates: the last entry of the batch wins, like the
  * reference's sequential loop.  max_priority (device DOUBLE since ABI 10 - the reference's _max_priority is a python float -,
- * nullable) tracks max(|prio| + eps) (buffer.py:189). */
+ * nullable) tracks max(|prio| + eps) over every entry of the batch, overridden duplicates included (buffer.py:182-189: one max()
+ * per entry of the sequential loop). */
 int mpg_per_update(double* sum_tree, double* min_tree, int* stamp, int capacity, int n, const int* idx,
                    const float* prio, double alpha, double eps, double* max_priority, mpg_stream_t stream);
 

@@ -33,7 +33,10 @@ __global__ void k_set_leaves(int n, int capacity, const int* __restrict__ idx, c
     min_tree[capacity + leaf] = v;
 }
 // the same with ONE atomic per wave for the running maximum (65 536 atomics on one address were 12 of the kernel's 17.6 us at TD3's batch):
-// every lane takes part in the wave's maximum (lanes without a leaf of their own contribute 0: every p is > 0)
+// every lane takes part in the wave's maximum (lanes past the batch contribute 0: every p is > 0).  EVERY entry of the batch counts,
+// an entry that a later duplicate of its index overrides included: the reference runs max() once per entry of its sequential loop
+// (buffer.py:182-189), so an overridden priority reaches _max_priority although its leaf value does not survive.  Only the stamp's
+// owner writes the leaf.
 __global__ void __launch_bounds__(256) k_set_leaves_wmax(int n, int capacity, const int* __restrict__ idx, const float* __restrict__ prio,
                                                          double alpha, double eps, const int* __restrict__ stamp, double* __restrict__ sum_tree,
                                                          double* __restrict__ min_tree, double* __restrict__ max_prio) {
@@ -42,12 +45,11 @@ __global__ void __launch_bounds__(256) k_set_leaves_wmax(int n, int capacity, co
     if (i < n) {
         const int leaf = idx[i];
         const float pr = prio[i];                        // (requested with the index: behind the stamp test it was a third round trip)
+        mine = fabs((double)pr) + eps;
         if (stamp[leaf] == i) {                          // (a later entry of the batch overrides the others)
-            const double p = fabs((double)pr) + eps;
-            const double v = pow(p, alpha);
+            const double v = pow(mine, alpha);
             sum_tree[capacity + leaf] = v;
             min_tree[capacity + leaf] = v;
-            mine = p;
         }
     }
 #pragma unroll
