@@ -1,66 +1,30 @@
 """mpg_worker_rollout on the GPU: the one launch against the chain of mpg_worker_step calls it replaces, from identical starts, bit
 for bit - env state, observations, last actions, last done flags, all five ring arrays WHOLE (prefilled with a sentinel, so the slots
 nobody writes count) and the status word; its callers - OffPolicyWorker.sample(one_launch_sample) against the loop, the native step
-driver with the launch against the same driver kept on the chain (sample_iters < 0).  Floats are compared as their 32-bit patterns
-(a NaN row has to match too)."""
+driver with the launch against the same driver kept on the chain (sample_iters < 0).  The buffers, the comparison (floats as their
+32-bit patterns: a NaN row has to match too) and the callers' pairs are those of tests/rollout_harness.py."""
 import ctypes
+from functools import partial
 
-import numpy as np
 import pytest
 import torch
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import rollout_harness as H
+from tests.rollout_harness import assert_same, bits, engine, ring_ptrs  # noqa: F401 (engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-NAMES = ('state', 'obs_io', 'act_out', 'done_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'status')
 
 
-def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
-@pytest.fixture(params=['split', 'f32'])
-def engine(request):
-    """both builds of the library (mpg_amd/_lib.py ENGINES): the split-fp16 product and the exact-fp32 engine"""
-    with L.engine(request.param):
-        yield request.param
-
-
-class Policy(object):
-    """a policy network and a cfg that points at its status word, with or without the packed weight image"""
-
-    def __init__(self, od, packed, seed=0):
-        from tests.golden_inputs import mlp_weights_flat
-        rng = np.random.Generator(np.random.PCG64(100 * od + seed))
-        self.od = od
-        self.cfg = ops.make_cfg(obs_dim=od)
-        self.pol = torch.as_tensor(mlp_weights_flat(rng, od, 4)).to(DEV)
-        self.wc = None
-        if packed:                                        # the packed-image instantiation: cfg.wcache[0] -> the policy's images
-            self.wc = ops.WeightCache(self.pol, [(od, 4)])
-            self.cfg.wcache[0] = self.wc.pointer
-        self.status = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.cfg.status = self.status.data_ptr()
+def Policy(od, packed, seed=0):
+    return H.PolicyNet(od, 4, ops.make_cfg(obs_dim=od), packed, 100 * od + seed)
 
 
 def start(p, n, cap, nan_row=None):
-    """one side's buffers: agents from the reset law (seed 4), rings full of a sentinel"""
+    """agents from the reset law (seed 4)"""
     from mpg_amd.envs import PathTrackingEnv
-    env = PathTrackingEnv(num_agent=n, num_future_data=p.od - 6, seed=4)
-    obs = env.reset().clone()
-    if nan_row is not None:                               # the agent and its observation: NaN from the start
-        env._state[:, nan_row] = float('nan')
-        obs[nan_row] = float('nan')
-    f = dict(dtype=torch.float32, device=DEV)
-    return dict(state=env._state, obs_io=obs, act_out=torch.full((n, 2), -7., **f), done_out=torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV),
-                ring_obs=torch.full((cap, p.od), -7., **f), ring_act=torch.full((cap, 2), -7., **f), ring_rew=torch.full((cap,), -7., **f),
-                ring_obs2=torch.full((cap, p.od), -7., **f), ring_done=torch.full((cap,), 0xAB, dtype=torch.uint8, device=DEV))
-
-
-def ring_ptrs(t):
-    return [L.ptr(t[k]) for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done')]
+    return H.start(PathTrackingEnv(num_agent=n, num_future_data=p.od - 6, seed=4), p.od, 2, n, cap, nan_row=nan_row)
 
 
 def run_chain(p, t, n, iters, sigma, cap, nxt, nctr, ectr):
@@ -81,18 +45,11 @@ def run_launch(p, t, n, iters, sigma, cap, nxt, nctr, ectr):
     t['status'] = p.status.clone()
 
 
-def both(p, n, iters, sigma, cap=None, nxt=5, nctr=7, ectr=3, nan_row=None):
-    cap = iters * n + 13 if cap is None else cap
-    a, b = start(p, n, cap, nan_row), start(p, n, cap, nan_row)
-    run_chain(p, a, n, iters, sigma, cap, nxt, nctr, ectr)
-    run_launch(p, b, n, iters, sigma, cap, nxt, nctr, ectr)
-    torch.cuda.synchronize()
-    return a, b
-
-
-def assert_same(a, b, what):
-    for k in NAMES:
-        assert torch.equal(bits(a[k]), bits(b[k])), (what, k)
+def both(p, n, iters, sigma, nan_row=None, **where):
+    """-> (chain, launch)"""
+    def at_sigma(run):
+        return lambda t, n, iters, *rest: run(p, t, n, iters, sigma, *rest)
+    return H.both((at_sigma(run_chain), at_sigma(run_launch)), partial(start, p, nan_row=nan_row), n, iters, **where)
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -107,11 +64,9 @@ def test_one_launch_equals_the_chain_of_worker_steps_bit_for_bit(engine, od, pac
                 a, b = both(p, n, iters, sigma)
                 assert_same(a, b, (n, iters, sigma))
                 assert int(b['status'].item()) == 0
-                cap = iters * n + 13
-                untouched = torch.ones(cap, dtype=torch.bool, device=DEV)
-                untouched[(5 + torch.arange(iters * n, device=DEV)) % cap] = False
-                assert (b['ring_rew'][untouched] == -7.).all() and (b['ring_rew'][~untouched] != -7.).all()
-                assert torch.isfinite(b['ring_obs2'][~untouched]).all() and (b['ring_done'][~untouched] == 1).all()   # SURVEY B-0
+                w = H.touched(iters * n + 13, 5, iters * n)
+                assert (b['ring_rew'][~w] == -7.).all() and (b['ring_rew'][w] != -7.).all()
+                assert torch.isfinite(b['ring_obs2'][w]).all() and (b['ring_done'][w] == 1).all()   # SURVEY B-0
 
 
 @pytest.mark.parametrize('od,packed', [(6, True), (9, False)])
@@ -121,7 +76,7 @@ def test_ring_wrap_inside_an_iteration_and_the_counters_carry(engine, od, packed
     p = Policy(od, packed, seed=1)
     for n, iters in ((8, 5), (40, 5), (16, 64)):
         cap = iters * n
-        a, b = both(p, n, iters, 0.1, cap=cap, nxt=cap - 3, nctr=2 ** 32 - 2, ectr=2 ** 32 - 2)
+        a, b = both(p, n, iters, 0.1, cap=cap, nxt=cap - 3, ctr=2 ** 32 - 2, ectr=2 ** 32 - 2)
         assert_same(a, b, (n, iters))
         assert (b['ring_rew'] != -7.).all() and (b['ring_done'] == 1).all()
     # the high words matter: the same start and the same low words under another high word draw other noise and other resets
@@ -146,8 +101,7 @@ def test_a_nan_start_row_is_reported_and_stored_like_the_chain(engine, od, packe
     assert int(a['status'].item()) == int(b['status'].item()) and int(b['status'].item()) & ops.STATUS_NAN
     slot = 5 + row                                         # the row's transition of iteration 0
     assert torch.isnan(b['ring_obs'][slot]).all() and torch.isnan(b['ring_act'][slot]).all() and torch.isnan(b['ring_rew'][slot])
-    keep = torch.ones(iters * n + 13, dtype=torch.bool, device=DEV)
-    keep[slot] = False
+    keep = ~H.touched(iters * n + 13, slot, 1)
     assert not torch.isnan(b['ring_rew'][keep]).any() and torch.isfinite(b['state']).all() and (b['done_out'] == 1).all()
 
 
@@ -156,49 +110,28 @@ def test_repeated_launches_are_bit_identical(engine, od):
     """100 launches from one start: the hand-overs between wave 0 and the policy pass through LDS are the new thing here"""
     p = Policy(od, True, seed=3)
     n, iters, cap = 40, 5, 40 * 5 + 13
-    first = None
-    for _ in range(100):
-        t = start(p, n, cap)
-        run_launch(p, t, n, iters, 0.1, cap, 5, 7, 3)
-        if first is None:
-            first = t
-        else:
-            assert_same(first, t, 'repeat')
+    H.assert_repeatable(lambda: start(p, n, cap), lambda t: run_launch(p, t, n, iters, 0.1, cap, 5, 7, 3), 100)
 
 
 # ---- OffPolicyWorker.sample ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('future', [0, 3])
 def test_worker_sample_one_launch_equals_the_loop(engine, future):
     from mpg_amd.config import default_args
-    from mpg_amd.policy import PolicyWithQs
-    from mpg_amd.worker import OffPolicyWorker
-    out = []
-    for one in (False, True):
-        more = dict(one_launch_sample=True) if one else {}
-        args = default_args('TD3', num_agent=8, batch_size=64, num_future_data=future, seed=5, init_seed=5, **more)
-        w = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
-        batches = [w.sample(), w.sample()]                 # two consecutive calls: the second continues from what the first left
-        torch.cuda.synchronize()
-        out.append((batches, w.obs, w.env.obs, w.env._state, w.env.done, (w._noise_ctr, w.env._ctr, w.num_sample, w.sample_times)))
-    (ba, oa, eoa, sa, da, ca), (bb, ob, eob, sb, db, cb) = out
-    assert ca == cb and ca[0] == 16 and ca[2:] == (128, 2), (ca, cb)
-    for x, y in zip(ba, bb):
-        assert len(x) == len(y) == 5
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(bits(u), bits(v))
-    assert torch.equal(bits(oa), bits(ob)) and torch.equal(bits(eoa), bits(eob)) and torch.equal(bits(sa), bits(sb)) and torch.equal(da, db)
+    (_, _, ca), (_, _, cb) = H.worker_sample_pair(partial(default_args, 'TD3', num_agent=8, batch_size=64, num_future_data=future, seed=5,
+                                                          init_seed=5))
+    assert ca[0] == 16 and ca[2:] == (128, 2), (ca, cb)
 
 
 # ---- native step driver ---------------------------------------------------------------------------------------------------------
-def _stack(alg, per, **over):
+def _stack(alg, per):
     from mpg_amd.buffer import PrioritizedReplayBuffer, ReplayBuffer
     from mpg_amd.config import default_args
     from mpg_amd.learners import MPGLearner, TD3Learner
     from mpg_amd.optimizer import SingleProcessOffPolicyOptimizer
     from mpg_amd.policy import PolicyWithQs
     from mpg_amd.worker import OffPolicyWorker
-    args = default_args(alg, replay_batch_size=64, max_buffer_size=over.pop('max_buffer_size', 8192), seed=3, init_seed=3,
-                        buffer_type='priority' if per else 'normal', nan_check_interval=10 ** 9, **over)
+    args = default_args(alg, replay_batch_size=64, max_buffer_size=8192, seed=3, init_seed=3, buffer_type='priority' if per else 'normal',
+                        nan_check_interval=10 ** 9)
     assert (args.num_agent, args.batch_size) == (8, 512)              # the reference's worker defaults: 64 iterations per sample
     worker = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
     learner = (TD3Learner if alg == 'TD3' else MPGLearner)(PolicyWithQs, args)
@@ -208,50 +141,18 @@ def _stack(alg, per, **over):
     return opt
 
 
-def _run(alg, per, chain, iters=25, **over):
-    opt = _stack(alg, per, **over)
-    assert opt._fused.c.sample_iters == 64
-    if chain:
-        opt._fused.c.sample_iters = -64                   # include/mpg_hip.h: the same 64 iterations, one mpg_worker_step each
-    for _ in range(iters):
-        opt.step()
-    torch.cuda.synchronize()
-    pw, rb, c, f = opt.worker.policy_with_value, opt.replay_buffer, opt._fused.c, opt._fused
-    tensors = [pw.params, pw.targets, pw.m, pw.v, rb.obs, rb.act, rb.rew, rb.obs2, rb.done, f.t['w_obs'], f.t['w_act'], f.t['w_done'],
-               opt.worker.env._state, opt.learner.flat, pw.status]
-    if per:
-        tensors += [rb._it_sum, rb._it_min, rb._stamp, rb._max_priority]
-    counters = (c.noise_ctr, c.env_ctr, c.ring_next, c.ring_size, c.replay_times, c.learner_counter, [c.opt_steps[i] for i in range(3)])
-    return [x.clone() for x in tensors], counters
-
-
 @pytest.mark.parametrize('alg,per', [('MPG-v2', False), ('TD3', False), ('TD3', True)], ids=['mpg_v2', 'td3', 'td3_priority'])
 def test_native_driver_with_the_launch_equals_the_driver_on_the_chain(engine, alg, per):
     """25 iterations (samples at 0, 10, 20) at the reference's worker defaults: the driver that issues mpg_worker_rollout for the first
-    63 (MPG-v2: the 64th pre-gathers the draw) or 64 (TD3) iterations of a sample against the same driver kept on the chain:
-    parameters, Adam moments, targets, ring, the trees of the prioritized pair (its mpg_per_add calls follow the launch, in iteration
-    order), worker buffers, status word and counters, bit for bit.  The ring of 8192 wraps at the third sample."""
-    a, ca = _run(alg, per, False)
-    b, cb = _run(alg, per, True)
-    assert ca == cb, (ca, cb)
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(bits(x), bits(y)), k
+    63 (MPG-v2: the 64th pre-gathers the draw) or 64 (TD3) iterations of a sample against the same driver kept on the chain (one
+    mpg_worker_step each): parameters, Adam moments, targets, ring, the trees of the prioritized pair (its mpg_per_add calls follow
+    the launch, in iteration order), worker buffers, status word and counters, bit for bit.  The ring of 8192 wraps at the third
+    sample."""
+    H.driver_chain_pair(partial(_stack, alg, per), 64, extra=H.per_trees if per else None)
 
 
 def test_native_driver_issues_one_worker_launch_per_sample():
     """the driver's own timer counts the worker's launches (slot 2): one per sample with the launch (TD3: all 64 iterations), 64 on the
     chain - the pair above does compare two different launch sequences"""
-    counts = []
-    for chain in (False, True):
-        opt = _stack('TD3', False)
-        if chain:
-            opt._fused.c.sample_iters = -64
-        prof = ops.Profiler(max_samples=256)
-        opt.set_profiler(prof)
-        prof.start(1)
-        opt.step()                                          # iteration 0 samples
-        torch.cuda.synchronize()
-        counts.append(prof.read(2)[1])
-        opt.set_profiler(None)
-        prof.close()
+    counts = H.worker_launch_counts(partial(_stack, 'TD3', False), 64, 256)
     assert counts == [1, 64], counts

@@ -2,10 +2,11 @@
 replaces, from identical starts, bit for bit - env state, observations, last actions, last done flags, all five ring arrays WHOLE
 (prefilled with a sentinel, so the slots nobody writes count) and the status word; its callers - OffPolicyWorker.sample
 (one_launch_sample) against the loop, the native step driver with the launch against the same driver kept on the chain
-(sample_iters < 0).  Floats are compared as their 32-bit patterns (a NaN row has to match too).  Unlike PathTracking's, this env's
-done flag is real: the tests assert on the device's own rows that agents were carried across iterations, fell, were re-drawn and
-went on."""
+(sample_iters < 0).  The buffers, the comparison (floats as their 32-bit patterns: a NaN row has to match too) and the callers' pairs
+are those of tests/rollout_harness.py.  Unlike PathTracking's, this env's done flag is real: the tests assert on the device's own
+rows that agents were carried across iterations, fell, were re-drawn and went on."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -13,43 +14,22 @@ import torch
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import rollout_harness as H
+from tests.rollout_harness import assert_same, bits, engine, ring_ptrs  # noqa: F401 (engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 ENV_ID = 'InvertedPendulumConti-v0'
-NAMES = ('state', 'obs_io', 'act_out', 'done_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'status')
 
 
-def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+def gentle_last_layer(flat):
+    flat[-(2 * 256 + 2):] *= np.float32(0.01)             # W3 [256][2] and b3 [2]
 
 
-@pytest.fixture(params=['split', 'f32'])
-def engine(request):
-    """both builds of the library (mpg_amd/_lib.py ENGINES): the split-fp16 product and the exact-fp32 engine"""
-    with L.engine(request.param):
-        yield request.param
-
-
-class Policy(object):
-    """the pendulum's policy network (4 inputs, mean | log-std) and a cfg that points at its status word, with or without the packed
-    weight image.  gentle: the last layer scaled by 0.01 - actions of a few hundredths, so that an agent near the upright stays up
-    for many iterations and falls on its own."""
-
-    def __init__(self, packed, seed=0, gentle=False):
-        from tests.golden_inputs import mlp_weights_flat
-        rng = np.random.Generator(np.random.PCG64(400 + seed))
-        flat = mlp_weights_flat(rng, 4, 2)
-        if gentle:
-            flat[-(2 * 256 + 2):] *= np.float32(0.01)     # W3 [256][2] and b3 [2]
-        self.cfg = ops.make_cfg(ENV_ID)                   # linear output with action_range 3: a = 3 tanh(mean)
-        self.pol = torch.as_tensor(flat).to(DEV)
-        self.wc = None
-        if packed:                                        # the packed-image instantiation: cfg.wcache[0] -> the policy's images
-            self.wc = ops.WeightCache(self.pol, [(4, 2)])
-            self.cfg.wcache[0] = self.wc.pointer
-        self.status = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.cfg.status = self.status.data_ptr()
+def Policy(packed, seed=0, gentle=False):
+    """the pendulum's policy network (4 inputs, mean | log-std) under a linear output with action_range 3: a = 3 tanh(mean).  gentle:
+    the last layer scaled by 0.01 - actions of a few hundredths, so that an agent near the upright stays up for many iterations and
+    falls on its own."""
+    return H.PolicyNet(4, 2, ops.make_cfg(ENV_ID), packed, 400 + seed, gentle_last_layer if gentle else None)
 
 
 def reset_law_starts(n, seed=7):
@@ -57,23 +37,19 @@ def reset_law_starts(n, seed=7):
     return np.random.Generator(np.random.PCG64(seed)).uniform(-0.01, 0.01, (n, 4)).astype(np.float32)
 
 
+def mixed_starts(n):
+    """even agents from the reset law; odd agents at p = 1.999 with pdot = 1: such an agent leaves |p| < 2 on the first step whatever
+    the action does (at the largest force, 300 N on the cart, p changes by at least 0.04 * 1 - 1/2 * 30 * 0.04^2 = +0.016)"""
+    s = reset_law_starts(n)
+    s[1::2, 0] = 1.999
+    s[1::2, 2] = 1.0
+    return s
+
+
 def start(n, cap, init_obs=None, nan_row=None):
-    """one side's buffers: agents from the reset law (seed 4) or from init_obs (through mpg_env_reset_from_obs), rings full of a
-    sentinel"""
+    """agents from the reset law (seed 4) or from init_obs (through mpg_env_reset_from_obs)"""
     from mpg_amd.envs import InvertedPendulumContiEnv
-    env = InvertedPendulumContiEnv(num_agent=n, seed=4)
-    obs = (env.reset() if init_obs is None else env.reset(init_obs=torch.as_tensor(init_obs).to(DEV))).clone()
-    if nan_row is not None:                               # the agent and its observation: NaN from the start
-        env._state[:, nan_row] = float('nan')
-        obs[nan_row] = float('nan')
-    f = dict(dtype=torch.float32, device=DEV)
-    return dict(state=env._state, obs_io=obs, act_out=torch.full((n, 1), -7., **f), done_out=torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV),
-                ring_obs=torch.full((cap, 4), -7., **f), ring_act=torch.full((cap, 1), -7., **f), ring_rew=torch.full((cap,), -7., **f),
-                ring_obs2=torch.full((cap, 4), -7., **f), ring_done=torch.full((cap,), 0xAB, dtype=torch.uint8, device=DEV))
-
-
-def ring_ptrs(t):
-    return [L.ptr(t[k]) for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done')]
+    return H.start(InvertedPendulumContiEnv(num_agent=n, seed=4), 4, 1, n, cap, init_obs, nan_row)
 
 
 def run_chain(p, t, n, iters, sigma, cap, nxt, nctr, ectr):
@@ -95,18 +71,11 @@ def run_launch(p, t, n, iters, sigma, cap, nxt, nctr, ectr):
     t['status'] = p.status.clone()
 
 
-def both(p, n, iters, sigma, cap=None, nxt=5, nctr=7, ectr=3, init_obs=None, nan_row=None):
-    cap = iters * n + 13 if cap is None else cap
-    a, b = start(n, cap, init_obs, nan_row), start(n, cap, init_obs, nan_row)
-    run_chain(p, a, n, iters, sigma, cap, nxt, nctr, ectr)
-    run_launch(p, b, n, iters, sigma, cap, nxt, nctr, ectr)
-    torch.cuda.synchronize()
-    return a, b
-
-
-def assert_same(a, b, what):
-    for k in NAMES:
-        assert torch.equal(bits(a[k]), bits(b[k])), (what, k)
+def both(p, n, iters, sigma, init_obs=None, nan_row=None, **where):
+    """-> (chain, launch)"""
+    def at_sigma(run):
+        return lambda t, n, iters, *rest: run(p, t, n, iters, sigma, *rest)
+    return H.both((at_sigma(run_chain), at_sigma(run_launch)), partial(start, init_obs=init_obs, nan_row=nan_row), n, iters, **where)
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -120,21 +89,10 @@ def test_one_launch_equals_the_chain_of_policy_and_env_launches_bit_for_bit(engi
                 a, b = both(p, n, iters, sigma)
                 assert_same(a, b, (n, iters, sigma))
                 assert int(b['status'].item()) == 0
-                cap = iters * n + 13
-                untouched = torch.ones(cap, dtype=torch.bool, device=DEV)
-                untouched[(5 + torch.arange(iters * n, device=DEV)) % cap] = False
-                assert (b['ring_rew'][untouched] == -7.).all() and (b['ring_rew'][~untouched] != -7.).all()
-                assert (b['ring_done'][untouched] == 0xAB).all() and (b['ring_done'][~untouched] <= 1).all()
-                assert torch.isfinite(b['ring_obs2'][~untouched]).all()
-
-
-def mixed_starts(n):
-    """even agents from the reset law; odd agents at p = 1.999 with pdot = 1: such an agent leaves |p| < 2 on the first step whatever
-    the action does (at the largest force, 300 N on the cart, p changes by at least 0.04 * 1 - 1/2 * 30 * 0.04^2 = +0.016)"""
-    s = reset_law_starts(n)
-    s[1::2, 0] = 1.999
-    s[1::2, 2] = 1.0
-    return s
+                w = H.touched(iters * n + 13, 5, iters * n)
+                assert (b['ring_rew'][~w] == -7.).all() and (b['ring_rew'][w] != -7.).all()
+                assert (b['ring_done'][~w] == 0xAB).all() and (b['ring_done'][w] <= 1).all()
+                assert torch.isfinite(b['ring_obs2'][w]).all()
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -175,7 +133,7 @@ def test_ring_wrap_inside_an_iteration_and_the_counters_carry(engine, packed):
     p = Policy(packed, seed=1)
     for n, iters in ((8, 5), (40, 5), (16, 64), (1, 64)):
         cap = iters * n
-        a, b = both(p, n, iters, 0.1, cap=cap, nxt=cap - 3, nctr=2 ** 32 - 2, ectr=2 ** 32 - 2, init_obs=mixed_starts(n))
+        a, b = both(p, n, iters, 0.1, cap=cap, nxt=cap - 3, ctr=2 ** 32 - 2, ectr=2 ** 32 - 2, init_obs=mixed_starts(n))
         assert_same(a, b, (n, iters))
         assert (b['ring_rew'] != -7.).all() and (b['ring_done'] <= 1).all()
     # the high words matter: the same start and the same low words under another high word draw other noise, and - the odd agents fall
@@ -205,8 +163,7 @@ def test_a_nan_start_row_is_reported_and_stored_like_the_chain(engine, packed):
     slot = 5 + row                                         # the row's transition of iteration 0
     assert torch.isnan(b['ring_obs'][slot]).all() and torch.isnan(b['ring_act'][slot]).all() and torch.isnan(b['ring_rew'][slot])
     assert torch.isnan(b['ring_obs2'][slot]).all() and int(b['ring_done'][slot]) == 1
-    keep = torch.ones(iters * n + 13, dtype=torch.bool, device=DEV)
-    keep[slot] = False
+    keep = ~H.touched(iters * n + 13, slot, 1)
     for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2'):
         assert torch.isfinite(b[k][keep]).all(), k
     assert torch.isfinite(b['state'][:4]).all() and torch.isfinite(b['obs_io']).all() and torch.isfinite(b['act_out']).all()
@@ -216,14 +173,7 @@ def test_repeated_launches_are_bit_identical(engine):
     """100 launches from one start: the hand-overs between the env lanes and the policy pass through LDS are the new thing here"""
     p = Policy(True, seed=3)
     n, iters, cap = 40, 5, 40 * 5 + 13
-    first = None
-    for _ in range(100):
-        t = start(n, cap, mixed_starts(n))
-        run_launch(p, t, n, iters, 0.1, cap, 5, 7, 3)
-        if first is None:
-            first = t
-        else:
-            assert_same(first, t, 'repeat')
+    H.assert_repeatable(lambda: start(n, cap, mixed_starts(n)), lambda t: run_launch(p, t, n, iters, 0.1, cap, 5, 7, 3), 100)
 
 
 # ---- OffPolicyWorker.sample ---------------------------------------------------------------------------------------------------
@@ -231,24 +181,13 @@ def test_repeated_launches_are_bit_identical(engine):
 @pytest.mark.parametrize('num_agent', [1, 8])
 def test_worker_sample_one_launch_equals_the_loop(engine, num_agent, sigma):
     from mpg_amd.config import default_args
-    from mpg_amd.policy import PolicyWithQs
-    from mpg_amd.worker import OffPolicyWorker
-    out = []
-    for one in (False, True):
-        more = dict(one_launch_sample=True) if one else {}
+
+    def make(**more):
         args = default_args('NADP', num_agent=num_agent, batch_size=64, explore_sigma=sigma, seed=5, init_seed=5, **more)
         assert args.env_id == ENV_ID
-        w = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
-        batches = [w.sample(), w.sample()]                 # two consecutive calls: the second continues from what the first left
-        torch.cuda.synchronize()
-        out.append((batches, w.obs, w.env.obs, w.env._state, w.env.done, (w._noise_ctr, w.env._ctr, w.num_sample, w.sample_times)))
-    (ba, oa, eoa, sa, da, ca), (bb, ob, eob, sb, db, cb) = out
-    assert ca == cb and ca[0] == 2 * (64 // num_agent) and ca[2:] == (128, 2), (ca, cb)
-    for x, y in zip(ba, bb):
-        assert len(x) == len(y) == 5
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(bits(u), bits(v))
-    assert torch.equal(bits(oa), bits(ob)) and torch.equal(bits(eoa), bits(eob)) and torch.equal(bits(sa), bits(sb)) and torch.equal(da, db)
+        return args
+    (_, _, ca), (_, _, cb) = H.worker_sample_pair(make)
+    assert ca[0] == 2 * (64 // num_agent) and ca[2:] == (128, 2), (ca, cb)
 
 
 # ---- native step driver ---------------------------------------------------------------------------------------------------------
@@ -271,23 +210,12 @@ def _stack(alg, per, **over):
     return opt
 
 
-def _run(alg, per, chain, iters=25, **over):
-    opt = _stack(alg, per, **over)
-    assert opt._fused.c.sample_iters == 512
-    if chain:
-        opt._fused.c.sample_iters = -512                  # include/mpg_hip.h: the same 512 iterations, two launches each
-    for _ in range(iters):
-        opt.step()
-    torch.cuda.synchronize()
-    pw, rb, c, f = opt.worker.policy_with_value, opt.replay_buffer, opt._fused.c, opt._fused
-    tensors = [pw.params, pw.targets, pw.m, pw.v, rb.obs, rb.act, rb.rew, rb.obs2, rb.done, f.t['w_obs'], f.t['w_act'], f.t['w_done'],
-               opt.worker.env._state, opt.learner.flat, pw.status]
-    if per:
-        tensors += [rb._it_sum, rb._it_min, rb._stamp, rb._max_priority]
-    counters = (c.noise_ctr, c.env_ctr, c.ring_next, c.ring_size, c.replay_times, c.learner_counter, [c.opt_steps[i] for i in range(3)])
-    assert c.noise_ctr >= 3 * 512 and c.ring_size == 1024             # samples at 0, 10 and 20: the ring of 1024 has wrapped
-    assert 0 < int(rb.done.sum().item()) < 1024                       # both branches of done went into the ring
-    return [x.clone() for x in tensors], counters
+def _pair(alg, per, **over):
+    """the driver with the launch against the driver on the chain (512 iterations, two launches each), 25 steps; either run wrapped
+    the ring and stored both branches of done"""
+    for tensors, c in H.driver_chain_pair(partial(_stack, alg, per, **over), 512, extra=H.per_trees if per else None):
+        assert c[0] >= 3 * 512 and c[3] == 1024                       # noise_ctr, ring_size: samples at 0, 10 and 20, the ring of 1024 has wrapped
+        assert 0 < int(tensors[8].sum().item()) < 1024                # the ring's done column: both branches of done went into it
 
 
 @pytest.mark.parametrize('sigma', [None, 0.1], ids=['no_noise', 'sigma_0.1'])
@@ -295,39 +223,19 @@ def test_native_driver_with_the_launch_equals_the_driver_on_the_chain(engine, si
     """NADP at the pendulum defaults, 25 iterations (samples at 0, 10, 20): the driver that issues mpg_worker_rollout_pendulum for the
     512 iterations of a sample against the same driver kept on the chain: parameters, Adam moments, targets, ring, worker buffers, env
     state, the learner's flat gradient, status word and counters, bit for bit."""
-    a, ca = _run('NADP', False, False, explore_sigma=sigma)
-    b, cb = _run('NADP', False, True, explore_sigma=sigma)
-    assert ca == cb, (ca, cb)
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(bits(x), bits(y)), k
+    _pair('NADP', False, explore_sigma=sigma)
 
 
 @pytest.mark.parametrize('per', [False, True], ids=['td3', 'td3_priority'])
 def test_native_td3_driver_with_the_launch_equals_the_driver_on_the_chain(engine, per):
     """TD3 on the pendulum, uniform and prioritized: the mpg_per_add calls follow the launch in iteration order, so the trees are
     compared too"""
-    a, ca = _run('TD3', per, False)
-    b, cb = _run('TD3', per, True)
-    assert ca == cb, (ca, cb)
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(bits(x), bits(y)), k
+    _pair('TD3', per)
 
 
 def test_native_driver_issues_one_worker_launch_per_sample():
     """the driver's own timer counts the worker's launches (slot 2): one per sample with the launch, 512 env launches on the chain
     (slot 2 brackets mpg_env_step_store_reset there; the 512 policy launches count in slot 3) - the pairs above do compare two
     different launch sequences"""
-    counts = []
-    for chain in (False, True):
-        opt = _stack('NADP', False)
-        if chain:
-            opt._fused.c.sample_iters = -512
-        prof = ops.Profiler(max_samples=2048)
-        opt.set_profiler(prof)
-        prof.start(1)
-        opt.step()                                          # iteration 0 samples
-        torch.cuda.synchronize()
-        counts.append(prof.read(2)[1])
-        opt.set_profiler(None)
-        prof.close()
+    counts = H.worker_launch_counts(partial(_stack, 'NADP', False), 512, 2048)
     assert counts == [1, 512], counts

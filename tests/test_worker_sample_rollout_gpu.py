@@ -3,9 +3,10 @@ mpg_policy_sample_squashed) + mpg_env_step_store_reset triples it replaces - and
 mpg_worker_sample_step calls - from identical starts, bit for bit: env state, observations, last actions, last done flags, all five
 ring arrays WHOLE (prefilled with a sentinel, so the slots nobody writes count) and the status word; its callers -
 OffPolicyWorker.sample(one_launch_sample) with a stochastic policy against the loop, the native SAC driver with the launch against the
-same driver kept on the chain (sample_iters < 0).  Floats are compared as their 32-bit patterns (a NaN row has to match too).  The
-harness is that of tests/test_worker_rollout_gpu.py."""
+same driver kept on the chain (sample_iters < 0).  The buffers, the comparison (floats as their 32-bit patterns: a NaN row has to match
+too) and the callers' pairs are those of tests/rollout_harness.py."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -13,67 +14,32 @@ import torch
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import rollout_harness as H
+from tests.rollout_harness import DEV, assert_same, bits, engine, ring_ptrs  # noqa: F401 (engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-NAMES = ('state', 'obs_io', 'act_out', 'done_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'status')
 SAMPLE_SEED, ENV_SEED = 11, 4
 RANGE = 1.5
 HEADS = ('plain', 'squashed')
 
 
-def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
-@pytest.fixture(params=['split', 'f32'])
-def engine(request):
-    """both builds of the library (mpg_amd/_lib.py ENGINES): the split-fp16 product and the exact-fp32 engine"""
-    with L.engine(request.param):
-        yield request.param
-
-
-class Policy(object):
-    """a four-output policy network (mean | log-std) and a cfg that points at its status word, with or without the packed weight
-    image.  head 'plain': the Gaussian head (no action range); 'squashed': a = RANGE tanh(mean + sigma eps).  Linear output (SAC's
-    default, and what the squashed head asks for) unless out_act says otherwise.  b3: the last layer's bias replaced, W3 scaled by 0.1
-    (the heads' edges)."""
-
-    def __init__(self, od, packed, head, seed=0, out_act='linear', b3=None):
-        from tests.golden_inputs import mlp_weights_flat
-        rng = np.random.Generator(np.random.PCG64(100 * od + seed))
-        self.od, self.head = od, head
-        self.cfg = ops.make_cfg(obs_dim=od, policy_out_activation=out_act, action_range=RANGE if head == 'squashed' else None)
-        flat = mlp_weights_flat(rng, od, 4)
-        if b3 is not None:
-            flat[-(4 * 256 + 4):-4] *= np.float32(0.1)
-            flat[-4:] = np.asarray(b3, dtype=np.float32)
-        self.pol = torch.as_tensor(flat).to(DEV)
-        self.wc = None
-        if packed:                                        # the packed-image instantiation: cfg.wcache[0] -> the policy's images
-            self.wc = ops.WeightCache(self.pol, [(od, 4)])
-            self.cfg.wcache[0] = self.wc.pointer
-        self.status = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.cfg.status = self.status.data_ptr()
-        self.sample_entry = 'mpg_policy_sample_squashed' if head == 'squashed' else 'mpg_policy_sample'
+def Policy(od, packed, head, seed=0, out_act='linear', b3=None):
+    """a four-output policy network (mean | log-std).  head 'plain': the Gaussian head (no action range); 'squashed': a = RANGE
+    tanh(mean + sigma eps).  Linear output (SAC's default, and what the squashed head asks for) unless out_act says otherwise.  b3:
+    the last layer's bias replaced, W3 scaled by 0.1 (the heads' edges)."""
+    def edges(flat):
+        flat[-(4 * 256 + 4):-4] *= np.float32(0.1)
+        flat[-4:] = np.asarray(b3, dtype=np.float32)
+    cfg = ops.make_cfg(obs_dim=od, policy_out_activation=out_act, action_range=RANGE if head == 'squashed' else None)
+    p = H.PolicyNet(od, 4, cfg, packed, 100 * od + seed, None if b3 is None else edges)
+    p.sample_entry = 'mpg_policy_sample_squashed' if head == 'squashed' else 'mpg_policy_sample'
+    return p
 
 
 def start(p, n, cap, nan_row=None):
-    """one side's buffers: agents from the reset law (seed 4), rings full of a sentinel"""
+    """agents from the reset law (seed 4)"""
     from mpg_amd.envs import PathTrackingEnv
-    env = PathTrackingEnv(num_agent=n, num_future_data=p.od - 6, seed=ENV_SEED)
-    obs = env.reset().clone()
-    if nan_row is not None:                               # the agent and its observation: NaN from the start
-        env._state[:, nan_row] = float('nan')
-        obs[nan_row] = float('nan')
-    f = dict(dtype=torch.float32, device=DEV)
-    return dict(state=env._state, obs_io=obs, act_out=torch.full((n, 2), -7., **f), done_out=torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV),
-                ring_obs=torch.full((cap, p.od), -7., **f), ring_act=torch.full((cap, 2), -7., **f), ring_rew=torch.full((cap,), -7., **f),
-                ring_obs2=torch.full((cap, p.od), -7., **f), ring_done=torch.full((cap,), 0xAB, dtype=torch.uint8, device=DEV))
-
-
-def ring_ptrs(t):
-    return [L.ptr(t[k]) for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done')]
+    return H.start(PathTrackingEnv(num_agent=n, num_future_data=p.od - 6, seed=ENV_SEED), p.od, 2, n, cap, nan_row=nan_row)
 
 
 def run_chain(p, t, n, iters, cap, nxt, sctr, ectr):
@@ -110,21 +76,10 @@ def run_launch(p, t, n, iters, cap, nxt, sctr, ectr):
     t['status'] = p.status.clone()
 
 
-def both(p, n, iters, cap=None, nxt=5, sctr=7, ectr=3, nan_row=None, steps=False):
+def both(p, n, iters, nan_row=None, steps=False, **where):
     """-> (chain, launch[, chain of mpg_worker_sample_step])"""
-    cap = iters * n + 13 if cap is None else cap
-    out = []
-    for run in (run_chain, run_launch) + ((run_steps,) if steps else ()):
-        t = start(p, n, cap, nan_row)
-        run(p, t, n, iters, cap, nxt, sctr, ectr)
-        out.append(t)
-    torch.cuda.synchronize()
-    return out
-
-
-def assert_same(a, b, what):
-    for k in NAMES:
-        assert torch.equal(bits(a[k]), bits(b[k])), (what, k)
+    runs = (run_chain, run_launch) + ((run_steps,) if steps else ())
+    return H.both([partial(run, p) for run in runs], partial(start, p, nan_row=nan_row), n, iters, **where)
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -143,15 +98,13 @@ def test_one_launch_equals_the_chain_of_draw_sample_and_env_launches_bit_for_bit
             if head == 'plain':
                 assert_same(out[2], b, (n, iters, 'mpg_worker_sample_step'))
             assert int(b['status'].item()) == 0
-            cap = iters * n + 13
-            untouched = torch.ones(cap, dtype=torch.bool, device=DEV)
-            untouched[(5 + torch.arange(iters * n, device=DEV)) % cap] = False
-            assert (b['ring_rew'][untouched] == -7.).all() and (b['ring_rew'][~untouched] != -7.).all()
-            assert (b['ring_done'][untouched] == 0xAB).all() and (b['ring_done'][~untouched] == 1).all()       # SURVEY B-0
+            w = H.touched(iters * n + 13, 5, iters * n)
+            assert (b['ring_rew'][~w] == -7.).all() and (b['ring_rew'][w] != -7.).all()
+            assert (b['ring_done'][~w] == 0xAB).all() and (b['ring_done'][w] == 1).all()                       # SURVEY B-0
             for k in ('ring_obs', 'ring_act', 'ring_obs2'):
-                assert (b[k][untouched] == -7.).all() and torch.isfinite(b[k][~untouched]).all(), k
+                assert (b[k][~w] == -7.).all() and torch.isfinite(b[k][w]).all(), k
             if head == 'squashed':
-                assert (b['ring_act'][~untouched].abs() <= RANGE).all()
+                assert (b['ring_act'][w].abs() <= RANGE).all()
 
 
 def test_the_output_activation_reaches_all_four_logits(engine):
@@ -171,7 +124,7 @@ def test_ring_wrap_inside_an_iteration_and_the_counters_carry(engine, head, od, 
     p = Policy(od, packed, head, seed=1)
     for n, iters in ((8, 5), (40, 5), (16, 64)):
         cap = iters * n
-        a, b = both(p, n, iters, cap=cap, nxt=cap - 3, sctr=2 ** 32 - 2, ectr=2 ** 32 - 2)
+        a, b = both(p, n, iters, cap=cap, nxt=cap - 3, ctr=2 ** 32 - 2, ectr=2 ** 32 - 2)
         assert_same(a, b, (n, iters))
         assert (b['ring_rew'] != -7.).all() and (b['ring_done'] == 1).all()
     # the high words matter: the same start and the same low words under another high word draw other actions and other resets
@@ -226,8 +179,7 @@ def test_a_nan_start_row_is_reported_and_stored_like_the_chain(engine, head, od,
     assert int(a['status'].item()) == int(b['status'].item()) and int(b['status'].item()) & ops.STATUS_NAN
     slot = 5 + row                                         # the row's transition of iteration 0
     assert torch.isnan(b['ring_obs'][slot]).all() and torch.isnan(b['ring_act'][slot]).all() and torch.isnan(b['ring_rew'][slot])
-    keep = torch.ones(iters * n + 13, dtype=torch.bool, device=DEV)
-    keep[slot] = False
+    keep = ~H.touched(iters * n + 13, slot, 1)
     assert not torch.isnan(b['ring_rew'][keep]).any() and torch.isfinite(b['state']).all() and (b['done_out'] == 1).all()
 
 
@@ -236,44 +188,25 @@ def test_repeated_launches_are_bit_identical(engine, head):
     """ten launches from one start: the hand-overs through LDS - observations to the pass, logits and actions within wave 0"""
     p = Policy(9, True, head, seed=3)
     n, iters, cap = 40, 5, 40 * 5 + 13
-    first = None
-    for _ in range(10):
-        t = start(p, n, cap)
-        run_launch(p, t, n, iters, cap, 5, 7, 3)
-        if first is None:
-            first = t
-        else:
-            assert_same(first, t, 'repeat')
+    H.assert_repeatable(lambda: start(p, n, cap), lambda t: run_launch(p, t, n, iters, cap, 5, 7, 3), 10)
 
 
 # ---- OffPolicyWorker.sample ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('stack', ['sac-0', 'sac-3', 'squashed'])
 def test_worker_sample_one_launch_equals_the_loop(engine, stack):
     from mpg_amd.config import default_args
-    from mpg_amd.policy import PolicyWithQs
-    from mpg_amd.worker import OffPolicyWorker
     kw = dict(squashed_head=True, action_range=RANGE) if stack == 'squashed' else dict(num_future_data=int(stack[-1]))
-    out = []
-    for one in (False, True):
-        more = dict(one_launch_sample=True) if one else {}
+
+    def make(**more):
         args = default_args('SAC', num_agent=8, batch_size=64, seed=5, init_seed=5, **kw, **more)
         assert args.explore_sigma is None and args.env_id == 'PathTracking-v0'
-        w = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+        return args
+    (wa, ba, ca), (wb, _, cb) = H.worker_sample_pair(make, extra_counters=True)
+    for w in (wa, wb):
         assert not w.policy_with_value.deterministic_policy and w.policy_with_value.squashed_head == (stack == 'squashed')
-        batches = [w.sample(), w.sample()]                 # two consecutive calls: the second continues from what the first left
-        torch.cuda.synchronize()
-        w.policy_with_value.check_status()
-        out.append((batches, w.obs, w.env.obs, w.env._state, w.env.done,
-                    (w._noise_ctr, w.env._ctr, w.num_sample, w.sample_times, w.policy_with_value._sample_ctr)))
-    (ba, oa, eoa, sa, da, ca), (bb, ob, eob, sb, db, cb) = out
-    assert ca == cb and ca[0] == 16 and ca[2:4] == (128, 2), (ca, cb)
-    for x, y in zip(ba, bb):
-        assert len(x) == len(y) == 5
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(bits(u), bits(v))
-        if stack == 'squashed':
-            assert x[1].abs().max().item() <= RANGE
-    assert torch.equal(bits(oa), bits(ob)) and torch.equal(bits(eoa), bits(eob)) and torch.equal(bits(sa), bits(sb)) and torch.equal(da, db)
+    assert ca[0] == 16 and ca[2:4] == (128, 2), (ca, cb)
+    if stack == 'squashed':
+        assert all(x[1].abs().max().item() <= RANGE for x in ba)
 
 
 # ---- native SAC driver -----------------------------------------------------------------------------------------------------------
@@ -295,36 +228,20 @@ def _stack(auto, **over):
     return opt
 
 
-def _run(auto, chain, iters=25, **over):
-    opt = _stack(auto, **over)
-    if chain:
-        opt._fused.c.sample_iters = -64                   # include/mpg_hip.h: the same 64 iterations, one mpg_worker_sample_step each
-    for _ in range(iters):
-        opt.step()
-    torch.cuda.synchronize()
-    pw, rb, c, f = opt.worker.policy_with_value, opt.replay_buffer, opt._fused.c, opt._fused
-    tensors = [pw.params, pw.targets, pw.m, pw.v, rb.obs, rb.act, rb.rew, rb.obs2, rb.done, f.t['w_obs'], f.t['w_act'], f.t['w_done'],
-               opt.worker.env._state, opt.learner.flat, pw.status]
-    if auto:
-        tensors.append(pw.alpha_state)
-    counters = (c.noise_ctr, c.env_ctr, c.ring_next, c.ring_size, c.replay_times, c.learner_counter, [c.opt_steps[i] for i in range(3)],
-                opt.num_sampled_steps)
-    return [x.clone() for x in tensors], counters
+def sac_state(auto, opt):
+    return [opt.worker.policy_with_value.alpha_state] if auto else [], (opt.num_sampled_steps,)
 
 
 @pytest.mark.parametrize('K', [0, 3], ids=['obs6', 'obs9'])
 @pytest.mark.parametrize('auto', [False, True], ids=['fixed-alpha', 'auto-alpha'])
 def test_native_driver_with_the_launch_equals_the_driver_on_the_chain(engine, auto, K):
     """25 iterations (samples at 0, 10, 20) at the reference's worker defaults, B = 256: the driver that issues mpg_worker_sample_rollout
-    for the 64 iterations of a sample against the same driver kept on the chain: parameters, Adam moments, targets, ring, worker
-    buffers, env state, gradients, status word, the temperature's state and counters, bit for bit.  The ring of 4096 wraps at the third
-    sample.  Both widths the driver's rule was measured at: six-entry observations and the 16-wide form."""
-    a, ca = _run(auto, False, num_future_data=K)
-    b, cb = _run(auto, True, num_future_data=K)
-    assert ca == cb, (ca, cb)
+    for the 64 iterations of a sample against the same driver kept on the chain (one mpg_worker_sample_step each): parameters, Adam
+    moments, targets, ring, worker buffers, env state, gradients, status word, the temperature's state and counters, bit for bit.  The
+    ring of 4096 wraps at the third sample.  Both widths the driver's rule was measured at: six-entry
+    observations and the 16-wide form."""
+    (a, ca), _ = H.driver_chain_pair(partial(_stack, auto, num_future_data=K), 64, extra=partial(sac_state, auto))
     assert ca[2:4] == ((3072 + 3 * 512) % 4096, 4096), ca              # it wrapped
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(bits(x), bits(y)), k
     assert all(torch.isfinite(t).all() for t in a[:4])
 
 
@@ -333,17 +250,5 @@ def test_native_driver_with_the_launch_equals_the_driver_on_the_chain(engine, au
 def test_native_driver_issues_one_worker_launch_per_sample(auto, K):
     """the driver's own timer counts the worker's launches (slot 2): one per sample with the launch, 64 on the chain - the pair above
     does compare two different launch sequences"""
-    counts = []
-    for chain in (False, True):
-        opt = _stack(auto, num_future_data=K)
-        if chain:
-            opt._fused.c.sample_iters = -64
-        prof = ops.Profiler(max_samples=256)
-        opt.set_profiler(prof)
-        prof.start(1)
-        opt.step()                                          # iteration 0 samples
-        torch.cuda.synchronize()
-        counts.append(prof.read(2)[1])
-        opt.set_profiler(None)
-        prof.close()
+    counts = H.worker_launch_counts(partial(_stack, auto, num_future_data=K), 64, 256)
     assert counts == [1, 64], counts

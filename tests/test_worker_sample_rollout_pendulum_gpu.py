@@ -2,9 +2,10 @@
 mpg_env_step_store_reset triples it replaces, from identical starts, bit for bit - env state, observations, last actions, last done
 flags, all five ring arrays WHOLE (prefilled with a sentinel, so the slots nobody writes count) and the status word; its caller -
 OffPolicyWorker.sample (one_launch_sample) with the tanh-squashed SAC policy against the loop, alone and under
-SingleProcessOffPolicyOptimizer.  Floats are compared as their 32-bit patterns (a NaN row has to match too).  The harness is that of
-tests/test_worker_rollout_pendulum_gpu.py; the policy here is the SAMPLED one: a = 3 tanh(mean + exp(clip(log_std)) eps)."""
+SingleProcessOffPolicyOptimizer.  The buffers, the comparison (floats as their 32-bit patterns: a NaN row has to match too) and the
+worker pair are those of tests/rollout_harness.py; the policy here is the SAMPLED one: a = 3 tanh(mean + exp(clip(log_std)) eps)."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -12,50 +13,28 @@ import torch
 
 from mpg_amd import _lib as L
 from mpg_amd import ops
+from tests import rollout_harness as H
+from tests.rollout_harness import DEV, assert_same, bits, engine, ring_ptrs  # noqa: F401 (engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 ENV_ID = 'InvertedPendulumConti-v0'
-NAMES = ('state', 'obs_io', 'act_out', 'done_out', 'ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done', 'status')
 SAMPLE_SEED, ENV_SEED = 11, 4
 GENTLE_LOG_STD = -3.5            # sigma = exp(-3.5) = 0.030 (test_both_branches_of_done_in_one_run says what the oracle showed)
 
 
-def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
-@pytest.fixture(params=['split', 'f32'])
-def engine(request):
-    """both builds of the library (mpg_amd/_lib.py ENGINES): the split-fp16 product and the exact-fp32 engine"""
-    with L.engine(request.param):
-        yield request.param
-
-
-class Policy(object):
-    """the pendulum's policy network (4 inputs, mean | log-std) and a cfg that points at its status word, with or without the packed
-    weight image.  gentle: the last layer scaled by 0.01 and the log-std bias at GENTLE_LOG_STD - means of a few hundredths under a
-    sigma of 0.03, so that an agent near the upright stays up for many iterations and falls on its own.  last_scale: the last layer
-    scaled UP (the head's edges)."""
-
-    def __init__(self, packed, seed=0, gentle=False, last_scale=None):
-        from tests.golden_inputs import mlp_weights_flat
-        rng = np.random.Generator(np.random.PCG64(400 + seed))
-        flat = mlp_weights_flat(rng, 4, 2)
+def Policy(packed, seed=0, gentle=False, last_scale=None):
+    """the pendulum's policy network (4 inputs, mean | log-std) under a linear output with action_range 3.  gentle: the last layer
+    scaled by 0.01 and the log-std bias at GENTLE_LOG_STD - means of a few hundredths under a sigma of 0.03, so that an agent near the
+    upright stays up for many iterations and falls on its own.  last_scale: the last layer scaled UP (the head's edges)."""
+    def last_layer(flat):
         if gentle:
             flat[-(2 * 256 + 2):] *= np.float32(0.01)     # W3 [256][2] and b3 [2]
             flat[-1] = np.float32(GENTLE_LOG_STD)         # b3[1]: the log-std column's bias
         if last_scale is not None:
             flat[-(2 * 256 + 2):] *= np.float32(last_scale)
-        self.cfg = ops.make_cfg(ENV_ID)                   # linear output with action_range 3
-        assert self.cfg.action_range == 3.0
-        self.pol = torch.as_tensor(flat).to(DEV)
-        self.wc = None
-        if packed:                                        # the packed-image instantiation: cfg.wcache[0] -> the policy's images
-            self.wc = ops.WeightCache(self.pol, [(4, 2)])
-            self.cfg.wcache[0] = self.wc.pointer
-        self.status = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.cfg.status = self.status.data_ptr()
+    cfg = ops.make_cfg(ENV_ID)
+    assert cfg.action_range == 3.0
+    return H.PolicyNet(4, 2, cfg, packed, 400 + seed, last_layer)
 
 
 def reset_law_starts(n, seed=7):
@@ -73,22 +52,9 @@ def mixed_starts(n):
 
 
 def start(n, cap, init_obs=None, nan_row=None):
-    """one side's buffers: agents from the reset law (seed 4) or from init_obs (through mpg_env_reset_from_obs), rings full of a
-    sentinel"""
+    """agents from the reset law (seed 4) or from init_obs (through mpg_env_reset_from_obs)"""
     from mpg_amd.envs import InvertedPendulumContiEnv
-    env = InvertedPendulumContiEnv(num_agent=n, seed=ENV_SEED)
-    obs = (env.reset() if init_obs is None else env.reset(init_obs=torch.as_tensor(init_obs).to(DEV))).clone()
-    if nan_row is not None:                               # the agent and its observation: NaN from the start
-        env._state[:, nan_row] = float('nan')
-        obs[nan_row] = float('nan')
-    f = dict(dtype=torch.float32, device=DEV)
-    return dict(state=env._state, obs_io=obs, act_out=torch.full((n, 1), -7., **f), done_out=torch.full((n,), 0xAB, dtype=torch.uint8, device=DEV),
-                ring_obs=torch.full((cap, 4), -7., **f), ring_act=torch.full((cap, 1), -7., **f), ring_rew=torch.full((cap,), -7., **f),
-                ring_obs2=torch.full((cap, 4), -7., **f), ring_done=torch.full((cap,), 0xAB, dtype=torch.uint8, device=DEV))
-
-
-def ring_ptrs(t):
-    return [L.ptr(t[k]) for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2', 'ring_done')]
+    return H.start(InvertedPendulumContiEnv(num_agent=n, seed=ENV_SEED), 4, 1, n, cap, init_obs, nan_row)
 
 
 def run_chain(p, t, n, iters, cap, nxt, sctr, ectr):
@@ -115,18 +81,9 @@ def run_launch(p, t, n, iters, cap, nxt, sctr, ectr):
     t['status'] = p.status.clone()
 
 
-def both(p, n, iters, cap=None, nxt=5, sctr=7, ectr=3, init_obs=None, nan_row=None):
-    cap = iters * n + 13 if cap is None else cap
-    a, b = start(n, cap, init_obs, nan_row), start(n, cap, init_obs, nan_row)
-    run_chain(p, a, n, iters, cap, nxt, sctr, ectr)
-    run_launch(p, b, n, iters, cap, nxt, sctr, ectr)
-    torch.cuda.synchronize()
-    return a, b
-
-
-def assert_same(a, b, what):
-    for k in NAMES:
-        assert torch.equal(bits(a[k]), bits(b[k])), (what, k)
+def both(p, n, iters, init_obs=None, nan_row=None, **where):
+    """-> (chain, launch)"""
+    return H.both((partial(run_chain, p), partial(run_launch, p)), partial(start, init_obs=init_obs, nan_row=nan_row), n, iters, **where)
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -140,13 +97,11 @@ def test_one_launch_equals_the_chain_of_draw_sample_and_env_launches_bit_for_bit
             a, b = both(p, n, iters)
             assert_same(a, b, (n, iters))
             assert int(b['status'].item()) == 0
-            cap = iters * n + 13
-            untouched = torch.ones(cap, dtype=torch.bool, device=DEV)
-            untouched[(5 + torch.arange(iters * n, device=DEV)) % cap] = False
-            assert (b['ring_rew'][untouched] == -7.).all() and (b['ring_rew'][~untouched] != -7.).all()
-            assert (b['ring_done'][untouched] == 0xAB).all() and (b['ring_done'][~untouched] <= 1).all()
-            assert (b['ring_act'][untouched] == -7.).all() and (b['ring_act'][~untouched].abs() <= 3.).all()
-            assert torch.isfinite(b['ring_obs'][~untouched]).all() and torch.isfinite(b['ring_obs2'][~untouched]).all()
+            w = H.touched(iters * n + 13, 5, iters * n)
+            assert (b['ring_rew'][~w] == -7.).all() and (b['ring_rew'][w] != -7.).all()
+            assert (b['ring_done'][~w] == 0xAB).all() and (b['ring_done'][w] <= 1).all()
+            assert (b['ring_act'][~w] == -7.).all() and (b['ring_act'][w].abs() <= 3.).all()
+            assert torch.isfinite(b['ring_obs'][w]).all() and torch.isfinite(b['ring_obs2'][w]).all()
 
 
 @pytest.mark.parametrize('packed', [False, True], ids=['strided', 'packed'])
@@ -216,7 +171,7 @@ def test_ring_wrap_inside_an_iteration_and_the_counters_carry(engine, packed):
     p = Policy(packed, seed=1)
     for n, iters in ((8, 5), (40, 5), (16, 64), (1, 64)):
         cap = iters * n
-        a, b = both(p, n, iters, cap=cap, nxt=cap - 3, sctr=2 ** 32 - 2, ectr=2 ** 32 - 2, init_obs=mixed_starts(n))
+        a, b = both(p, n, iters, cap=cap, nxt=cap - 3, ctr=2 ** 32 - 2, ectr=2 ** 32 - 2, init_obs=mixed_starts(n))
         assert_same(a, b, (n, iters))
         assert (b['ring_rew'] != -7.).all() and (b['ring_done'] <= 1).all()
     # the high words matter: the same start and the same low words under another high word draw other actions, and - the odd agents
@@ -247,8 +202,7 @@ def test_a_nan_start_row_is_reported_and_stored_like_the_chain(engine, packed):
     slot = 5 + row                                         # the row's transition of iteration 0
     assert torch.isnan(b['ring_obs'][slot]).all() and torch.isnan(b['ring_act'][slot]).all() and torch.isnan(b['ring_rew'][slot])
     assert torch.isnan(b['ring_obs2'][slot]).all() and int(b['ring_done'][slot]) == 1
-    keep = torch.ones(iters * n + 13, dtype=torch.bool, device=DEV)
-    keep[slot] = False
+    keep = ~H.touched(iters * n + 13, slot, 1)
     for k in ('ring_obs', 'ring_act', 'ring_rew', 'ring_obs2'):
         assert torch.isfinite(b[k][keep]).all(), k
     assert torch.isfinite(b['state'][:4]).all() and torch.isfinite(b['obs_io']).all() and torch.isfinite(b['act_out']).all()
@@ -258,42 +212,23 @@ def test_repeated_launches_are_bit_identical(engine):
     """100 launches from one start: the hand-overs through LDS - observations to the pass, logits to the env lanes - are the new thing"""
     p = Policy(True, seed=3)
     n, iters, cap = 40, 5, 40 * 5 + 13
-    first = None
-    for _ in range(100):
-        t = start(n, cap, mixed_starts(n))
-        run_launch(p, t, n, iters, cap, 5, 7, 3)
-        if first is None:
-            first = t
-        else:
-            assert_same(first, t, 'repeat')
+    H.assert_repeatable(lambda: start(n, cap, mixed_starts(n)), lambda t: run_launch(p, t, n, iters, cap, 5, 7, 3), 100)
 
 
 # ---- OffPolicyWorker.sample ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('num_agent', [1, 8])
 def test_worker_sample_one_launch_equals_the_loop(engine, num_agent):
     from mpg_amd.config import default_args
-    from mpg_amd.policy import PolicyWithQs
-    from mpg_amd.worker import OffPolicyWorker
-    out = []
-    for one in (False, True):
-        more = dict(one_launch_sample=True) if one else {}
+
+    def make(**more):
         args = default_args('SAC', env_id=ENV_ID, squashed_head=True, num_agent=num_agent, batch_size=64, seed=5, init_seed=5, **more)
         assert args.action_range == 3.0 and args.explore_sigma is None
-        w = OffPolicyWorker(PolicyWithQs, args.env_id, args, 0)
+        return args
+    (wa, ba, ca), (wb, _, cb) = H.worker_sample_pair(make, extra_counters=True)
+    for w in (wa, wb):
         assert w.policy_with_value.squashed_head and not w.policy_with_value.deterministic_policy
-        batches = [w.sample(), w.sample()]                 # two consecutive calls: the second continues from what the first left
-        torch.cuda.synchronize()
-        w.policy_with_value.check_status()
-        out.append((batches, w.obs, w.env.obs, w.env._state, w.env.done,
-                    (w._noise_ctr, w.env._ctr, w.num_sample, w.sample_times, w.policy_with_value._sample_ctr)))
-    (ba, oa, eoa, sa, da, ca), (bb, ob, eob, sb, db, cb) = out
-    assert ca == cb and ca[0] == 2 * (64 // num_agent) and ca[2:4] == (128, 2), (ca, cb)
-    for x, y in zip(ba, bb):
-        assert len(x) == len(y) == 5
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(bits(u), bits(v))
-        assert x[1].abs().max().item() <= 3.0
-    assert torch.equal(bits(oa), bits(ob)) and torch.equal(bits(eoa), bits(eob)) and torch.equal(bits(sa), bits(sb)) and torch.equal(da, db)
+    assert ca[0] == 2 * (64 // num_agent) and ca[2:4] == (128, 2), (ca, cb)
+    assert all(x[1].abs().max().item() <= 3.0 for x in ba)
 
 
 # ---- the loop (the _stack of tests/test_sac_tanh_gpu.py section 8, restated) -------------------------------------------------------
