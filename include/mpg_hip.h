@@ -591,6 +591,44 @@ int mpg_eval_rollout_pendulum(const mpg_cfg_t* cfg, const float* policy_params, 
 int mpg_eval_metrics(int env_kind, int n, int steps, int obs_dim, const float* obs_traj, const float* act_traj, const float* rew_traj,
                      double* per_episode /* [K][n] */, double* mean /* [K] */, mpg_stream_t stream);
 
+/* ---- The differentiable models on their own (the model side of what mpg_eval_rollout records on the env) ----
+ * ONE rollout_out of the model cfg->env_kind names, for `rows` independent rows, as ONE elementwise launch (one lane per row): what the
+ * forward sweep of the rollout entry points computes per step, with the same device functions.
+ *   MPG_ENV_PATH_TRACKING (obs_dim 6 .. 16, act_dim 2): PathTrackingModel at 10 Hz.  The observation is taken as given - delta_phi is not
+ *     wrapped on the way in, the look-ahead entries 6 .. of the input are not read - and every look-ahead entry of obs_next is a copy of
+ *     its delta_y (entry 3), as in every MODEL observation.  Model noise: delta_y += 0.5 + 0.01 eps.
+ *   MPG_ENV_INVERTED_PENDULUM (4, 1): InvertedPendulumModel; p += 0.1 + 0.5 eps.
+ *   MPG_ENV_INVERTED_DOUBLE_PENDULUM (11, 1): InvertedDoublePendulumModel.  The state is atan2 of the observation's sines and cosines,
+ *     as the sweeps take a start observation; obs_next holds the 11 features of the new state (entries 8 .. 10 zero).  No model noise:
+ *     eps is not read.  This kind is SERVED here: the model is what exists of this env.
+ * obs [rows][obs_dim], act [rows][act_dim] (taken as given, nothing is clipped beyond what the model clips), eps [rows] standard normal
+ * or NULL = zeros (the noise terms at their means), obs_next [rows][obs_dim], rew [rows] RAW (before rew_shift / rew_scale).  The status
+ * word of cfg is not touched.
+ * Refused before any launch with MPG_EINVAL, "mpg_model_step" and a text of its own each, the outputs untouched: a null configuration,
+ * an unknown env kind, an obs_dim / act_dim that is not the kind's, rows <= 0, a null pointer other than eps, a tanh output activation
+ * with an action range (the cfg no entry point takes).
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_model_step(const mpg_cfg_t* cfg, int rows, const float* obs, const float* act, const float* eps /* nullable */, float* obs_next,
+                   float* rew, mpg_stream_t stream);
+
+/* A policy's closed loop on the model - inverted_double_pendulum_model.py:245-265: model.reset(obs), then compute_action -> rollout_out
+ * `steps` times - as ONE launch, for n independent trajectories from obs0 [n][obs_dim].  Everything these `steps` consecutive pairs leave
+ * behind, t = 0 .. steps - 1 with o_0 = obs0,
+ *   mpg_policy_action(cfg, policy_params, n, o_t, 0, 0, 0, act_traj + t * n * act_dim, stream);
+ *   mpg_model_step(cfg, n, o_t, act_traj + t * n * act_dim, eps ? eps + t * n : NULL, o_{t+1}, rew_traj + t * n, stream);
+ * is bit-identical: obs_traj [steps][n][obs_dim] = o_t (the observations BEFORE each step), act_traj [steps][n][act_dim], rew_traj
+ * [steps][n] RAW, last_obs [n][obs_dim] = o_steps, and the sticky status word - for both weight forms (packed image and strided).  The
+ * record's layout is mpg_eval_rollout's, so mpg_eval_metrics reads it as it stands.  For a stochastic stack the action is the mean
+ * columns under the cfg's output rule.  There is no done flag, and nothing is clipped beyond what the model clips.  eps [steps][n]
+ * standard normal, or NULL = zeros.  One workgroup keeps a 16-trajectory group's policy weights and observation rows in registers for all
+ * steps; nothing the launch wrote is read back.
+ * Refused before any launch with MPG_EINVAL, "mpg_model_rollout" and a text of its own each, the outputs untouched: a null configuration,
+ * an unknown env kind, an obs_dim / act_dim that is not the kind's (6 .. 16 / 2; 4 / 1; 11 / 1), n <= 0, steps < 1, steps > 1024 (what
+ * bounds one launch's run time), a null pointer other than eps, a tanh output activation with an action range.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+int mpg_model_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, const float* obs0, const float* eps /* nullable */,
+                      float* obs_traj, float* act_traj, float* rew_traj, float* last_obs, mpg_stream_t stream);
+
 /* ---- The MPC baseline, SLSQP form (mpc/main.py:75-165) ----
  * ModelPredictiveControl.cost_function for `rows` independent problems.  x0 [rows][6] = [v_x, v_y, r, delta_y, delta_phi, x] with
  * entry 0 the SPEED in m/s as compute_rew reads it (:133; not the env's v_x - 20), u [rows][horizon][2] NORMALISED controls.

@@ -42,6 +42,21 @@ inline int env_cfg_refusal(const char* entry, const EnvDesc& e, const mpg_cfg_t*
     return MPG_OK;
 }
 
+// what the entry points on the differentiable MODELS (model_rollout.hip) ask of a cfg: one of the three models - the double pendulum
+// is served there - with that model's widths
+inline int model_cfg_refusal(const char* entry, const mpg_cfg_t* cfg) {
+    constexpr EnvDesc MODELS[] = {PATH_TRACKING_ENV, PENDULUM_ENV, {MPG_ENV_INVERTED_DOUBLE_PENDULUM, 11, 11, 1, "double-pendulum", "11"}};
+    MPG_REQUIRE(cfg, "%s: null configuration", entry);
+    const EnvDesc* m = nullptr;
+    for (const EnvDesc& d : MODELS)
+        if (d.kind == cfg->env_kind) m = &d;
+    MPG_REQUIRE(m, "%s: unknown env kind %d (the models: 0 path tracking, 1 pendulum, 2 double pendulum)", entry, cfg->env_kind);
+    MPG_REQUIRE(cfg->obs_dim >= m->obs_lo && cfg->obs_dim <= m->obs_hi, "%s: the %s model has obs_dim %s (got %d)", entry, m->name,
+                m->obs_dims, cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == m->act_dim, "%s: the %s model has act_dim %d (got %d)", entry, m->name, m->act_dim, cfg->act_dim);
+    return MPG_OK;
+}
+
 // (the same refusal as net_cfg_ok, host_glue.h: tanh output WITH an action range is not what the reference computes)
 inline int tanh_range_refusal(const char* entry, const mpg_cfg_t* cfg) {
     MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "%s: tanh policy with an action range", entry);

@@ -6,11 +6,14 @@ still learns (the reference's plots use a base score of -30, ploter.py:85).
 `args.one_launch_eval = True` (named like args.one_launch_sample; off by default): all steps of an evaluation are ONE launch
 (ops.eval_rollout: mpg_eval_rollout on PathTracking-v0, mpg_eval_rollout_pendulum on InvertedPendulumConti-v0, bit-identical to the
 2 * fixed_steps launches of the loop), the metrics a second one (ops.eval_metrics, float64 on the device) and ONE copy brings them to
-the host; run_evaluation then follows evaluator.py:222-225 (one eval agent: num_eval_episode serial episodes)."""
+the host; run_evaluation then follows evaluator.py:222-225 (one eval agent: num_eval_episode serial episodes).
+
+ModelEvaluator (below) runs the same episodes on the differentiable MODEL - the only evaluation InvertedDoublePendulum-v2 has here -
+and measures the model's gap to the env where both exist."""
 import torch
 
 from . import ops
-from .envs import make_env
+from .envs import ENV_KIND, make_env
 
 MAX_ONE_LAUNCH_STEPS = 1024      # what mpg_eval_rollout accepts (it bounds one launch's run time)
 
@@ -154,3 +157,87 @@ class Evaluator(object):
             _, mean = self.run_n_episodes_parallel()
         self.stats = dict(iteration=iteration, **mean)
         return mean
+
+
+
+class ModelEvaluator(object):
+    """The evaluator on the differentiable MODEL instead of the env (inverted_double_pendulum_model.py:245-265: model.reset(obs), then
+    compute_action -> rollout_out in a loop): `fixed_steps` deterministic steps of every episode in ONE launch (ops.model_rollout).
+    It serves the three models, InvertedDoublePendulum-v2 included, whose real env does not exist here - there the start observations
+    have to be given, and the metrics are the two the reference gives an env id it has no branch for.  On PathTracking-v0 and
+    InvertedPendulumConti-v0 the record has eval_rollout's layout and the metrics are ops.eval_metrics on it: one more launch, one copy."""
+
+    def __init__(self, policy_cls, env_id, args, device='cuda'):
+        self.env_id = env_id
+        self.args = args
+        self.device = torch.device(device)
+        self.kind = ENV_KIND[env_id]
+        self.num_eval_agent = int(getattr(args, 'num_eval_agent', 5))
+        self.fixed_steps = int(getattr(args, 'fixed_steps', 200))
+        if not 1 <= self.fixed_steps <= MAX_ONE_LAUNCH_STEPS:
+            raise ValueError('a model evaluation takes 1 .. %d steps per launch (fixed_steps = %d)' % (MAX_ONE_LAUNCH_STEPS, self.fixed_steps))
+        # the two envs that exist: the start observations' reset law, and the env side of gap_to_env
+        self.env = None
+        if self.kind != ENV_KIND[ops.DOUBLE_PENDULUM]:
+            self.env = make_env(env_id, num_agent=self.num_eval_agent, num_future_data=getattr(args, 'num_future_data', 0), device=device,
+                                seed=int(getattr(args, 'seed', 0)) + 424242)
+        self.policy_with_value = policy_cls(**vars(args), device=device)
+
+    def set_weights(self, weights):
+        if weights is self.policy_with_value:
+            return
+        self.policy_with_value.set_weights(weights)
+
+    def share_policy(self, policy):
+        self.policy_with_value = policy
+
+    def _start(self, init_obs):
+        if init_obs is None:
+            if self.env is None:
+                raise ValueError('%s: init_obs is required - there is no env for this id here (the real one is MuJoCo), hence no reset law '
+                                 'to draw start observations from' % self.env_id)
+            self.env._initialised = False                  # fresh draw of every agent
+            return self.env.reset()
+        return init_obs.to(self.device, torch.float32).contiguous()
+
+    def run_n_episodes_parallel(self, init_obs=None, eps=None):
+        """One episode per row of init_obs ([rows, obs_dim]; default: a reset() draw of num_eval_agent rows) on the model, eps
+        [fixed_steps, rows] its standard-normal noise (None: the noise terms at their means).  Returns (per_episode, mean) in the
+        reference's key order, per_episode's values float64 HOST tensors [rows]."""
+        pw = self.policy_with_value
+        obs = self._start(init_obs)
+        rows = obs.shape[0]
+        obs_traj, act_traj, rew_traj, _ = ops.model_rollout(pw.cfg, pw.net('policy'), obs, self.fixed_steps, eps)
+        if self.env is None:
+            ret = rew_traj.double().sum(0).cpu()           # python's sum() over an episode's rewards promotes to float64
+            per_episode = dict(episode_return=ret, episode_len=torch.full((rows,), float(self.fixed_steps), dtype=torch.float64))
+            mean = {k: float(v.mean().item()) for k, v in per_episode.items()}
+        else:
+            keys = ops.EVAL_METRIC_KEYS[self.kind]
+            host = ops.eval_metrics_flat(self.kind, obs_traj, act_traj, rew_traj).cpu()     # ONE device-to-host copy: [K * rows | K]
+            per_episode = {k: host[j * rows:(j + 1) * rows] for j, k in enumerate(keys)}
+            mean = {k: float(host[len(keys) * rows + j]) for j, k in enumerate(keys)}
+        pw.check_status()          # NaN observations / actions, the engine's envelope: an evaluation on invalid numbers raises
+        return per_episode, mean
+
+    @staticmethod
+    def gap_of_records(env_record, model_record):
+        """(obs_traj, act_traj, rew_traj) of the env and of the model from one start: per step the mean over the episodes of the
+        absolute difference of every observation column (obs_gap [steps, obs_dim]) and of the reward (rew_gap [steps]), and the two mean
+        returns - float64 host tensors and floats.  A measurement: no threshold is attached."""
+        (eo, _, er), (mo, _, mr) = [[x.double() for x in r] for r in (env_record, model_record)]
+        return dict(obs_gap=(eo - mo).abs().mean(1).cpu(), rew_gap=(er - mr).abs().mean(1).cpu(),
+                    env_return=float(er.sum(0).mean().item()), model_return=float(mr.sum(0).mean().item()))
+
+    def gap_to_env(self, init_obs=None, eps=None):
+        """The env's closed loop (ops.eval_rollout) and the model's (ops.model_rollout) under the same policy from the same start
+        observations ([num_eval_agent, obs_dim]; default: a reset() draw), step by step (inverted_double_pendulum_model.py:203-242):
+        gap_of_records of the two records.  For the two envs that exist."""
+        if self.env is None:
+            raise ValueError('%s: gap_to_env compares with the env, and there is none for this id here' % self.env_id)
+        pw = self.policy_with_value
+        obs = self.env.reset(init_obs=init_obs) if init_obs is not None else self._start(None)
+        env_record = ops.eval_rollout(pw.cfg, pw.net('policy'), self.env._state, obs, self.fixed_steps)[:3]
+        model_record = ops.model_rollout(pw.cfg, pw.net('policy'), obs, self.fixed_steps, eps)[:3]
+        pw.check_status()
+        return self.gap_of_records(env_record, model_record)

@@ -357,6 +357,49 @@ def eval_metrics_flat(env_kind, obs_traj, act_traj, rew_traj):
     return out
 
 
+def _model_eps(eps, shape, name):
+    if eps is None:
+        return None
+    if tuple(eps.shape) != shape:
+        raise ValueError('%s: eps has shape %s, the model noise of this call is %s (or None for zeros)' % (name, tuple(eps.shape), shape))
+    return _f32(eps)
+
+
+def model_step(cfg, obs, act, eps=None):
+    """mpg_model_step: ONE rollout_out of the differentiable model cfg.env_kind names (the double pendulum included) on obs [rows, obs_dim]
+    and act [rows, act_dim]; eps [rows] standard-normal model noise, None = zeros.  Returns (obs_next [rows, obs_dim], rew [rows] RAW)."""
+    rows, dev = obs.shape[0], obs.device
+    if tuple(obs.shape) != (rows, cfg.obs_dim) or tuple(act.shape) != (rows, cfg.act_dim):
+        raise ValueError('model_step: obs %s and act %s are not [rows, %d] and [rows, %d]'
+                         % (tuple(obs.shape), tuple(act.shape), cfg.obs_dim, cfg.act_dim))
+    eps = _model_eps(eps, (rows,), 'model_step')
+    obs_next = torch.empty(rows, cfg.obs_dim, dtype=torch.float32, device=dev)
+    rew = torch.empty(rows, dtype=torch.float32, device=dev)
+    L.call('mpg_model_step', ctypes.byref(cfg), L.c_int(rows), L.ptr(_f32(obs)), L.ptr(_f32(act)), L.ptr(eps), L.ptr(obs_next), L.ptr(rew),
+           L.stream())
+    return obs_next, rew
+
+
+def model_rollout(cfg, policy_params, obs0, steps, eps=None):
+    """mpg_model_rollout: the policy's closed loop on the model from obs0 [n, obs_dim] - `steps` pairs of policy_action (no noise) and
+    model_step - in ONE launch, bit-identical to that chain; eps [steps, n] standard-normal model noise, None = zeros.  Returns (obs_traj
+    [steps, n, obs_dim] - the observations BEFORE each step -, act_traj [steps, n, act_dim], rew_traj [steps, n] RAW, last_obs
+    [n, obs_dim]): eval_rollout's record."""
+    n, dev, steps = obs0.shape[0], obs0.device, int(steps)
+    od, ad = cfg.obs_dim, cfg.act_dim
+    if tuple(obs0.shape) != (n, od):
+        raise ValueError('model_rollout: obs0 %s is not [n, %d]' % (tuple(obs0.shape), od))
+    eps = _model_eps(eps, (steps, n), 'model_rollout')
+    rows = max(steps, 0)
+    obs_traj = torch.empty(rows, n, od, dtype=torch.float32, device=dev)
+    act_traj = torch.empty(rows, n, ad, dtype=torch.float32, device=dev)
+    rew_traj = torch.empty(rows, n, dtype=torch.float32, device=dev)
+    last_obs = torch.empty(n, od, dtype=torch.float32, device=dev)
+    L.call('mpg_model_rollout', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(steps), L.ptr(_f32(obs0)), L.ptr(eps),
+           L.ptr(obs_traj), L.ptr(act_traj), L.ptr(rew_traj), L.ptr(last_obs), L.stream())
+    return obs_traj, act_traj, rew_traj, last_obs
+
+
 def q_loss_grad(cfg, q_params, obs, act, y, inv_b_global=None, grad_out=None, loss_out=None, want_td=False):
     rows = obs.shape[0]
     dev = obs.device
