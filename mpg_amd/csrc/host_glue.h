@@ -9,7 +9,15 @@ namespace mlp {
 // measuring arena (no buffer) it yields the `*_workspace_bytes` answer, run on the caller's buffer it yields the arrays, and fits()
 // says whether they lie inside it - the same code, so the size a query reports and the carve behind it cannot disagree.
 // Every array is charged its bytes rounded up to 256 plus 256: that covers the alignment of an unaligned buffer, and the rest is
-// slack behind each array that no one has shown the kernels' clamped / wide loads can do without.
+// slack behind each array.
+// Shown (tests/test_workspace_guard_gpu.py, both engines, every entry point that takes a workspace, at row counts with dead rows in a
+// group, a short last weight-gradient chunk and fewer thin partials than the array holds): the entry points run in exactly the queried
+// size, from a 256-byte aligned buffer and from one 4 bytes off such a line; they write nothing outside it (1 MiB guards on either side
+// stay intact); and their results do not depend on what it held - bit-identical after 0xFF bytes (every float a NaN) and after zeros,
+// although a call leaves part of the words unwritten (the test prints how many).  The kernels write whatever they read: there is no
+// memset here to rely on.
+// Not shown: that the kernels' clamped / wide loads and stores can do without the 256 bytes behind each array - a write into that slack
+// lies inside the workspace, where guards at its two ends cannot see it.
 struct Arena {
     uintptr_t p;            // next array (0: measuring)
     size_t have, need = 0;
