@@ -629,6 +629,60 @@ int mpg_model_step(const mpg_cfg_t* cfg, int rows, const float* obs, const float
 int mpg_model_rollout(const mpg_cfg_t* cfg, const float* policy_params, int n, int steps, const float* obs0, const float* eps /* nullable */,
                       float* obs_traj, float* act_traj, float* rew_traj, float* last_obs, mpg_stream_t stream);
 
+/* ---- The double pendulum's model as an ENVIRONMENT (MPG_ENV_INVERTED_DOUBLE_PENDULUM only) ----
+ * The real InvertedDoublePendulum-v2 is MuJoCo and is not provided; what a worker steps here is the reference authors' own model of it
+ * (mpg_model_step), made an env by this project's choice of a done law, an episode limit and a reset law.  The env is stateless in the
+ * observation: its state is the 11-entry observation row plus one int32 step count per agent (`age`).  mpg_env_*, mpg_eval_* and the
+ * native step driver keep refusing env kind 2.
+ *   Step: obs_next and the RAW rew are bit for bit mpg_model_step's for (obs, act) - atan2 of the row's sines and cosines, five Euler
+ *     sub-steps of f_xu_old with u = 500 a, the model's reward; no alive bonus, no action clip, no noise; entries 8 .. 10 of the new row
+ *     are zero.
+ *   Done: fell = !(tip_y > 1.0f) with tip_y = 0.6f * obs_next[3] + 0.6f * obs_next[4], two rounded products and one rounded sum (gym's
+ *     done = y <= 1 on the model's tip height; upright is 1.2); negated so that a NaN row is done and is re-drawn.  truncated =
+ *     max_steps > 0 && age + 1 >= max_steps (gym registers 1000 for this id; 0: no limit).  done = fell | truncated, one byte 0 / 1.
+ *     age becomes age + 1, or 0 after a reset.
+ *   Reset (the shape of gym's reset_model): p, theta1, theta2 ~ U(-0.1, 0.1), pdot, theta1dot, theta2dot ~ 0.1 N(0, 1) from
+ *     Philox4x32-10 keyed (seed, ctr, agent); the row is the 11 features of that state (entries 8 .. 10 zero), age 0.
+ * Known differences from MuJoCo beside the dynamics: the model's theta2 is an ABSOLUTE angle, and nothing bounds the cart position.
+ * Every entry point below refuses before any launch with MPG_EINVAL, its own name and a text of its own each, the outputs untouched: a
+ * null configuration, env kind 0 or 1 (they have a real env: mpg_env_*), an unknown env kind, obs_dim != 11, act_dim != 1, a tanh output
+ * activation with an action range, a null pointer other than the nullable ones, n <= 0, max_steps < 0, and where there is a ring
+ * capacity < n and next_idx outside [0, capacity).
+ * (added without a signature change elsewhere: the ABI version stays 10)
+ *
+ * Re-draws the agents whose done_mask byte is not 0 (NULL: all n) into obs_io [n][11] and sets their age_io [n] to 0; an agent whose
+ * byte is 0 is left untouched, bit for bit. */
+int mpg_model_env_reset(const mpg_cfg_t* cfg, int n, float* obs_io, int* age_io, const uint8_t* done_mask /* nullable */, uint64_t seed,
+                        uint64_t ctr, mpg_stream_t stream);
+
+/* One env step of n agents: obs [n][11], act [n][1] -> obs_next [n][11], rew [n] RAW, done [n]; age_io [n] is advanced by one (the
+ * caller resets the done agents: mpg_model_env_reset with done as the mask).  The status word of cfg is not touched. */
+int mpg_model_env_step(const mpg_cfg_t* cfg, int n, const float* obs, const float* act, int max_steps, int* age_io, float* obs_next,
+                       float* rew, uint8_t* done, mpg_stream_t stream);
+
+/* mpg_env_step_store_reset for this env, ONE launch: the transition (obs, act, raw rew, obs', done) of agent i goes to ring slot
+ * (next_idx + i) % capacity, done agents are then re-drawn keyed (seed, ctr), and obs_io [n][11] holds the rows after the reset.  It
+ * leaves behind exactly what mpg_model_env_step + mpg_replay_add + mpg_model_env_reset(done_mask = done) leave, bit for bit: obs_io,
+ * age_io, the five ring arrays and done_out [n] (nullable). */
+int mpg_model_env_step_store_reset(const mpg_cfg_t* cfg, int n, float* obs_io, const float* act, int max_steps, int* age_io, int capacity,
+                                   int next_idx, float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done,
+                                   uint64_t seed, uint64_t ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
+/* A worker sample on the model env as ONE launch, with mpg_worker_rollout_pendulum's residency: one workgroup keeps a 16-agent group's
+ * policy weights in registers and one agent's row and age per lane for all iterations.  Everything these `iters` consecutive pairs
+ * leave behind, it = 0 .. iters - 1,
+ *   mpg_policy_action(cfg, policy_params, n, obs_io, explore_sigma, noise_seed, noise_ctr + it, act_out, stream);
+ *   mpg_model_env_step_store_reset(cfg, n, obs_io, act_out, max_steps, age_io, capacity, (next_idx + it * n) % capacity, ring...,
+ *                                  env_seed, env_ctr + it, done_out, stream);
+ * is bit-identical: obs_io [n][11], age_io [n], act_out [n][1] and done_out [n] (nullable) of the LAST iteration, every ring array -
+ * iteration `it` writes the slots (next_idx + it * n + i) % capacity - and the sticky status word, for both weight forms (packed image
+ * and strided).  The counters are 64-bit sums (the carry into the high word included).  Deterministic policy only.
+ * Refused as above, and: iters < 1, iters > 1024 (what bounds one launch's run time), iters * n > capacity. */
+int mpg_worker_rollout_model(const mpg_cfg_t* cfg, const float* policy_params, int n, int iters, float* obs_io, int* age_io, int max_steps,
+                             float explore_sigma, uint64_t noise_seed, uint64_t noise_ctr, float* act_out, int capacity, int next_idx,
+                             float* ring_obs, float* ring_act, float* ring_rew, float* ring_obs2, uint8_t* ring_done, uint64_t env_seed,
+                             uint64_t env_ctr, uint8_t* done_out /* nullable */, mpg_stream_t stream);
+
 /* ---- The MPC baseline, SLSQP form (mpc/main.py:75-165) ----
  * ModelPredictiveControl.cost_function for `rows` independent problems.  x0 [rows][6] = [v_x, v_y, r, delta_y, delta_phi, x] with
  * entry 0 the SPEED in m/s as compute_rew reads it (:133; not the env's v_x - 20), u [rows][horizon][2] NORMALISED controls.

@@ -61,7 +61,7 @@ EXTRA = {'env_path_tracking.hip': ['-ffp-contract=off'] + os.environ.get('MPG_EN
          'rollout_bwd_double_pendulum.hip': os.environ.get('MPG_BWDD_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split(),
          'rollout_fwd_double_pendulum.hip': os.environ.get('MPG_FWDD_CFLAGS', '-mllvm -amdgpu-sched-strategy=max-memory-clause').split(),
          # the models on their own (mpg_model_step, mpg_model_rollout): ONE unit for the step kernel and the one-launch closed loop,
-         # under the common flags alone: the two call one row step, under one contraction mode
+         # under the common flags alone: the two call one row step, under one contraction mode (and so do the model-backed env's kernels)
          'model_rollout.hip': []}
 
 

@@ -10,7 +10,8 @@ Wire format: one uncompressed `.npz` (zip of `.npy`, readable without this packa
   meta                     JSON (utf-8 bytes): format version, class names, names of the networks, scalars / counters
   policy/{params,targets,m,v,nonfinite}      flat float32 in the reference's Keras order Q1,(Q2),policy
   policy/alpha_state                         SAC with the learned temperature only: log_alpha, its Adam moments, the last snapshot
-  worker/{env_state,obs,done}                SoA env state [8, num_agent], last observation, done mask
+  worker/{env_state,obs,done}                SoA env state [8, num_agent] (the model-backed env: its int32 step counts [num_agent]), last
+                                             observation, done mask
   learner/batch_*                            the minibatch cached across `num_batch_reuse` calls (+ its targets)
   learner/noise_gen                          torch generator state of the host-drawn noise stream (NADP / TD3)
   buffer/{obs,act,rew,obs2,done}             the first `size` ring rows

@@ -63,6 +63,32 @@ inline int tanh_range_refusal(const char* entry, const mpg_cfg_t* cfg) {
     return MPG_OK;
 }
 
+// what the entry points of the MODEL-BACKED env (model_rollout.hip: mpg_model_env_*, mpg_worker_rollout_model) ask of a cfg: the double
+// pendulum, the one kind without a real env - the two kinds that have one are sent to their entry points -, its widths, and no tanh
+// output under an action range
+inline int model_env_cfg_refusal(const char* entry, const mpg_cfg_t* cfg) {
+    MPG_REQUIRE(cfg, "%s: null configuration", entry);
+    MPG_REQUIRE(cfg->env_kind != MPG_ENV_PATH_TRACKING && cfg->env_kind != MPG_ENV_INVERTED_PENDULUM,
+                "%s: env kind %d has a real env (mpg_env_* and the worker entry points on it); the model-backed env is the double pendulum's",
+                entry, cfg->env_kind);
+    MPG_REQUIRE(cfg->env_kind == MPG_ENV_INVERTED_DOUBLE_PENDULUM, "%s: unknown env kind %d (the model-backed env: 2 double pendulum)", entry,
+                cfg->env_kind);
+    MPG_REQUIRE(cfg->obs_dim == 11, "%s: the double-pendulum model env has obs_dim 11 (got %d)", entry, cfg->obs_dim);
+    MPG_REQUIRE(cfg->act_dim == 1, "%s: the double-pendulum model env has act_dim 1 (got %d)", entry, cfg->act_dim);
+    MPG_REQUIRE(!(cfg->policy_out_act == MPG_ACT_TANH && cfg->action_range > 0.f), "%s: tanh policy with an action range", entry);
+    return MPG_OK;
+}
+
+// ... and of the agent count, the episode limit and - `ring` not null - the ring position (pointers are judged before this)
+inline int model_env_size_refusal(const char* entry, int n, int max_steps, const RingPtrs* ring, int capacity, int next_idx) {
+    MPG_REQUIRE(n > 0, "%s: no agents (n %d)", entry, n);
+    MPG_REQUIRE(max_steps >= 0, "%s: max_steps >= 0, 0 for no episode limit (got %d)", entry, max_steps);
+    if (!ring) return MPG_OK;
+    MPG_REQUIRE(capacity >= n, "%s: the ring's capacity %d is below n %d", entry, capacity, n);
+    MPG_REQUIRE(next_idx >= 0 && next_idx < capacity, "%s: next_idx %d outside [0, capacity %d)", entry, next_idx, capacity);
+    return MPG_OK;
+}
+
 // what the step -> ring entry points ask of the agent count and the ring
 inline bool ring_ok(int n, int capacity, int next_idx, const RingPtrs& ring) {
     return n > 0 && capacity >= n && next_idx >= 0 && next_idx < capacity && ring.obs && ring.act && ring.rew && ring.obs2 && ring.done;

@@ -1,7 +1,11 @@
 """Device-resident vectorised environments - mirrors of PathTrackingEnv
 (envs_and_models/path_tracking_env.py:356-487) and of the vectorised InvertedPendulumContiEnv
 (envs_and_models/inverted_pendulum_conti.py:5-30 behind utils/dummy_vec_env.py): same method names, argument meaning
-and quirks (PathTracking's done is always True); arrays are torch tensors on the GPU instead of numpy."""
+and quirks (PathTracking's done is always True); arrays are torch tensors on the GPU instead of numpy.
+InvertedDoublePendulum-v2 has no real env here (MuJoCo); InvertedDoublePendulumModelEnv makes the reference authors' differentiable
+model of it an env (make_model_env) - make_env keeps refusing that id."""
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -93,6 +97,65 @@ class InvertedPendulumContiEnv(_DeviceVecEnv):
 
     def __init__(self, num_agent=1, device='cuda', seed=0, **kwargs):
         super().__init__(num_agent, device, seed)
+
+
+class InvertedDoublePendulumModelEnv(_DeviceVecEnv):
+    """InvertedDoublePendulum-v2 on the reference authors' MODEL of it (inverted_double_pendulum_model.py; mpg_model_env_*,
+    include/mpg_hip.h): step() is mpg_model_step's row step, done = the model's tip height <= 1 or `max_episode_steps` steps (gym's
+    registered limit for this id is 1000; 0: none), reset() re-draws the done agents from a law of the shape of gym's reset_model.
+    The env is stateless in the observation: `_state` is the per-agent step count (int32 [num_agent]).  Beside the dynamics it differs
+    from MuJoCo's env in that theta2 is an absolute angle and nothing bounds the cart position."""
+    kind, obs_dim, act_dim = 2, 11, 1
+
+    def __init__(self, num_agent=1, device='cuda', seed=0, max_episode_steps=1000, **kwargs):
+        super().__init__(num_agent, device, seed)
+        if int(max_episode_steps) < 0:
+            raise ValueError('max_episode_steps >= 0, 0 for no episode limit (got %r)' % (max_episode_steps,))
+        self.max_episode_steps = int(max_episode_steps)
+        self._state = torch.zeros(num_agent, dtype=torch.int32, device=self.device)
+        from .ops import make_cfg
+        self.cfg = make_cfg('InvertedDoublePendulum-v2')       # (the env entry points read the kind and the widths of it, nothing else)
+
+    def reset(self, **kwargs):
+        """reset(init_obs=obs) takes obs as the agents' rows and zeroes their step counts; reset() re-draws agents with done==1 - every
+        agent on the first call."""
+        if 'init_obs' in kwargs:
+            init_obs = kwargs['init_obs'].to(self.device, torch.float32).contiguous()
+            assert init_obs.shape == (self.num_agent, self.obs_dim), (init_obs.shape, self.obs_dim)
+            self._state.zero_()
+            self.obs = init_obs
+            self._initialised = True
+            return self.obs
+        mask = self.done if self._initialised else None
+        obs = self.obs.clone()                  # never write into a tensor already handed to the caller
+        L.call('mpg_model_env_reset', ctypes.byref(self.cfg), L.c_int(self.num_agent), L.ptr(obs), L.ptr(self._state), L.ptr(mask),
+               L.c_u64(self.seed), L.c_u64(self._ctr), L.stream())
+        self._ctr += 1
+        self._initialised = True
+        self.obs = obs
+        return self.obs
+
+    def step(self, action):
+        """action [num_agent, 1] -> (obs, RAW reward, done, info)."""
+        if not (action.dtype == torch.float32 and action.device == self.device and action.is_contiguous()):
+            action = action.to(self.device, torch.float32).contiguous()
+        assert action.shape == (self.num_agent, self.act_dim)
+        obs = torch.empty_like(self.obs)
+        reward = torch.empty_like(self.reward)
+        done = torch.empty_like(self.done)      # fresh outputs: callers keep them (replay batches)
+        L.call('mpg_model_env_step', ctypes.byref(self.cfg), L.c_int(self.num_agent), L.ptr(self.obs), L.ptr(action),
+               L.c_int(self.max_episode_steps), L.ptr(self._state), L.ptr(obs), L.ptr(reward), L.ptr(done), L.stream())
+        self.obs, self.reward, self.done = obs, reward, done
+        return self.obs, self.reward, self.done, {}
+
+
+def make_model_env(env_id, num_agent=1, device='cuda', seed=0, max_episode_steps=1000):
+    """the env of `env_id` on its differentiable MODEL, for the one id whose real env is not provided (args.env_on_model of
+    OffPolicyWorker); the other two ids have real envs: make_env"""
+    if env_id == 'InvertedDoublePendulum-v2':
+        return InvertedDoublePendulumModelEnv(num_agent=num_agent, device=device, seed=seed, max_episode_steps=max_episode_steps)
+    raise ValueError('no model-backed environment for %r: it is built for InvertedDoublePendulum-v2 only (PathTracking-v0 and '
+                     'InvertedPendulumConti-v0 have real envs: make_env)' % (env_id,))
 
 
 def make_env(env_id, num_agent=1, num_future_data=0, device='cuda', seed=0):

@@ -60,6 +60,8 @@ def native_stack(worker, learner, rb):
     from .buffer import PrioritizedReplayBuffer
     from .learners import AMPCLearner, MPGLearner, NADPLearner, NDPGLearner, SACLearner, TD3Learner
     per, kind = isinstance(rb, PrioritizedReplayBuffer), type(learner)
+    if getattr(getattr(worker, 'env', None), 'kind', None) == 2:
+        return None                     # the model-backed env (args.env_on_model): the driver's sample steps the real envs only
     if per != (getattr(getattr(learner, 'args', None), 'buffer_type', 'normal') != 'normal'):
         return None
     if kind is TD3Learner:              # the one learner whose replay may be prioritized

@@ -400,6 +400,53 @@ def model_rollout(cfg, policy_params, obs0, steps, eps=None):
     return obs_traj, act_traj, rew_traj, last_obs
 
 
+def _i32(t):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.is_contiguous())
+    return t
+
+
+def _model_env_rows(name, cfg, obs, age, act=None):
+    n = obs.shape[0]
+    if tuple(obs.shape) != (n, cfg.obs_dim) or tuple(age.shape) != (n,) or (act is not None and tuple(act.shape) != (n, cfg.act_dim)):
+        raise ValueError('%s: obs %s, age %s%s are not [n, %d], [n]%s' % (
+            name, tuple(obs.shape), tuple(age.shape), '' if act is None else ' and act %s' % (tuple(act.shape),), cfg.obs_dim,
+            '' if act is None else ' and [n, %d]' % cfg.act_dim))
+    return n
+
+
+def model_env_reset(cfg, obs_io, age_io, seed, ctr, done_mask=None):
+    """mpg_model_env_reset: re-draws the agents of the model-backed env (env_kind 2) whose done_mask byte is not 0 (None: all) in place -
+    obs_io [n, 11], age_io [n] int32 - keyed (seed, ctr); the others are left untouched."""
+    n = _model_env_rows('model_env_reset', cfg, obs_io, age_io)
+    assert done_mask is None or (done_mask.dtype == torch.uint8 and tuple(done_mask.shape) == (n,))
+    L.call('mpg_model_env_reset', ctypes.byref(cfg), L.c_int(n), L.ptr(_f32(obs_io)), L.ptr(_i32(age_io)), L.ptr(done_mask), L.c_u64(seed),
+           L.c_u64(ctr), L.stream())
+
+
+def model_env_step(cfg, obs, act, age_io, max_steps=0):
+    """mpg_model_env_step: one step of the model-backed env - model_step's (obs_next, RAW rew) and done [n] uint8 = fell | truncated
+    (age + 1 >= max_steps > 0); age_io [n] int32 is advanced in place.  Returns (obs_next, rew, done)."""
+    n, dev = _model_env_rows('model_env_step', cfg, obs, age_io, act), obs.device
+    obs_next = torch.empty(n, cfg.obs_dim, dtype=torch.float32, device=dev)
+    rew = torch.empty(n, dtype=torch.float32, device=dev)
+    done = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.call('mpg_model_env_step', ctypes.byref(cfg), L.c_int(n), L.ptr(_f32(obs)), L.ptr(_f32(act)), L.c_int(int(max_steps)),
+           L.ptr(_i32(age_io)), L.ptr(obs_next), L.ptr(rew), L.ptr(done), L.stream())
+    return obs_next, rew, done
+
+
+def model_env_step_store_reset(cfg, obs_io, act, age_io, max_steps, ring, capacity, next_idx, seed, ctr, done_out=None):
+    """mpg_model_env_step_store_reset: model_env_step, the transition into ring = (obs, act, rew, obs2, done) at (next_idx + i) % capacity
+    and model_env_reset of the done agents keyed (seed, ctr) in ONE launch, bit-identical to the three calls; obs_io and age_io are
+    advanced in place."""
+    n = _model_env_rows('model_env_step_store_reset', cfg, obs_io, age_io, act)
+    r_obs, r_act, r_rew, r_obs2, r_done = ring
+    assert r_done.dtype == torch.uint8 and (done_out is None or done_out.dtype == torch.uint8)
+    L.call('mpg_model_env_step_store_reset', ctypes.byref(cfg), L.c_int(n), L.ptr(_f32(obs_io)), L.ptr(_f32(act)), L.c_int(int(max_steps)),
+           L.ptr(_i32(age_io)), L.c_int(int(capacity)), L.c_int(int(next_idx)), L.ptr(_f32(r_obs)), L.ptr(_f32(r_act)), L.ptr(_f32(r_rew)),
+           L.ptr(_f32(r_obs2)), L.ptr(r_done), L.c_u64(seed), L.c_u64(ctr), L.ptr(done_out), L.stream())
+
+
 def q_loss_grad(cfg, q_params, obs, act, y, inv_b_global=None, grad_out=None, loss_out=None, want_td=False):
     rows = obs.shape[0]
     dev = obs.device
@@ -585,18 +632,27 @@ def worker_sample_step(cfg, policy_params, state, obs_io, sample_seed, sample_ct
 
 
 def worker_rollout(cfg, policy_params, iters, state, obs_io, explore_sigma, noise_seed, noise_ctr, ring, capacity, next_idx, env_seed,
-                   env_ctr, done_out=None):
+                   env_ctr, done_out=None, max_steps=0):
     """mpg_worker_rollout: `iters` iterations of OffPolicyWorker.sample's loop for a deterministic policy (policy -> + N(0, sigma) ->
     env.step -> ring -> env.reset) in ONE launch, bit-identical to `iters` mpg_worker_step calls with the counters advancing by one and
     the ring position by n.  state [8, n] and obs_io [n, obs_dim] are advanced in place; ring = (obs, act, rew, obs2, done) arrays of
     `capacity` >= iters * n rows, iteration `it` writes the slots (next_idx + it * n + i) % capacity; done_out [n] (optional) receives
     the last iteration's done flags.  Returns the last iteration's actions [n, 2].
     A pendulum cfg (env_kind 1: obs_dim 4, actions [n, 1]) goes to mpg_worker_rollout_pendulum, the same contract against `iters`
-    pairs of mpg_policy_action + mpg_env_step_store_reset."""
+    pairs of mpg_policy_action + mpg_env_step_store_reset.
+    A double-pendulum cfg (env_kind 2: obs_dim 11, actions [n, 1]) goes to mpg_worker_rollout_model, the sample on the model-backed env:
+    `state` is the agents' step counts [n] int32, max_steps the episode limit (0: none; read by this kind only), the contract the same
+    against `iters` pairs of mpg_policy_action + mpg_model_env_step_store_reset."""
     n, dev = obs_io.shape[0], obs_io.device
     act = torch.empty(n, cfg.act_dim, dtype=torch.float32, device=dev)
     r_obs, r_act, r_rew, r_obs2, r_done = ring
     assert r_done.dtype == torch.uint8 and (done_out is None or done_out.dtype == torch.uint8)
+    if cfg.env_kind == 2:
+        L.call('mpg_worker_rollout_model', ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)), L.ptr(_f32(obs_io)),
+               L.ptr(_i32(state)), L.c_int(int(max_steps)), L.c_float(explore_sigma), L.c_u64(noise_seed), L.c_u64(noise_ctr), L.ptr(act),
+               L.c_int(int(capacity)), L.c_int(int(next_idx)), L.ptr(_f32(r_obs)), L.ptr(_f32(r_act)), L.ptr(_f32(r_rew)), L.ptr(_f32(r_obs2)),
+               L.ptr(r_done), L.c_u64(env_seed), L.c_u64(env_ctr), L.ptr(done_out), L.stream())
+        return act
     entry = 'mpg_worker_rollout_pendulum' if cfg.env_kind == 1 else 'mpg_worker_rollout'
     L.call(entry, ctypes.byref(cfg), L.ptr(_f32(policy_params)), L.c_int(n), L.c_int(int(iters)), L.ptr(_f32(state)),
            L.ptr(_f32(obs_io)), L.c_float(explore_sigma), L.c_u64(noise_seed), L.c_u64(noise_ctr), L.ptr(act), L.c_int(int(capacity)),

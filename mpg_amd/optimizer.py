@@ -79,6 +79,8 @@ class SingleProcessOffPolicyOptimizer(object):
                 % (type(learner).__name__, cls.__name__)
         if isinstance(replay_buffer, PrioritizedReplayBuffer) or getattr(args, 'buffer_type', 'normal') != 'normal':
             return 'a prioritized replay buffer is not served by the native %s step (uniform ReplayBuffer only)' % what
+        if getattr(getattr(worker, 'env', None), 'kind', None) == 2:
+            return 'the worker samples the model-backed env (env_on_model), which the native step driver does not step'
         if keyword == 'native_ampc':
             # what mpg_step_begin refuses of a learner_version 8 context (include/mpg_hip.h), said where the stack is built
             if not 1 <= learner.n <= 31:

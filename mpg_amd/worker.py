@@ -5,10 +5,11 @@ env.step -> env.reset, worker.py:91-119) but every stage is one HIP launch over 
 loop: mpg_worker_rollout on PathTracking-v0, mpg_worker_rollout_pendulum on InvertedPendulumConti-v0 (where the reference's
 defaults make a sample one agent's 512 iterations) - and there also with the tanh-squashed Gaussian policy (squashed_head=True):
 mpg_worker_sample_rollout_pendulum.  A stochastic policy on PathTracking-v0 (SAC: the Gaussian head or the squashed one) takes
-mpg_worker_sample_rollout."""
+mpg_worker_sample_rollout.  With `args.env_on_model = True` the env is the model-backed one (envs.make_model_env:
+InvertedDoublePendulum-v2, whose real env is not provided); its one-launch sample is mpg_worker_rollout_model."""
 import torch
 
-from .envs import make_env
+from .envs import make_env, make_model_env
 from . import ops
 
 # args.one_launch_sample, stated once: (env.kind, stochastic policy) -> the method sample() takes, what it says to the other policy kind
@@ -25,6 +26,10 @@ ONE_LAUNCH = {
     (1, True): ('_sample_one_launch_stochastic_pendulum',
                 '_sample_one_launch_stochastic_pendulum serves a stochastic policy (a deterministic one takes _sample_one_launch_pendulum)',
                 '_sample_one_launch_stochastic_pendulum serves InvertedPendulumConti-v0 only (the env is %s)', 'with the squashed head'),
+    (2, False): ('_sample_one_launch_model',
+                 'one_launch_sample on the model env serves a deterministic policy only: a one-launch step for a stochastic policy is '
+                 'not built for this env',
+                 '_sample_one_launch_model serves the model-backed InvertedDoublePendulum-v2 env only (the env is %s)', 'on the model env'),
     (0, True): ('_sample_one_launch_stochastic',
                 '_sample_one_launch_stochastic serves a stochastic policy (a deterministic one takes _sample_one_launch)',
                 '_sample_one_launch_stochastic serves PathTracking-v0 only (the env is %s)', 'with a stochastic policy'),
@@ -40,7 +45,13 @@ class OffPolicyWorker(object):
         seed = int(getattr(args, 'seed', 0)) * 1000003 + int(worker_id)
         # PathTracking-v0, or InvertedPendulumConti-v0 (the reference wraps the single MuJoCo env in DummyVecEnv with
         # num_agent 1, train_script4mujoco.py:328; here `num_agent` pendulums step in one launch)
-        self.env = make_env(env_id, num_agent=self.num_agent, num_future_data=getattr(args, 'num_future_data', 0), device=device, seed=seed)
+        # args.env_on_model = True: the env is the differentiable MODEL of env_id made an env (envs.make_model_env: InvertedDoublePendulum-v2,
+        # whose real env is not provided; args.max_episode_steps, default 1000, is its episode limit)
+        if getattr(args, 'env_on_model', False):
+            self.env = make_model_env(env_id, num_agent=self.num_agent, device=device, seed=seed,
+                                      max_episode_steps=getattr(args, 'max_episode_steps', 1000))
+        else:
+            self.env = make_env(env_id, num_agent=self.num_agent, num_future_data=getattr(args, 'num_future_data', 0), device=device, seed=seed)
         self.policy_with_value = policy_cls(**vars(args), device=device)
         self.batch_size = int(args.batch_size)
         self.obs = self.env.reset()
@@ -129,6 +140,11 @@ class OffPolicyWorker(object):
         iterations).  Deterministic policy only, at most 1024 iterations."""
         return self._one_launch_checked(1, False, iters)
 
+    def _sample_one_launch_model(self, iters):
+        """_sample_one_launch for the model-backed InvertedDoublePendulum-v2 env (args.env_on_model): mpg_worker_rollout_model (the
+        reference-shaped defaults make a sample one agent's 512 iterations).  Deterministic policy only, at most 1024 iterations."""
+        return self._one_launch_checked(2, False, iters)
+
     def _sample_one_launch_stochastic_pendulum(self, iters):
         """_sample_one_launch_pendulum for the tanh-squashed Gaussian policy (squashed_head=True: SAC with an action range, the one
         stochastic head built for this env): mpg_worker_sample_rollout_pendulum instead of the loop's launches per iteration (the draw,
@@ -175,7 +191,7 @@ class OffPolicyWorker(object):
                                       env._ctr, done_out=done)
         else:
             ops.worker_rollout(pw.cfg, pw.net('policy'), iters, env._state, obs_io, float(self.explore_sigma or 0.), self.seed, self._noise_ctr,
-                               ring, rows, 0, env.seed, env._ctr, done_out=done)
+                               ring, rows, 0, env.seed, env._ctr, done_out=done, max_steps=getattr(env, 'max_episode_steps', 0))
         self._noise_ctr += iters
         env._ctr += iters
         env.obs, env.done, env.reward = obs_io, done, ring[2][rows - n:]

@@ -28,7 +28,11 @@ The rule for the driver: it calls (b) for a width only if (b)'s median is at or 
         mpg_policy_sample_squashed + mpg_env_step_store_reset - against (b) mpg_worker_sample_rollout at the four cases of the
         deterministic measurement, (d) OffPolicyWorker.sample() of both SAC stacks at 8 x 64 on the loop and with one_launch_sample, and
         (c) one native SAC step (fixed and learned temperature) as the driver decides against the chain kept (sample_iters = -64);
-        --steps-only: (c) alone.  The driver's rule per width is the one above, on the plain head's rows."""
+        --steps-only: (c) alone.  The driver's rule per width is the one above, on the plain head's rows.
+    python tools/bench_worker_rollout.py --env model [--json out.json]   the model-backed InvertedDoublePendulum-v2 env: (a) the chain of
+        `iters` pairs mpg_policy_action + mpg_model_env_step_store_reset against (b) mpg_worker_rollout_model at (agents, iters,
+        explore_sigma) = (1, 512, 0) - the reference-shaped defaults -, (1, 512, 0.1) and (64, 8, 0).  The launch is taken on request
+        (args.one_launch_sample) and the native step driver does not serve this env: no rule, no step times."""
 import argparse
 import ctypes
 import json
@@ -171,6 +175,62 @@ def sample_case_pendulum(n, iters, sigma):
         a, b = sides[0][0][k], sides[1][0][k]
         assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
     fell = int(sides[1][0]['ring_done'].sum().item())             # (this env's done is real: how many of the ring's rows ended an episode)
+    del keep, wc
+    return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb)), fell, cap
+
+
+MODEL_CASES = ((1, 512, 0.), (1, 512, 0.1), (64, 8, 0.))             # (agents, iters, explore_sigma); 1 x 512: the reference-shaped defaults
+
+
+def sample_case_model(n, iters, sigma, max_steps=1000):
+    """--env model: (a) the chain of `iters` pairs mpg_policy_action + mpg_model_env_step_store_reset (two launches per iteration, what
+    sample's loop enqueues on the model-backed InvertedDoublePendulum-v2 env) against (b) mpg_worker_rollout_model, as sample_case does it"""
+    import numpy as np
+    import torch
+    from mpg_amd import _lib as L
+    from mpg_amd import ops
+    from mpg_amd.envs import InvertedDoublePendulumModelEnv
+    from tests.golden_inputs import mlp_weights_flat
+    rng = np.random.Generator(np.random.PCG64(n + 11))
+    dev = 'cuda'
+    cfg = ops.make_cfg('InvertedDoublePendulum-v2')
+    pol = torch.as_tensor(mlp_weights_flat(rng, 11, 2)).to(dev)
+    wc = ops.WeightCache(pol, [(11, 2)])
+    cfg.wcache[0] = wc.pointer
+    cap = 4 * iters * n + 3 * n                   # (the ring position wraps inside a sample now and then)
+    sides, keep = [], []
+    for _ in range(2):
+        env = InvertedDoublePendulumModelEnv(num_agent=n, seed=4, max_episode_steps=max_steps)
+        t = dict(state=env._state, obs=env.reset().clone(), act=torch.empty(n, 1, device=dev), ring_obs=torch.zeros(cap, 11, device=dev),
+                 ring_act=torch.zeros(cap, 1, device=dev), ring_rew=torch.zeros(cap, device=dev), ring_obs2=torch.zeros(cap, 11, device=dev),
+                 ring_done=torch.zeros(cap, dtype=torch.uint8, device=dev), done=torch.zeros(n, dtype=torch.uint8, device=dev))
+        sd = Side(capacity=cap, next_idx=0, ctr=1)
+        for k, v in t.items():
+            setattr(sd, k, v.data_ptr())
+        sides.append((t, sd))
+        keep.append(env)
+    lib, s, c = L.lib(), L.stream(), ctypes.byref(cfg)
+    fp = lambda f: ctypes.cast(f, ctypes.c_void_p)
+    host = host_loops()
+
+    def chain(reps):
+        assert host.bench_chain_model(fp(lib.mpg_policy_action), fp(lib.mpg_model_env_step_store_reset), c, L.ptr(pol), I(n), I(iters),
+                                      I(max_steps), F(sigma), ctypes.byref(sides[0][1]), s, I(reps)) == 0
+
+    def launch(reps):
+        assert host.bench_launch_model(fp(lib.mpg_worker_rollout_model), c, L.ptr(pol), I(n), I(iters), I(max_steps), F(sigma),
+                                       ctypes.byref(sides[1][1]), s, I(reps)) == 0
+    chain(WARMUP), launch(WARMUP)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(REGIONS):                                      # alternating: both see the same machine
+        ta.append(timed(chain, batched=True))
+        tb.append(timed(launch, batched=True))
+    torch.cuda.synchronize()
+    for k in sides[0][0]:                                         # the two did the same work: bit-identical at the end
+        a, b = sides[0][0][k], sides[1][0][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
+    fell = int(sides[1][0]['ring_done'].sum().item())             # (how many of the ring's rows ended an episode: a fall or the limit)
     del keep, wc
     return statistics.median(ta), statistics.median(tb), (min(ta), max(ta)), (min(tb), max(tb)), fell, cap
 
@@ -484,8 +544,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--json', default=None)
     ap.add_argument('--steps-only', action='store_true', help='the native step times alone')
-    ap.add_argument('--env', default='path_tracking', choices=('path_tracking', 'pendulum'),
-                    help='pendulum: mpg_worker_rollout_pendulum against its chain, and the native NADP step at the pendulum defaults')
+    ap.add_argument('--env', default='path_tracking', choices=('path_tracking', 'pendulum', 'model'),
+                    help='pendulum: mpg_worker_rollout_pendulum against its chain, and the native NADP step at the pendulum defaults; '
+                         'model: mpg_worker_rollout_model against its chain on the model-backed InvertedDoublePendulum-v2 env')
     ap.add_argument('--stochastic', action='store_true',
                     help='the stochastic (SAC) policy: mpg_worker_sample_rollout on PathTracking-v0 (both heads; with --steps-only the native '
                          'SAC step alone), or with --env pendulum mpg_worker_sample_rollout_pendulum (the tanh-squashed Gaussian policy), '
@@ -495,11 +556,22 @@ def main():
     assert not a.tree or a.steps_only, '--tree times the native steps of another checkout: pass --steps-only'
     assert not (a.stochastic and a.env == 'pendulum' and a.steps_only), '--stochastic --env pendulum has no native step to time'
     assert not (a.stochastic and a.tree), '--tree times the deterministic learners\' native steps'
+    assert not (a.env == 'model' and (a.stochastic or a.steps_only or a.tree)), \
+        '--env model times the deterministic sample alone: the launch is taken on request and the native step does not serve this env'
     sys.path.insert(0, os.path.abspath(a.tree) if a.tree else os.path.dirname(HERE))
     import torch
     assert torch.cuda.is_available(), 'bench_worker_rollout.py needs a GPU: nothing here is measured without one'
     out = {'sample': [], 'step': []}
-    if a.stochastic and a.env != 'pendulum':
+    if a.env == 'model':
+        print('| agents | iters | explore_sigma | (a) chain of mpg_policy_action + mpg_model_env_step_store_reset, ms | '
+              '(b) mpg_worker_rollout_model, ms | (a) / (b) | done rows in the ring |\n|---|---|---|---|---|---|---|', flush=True)
+        for n, iters, sigma in MODEL_CASES:
+            ma, mb, ra, rb, fell, cap = sample_case_model(n, iters, sigma)
+            out['sample'].append(dict(agents=n, iters=iters, explore_sigma=sigma, chain_ms=ma, chain_range=ra, launch_ms=mb,
+                                      launch_range=rb, done_rows=fell, ring_rows=cap))
+            print('| %d | %d | %g | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f | %d of %d |'
+                  % (n, iters, sigma, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb, fell, cap), flush=True)
+    elif a.stochastic and a.env != 'pendulum':
         if not a.steps_only:
             out['worker_sample'] = []
             print('| head | agents | iters | obs_dim | (a) chain, ms | (b) mpg_worker_sample_rollout, ms | (a) / (b) |\n|---|---|---|---|---|---|---|',
@@ -544,7 +616,7 @@ def main():
             out['sample'].append(dict(agents=n, iters=iters, obs_dim=od, chain_ms=ma, chain_range=ra, launch_ms=mb, launch_range=rb))
             print('| %d | %d | %d | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f |' % (n, iters, od, ma, ra[0], ra[1], mb, rb[0], rb[1], ma / mb),
                   flush=True)
-    if a.env != 'pendulum' and not a.stochastic:
+    if a.env == 'path_tracking' and not a.stochastic:
         step_cases(out, ab=not a.tree)       # (another checkout may not know the chain-kept form)
     if a.json:
         with open(a.json, 'w') as fh:

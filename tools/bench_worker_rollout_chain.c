@@ -145,3 +145,38 @@ int bench_chain_sample(normal_fill_fn normal_fill, sample_squashed_fn policy_sam
         }
     return 0;
 }
+
+/* the model-backed double pendulum env (bench_worker_rollout.py --env model): two launches per iteration, mpg_policy_action +
+ * mpg_model_env_step_store_reset, as sample's loop enqueues them, against mpg_worker_rollout_model.  The side's `state` is the agents'
+ * step counts (int32 [n]); max_steps is the episode limit */
+typedef int (*model_step_store_fn)(const mpg_cfg_t*, int, float*, const float*, int, int*, int, int, float*, float*, float*, float*, uint8_t*,
+                                   uint64_t, uint64_t, uint8_t*, mpg_stream_t);
+typedef int (*model_rollout_fn)(const mpg_cfg_t*, const float*, int, int, float*, int*, int, float, uint64_t, uint64_t, float*, int, int, float*,
+                                float*, float*, float*, uint8_t*, uint64_t, uint64_t, uint8_t*, mpg_stream_t);
+
+int bench_chain_model(action_fn policy_action, model_step_store_fn step_store_reset, const mpg_cfg_t* cfg, const float* policy, int n, int iters,
+                      int max_steps, float sigma, worker_side_t* w, mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r)
+        for (int it = 0; it < iters; ++it) {
+            int rc = policy_action(cfg, policy, n, w->obs, sigma, 11, w->ctr, w->act, s);
+            if (rc) return rc;
+            rc = step_store_reset(cfg, n, w->obs, w->act, max_steps, (int*)w->state, w->capacity, w->next_idx, w->ring_obs, w->ring_act,
+                                  w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
+            if (rc) return rc;
+            w->ctr++;
+            w->next_idx = (w->next_idx + n) % w->capacity;
+        }
+    return 0;
+}
+
+int bench_launch_model(model_rollout_fn worker_rollout, const mpg_cfg_t* cfg, const float* policy, int n, int iters, int max_steps, float sigma,
+                       worker_side_t* w, mpg_stream_t s, int reps) {
+    for (int r = 0; r < reps; ++r) {
+        int rc = worker_rollout(cfg, policy, n, iters, w->obs, (int*)w->state, max_steps, sigma, 11, w->ctr, w->act, w->capacity, w->next_idx,
+                                w->ring_obs, w->ring_act, w->ring_rew, w->ring_obs2, w->ring_done, 4, w->ctr, w->done, s);
+        if (rc) return rc;
+        w->ctr += (uint64_t)iters;
+        w->next_idx = (int)(((long)w->next_idx + (long)iters * n) % w->capacity);
+    }
+    return 0;
+}
