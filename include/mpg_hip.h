@@ -731,6 +731,62 @@ int mpg_mpc_cost_grad(int rows, int horizon, const float* x0 /* [rows][6] */, co
 int mpg_mpc_solve(int rows, int horizon, int iters, float tol, const float* x0, float* u_io /* start point in, solution out */,
                   float* cost_out /* [rows] */, float* pgnorm_out /* [rows] */, int* info /* [rows] */, mpg_stream_t stream);
 
+/* ---- MPC on the learners' OWN models ----
+ * The undiscounted horizon cost of a control sequence on the model cfg->env_kind names - the three models of mpg_model_step, the ones
+ * NADP, AMPC and MPG's policy half differentiate through; NOT mpg_mpc_*'s problem above - for `rows` independent start rows:
+ *   s_0 = the model's reading of obs0's row, exactly as the sweeps and mpg_model_rollout take a START observation: PathTracking (obs_dim
+ *     6 .. 16) the six base entries, not wrapped, the look-ahead entries not read; pendulum the four entries; double pendulum atan2 of
+ *     the row's sines and cosines, ONCE.
+ *   for t < horizon:  (s_{t+1}, rew_t) = finish(pre(s_t, eps_t), u_t)   on the CARRIED state - the forward sweep's chain, whose processed
+ *     rewards mpg_ampc_pg sums.  On the double pendulum this is not the chain of mpg_model_step calls, which reads atan2 of the new row's
+ *     sines and cosines again at every step: the two are equal in exact arithmetic, not in bits.
+ *   cost = - sum_t rew_t:  RAW rewards (before rew_shift / rew_scale), undiscounted, summed with t ascending.
+ * eps [horizon][rows] standard normal in mpg_model_rollout's layout, NULL = zeros: the noise terms at their means (delta_y += 0.5 per
+ * step on PathTracking, p += 0.1 on the pendulum; the double pendulum's model has none, eps is not read).  u [rows][horizon][act_dim] are
+ * actions in the policy's tanh range; the models apply their own scales (1.2 pi / 9 and 3; 100; 500).
+ * mpg_model_mpc_cost_grad, ONE launch, takes u as given (nothing is clamped beyond what the model clamps): cost [rows]; grad (nullable)
+ * [rows][horizon][act_dim] = d cost / d u by the chain of the sweeps' hand adjoint of the step from lam_horizon = 0 with rho = -1 -
+ * PathTracking's gate on the v_x clamp comes with it (a step whose raw v_x leaves [1, 35] passes no adjoint through v_x); its x (entry
+ * 5) is carried for obs_traj and has no adjoint.  obs_traj (nullable) [rows][horizon + 1][obs_dim]: row 0 is obs0's row as given, row
+ * t + 1 the observation of s_{t+1} in mpg_model_step's row format (PathTracking's look-ahead entries are copies of delta_y, the double
+ * pendulum's eleven features have zeros in 8 .. 10).  rew_traj (nullable) [rows][horizon] RAW.  cost is the same bits whether grad,
+ * obs_traj and rew_traj are asked for or not.  float32; the models' own arithmetic (hardware reciprocal / sine / cosine on PathTracking,
+ * library sincosf on the pendulums, exact division on the double pendulum), compiled without contraction.
+ *
+ * mpg_model_mpc_solve, ONE launch: minimises that cost over the box [-1, 1]^(horizon * act_dim) for every row by mpg_mpc_solve's method -
+ * the same device loop - with its constants MPG_MPC_SPG_*: spectral projected gradient with the non-monotone line search, the setup
+ * u = clamp(u_io, -1, 1), the stop rule max_j |clamp(u - g, -1, 1) - u|_j <= tol (tol 0: never), info = the accepted iterations k, or
+ * -(k + 1) behind a failed search.  A NaN (in obs0's row, eps or the start point) fails the first search: info -1, the last accepted
+ * point - the clamped start - is kept.  u_io [rows][horizon][act_dim]: start point in, solution out; cost_out [rows] is bit for bit
+ * mpg_model_mpc_cost_grad's at the returned u (same eps); pgnorm_out [rows] the norm above at that point.  A row's result does not
+ * depend on which other rows share the launch.
+ *   INVARIANT: cost_out <= the cost of the clamped start point, for every row.  The cost history starts as [f_0, -inf, ...], so the
+ *   first accepted cost is <= f_0 + gamma lambda <g, d> <= f_0 (<g, d> <= 0 for a projected step), and by induction every accepted
+ *   cost is below the maximum of costs that are themselves <= f_0.  (A row that accepts nothing keeps f_0.)
+ * One lane per row, workgroups of one wave, the lane's arrays in LDS as [index][lane]: per 64 rows (3 act_dim + obs) * horizon + obs
+ * floats per lane with obs = 6 / 4 / 6, horizon more for the noise where the model has one, and 25 for the double pendulum's adjoint
+ * (102 272 / 64 512 / 79 360 bytes at horizon 31).  Every loop has a fixed bound (iters, the halvings, horizon, the five sub-steps);
+ * early exits are wave-uniform.
+ * MPG_MODEL_MPC_MAX_ITERS_*: the per-kind bound on iters, the largest round number whose launch at horizon 31 with every CU busy
+ * (rows = 64 * the CU count, tol 0) stays under the 0.35 s mpg_mpc_rollout's comment below gives the longest MPC launch on a shared
+ * device, and at most MPG_MPC_MAX_ITERS.  Measured on one MI355X, 256 CUs, 16 384 rows, 100 iterations (tools/bench_model_mpc.py --caps):
+ * 13.7 / 15.2 / 83.2 ms, the ms per iteration beside each define.
+ * Both refuse before any launch with MPG_EINVAL, their own name and a text of its own each, the outputs untouched: a null configuration,
+ * an unknown env kind, an obs_dim / act_dim that is not the kind's (6 .. 16 / 2; 4 / 1; 11 / 1), rows <= 0, horizon < 1, horizon >
+ * MPG_MPC_MAX_HORIZON, (solve) iters < 0, iters > the kind's MPG_MODEL_MPC_MAX_ITERS_*, a negative or NaN tol, a null pointer other than
+ * eps / grad / obs_traj / rew_traj, a tanh output activation with an action range (the cfg no entry point takes).
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+#define MPG_MODEL_MPC_MAX_ITERS_PATH_TRACKING 1000   /* 0.137 ms per iteration: 2556 fit, MPG_MPC_MAX_ITERS bounds it */
+#define MPG_MODEL_MPC_MAX_ITERS_PENDULUM 1000        /* 0.152 ms per iteration: 2307 fit, MPG_MPC_MAX_ITERS bounds it */
+#define MPG_MODEL_MPC_MAX_ITERS_DOUBLE_PENDULUM 400  /* 0.832 ms per iteration (five sub-steps, library sincosf, exact division): 420 fit */
+int mpg_model_mpc_cost_grad(const mpg_cfg_t* cfg, int rows, int horizon, const float* obs0 /* [rows][obs_dim] */,
+                            const float* u /* [rows][horizon][act_dim] */, const float* eps /* nullable, [horizon][rows] */,
+                            float* cost /* [rows] */, float* grad /* nullable, [rows][horizon][act_dim] */,
+                            float* obs_traj /* nullable, [rows][horizon + 1][obs_dim] */, float* rew_traj /* nullable, [rows][horizon] */,
+                            mpg_stream_t stream);
+int mpg_model_mpc_solve(const mpg_cfg_t* cfg, int rows, int horizon, int iters, float tol, const float* obs0, const float* eps /* nullable */,
+                        float* u_io, float* cost_out, float* pgnorm_out, int* info, mpg_stream_t stream);
+
 /* mpg_mpc_rollout, ONE launch: the MPC side of the closed loop of mpc/main.py:168-223 for n agents of PathTracking-v0 with
  * num_future_data = 0 (observations of 6 entries), `steps` env steps with one solve each.  Everything the following chain leaves behind,
  * bit for bit, for t = 0 .. steps - 1:

@@ -138,13 +138,30 @@ struct Solved {
     int info;                                   // accepted iterations k, or -(k + 1) behind a failed line search
 };
 
-// One whole solve of mpg_mpc_solve for this lane's row from the start point the caller left in U, ALREADY inside the box.  The lane's
-// four arrays: U the last accepted point [2 H][WAVE] (the solution on return), G its gradient, T the trial point, X the states of the
-// last forward pass [NX H][WAVE].  A lane with `valid` false (behind the last row) takes part in the wave's control flow only.
-__device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid, const State& s0, float* U, float* G, float* T, float* X) {
-    float f = forward(H, s0, U, X, nullptr);
+// mpg_mpc_solve's problem for one lane, as solve() below takes a problem: the number of controls, forward(P) = the cost at the point P
+// (which leaves what the reverse pass needs), and reverse<UPDATE>(P, U, G, pg, ss, sy) with the contract of the function above.
+struct PathProblem {
+    int H;
+    const State& s0;
+    float* X;                                   // the states of the last forward pass [NX H][WAVE]
+    __device__ __forceinline__ int controls() const { return 2 * H; }
+    __device__ __forceinline__ float forward(const float* P) const { return mpc::forward(H, s0, P, X, nullptr); }
+    template <bool UPDATE>
+    __device__ __forceinline__ void reverse(const float* P, float* U, float* G, float& pg, float& ss, float& sy) const {
+        mpc::reverse<UPDATE>(H, P, X, U, G, pg, ss, sy);
+    }
+};
+
+// One whole solve of the method of mpg_mpc_solve for this lane's row of the problem `prob` (PathProblem above; model_mpc.h has the
+// learners' models) from the start point the caller left in U, ALREADY inside the box.  The lane's arrays of prob.controls() floats
+// each, [index][WAVE]: U the last accepted point (the solution on return), G its gradient, T the trial point.  A lane with `valid`
+// false (behind the last row) takes part in the wave's control flow only.
+template <class PROB>
+__device__ __forceinline__ Solved solve(const PROB& prob, int iters, float tol, bool valid, float* U, float* G, float* T) {
+    const int n = prob.controls();
+    float f = prob.forward(U);
     float pg, ss, sy;
-    reverse<false>(H, U, X, U, G, pg, ss, sy);
+    prob.template reverse<false>(U, U, G, pg, ss, sy);
 
     // the last MPG_MPC_SPG_M accepted costs, newest first, as named registers (an array indexed by k % M would be scratch)
     static_assert(MPG_MPC_SPG_M == 5, "the cost history below is written out for M = 5");
@@ -161,7 +178,7 @@ __device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid,
             // (by four in every kernel this is inlined into: left to itself the compiler unrolled it in k_mpc_solve and not in
             // k_mpc_rollout, where every element then waited out its own LDS round trip)
 #pragma unroll 4
-            for (int j = 0; j < 2 * H; ++j) {
+            for (int j = 0; j < n; ++j) {
                 const float uj = U[j * WAVE], gj = G[j * WAVE];
                 gd += gj * (box(uj - alpha * gj) - uj);
             }
@@ -171,11 +188,11 @@ __device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid,
         for (int h = 0; h <= MPG_MPC_SPG_HALVINGS; ++h) {
             if (!__any(searching)) break;
             if (searching) {
-                for (int j = 0; j < 2 * H; ++j) {
+                for (int j = 0; j < n; ++j) {
                     const float uj = U[j * WAVE], gj = G[j * WAVE];
                     T[j * WAVE] = box(uj + lambda * (box(uj - alpha * gj) - uj));
                 }
-                const float ft = forward(H, s0, T, X, nullptr);
+                const float ft = prob.forward(T);
                 if (ft <= fmax + MPG_MPC_SPG_GAMMA * lambda * gd) {
                     searching = false;
                     fnew = ft;
@@ -189,7 +206,7 @@ __device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid,
             failed = 1;
         }
         if (live) {
-            reverse<true>(H, T, X, U, G, pg, ss, sy);
+            prob.template reverse<true>(T, U, G, pg, ss, sy);
             alpha = sy > 0.f ? ss / sy : MPG_MPC_SPG_ALPHA_MAX_STEP;
             alpha = fminf(fmaxf(alpha, MPG_MPC_SPG_ALPHA_LO), MPG_MPC_SPG_ALPHA_HI);
             f = fnew;
@@ -199,6 +216,11 @@ __device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid,
         }
     }
     return Solved{f, pg, failed ? -(accepted + 1) : accepted};
+}
+
+// mpg_mpc_solve's own problem; X: the states of the last forward pass [NX H][WAVE]
+__device__ __forceinline__ Solved solve(int H, int iters, float tol, bool valid, const State& s0, float* U, float* G, float* T, float* X) {
+    return solve(PathProblem{H, s0, X}, iters, tol, valid, U, G, T);
 }
 
 // LDS of one workgroup: n_arrays_of_2H lane arrays of 2 H floats and the stored states

@@ -241,3 +241,38 @@ class ModelEvaluator(object):
         model_record = ops.model_rollout(pw.cfg, pw.net('policy'), obs, self.fixed_steps, eps)[:3]
         pw.check_status()
         return self.gap_of_records(env_record, model_record)
+
+    def gap_to_mpc(self, init_obs=None, horizon=None, iters=200, tol=0.):
+        """How far the policy's horizon cost on the model is from what is attainable there, per start row of init_obs ([rows, obs_dim];
+        default: a reset() draw where an env exists), noise terms at their means.  horizon None: the stack's
+        num_rollout_list_for_policy_update[-1], the horizon the policy is trained on.
+          policy_cost: the policy's closed loop (ops.model_rollout, `horizon` steps), its actions clamped to the box [-1, 1] and costed
+            by mpc.model_mpc_cost_grad - so that both sides are one function's output; rollout_cost is - sum rew_traj of the loop itself
+            (on the double pendulum the loop re-reads atan2 at every step, the cost carries the state: equal in exact arithmetic).
+          mpc_cost: the lower of two solves (mpc.model_mpc_solve), one from zeros and one from the policy's own clamped actions; the
+            second can only improve on its start point, so mpc_cost <= policy_cost for every row.
+          gap = policy_cost - mpc_cost; mean_* the means over the rows.  Beside them the two device tensors policy_u and mpc_u [rows, horizon,
+            act_dim], from_policy_won [rows] (which solve gave mpc_cost) and the two solves' info.
+        The box is the tanh range: a policy whose action range is wider (the pendulum's default of 3) is measured at its clamped actions.
+        float64 host tensors [rows] and floats.  A measurement: no threshold is attached."""
+        from . import mpc as MPC
+        pw = self.policy_with_value
+        obs = self._start(init_obs)
+        if horizon is None:
+            horizon = int(self.args.num_rollout_list_for_policy_update[-1])
+        _, act_traj, rew_traj, _ = ops.model_rollout(pw.cfg, pw.net('policy'), obs, int(horizon))
+        u_pi = act_traj.permute(1, 0, 2).clamp(-1., 1.).contiguous()                      # [rows, horizon, act_dim]
+        policy_cost = MPC.model_mpc_cost_grad(pw.cfg, obs, u_pi, want_grad=False)[0]
+        from_zeros = MPC.model_mpc_solve(pw.cfg, obs, None, iters, tol, horizon=horizon)
+        from_policy = MPC.model_mpc_solve(pw.cfg, obs, u_pi, iters, tol)
+        better = from_policy[1] < from_zeros[1]
+        mpc_cost = torch.where(better, from_policy[1], from_zeros[1])
+        mpc_u = torch.where(better[:, None, None], from_policy[0], from_zeros[0])
+        pw.check_status()
+        out = dict(policy_cost=policy_cost.double().cpu(), mpc_cost=mpc_cost.double().cpu(), rollout_cost=-rew_traj.double().sum(0).cpu())
+        out['gap'] = out['policy_cost'] - out['mpc_cost']
+        for k in ('policy_cost', 'mpc_cost', 'gap'):
+            out['mean_' + k] = float(out[k].mean().item())
+        out.update(policy_u=u_pi, mpc_u=mpc_u, from_policy_won=better.cpu(), info_from_zeros=from_zeros[3].cpu(),
+                   info_from_policy=from_policy[3].cpu())
+        return out

@@ -4,13 +4,21 @@ closed loop that measures a policy against it.  Names follow the reference.
 Where mpc/main.py runs one scipy SLSQP solve with finite-difference gradients per env step (about 2 s each), ModelPredictiveControl
 here holds B start states and solves all of them in ONE launch (mpg_mpc_solve: spectral projected gradient on the hand adjoint of the
 25-step rollout; include/mpg_hip.h states the problem, the method and its constants), and the closed loop's MPC side runs as ONE launch
-per chunk of steps (mpg_mpc_rollout).  The IPOPT form (mpc/mpc_ipopt.py) needs casadi and is not provided."""
+per chunk of steps (mpg_mpc_rollout).  The IPOPT form (mpc/mpc_ipopt.py) needs casadi and is not provided.
+
+Below those, the same on the models the LEARNERS optimise through (model_mpc_cost_grad, model_mpc_solve, ModelMPC, run_model_mpc:
+mpg_model_mpc_*): the reference's baseline solves main.py's own problem, which is not the model AMPC's objective is taken on."""
+import ctypes
+
 import torch
 
 from . import _lib as L
+from . import ops
 from .envs import PathTrackingEnv
 
 MAX_HORIZON, MAX_ITERS = 31, 1000        # MPG_MPC_MAX_HORIZON, MPG_MPC_MAX_ITERS
+# MPG_MODEL_MPC_MAX_ITERS_PATH_TRACKING, _PENDULUM, _DOUBLE_PENDULUM by env kind: what mpg_model_mpc_solve accepts (a launch's run time)
+MODEL_MAX_ITERS = {0: 1000, 1: 1000, 2: 400}
 MAX_ROLLOUT_STEPS, MAX_ROLLOUT_WORK = 1024, 2048      # MPG_MPC_ROLLOUT_MAX_STEPS, MPG_MPC_ROLLOUT_MAX_WORK (steps * iters of one launch)
 
 
@@ -213,4 +221,116 @@ def mpc_rl_summary(rec):
         for name, col in (('delta_y', 3), ('delta_v', 0), ('delta_phi', 4)):
             out['%s_%s_mse' % (who, name)] = obs[:, :, col].square().mean(0).sqrt()
         out[who + '_rew_sum'] = rec[who + '_rew'].double().sum(0)
+    return out
+
+
+# ---- MPC on the learners' own models (include/mpg_hip.h, "MPC on the learners' OWN models") -----------------------------------------
+def _model_rows(name, cfg, obs0, u):
+    rows = obs0.shape[0]
+    if tuple(obs0.shape) != (rows, cfg.obs_dim) or u.dim() != 3 or (u.shape[0], u.shape[2]) != (rows, cfg.act_dim):
+        raise ValueError('%s: obs0 %s and u %s are not [rows, %d] and [rows, horizon, %d]'
+                         % (name, tuple(obs0.shape), tuple(u.shape), cfg.obs_dim, cfg.act_dim))
+    return rows, u.shape[1]
+
+
+def model_mpc_cost_grad(cfg, obs0, u, eps=None, want_grad=True, want_traj=False):
+    """mpg_model_mpc_cost_grad on the model cfg names: obs0 [B, obs_dim], u [B, H, act_dim] in the policy's tanh range (taken as given),
+    eps [H, B] standard-normal model noise (None: the noise terms at their means) -> (cost [B] = - sum of the raw rewards, grad [B, H,
+    act_dim] or None, obs_traj [B, H + 1, obs_dim] or None, rew_traj [B, H] or None; the two records come together), one launch"""
+    rows, horizon = _model_rows('model_mpc_cost_grad', cfg, obs0, u)
+    dev = obs0.device
+    eps = ops._model_eps(eps, (horizon, rows), 'model_mpc_cost_grad')
+    cost = torch.empty(rows, dtype=torch.float32, device=dev)
+    grad = torch.empty(rows, horizon, cfg.act_dim, dtype=torch.float32, device=dev) if want_grad else None
+    obs_traj = torch.empty(rows, horizon + 1, cfg.obs_dim, dtype=torch.float32, device=dev) if want_traj else None
+    rew_traj = torch.empty(rows, horizon, dtype=torch.float32, device=dev) if want_traj else None
+    L.call('mpg_model_mpc_cost_grad', ctypes.byref(cfg), L.c_int(rows), L.c_int(horizon), L.ptr(_f32(obs0)), L.ptr(_f32(u)), L.ptr(eps),
+           L.ptr(cost), L.ptr(grad), L.ptr(obs_traj), L.ptr(rew_traj), L.stream())
+    return cost, grad, obs_traj, rew_traj
+
+
+def model_mpc_solve(cfg, obs0, u_init=None, iters=200, tol=0., eps=None, horizon=None):
+    """mpg_model_mpc_solve: obs0 [B, obs_dim], u_init [B, H, act_dim] (left as it is; None: zeros, then `horizon` says how many steps) ->
+    (u [B, H, act_dim] in the box [-1, 1], cost [B], pgnorm [B], info [B] int32), one launch.  cost <= the cost of the clamped start
+    point, for every row."""
+    if u_init is None:
+        if horizon is None:
+            raise ValueError('model_mpc_solve: a start point u_init or a horizon')
+        u_init = torch.zeros(obs0.shape[0], int(horizon), cfg.act_dim, dtype=torch.float32, device=obs0.device)
+    rows, horizon = _model_rows('model_mpc_solve', cfg, obs0, u_init)
+    dev = obs0.device
+    eps = ops._model_eps(eps, (horizon, rows), 'model_mpc_solve')
+    u = u_init.to(torch.float32).contiguous().clone()
+    cost = torch.empty(rows, dtype=torch.float32, device=dev)
+    pgnorm = torch.empty(rows, dtype=torch.float32, device=dev)
+    info = torch.empty(rows, dtype=torch.int32, device=dev)
+    L.call('mpg_model_mpc_solve', ctypes.byref(cfg), L.c_int(rows), L.c_int(horizon), L.c_int(int(iters)), L.c_float(float(tol)),
+           L.ptr(_f32(obs0)), L.ptr(eps), L.ptr(u), L.ptr(cost), L.ptr(pgnorm), L.ptr(info), L.stream())
+    return u, cost, pgnorm, info
+
+
+def _model_cfg(env_id_or_cfg):
+    return ops.make_cfg(env_id_or_cfg) if isinstance(env_id_or_cfg, str) else env_id_or_cfg
+
+
+class ModelMPC(object):
+    """ModelPredictiveControl's interface on the model the learners optimise through: env_id_or_cfg an env id (the project's default cfg
+    of it) or a cfg; init_obs [obs_dim] or [B, obs_dim] START observations on the device, read the way the rollout sweeps read them;
+    controls are actions in the policy's tanh range, [horizon, act_dim] (flat accepted) or [B, horizon, act_dim].  eps [horizon, B]: the
+    model noise every cost of this object is taken under (None: the noise terms at their means)."""
+
+    def __init__(self, env_id_or_cfg, init_obs, horizon, eps=None):
+        self.cfg = _model_cfg(env_id_or_cfg)
+        self.horizon = int(horizon)
+        self.eps = eps
+        self.reset_init_obs(init_obs)
+
+    def reset_init_obs(self, init_obs):
+        self.single = init_obs.dim() == 1
+        self.init_obs = _f32(init_obs.reshape(-1, self.cfg.obs_dim))
+
+    def _u(self, u):
+        return _f32(u.to(self.init_obs.device).reshape(self.init_obs.shape[0], self.horizon, self.cfg.act_dim))
+
+    def cost_function(self, u):
+        """A Python float for one row (this reads the device), a tensor [B] for a batch."""
+        cost = model_mpc_cost_grad(self.cfg, self.init_obs, self._u(u), self.eps, want_grad=False)[0]
+        return float(cost[0]) if self.single else cost
+
+    def cost_and_gradient(self, u):
+        """(cost, d cost / d u), the gradient in the shape of u; tensors in both forms"""
+        cost, grad = model_mpc_cost_grad(self.cfg, self.init_obs, self._u(u), self.eps)[:2]
+        return (cost[0], grad[0].reshape(u.shape)) if self.single else (cost, grad.reshape(u.shape))
+
+    def solve(self, u_init=None, iters=200, tol=0.0):
+        """minimise over the box from u_init (None: zeros) -> (u, cost, pgnorm, info); info: the accepted iterations, negative for a row
+        whose line search failed.  Tensors [B, ...]; for one row u is [horizon, act_dim] and the rest are 0-d tensors."""
+        u0 = None if u_init is None else self._u(u_init)
+        u, cost, pgnorm, info = model_mpc_solve(self.cfg, self.init_obs, u0, iters, tol, self.eps, horizon=self.horizon)
+        return (u[0], cost[0], pgnorm[0], info[0]) if self.single else (u, cost, pgnorm, info)
+
+
+def run_model_mpc(env_id_or_cfg, init_obs, steps, horizon, iters=200, tol=0., warm_start=False):
+    """The receding-horizon closed loop ON THE MODEL from init_obs [n, obs_dim]: per step one solve from the current observation
+    (model_mpc_solve, noise terms at their means) and one ops.model_step with the plan's first action - a Python loop of two launches per
+    step.  warm_start: every solve but the first starts from the plan of the step before moved up by one action, its last one repeated;
+    otherwise from zeros.  Returns a dict: mpg_model_rollout's record - obs_traj [steps, n, obs_dim] (the observations BEFORE each step),
+    act_traj [steps, n, act_dim], rew_traj [steps, n] RAW, last_obs [n, obs_dim], as ops.eval_metrics and ModelEvaluator's metric code
+    read it - plus cost, pgnorm [steps, n] and info [steps, n] int32 of every step's solve."""
+    cfg = _model_cfg(env_id_or_cfg)
+    obs = _f32(init_obs)
+    keys = ('obs_traj', 'act_traj', 'rew_traj', 'cost', 'pgnorm', 'info')
+    rec = {k: [] for k in keys}
+    u_init = None
+    for _ in range(int(steps)):
+        plan, cost, pgnorm, info = model_mpc_solve(cfg, obs, u_init, iters, tol, horizon=horizon)
+        if warm_start:
+            u_init = _shifted(plan)
+        act = plan[:, 0, :].contiguous()
+        nxt, rew = ops.model_step(cfg, obs, act)
+        for k, v in zip(keys, (obs, act, rew, cost, pgnorm, info)):
+            rec[k].append(v)
+        obs = nxt
+    out = {k: torch.stack(v) for k, v in rec.items()}
+    out['last_obs'] = obs
     return out
