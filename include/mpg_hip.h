@@ -787,6 +787,64 @@ int mpg_model_mpc_cost_grad(const mpg_cfg_t* cfg, int rows, int horizon, const f
 int mpg_model_mpc_solve(const mpg_cfg_t* cfg, int rows, int horizon, int iters, float tol, const float* obs0, const float* eps /* nullable */,
                         float* u_io, float* cost_out, float* pgnorm_out, int* info, mpg_stream_t stream);
 
+/* mpg_model_mpc_rollout, ONE launch: MPC's receding-horizon closed loop ON THE MODEL cfg->env_kind names, for n
+ * agents and `steps` model steps with one solve each - mpg_mpc_rollout (below) for the three models of mpg_model_step.  Everything the
+ * following chain leaves behind, bit for bit, for t = 0 .. steps - 1:
+ *   1. obs_traj[t] = obs_io
+ *   2. u = a copy of u_io;  mpg_model_mpc_solve on (cfg, n, horizon, iters, tol, obs_io, eps = NULL, u, cost_traj[t], pgnorm_traj[t],
+ *      info_traj[t]) - the planner plans at the noise means;  plan_traj[t] = u
+ *   3. warm_start 1: u_io[:, i] = u[:, i + 1] for i < horizon - 1 and u_io[:, horizon - 1] = u[:, horizon - 1] - the plan one action
+ *      later, its last action repeated.  warm_start 0: u_io is only read, every solve starts from it.
+ *   4. the plant step: mpg_model_mpc_cost_grad on (cfg, n, horizon = 1, obs_io, u[:, 0:1, :], eps ? eps + t * n : NULL, cost = - rew,
+ *      grad = NULL, obs_traj', rew_traj[t]);  row 1 of its observation record obs_traj' becomes obs_io.
+ * Step 4 is NOT mpg_model_step.  That one's body lives in model_rollout.hip under fp contract(fast) and is kept out of line there because
+ * its bits depend on the unit it is compiled in; the solver's model bodies are compiled under contract(off) in model_mpc.hip, and the
+ * library is built without relocatable device code: one kernel cannot hold both forms of the model bodies.  The one-step horizon cost is
+ * the same model step, in mpg_model_step's row format, under the solver's unit's own rule - and its bits do not depend on which kernel it
+ * is inlined into, the property mpg_model_mpc_solve's cost_out already rests on.  The two steps are equal in exact arithmetic and differ
+ * by rounding; on the double pendulum both read atan2 of the row's sines and cosines again at every step.
+ * eps (nullable) [steps][n] standard normal: the PLANT's model noise (NULL = zeros, the same bits; the double pendulum's model has none,
+ * eps is not read).  The planner never sees it.
+ * obs_io [n][obs_dim] and (warm) u_io [n][horizon][act_dim] carry everything from one step to the next, so two calls of s1 and s2 steps
+ * - eps advanced by s1 * n for the second - equal one call of s1 + s2 steps bit for bit.  Both are written after the LAST step only.
+ * From the second step on an observation row is what the step writes: PathTracking's look-ahead entries are copies of delta_y, the
+ * double pendulum's entries 8 .. 10 are zeros; obs_traj[0] is the caller's row as given.  obs_traj [steps][n][obs_dim], plan_traj
+ * [steps][n][horizon][act_dim] and rew_traj [steps][n] (RAW) are required; cost_traj, pgnorm_traj [steps][n] float and info_traj
+ * [steps][n] int are nullable, each on its own.
+ * One lane per agent, workgroups of one wave; the lane keeps the entries of its observation row that the model reads (6 / 4 / 8) in
+ * registers across the steps, the solver's arrays in LDS as in mpg_model_mpc_solve and of its size, the planner's noise array zeros.
+ * Global memory is read in the prologue and then written, never read back - but for u_io with warm_start 0, which no launch of this
+ * entry point writes and every solve reads, and eps, one value per lane and step.  An agent's results do not depend on which other
+ * agents share the launch.  Every loop has a fixed bound; early exits are wave-uniform.
+ * MPG_MODEL_MPC_ROLLOUT_MAX_WORK_* bound steps * iters per kind, the iterations one lane can run in a launch: DERIVED from the
+ * per-iteration times above (horizon 31, every CU busy: 0.137 / 0.152 / 0.832 ms) and the 0.35 s mpg_mpc_rollout states as the longest
+ * MPC launch on a shared device - 2556 / 2307 / 420 iterations fit under it; 2048 / 2048 / 400 are the round numbers below them.
+ * MEASURED for this kernel, one launch at each cap on one MI355X (256 CUs; horizon 31, rows = 64 * the CU count = 16 384, tol 0, cold
+ * start; tools/bench_model_mpc.py --caps, the entry point alone between two device events): 16 steps * 128 iterations = 2048 in 0.339 s
+ * (PathTracking) and 0.259 s (pendulum), 4 * 100 = 400 in 0.324 s (double pendulum) - all under 0.35 s, no cap was lowered; the times
+ * stand beside the defines.  iters stays bounded by the kind's MPG_MODEL_MPC_MAX_ITERS_* as well.  Longer loops run in chunks.
+ * WHAT THE BOUND DOES NOT COUNT: every step's solve has a setup forward and reverse pass before its iterations and the plant's step comes
+ * on top, about one iteration-equivalent per step that steps * iters leaves out (1 % at 100 iterations per solve).  With few iterations
+ * and many steps only MPG_MODEL_MPC_ROLLOUT_MAX_STEPS limits it.  Measured in the same run: PathTracking 1024 steps * 0 / 1 / 2
+ * iterations 0.026 / 0.115 / 0.155 s, pendulum 0.021 / 0.133 / 0.169 s - under 0.35 s; double pendulum 1024 * 0: 0.193 s, but 400 * 1:
+ * 0.533 s and 200 * 2: 0.382 s - ABOVE it.  A caller on a shared device who runs the double pendulum at one or two iterations per solve
+ * keeps steps at 200 or 100.
+ * Refuses before any launch with MPG_EINVAL, its own name and a text of its own each, the outputs untouched: what mpg_model_mpc_solve
+ * refuses of a configuration, n <= 0, steps < 1, steps > MPG_MODEL_MPC_ROLLOUT_MAX_STEPS, horizon < 1, horizon > MPG_MPC_MAX_HORIZON,
+ * iters < 0, iters > the kind's MPG_MODEL_MPC_MAX_ITERS_*, steps * iters > the kind's MPG_MODEL_MPC_ROLLOUT_MAX_WORK_*, a negative or NaN
+ * tol, warm_start other than 0 or 1, a null pointer among the required ones, a tanh output activation with an action range.
+ * (added without a signature change elsewhere: the ABI version stays 10) */
+#define MPG_MODEL_MPC_ROLLOUT_MAX_STEPS 1024
+#define MPG_MODEL_MPC_ROLLOUT_MAX_WORK_PATH_TRACKING 2048    /* steps * iters of one launch; 16 * 128 measured at 0.339 s: 2115 fit */
+#define MPG_MODEL_MPC_ROLLOUT_MAX_WORK_PENDULUM 2048         /* 16 * 128 measured at 0.259 s: 2764 fit */
+#define MPG_MODEL_MPC_ROLLOUT_MAX_WORK_DOUBLE_PENDULUM 400   /* 4 * 100 measured at 0.324 s: 432 fit */
+int mpg_model_mpc_rollout(const mpg_cfg_t* cfg, int n, int steps, int horizon, int iters, float tol, int warm_start,
+                          float* obs_io /* [n][obs_dim] */, float* u_io /* [n][horizon][act_dim]: the start point of the first solve */,
+                          const float* eps /* nullable, [steps][n]: the PLANT's model noise */, float* obs_traj /* [steps][n][obs_dim] */,
+                          float* plan_traj /* [steps][n][horizon][act_dim] */, float* rew_traj /* [steps][n] RAW */,
+                          float* cost_traj /* nullable */, float* pgnorm_traj /* nullable */, int* info_traj /* nullable */,
+                          mpg_stream_t stream);
+
 /* mpg_mpc_rollout, ONE launch: the MPC side of the closed loop of mpc/main.py:168-223 for n agents of PathTracking-v0 with
  * num_future_data = 0 (observations of 6 entries), `steps` env steps with one solve each.  Everything the following chain leaves behind,
  * bit for bit, for t = 0 .. steps - 1:

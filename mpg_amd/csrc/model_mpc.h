@@ -1,4 +1,4 @@
-// MPC on the learners' OWN models (mpg_model_mpc_cost_grad, mpg_model_mpc_solve; model_mpc.hip): the horizon cost of a control sequence
+// MPC on the learners' OWN models (mpg_model_mpc_cost_grad, mpg_model_mpc_solve, mpg_model_mpc_rollout; model_mpc.hip): the horizon cost of a control sequence
 // on rollout::PathTracking / Pendulum / DoublePendulum (rollout_common.h), its gradient by the chain of ENV::vjp, and the problem type
 // that mpc::solve (mpc_core.h) minimises it through - the one SPG loop of the project.  include/mpg_hip.h states the problem.
 //
@@ -181,5 +181,64 @@ struct Problem {
         model_mpc::reverse<ENV, UPDATE>(H, P, m.X, m.adj, U, G, pg, ss, sy);
     }
 };
+
+// ---- the closed loop (mpg_model_mpc_rollout): an observation row carried in registers from one step to the next ------------------------
+// The entries of a row that the model reads: PathTracking's six base entries, the pendulum's four, the double pendulum's eight (the
+// look-ahead entries and the double pendulum's 8 .. 10 never reach a model).
+template <class ENV> constexpr int row_regs() { return rollout::has_features<ENV>::value ? 8 : ENV::OBS; }
+
+// load_start's reading of a row held in registers: the same values from the same entries (an idle lane's row is zeros)
+template <class ENV>
+__device__ __forceinline__ Start start_of(const float (&o)[8]) {
+    Start r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.s[k] = 0.f;
+    if constexpr (rollout::has_features<ENV>::value) {
+        ENV::reset(o, r.s);
+    } else {
+#pragma unroll
+        for (int k = 0; k < ENV::OBS; ++k) r.s[k] = o[k];
+    }
+    return r;
+}
+
+// a row in mpg_model_step's format from its carried entries, as forward() writes rows 1 .. H of an observation record
+template <class ENV>
+__device__ __forceinline__ void store_row(float* dst, const float (&o)[8], int od) {
+    constexpr int NR = row_regs<ENV>();
+#pragma unroll
+    for (int k = 0; k < NR; ++k) dst[k] = o[k];
+    if constexpr (rollout::has_features<ENV>::value) {
+#pragma unroll
+        for (int k = NR; k < ENV::NFEAT; ++k) dst[k] = 0.f;
+    } else {
+        for (int k = NR; k < od; ++k) dst[k] = o[ENV::FUT_SRC];
+    }
+}
+
+// The plant's step: forward() with ONE step from s0 with the action P[k * WAVE], k < ACT, under the noise eps - the one-step horizon
+// cost, whose row 1 of the observation record is the new row `on` and whose raw reward is returned.  E[0], the planner's zero, holds
+// eps for the step only.  The feature model's row comes out of forward() through a record in registers (the step count is the literal
+// 1, so every index into it is a constant); the others' rows are the carried state itself, which forward() leaves behind its last
+// step in X - the values it writes to a record.
+template <class ENV>
+__device__ __forceinline__ float plant_step(const Start& s0, const float* P, const Arrays<ENV>& m, float eps, float (&on)[8]) {
+    float rew;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) on[k] = 0.f;
+    if constexpr (has_noise<ENV>()) m.E[0] = eps;
+    if constexpr (rollout::has_features<ENV>::value) {
+        float rec[2 * ENV::NFEAT];
+        forward<ENV>(1, s0, P, m.E, m.X, rec, &rew, ENV::NFEAT);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) on[k] = rec[ENV::NFEAT + k];
+    } else {
+        forward<ENV>(1, s0, P, m.E, m.X, nullptr, &rew, 0);
+#pragma unroll
+        for (int k = 0; k < ENV::OBS; ++k) on[k] = m.X[(ENV::OBS + k) * WAVE];
+    }
+    if constexpr (has_noise<ENV>()) m.E[0] = 0.f;
+    return rew;
+}
 
 }  // namespace model_mpc

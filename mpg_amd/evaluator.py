@@ -276,3 +276,35 @@ class ModelEvaluator(object):
         out.update(policy_u=u_pi, mpc_u=mpc_u, from_policy_won=better.cpu(), info_from_zeros=from_zeros[3].cpu(),
                    info_from_policy=from_policy[3].cpu())
         return out
+
+    def gap_to_mpc_closed_loop(self, init_obs=None, steps=None, horizon=None, iters=200, tol=1e-3, warm_start=True, eps=None):
+        """How the policy DRIVES on the model against what MPC attains there in closed loop, per start row of init_obs ([rows, obs_dim];
+        default: a reset() draw where an env exists): the policy's closed loop (ops.model_rollout) and MPC's receding-horizon loop
+        (mpc.run_model_mpc(one_launch=True): one solve per step at the noise means over `horizon` steps, the plan's first action applied)
+        from the same start rows, `steps` steps each (None: fixed_steps) under the same plant noise eps [steps, rows] (None: the noise
+        terms at their means).  horizon None: the stack's num_rollout_list_for_policy_update[-1].
+          policy_return, mpc_return [rows]: the two sums of raw rewards; gap = mpc_return - policy_return; mean_* the means over the rows.
+          mean_iters: the mean accepted iterations per solve (|info|, a failed search's -(k + 1) counted as k); failed_share: the share
+            of solves whose info is negative.  Beside them the two records policy_record and mpc_record (device tensors).
+        The policy acts in its own range and MPC in the box [-1, 1], the tanh range: a policy whose action range is wider (the
+        pendulum's default of 3) can reach what MPC cannot.  The two loops' steps are the same model step under two compilation rules
+        (run_model_mpc says how they differ).  float64 host tensors [rows] and floats.  A measurement: no threshold is attached."""
+        from . import mpc as MPC
+        pw = self.policy_with_value
+        obs = self._start(init_obs)
+        steps = self.fixed_steps if steps is None else int(steps)
+        if horizon is None:
+            horizon = int(self.args.num_rollout_list_for_policy_update[-1])
+        eps = ops._model_eps(eps, (steps, obs.shape[0]), 'gap_to_mpc_closed_loop')
+        obs_traj, act_traj, rew_traj, last_obs = ops.model_rollout(pw.cfg, pw.net('policy'), obs, steps, eps)
+        rec = MPC.run_model_mpc(pw.cfg, obs, steps, int(horizon), iters, tol, warm_start, one_launch=True, eps=eps)
+        pw.check_status()
+        info = rec['info']
+        accepted = torch.where(info < 0, -info - 1, info).double()
+        out = dict(policy_return=rew_traj.double().sum(0).cpu(), mpc_return=rec['rew_traj'].double().sum(0).cpu())
+        out['gap'] = out['mpc_return'] - out['policy_return']
+        for k in ('policy_return', 'mpc_return', 'gap'):
+            out['mean_' + k] = float(out[k].mean().item())
+        out.update(mean_iters=float(accepted.mean().item()), failed_share=float((info < 0).double().mean().item()),
+                   policy_record=dict(obs_traj=obs_traj, act_traj=act_traj, rew_traj=rew_traj, last_obs=last_obs), mpc_record=rec)
+        return out

@@ -20,6 +20,10 @@ MAX_HORIZON, MAX_ITERS = 31, 1000        # MPG_MPC_MAX_HORIZON, MPG_MPC_MAX_ITER
 # MPG_MODEL_MPC_MAX_ITERS_PATH_TRACKING, _PENDULUM, _DOUBLE_PENDULUM by env kind: what mpg_model_mpc_solve accepts (a launch's run time)
 MODEL_MAX_ITERS = {0: 1000, 1: 1000, 2: 400}
 MAX_ROLLOUT_STEPS, MAX_ROLLOUT_WORK = 1024, 2048      # MPG_MPC_ROLLOUT_MAX_STEPS, MPG_MPC_ROLLOUT_MAX_WORK (steps * iters of one launch)
+# MPG_MODEL_MPC_ROLLOUT_MAX_STEPS and MPG_MODEL_MPC_ROLLOUT_MAX_WORK_PATH_TRACKING, _PENDULUM, _DOUBLE_PENDULUM by env kind: steps * iters
+# of one mpg_model_mpc_rollout launch
+MODEL_MAX_ROLLOUT_STEPS = 1024
+MODEL_MAX_ROLLOUT_WORK = {0: 2048, 1: 2048, 2: 400}
 
 
 def _f32(t):
@@ -310,24 +314,87 @@ class ModelMPC(object):
         return (u[0], cost[0], pgnorm[0], info[0]) if self.single else (u, cost, pgnorm, info)
 
 
-def run_model_mpc(env_id_or_cfg, init_obs, steps, horizon, iters=200, tol=0., warm_start=False):
+def model_mpc_rollout(cfg, obs, u, steps, iters=200, tol=0., warm_start=False, eps=None):
+    """mpg_model_mpc_rollout: `steps` steps of MPC's closed loop ON THE MODEL cfg names - solve from the row at the noise means, step the
+    plant with the plan's first action under eps - in ONE launch, bit-identical to the chain of model_mpc_solve (eps None), _shifted and
+    model_mpc_cost_grad at horizon 1 (include/mpg_hip.h writes it out).  obs [n, obs_dim] the start rows, u [n, horizon, act_dim] the
+    start point of the first solve, eps [steps, n] the PLANT's standard-normal model noise (None: zeros; the planner never sees it).
+    Nothing handed in is written.  Returns (obs_traj [steps, n, obs_dim] - the rows BEFORE each step -, plan_traj [steps, n, horizon,
+    act_dim], rew_traj [steps, n] raw, cost_traj, pgnorm_traj [steps, n], info_traj [steps, n] int32, last_obs [n, obs_dim], u_next
+    [n, horizon, act_dim]: the start point of the solve after the last one - with warm_start the last plan moved up by one action, its
+    last action repeated; without, u)."""
+    n, horizon = _model_rows('model_mpc_rollout', cfg, obs, u)
+    dev, steps = obs.device, int(steps)
+    eps = ops._model_eps(eps, (steps, n), 'model_mpc_rollout')
+    obs_io = obs.to(torch.float32).contiguous().clone()          # never write into a tensor the caller handed in
+    u_io = u.to(dev, torch.float32).contiguous().clone()
+    rows = max(steps, 0)
+    obs_traj = torch.empty(rows, n, cfg.obs_dim, dtype=torch.float32, device=dev)
+    plan_traj = torch.empty(rows, n, horizon, cfg.act_dim, dtype=torch.float32, device=dev)
+    rew_traj, cost_traj, pgnorm_traj = (torch.empty(rows, n, dtype=torch.float32, device=dev) for _ in range(3))
+    info_traj = torch.empty(rows, n, dtype=torch.int32, device=dev)
+    L.call('mpg_model_mpc_rollout', ctypes.byref(cfg), L.c_int(n), L.c_int(steps), L.c_int(horizon), L.c_int(int(iters)), L.c_float(float(tol)),
+           L.c_int(1 if warm_start else 0), L.ptr(obs_io), L.ptr(u_io), L.ptr(eps), L.ptr(obs_traj), L.ptr(plan_traj), L.ptr(rew_traj),
+           L.ptr(cost_traj), L.ptr(pgnorm_traj), L.ptr(info_traj), L.stream())
+    return obs_traj, plan_traj, rew_traj, cost_traj, pgnorm_traj, info_traj, obs_io, u_io
+
+
+def model_rollout_chunk(steps, iters, work_cap, max_steps=MODEL_MAX_ROLLOUT_STEPS):
+    """the steps of one mpg_model_mpc_rollout launch of a loop of `steps` steps with `iters` iterations per solve: as many as the work
+    cap allows (steps * iters <= work_cap; no iterations are no work), at least one, at most max_steps and the loop's own length"""
+    steps, iters, work_cap, max_steps = int(steps), int(iters), int(work_cap), int(max_steps)
+    fit = work_cap // iters if iters > 0 else max_steps
+    return max(1, min(fit, max_steps, steps))
+
+
+def _run_model_mpc_one_launch(cfg, obs, steps, horizon, iters, tol, warm_start, eps, work_cap=None):
+    """run_model_mpc's record from chunks of model_mpc_rollout: the row, the start point and the eps slice carry over (two calls of s1 and
+    s2 steps are one call of s1 + s2).  work_cap None: the kind's MODEL_MAX_ROLLOUT_WORK."""
+    n, dev = obs.shape[0], obs.device
+    chunk = model_rollout_chunk(steps, iters, MODEL_MAX_ROLLOUT_WORK[int(cfg.env_kind)] if work_cap is None else work_cap)
+    u = torch.zeros(n, int(horizon), cfg.act_dim, dtype=torch.float32, device=dev)
+    parts = []
+    for t0 in range(0, steps, chunk):
+        s = min(chunk, steps - t0)
+        out = model_mpc_rollout(cfg, obs, u, s, iters, tol, warm_start, None if eps is None else eps[t0:t0 + s])
+        obs, u = out[6], out[7]
+        parts.append(out[:6])
+    obs_traj, plan, rew, cost, pgnorm, info = (torch.cat([p[k] for p in parts]) for k in range(6))
+    return dict(obs_traj=obs_traj, act_traj=plan[:, :, 0, :].contiguous(), rew_traj=rew, cost=cost, pgnorm=pgnorm, info=info, last_obs=obs)
+
+
+def run_model_mpc(env_id_or_cfg, init_obs, steps, horizon, iters=200, tol=0., warm_start=False, one_launch=False, eps=None):
     """The receding-horizon closed loop ON THE MODEL from init_obs [n, obs_dim]: per step one solve from the current observation
     (model_mpc_solve, noise terms at their means) and one ops.model_step with the plan's first action - a Python loop of two launches per
     step.  warm_start: every solve but the first starts from the plan of the step before moved up by one action, its last one repeated;
-    otherwise from zeros.  Returns a dict: mpg_model_rollout's record - obs_traj [steps, n, obs_dim] (the observations BEFORE each step),
+    otherwise from zeros.  eps [steps, n]: the PLANT's standard-normal model noise (None: zeros), eps[t] handed to step t; the planner
+    plans at the noise means either way - the setting the learners' rollouts see.
+    one_launch: the same dict from model_mpc_rollout (mpg_model_mpc_rollout), one launch per chunk of model_rollout_chunk(steps, iters,
+    the kind's MODEL_MAX_ROLLOUT_WORK) steps.  The two forms' STEPS differ: the loop's is mpg_model_step, compiled with contraction in
+    the rollouts' unit; the launch's is the one-step horizon cost of the solver's unit, compiled without (one kernel cannot hold both
+    forms of the model bodies).  They are the same model step in the same row format, equal in exact arithmetic and different by
+    rounding, so the first step's obs_traj, act_traj, cost, pgnorm and info are the loop's bit for bit and everything behind it agrees
+    to rounding as far as the closed loop keeps rounding small.  The default is the loop as it was.
+    Returns a dict: mpg_model_rollout's record - obs_traj [steps, n, obs_dim] (the observations BEFORE each step),
     act_traj [steps, n, act_dim], rew_traj [steps, n] RAW, last_obs [n, obs_dim], as ops.eval_metrics and ModelEvaluator's metric code
     read it - plus cost, pgnorm [steps, n] and info [steps, n] int32 of every step's solve."""
     cfg = _model_cfg(env_id_or_cfg)
     obs = _f32(init_obs)
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError('run_model_mpc: steps >= 1 (got %d)' % steps)
+    eps = ops._model_eps(eps, (steps, obs.shape[0]), 'run_model_mpc')
+    if one_launch:
+        return _run_model_mpc_one_launch(cfg, obs, steps, horizon, iters, tol, warm_start, eps)
     keys = ('obs_traj', 'act_traj', 'rew_traj', 'cost', 'pgnorm', 'info')
     rec = {k: [] for k in keys}
     u_init = None
-    for _ in range(int(steps)):
+    for t in range(steps):
         plan, cost, pgnorm, info = model_mpc_solve(cfg, obs, u_init, iters, tol, horizon=horizon)
         if warm_start:
             u_init = _shifted(plan)
         act = plan[:, 0, :].contiguous()
-        nxt, rew = ops.model_step(cfg, obs, act)
+        nxt, rew = ops.model_step(cfg, obs, act, None if eps is None else eps[t])
         for k, v in zip(keys, (obs, act, rew, cost, pgnorm, info)):
             rec[k].append(v)
         obs = nxt

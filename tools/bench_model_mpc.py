@@ -7,16 +7,26 @@ warm-up, with the range - tools/bench_mpc.py's form:
   --caps: (b) one solve per model at horizon 31 with every CU busy (rows = 64 x CU count), tol 0, CAP_ITERS iterations: ms per iteration
       and the largest round iteration count whose launch stays under 0.35 s - what MPG_MODEL_MPC_MAX_ITERS_* in include/mpg_hip.h are
       set from (at most MPG_MPC_MAX_ITERS);
+      and (b') one mpg_model_mpc_rollout launch per model AT its work cap MPG_MODEL_MPC_ROLLOUT_MAX_WORK_* (steps * iters = the cap,
+      at most CAP_ROLLOUT_ITERS iterations per solve), horizon 31, rows = 64 x CU count, tol 0, cold start: seconds of the entry point
+      alone (buffers allocated before) against the 0.35 s; and the corner the cap does not count, as many steps as pass with 0, 1 and 2
+      iterations per solve;
+  --closed-loop: (d) run_model_mpc per model for 64 and 256 agents x 90 steps at horizon 25, 200 iterations, warm with tol = 1e-3 and cold
+      with tol = 0: the loop form (two launches per step - the parent commit's run_model_mpc, which the default path still is bit for
+      bit) against one_launch=True, wall time of the whole call between synchronisations; the accepted iterations per solve and the mean
+      reward sum in both settings.  No ratio is fixed in advance;
   --gap: (c) ModelEvaluator.gap_to_mpc on the double pendulum's model, 64 reset-law rows, horizon 25, for a fresh AMPC policy and for
       the same stack after --iters optimizer steps of tools/train_model_env.py's loop (its objects, its settings).  A measurement: no
       threshold is attached.
 
-    python tools/bench_model_mpc.py [--caps | --gap [--iters 3000]] [--json out.json]      prints markdown tables"""
+    python tools/bench_model_mpc.py [--caps | --closed-loop | --gap [--iters 3000]] [--json out.json]
+prints markdown tables"""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -28,6 +38,8 @@ from mpg_amd import ops                                      # noqa: E402
 REGIONS, WARMUP = 7, 2
 HORIZON, ITERS = 25, 200
 CAP_HORIZON, CAP_ITERS, CAP_SECONDS = 31, 100, 0.35
+CAP_ROLLOUT_ITERS = 128          # at most: the largest divisor of the work cap up to it (128 x 16 steps = 2048, 100 x 4 = 400)
+LOOP_STEPS, LOOP_AGENTS = 90, (64, 256)
 MODELS = (('PathTracking-v0', 0), ('InvertedPendulumConti-v0', 1), ('InvertedDoublePendulum-v2', 2))
 
 
@@ -66,6 +78,30 @@ def solve_case(env_id, rows, horizon, iters, reps):
     return statistics.median(t), (min(t), max(t)), float(info.abs().float().mean()), int((info < 0).sum())
 
 
+def rollout_launch_seconds(cfg, obs0, steps, horizon, iters, regions):
+    """seconds of ONE mpg_model_mpc_rollout launch (tol 0, cold from zeros, eps NULL), the entry point alone between two device events:
+    every buffer is allocated before, and the start rows are copied back into obs_io outside the timed region"""
+    import ctypes
+    from mpg_amd import _lib as L
+    n, od, ad = obs0.shape[0], cfg.obs_dim, cfg.act_dim
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device='cuda')
+    obs_io, u_io = obs0.clone(), torch.zeros(n, horizon, ad, device='cuda')
+    obs_traj, plan_traj, rew, cost, pg = f(steps, n, od), f(steps, n, horizon, ad), f(steps, n), f(steps, n), f(steps, n)
+    info = torch.empty(steps, n, dtype=torch.int32, device='cuda')
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t = []
+    for i in range(1 + regions):                 # one warm-up launch
+        obs_io.copy_(obs0)
+        e0.record()
+        L.call('mpg_model_mpc_rollout', ctypes.byref(cfg), L.c_int(n), L.c_int(steps), L.c_int(horizon), L.c_int(iters), L.c_float(0.), L.c_int(0),
+               L.ptr(obs_io), L.ptr(u_io), L.ptr(None), L.ptr(obs_traj), L.ptr(plan_traj), L.ptr(rew), L.ptr(cost), L.ptr(pg), L.ptr(info), L.stream())
+        e1.record()
+        e1.synchronize()
+        if i >= 1:
+            t.append(e0.elapsed_time(e1) / 1e3)
+    return t
+
+
 def round_down(n):
     """the largest 'round' number <= n: one or two leading digits of 1, 1.5, 2, 2.5, 3, 4, 5, 6, 8"""
     if n < 10:
@@ -89,6 +125,65 @@ def caps(a):
         cap = min(round_down(fit), M.MAX_ITERS)
         out['caps'].append(dict(env=env_id, rows=rows, ms=m, range=r, ms_per_iteration=per, fits=fit, cap=cap, mean_abs_info=it, failed=failed))
         print('| %s | %d | %.2f (%.2f .. %.2f) | %.4f | %d | %d |' % (env_id, rows, m, r[0], r[1], per, fit, cap), flush=True)
+    # one closed-loop launch at each kind's work cap, and the corner the cap does not count: many steps of few iterations (every step's
+    # solve has a setup forward and reverse pass, and the plant's step comes on top: about one iteration-equivalent per step)
+    out['rollout_caps'] = []
+    print('\n| model | rows | steps x iterations | steps * iters | one launch, horizon %d, tol 0, cold: s | ms per (iteration + 1 per step) '
+          '| largest round work under %.2f s |\n|---|---|---|---|---|---|---|' % (CAP_HORIZON, CAP_SECONDS), flush=True)
+    for env_id, kind in MODELS:
+        cfg = ops.make_cfg(env_id)
+        work = M.MODEL_MAX_ROLLOUT_WORK[kind]
+        its = max(d for d in range(1, CAP_ROLLOUT_ITERS + 1) if work % d == 0)
+        cases = [(work // its, its, REGIONS)] + [(min(M.MODEL_MAX_ROLLOUT_STEPS, work // k if k else work + M.MODEL_MAX_ROLLOUT_STEPS), k, 3)
+                                                for k in (0, 1, 2)]
+        obs0 = start_rows(env_id, rows)
+        for steps, k, regions in cases:
+            t = rollout_launch_seconds(cfg, obs0, steps, CAP_HORIZON, k, regions)
+            m = statistics.median(t)
+            at_cap = steps * k == work and k == its
+            fit = int(work * CAP_SECONDS / m) if at_cap else None
+            out['rollout_caps'].append(dict(env=env_id, rows=rows, steps=steps, iters=k, work=steps * k, seconds=m, range=(min(t), max(t)),
+                                            ms_per_pass=1e3 * m / (steps * (k + 1)), fits=fit, round=round_down(fit) if fit else None))
+            print('| %s | %d | %d x %d | %d | %.4f (%.4f .. %.4f) | %.4f | %s |'
+                  % (env_id, rows, steps, k, steps * k, m, min(t), max(t), 1e3 * m / (steps * (k + 1)),
+                     '%d (%d fit)' % (round_down(fit), fit) if fit else '-'), flush=True)
+    if a.json:
+        with open(a.json, 'w') as fh:
+            json.dump(out, fh, indent=1)
+
+
+def closed_loop(a):
+    out = {'closed_loop': []}
+    print('| model | agents | setting | loop form (2 launches per step), s | one launch per chunk, s | loop / one launch | accepted iterations per solve '
+          '| failed searches | mean reward sum, loop | mean reward sum, one launch |\n|---|---|---|---|---|---|---|---|---|---|', flush=True)
+    for env_id, _ in MODELS:
+        if a.models and env_id not in a.models:
+            continue
+        cfg = ops.make_cfg(env_id)
+        for n in (a.agents or LOOP_AGENTS):
+            obs0 = start_rows(env_id, n)
+            for name, tol, warm in (('warm, tol 1e-3', 1e-3, True), ('cold, tol 0', 0., False)):
+                if a.setting and not name.startswith(a.setting):
+                    continue
+                t, rec = {}, {}
+                for form in (False, True):
+                    ts = []
+                    for i in range(a.warmup + a.regions):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        rec[form] = M.run_model_mpc(cfg, obs0, LOOP_STEPS, HORIZON, ITERS, tol, warm, one_launch=form)
+                        torch.cuda.synchronize()
+                        if i >= a.warmup:
+                            ts.append(time.perf_counter() - t0)
+                    t[form] = (statistics.median(ts), min(ts), max(ts))
+                info = rec[True]['info']
+                accepted = float(torch.where(info < 0, -info - 1, info).float().mean())
+                row = dict(env=env_id, agents=n, setting=name, loop=t[False], one_launch=t[True], ratio=t[False][0] / t[True][0], accepted=accepted,
+                           failed=int((info < 0).sum()), rew_loop=float(rec[False]['rew_traj'].double().sum(0).mean()),
+                           rew_one_launch=float(rec[True]['rew_traj'].double().sum(0).mean()))
+                out['closed_loop'].append(row)
+                print('| %s | %d | %s | %.4f (%.4f .. %.4f) | %.4f (%.4f .. %.4f) | %.2f | %.1f | %d | %.4f | %.4f |'
+                      % ((env_id, n, name) + t[False] + t[True] + (row['ratio'], accepted, row['failed'], row['rew_loop'], row['rew_one_launch'])), flush=True)
     if a.json:
         with open(a.json, 'w') as fh:
             json.dump(out, fh, indent=1)
@@ -135,11 +230,19 @@ def main():
     ap.add_argument('--json', default=None)
     ap.add_argument('--caps', action='store_true')
     ap.add_argument('--gap', action='store_true')
+    ap.add_argument('--closed-loop', action='store_true')
+    ap.add_argument('--models', nargs='*', default=None, help='--closed-loop: env ids (default: all three)')
+    ap.add_argument('--agents', nargs='*', type=int, default=None, help='--closed-loop: agent counts (default: 64 256)')
+    ap.add_argument('--setting', choices=('warm', 'cold'), default=None, help='--closed-loop: one setting only')
+    ap.add_argument('--regions', type=int, default=REGIONS)
+    ap.add_argument('--warmup', type=int, default=WARMUP)
     ap.add_argument('--iters', type=int, default=3000)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_model_mpc.py needs a GPU: nothing here is measured without one'
     if a.caps:
         return caps(a)
+    if a.closed_loop:
+        return closed_loop(a)
     if a.gap:
         return gap(a)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
